@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 512x512 images/sec @ 50 DDIM steps, batch 8 per GPU (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config1|config2|config3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config1|config2|config3] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -82,8 +82,14 @@ def parse():
                          "costs ~9 us of stream time: every 7th launch measured 833 ms per batch against 822 ms untimed, every 29th "
                          "824 ms (still ~160 samples of the dominant kernel in three batches; 29 is coprime to its 31 launches per "
                          "forward, so every shape is sampled)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy in float32: "
+                         "frames (the gathered uint8 frames) and latents (this rank's final latents); at most 64 MB in all")
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build_model(device, dtype):
@@ -152,6 +158,37 @@ def traffic_record():
     src = {"file": "profiles/traffic_latest.json", "commit": d.get("commit"), "measured_in_run": False,
            "method": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in two separate passes of `bench.py --steps 1`, FETCH_SIZE x 2 (gfx950)"}
     return (k or {}).get("hbm_bytes_per_launch"), src
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor of `arrays` (name -> tensor) as DIR/<name>.npy in float32.  Arrays that do not fit their share of
+    DUMP_BYTES are cut to a sample of their leading-dimension rows (images) drawn with a fixed seed and kept in ascending
+    order, so that every run with the same arguments writes the same rows.  Returns the shapes and sampled rows."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    left, info = DUMP_BYTES - 1024 * len(arrays), {}
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        n, row_bytes = t.shape[0], t[0].numel() * 4
+        share = left // (len(items) - i)
+        rows = None
+        if n * row_bytes > share:
+            k = share // row_bytes
+            assert k >= 1, (name, tuple(t.shape))
+            rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t[rows.to(t.device)]
+        a = t.detach().float().cpu().numpy()
+        np.save(d / f"{name}.npy", a)
+        left -= a.nbytes
+        info[name] = {"shape": list(arrays[name].shape), "rows": None if rows is None else rows.tolist()}
+    total = sum((d / f"{name}.npy").stat().st_size for name in arrays)
+    assert total <= DUMP_BYTES, total
+    return {"dir": os.fspath(d), "dtype": "float32", "bytes": total, "arrays": info}
 
 
 def main():
@@ -223,7 +260,7 @@ def main():
         model = build_model(device, args.dtype)
         run_micro, conds = make_runner(model)
 
-    last_latent = [None]
+    step_latents = []       # the final latents of every micro-batch of the latest step
 
     # (round 3 measured `AutoencoderKL.decode` of batch i on a second stream under the denoising of batch i + 1 at +0.4 %:
     # DESIGN.md section 5; the variant left the bench in round 4 -- `git show d4cf8f4:bench.py` has it)
@@ -231,10 +268,11 @@ def main():
 
     def step():
         frames = []
+        step_latents.clear()
         for i in range(n_micro):
             f, lat = run_micro(x_T_all[i * B:(i + 1) * B], c_all[i * B * 16:(i + 1) * B * 16] if stub else conds[i])
             frames.append(f)
-            last_latent[0] = lat
+            step_latents.append(lat)
         frames = frames[0] if n_micro == 1 else torch.cat(frames)
         if stub or not dist.is_initialized():
             return gather_frames(frames, global_batch=G)  # one all-gather per step (no process group: returns its input)
@@ -280,6 +318,9 @@ def main():
         lib.af_prof_enable(0)
         flops_executed = float(lib.af_flops_issued(1))   # this rank's GEMM / conv / attention FLOPs inside the timed region
     assert out.shape[0] == G and out.shape[-1] == 3 and out.dtype == torch.uint8
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"frames": out, "latents": torch.cat(step_latents)})
     # per-rank view (outside the timed region): this rank's own wall time and its all-gather durations, so that a SCALE line can
     # tell compute skew between the ranks from the cost of the collective.  `value` uses the MAX over ranks, as the contract says.
     dt_rank = dt
@@ -403,7 +444,7 @@ def main():
     # ---- untimed parity leg (rank 0, N = 1): the SAME batch in f32 parity mode ----
     parity = None
     if rank == 0 and world == 1 and not stub and not args.no_parity_leg and args.dtype in ("bf16", "fp8"):
-        lat16 = last_latent[0].clone()
+        lat16 = step_latents[-1].clone()
         model.set_compute_dtype("f32")
         run_micro(x_T_all[(n_micro - 1) * B:], conds[-1])          # engine build + weight upload + first call
         torch.cuda.synchronize()
@@ -454,6 +495,7 @@ def main():
             "device_clock_probe": clock,
             "distributed": dict(STATS, per_rank=per_rank),
             "roofline": roof, "kernels": kernels, "parity": parity, "two_requests_in_flight": inflight,
+            "dumped_outputs": dumped,
         }
         if stub:
             res.update(metric="PLUMBING TEST - stub in place of the HIP path, nothing measured", value=None, dtype="none",

@@ -252,6 +252,23 @@ def test_bench_config4_plumbing_is_strong_scaling_batch_64():
     assert j["config"]["global_batch"] == 64 and j["scaling"] == "strong" and "identity" in j["config"]["workload"]
 
 
+def test_bench_dump_outputs_is_float32_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's frames and final latents as float32 .npy files, the same
+    bytes on every run with the same arguments (driven through the stubbed path)."""
+    common = ["--gpus", "1", "--plumbing-test", "--steps", "2", "--warmup", "1", "--batch", "2", "--global-batch", "4"]
+    runs = []
+    for name in ("a", "b"):
+        r, j = _run_bench([*common, "--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert j["dumped_outputs"]["bytes"] <= 64_000_000
+        runs.append({p.name: p.read_bytes() for p in (tmp_path / name).glob("*.npy")})
+    assert sorted(runs[0]) == ["frames.npy", "latents.npy"] and runs[0] == runs[1]
+    frames, latents = np.load(tmp_path / "a" / "frames.npy"), np.load(tmp_path / "a" / "latents.npy")
+    assert frames.dtype == latents.dtype == np.float32
+    assert frames.shape == (4, 8, 8, 3) and latents.shape == (4, 4, 64, 64)
+    assert j["dumped_outputs"]["arrays"]["frames"]["shape"] == [4, 8, 8, 3]
+
+
 def test_adaprompt_context_differs_per_layer_only_in_subject_rows():
     from adaface_amd.synth import synth_context, synth_context_adaprompt
     c = synth_context_adaprompt(3, seed=100, device="cpu").reshape(3, 16, 77, 768)

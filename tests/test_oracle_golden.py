@@ -46,7 +46,13 @@ def test_guidance_annealing():
 
 def test_timestep_embedding(tiny):
     got = O.timestep_embedding(torch.tensor(tiny["temb_t"]), 320).numpy()
-    np.testing.assert_array_equal(got, tiny["temb_320"])
+    # torch's fp32 exp / sin / cos on the CPU come from a vector-math library whose code path depends on the host CPU, and
+    # two paths may differ in the last bit.  One ulp of a frequency moves t * f by about one ulp of t * f (t up to 981), so
+    # the golden is matched to two ulps of the argument plus two of the result, not bit for bit.
+    args = np.float32(tiny["temb_t"][:, None] * np.exp(-np.log(10000.0) * np.arange(160) / 160)[None])
+    bound = 2 * np.spacing(np.abs(np.concatenate([args, args], axis=1))) + 2 * np.spacing(np.float32(1))
+    assert got.shape == tiny["temb_320"].shape
+    assert (np.abs(got - tiny["temb_320"]) <= bound).all(), np.abs(got - tiny["temb_320"]).max()
 
 
 def test_param_inventory_counts():
@@ -201,14 +207,39 @@ def test_tiny_ddim_score_corrector_and_quantize_match_reference_sampler(tiny):
     sd = O.synth_state_dict(O.unet_param_shapes(cfg), seed=11)
     apply = lambda x, t, c: O.unet_forward(sd, cfg, x, t, c)
     corr = lambda e, x, t: 0.9 * e + 0.05 * x
-    quant = lambda z: torch.round(z * 4.0) / 4.0
-    for key, kw in (("corr_S5_samples", dict(score_corrector=corr)), ("quant_S5_samples", dict(quantize=quant)),
-                    ("corrquant_S5_samples", dict(score_corrector=corr, quantize=quant))):
-        out = O.ddim_sample(apply, O.register_schedule(), 5, torch.tensor(tiny["ddim_xT"]), torch.tensor(tiny["ddim_c"]),
-                            torch.tensor(tiny["ddim_uc"]), guidance_scale=(7.0, 3.0), **kw)
+
+    def quantiser(flip=None):
+        """round(4 z) / 4, recording the ties: elements whose 4 z lies within 1e-5 of max|4 z| of a rounding boundary.  The
+        element flip = (call, flat index) is rounded to its other neighbour instead."""
+        calls, ties = [0], []
+
+        def quant(z):
+            z4 = (z * 4.0).reshape(-1)
+            q = torch.round(z4)
+            near = (z4 - torch.floor(z4) - 0.5).abs() < 1e-5 * z4.abs().max()
+            ties.extend((calls[0], i) for i in near.nonzero().flatten().tolist())
+            if flip is not None and flip[0] == calls[0]:
+                q[flip[1]] += 1.0 if q[flip[1]] < z4[flip[1]] else -1.0
+            calls[0] += 1
+            return (q / 4.0).view_as(z)
+        return quant, ties
+
+    for key, c, quantized in (("corr_S5_samples", corr, False), ("quant_S5_samples", None, True),
+                              ("corrquant_S5_samples", corr, True)):
         ref = tiny[key]
-        # (a quantiser is discontinuous: an fp32 rounding difference that crosses a step moves that element by 1/4.  None does here.)
-        assert np.abs(out.numpy() - ref).max() < 1e-5 * np.abs(ref).max(), key
+
+        def matches(quantize):
+            out = O.ddim_sample(apply, O.register_schedule(), 5, torch.tensor(tiny["ddim_xT"]), torch.tensor(tiny["ddim_c"]),
+                                torch.tensor(tiny["ddim_uc"]), guidance_scale=(7.0, 3.0), score_corrector=c, quantize=quantize)
+            return np.abs(out.numpy() - ref).max() < 1e-5 * np.abs(ref).max()
+        if not quantized:
+            assert matches(None), key
+            continue
+        # A quantiser is discontinuous: where this host's fp32 math differs in the last bit from the golden's (the CPU's
+        # vector-math code path), a tie may round the other way and its 1/4 spreads through the later steps.  So the
+        # golden must be met as computed, or with exactly one tie rounded the other way.
+        quant, ties = quantiser()
+        assert matches(quant) or any(matches(quantiser(flip)[0]) for flip in ties), (key, ties)
 
 
 def test_tiny_unet_compel_cfg_matches_reference(tiny):

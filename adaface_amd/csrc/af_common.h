@@ -97,7 +97,7 @@ struct AfKnobs {
   int conv_halo8;           // AF_CONV_HALO8           bit 0: 3x3 / stride-1 convs of the 64x64 / 32x32 / 16x16 maps on conv3x3_halo8_kernel,
                             //                         bit 1: those of the 8x8 maps on conv3x3_s8_kernel; 0 = all on the gathering kernel
   int conv_fast_taps;       // AF_CONV_FAST_TAPS       0 = ping-pong convs recompute every tap's bounds check in the staging phase
-  int pp_stagger;           // AF_PP_STAGGER           merged schedule: 1 = the two wave groups issue their LDS-DMA pieces behind alternate MFMAs
+  int pp_stagger;           // AF_PP_STAGGER           merged schedule: 1 = the two wave groups issue their LDS-DMA pieces behind alternate MFMAs (conv3x3_halo8_kernel always does)
   int gn_producer;          // AF_GN_PRODUCER          0 = GroupNorm always runs its own statistics pass (no sums from the producer convolution)
   int conv_up_phase4;       // AF_CONV_UP_PHASE4       0 = upsampled 3x3 convolutions gather all nine taps from the upsampled map
   int pp_sched;             // AF_PP_SCHED             eight-wave kernel: 0 = round-1 compute phase (two K halves, a full LDS drain

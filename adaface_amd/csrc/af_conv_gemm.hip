@@ -1395,6 +1395,16 @@ struct Halo8Cfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
+// The K loop is a loop over the slice's channel chunks whose body is the nine tap steps, unrolled at compile time, one body
+// per wave group: the tap and (ky, kx), the weight slot a step reads (tap % 3) and the one it stages ((tap + 2) % 3), the
+// halo piece it stages (piece tap) and every s_waitcnt count are constants of the body.  Per chunk only the halo buffer
+// parity, the channel offset and the record count of the two descriptors that stage for the NEXT chunk change: that count
+// is 0 on the slice's last chunk, so its dead pieces return zeros without memory traffic and the vmcnt accounting stays as
+// it is.  (The former per-step bookkeeping -- tap / chunk divisions, a switch over the halo piece, per-lane selects of the
+// dead pieces, runtime tests of the wave group -- issued ~190 SALU and ~40 branches per step around 40 MFMAs.)
+// LABL: lab builds only (-DAF_LAB_ABLATE, scripts/lab/ablate_conv.sh): the phase removals inside the loop as template bits,
+// 1 no LDS-DMA, 2 no fragment reads, 4 no MFMAs; the library instantiates LABL = 0 only.
+template <int LABL>
 __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams p) {
   using C = PpCfg<160>;
   using H = Halo8Cfg;
@@ -1408,25 +1418,26 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
   tile_coords(blockIdx.x, gridDim.x, ntm, ntn, p.group_m, tm, tn);
   const int m0 = tm * 256, n0 = tn * BN;
   const int zk = blockIdx.z;
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.src)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.W)), 0, (int)0xFFFFFFF0u, 0x00020000);
+  T* const xsrc = const_cast<T*>(reinterpret_cast<const T*>(p.src));
+  T* const wsrc = const_cast<T*>(reinterpret_cast<const T*>(p.W));
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(xsrc, 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(wsrc, 0, (int)0xFFFFFFF0u, 0x00020000);
 
   // K range: steps s = (chunk, tap), nine per chunk; a slice is a whole number of chunks (the launcher checks)
   const int KT_all = p.K / 64;
   const int kt_per = (KT_all + p.splitk - 1) / p.splitk;
   const int kt_begin = zk * kt_per;
 #ifdef AF_LAB_ABLATE
-  // timing ablations (wrong results; scripts/lab/ablate_conv.sh halo): bits 4.. of the conv_fast_taps knob: 1 no LDS-DMA in
-  // the loop, 2 no fragment reads, 4 no MFMAs, 8 no epilogue, 16 one K step only, 32 no prologue staging
+  // timing ablations (wrong results; scripts/lab/ablate_conv.sh halo): bits 4.. of the conv_fast_taps knob: 1 / 2 / 4 see
+  // LABL, 8 no epilogue, 16 one chunk (nine K steps) only, 32 no prologue staging, 64 time stamps
   const int lab = p.fast_taps >> 4;
-  const int KT = (lab & 16) ? 1 : min(KT_all, kt_begin + kt_per) - kt_begin;
+  const int KT = (lab & 16) ? 9 : min(KT_all, kt_begin + kt_per) - kt_begin;
 #else
   constexpr int lab = 0;
   const int KT = min(KT_all, kt_begin + kt_per) - kt_begin;
 #endif
   const int chunk0 = kt_begin / 9;
+  const int nch = KT / 9;
 #ifdef AF_LAB_ABLATE
   unsigned long long st0 = 0, st1 = 0, st2 = 0;
   if (lab & 64) st0 = lab_now();
@@ -1456,6 +1467,11 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
     h_off[q] = ok ? (unsigned)((long)img * p.src_batch_stride * 2) + (unsigned)((iy >> p.up) * p.Ws + (ix >> p.up)) * ldcb + dchunk * 16u
                   : 0xFFFFFFFFu;
   }
+  // Piece 6 exists for waves 0 and 1 only.  In the loop, waves 2 and 3 (the rest of their group) stage their piece 0 a
+  // second time in its place -- the same bytes to the same LDS, still ahead of the next chunk's barrier -- so that one body
+  // and one vmcnt count serve the whole group; waves 4-7 have no tap-6 halo piece in their body.
+  const unsigned hl6 = (unsigned)(wid < 2 ? 8 * (NHQ - 1) * 1024 : 0);
+  if (wid >= 2) h_off[NHQ - 1] = h_off[0];
   // weight pieces of this wave: piece wid + 8 q, q < 3 (waves 0-3) or 2 (waves 4-7)
   unsigned w_off[3];
 #pragma unroll
@@ -1463,193 +1479,177 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
     const int n = n0 + (wid + 8 * q) * 8 + srow;
     w_off[q] = (n < p.Wrows && (wid + 8 * q) < BN / 8) ? (unsigned)((long)n * p.ldw * 2) + dchunk * 16u : 0xFFFFFFFFu;
   }
-  const int nwq = g == 0 ? 3 : 2;
+  const unsigned cin2 = (unsigned)p.Cin * 2u;   // bytes of one tap's K range in a weight row
 
   // ---- fragment addressing ----
   const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)((__attribute__((address_space(3))) char*)smem);
   const unsigned fch0 = (unsigned)((lane >> 4) ^ (lane & 7)) * 16u;
   const unsigned fch1 = (unsigned)(((lane >> 4) + 4) ^ (lane & 7)) * 16u;
   const unsigned w_base = (unsigned)((g * C::HN + (lane & 15)) * 128);
-  // halo pixel of tap (0, 0) for this lane's output pixel of block j: tile pixel t = wq * 64 + j * 16 + (lane & 15)
-  int xhp[MI];
+  // weight fragments of slot 0; the slot and the 16-row block are immediate offsets of the reads
+  const unsigned wrd0 = lds0 + (unsigned)H::W_BASE + w_base + fch0, wrd1 = lds0 + (unsigned)H::W_BASE + w_base + fch1;
+  // halo fragments: the lane's output pixel of block j is tile pixel t = wq * 64 + j * 16 + (lane & 15), at halo pixel
+  // xhp(j) + ky * HW + kx for tap (ky, kx).  With u = (buffer base >> 3) + 16 hp the read address is
+  // (u << 3) | ((u ^ 16 qsel) & 0x70), hp << 7 plus the swizzle slot (hp ^ qsel) & 7 (the base is a multiple of 1024:
+  // bits 4-6 of u are those of 16 hp): a few VALU per block and tap, no select.
+  unsigned xh16[MI];
 #pragma unroll
   for (int j = 0; j < MI; ++j) {
     const int t = wq * 64 + j * 16 + (lane & 15);
-    xhp[j] = (t >> wsh) * HW + (t & (Wo - 1));
+    xh16[j] = (unsigned)((t >> wsh) * HW + (t & (Wo - 1))) << 4;
   }
-  const unsigned qsel = (unsigned)(lane >> 4);
+  const unsigned qsel16 = (unsigned)(lane >> 4) << 4;
+  const unsigned hw16 = (unsigned)HW * 16u;
 
   f32x4 acc[NI][MI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  pp_u32x4 w8[NI][2], xa8[MI][2], xb8[MI][2];
+  // w8: the weight fragments of the current step (block NI - 1 is held over into the next one); xp: the activation
+  // fragments of the previous step
+  pp_u32x4 w8[NI][2], xp[MI][2];
 #pragma unroll
   for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-  for (int j = 0; j < MI; ++j) xa8[j][0] = xa8[j][1] = xb8[j][0] = xb8[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+  for (int j = 0; j < MI; ++j) xp[j][0] = xp[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
   auto mfma2 = [&](f32x4& c, const pp_u32x4 (&wv)[2], const pp_u32x4 (&xv)[2]) {
-    if (lab & 4) return;
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[0]), __builtin_bit_cast(bf16x8, xv[0]), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[1]), __builtin_bit_cast(bf16x8, xv[1]), c, 0, 0, 0);
-    asm volatile("" : "+v"(c));
+    if constexpr ((LABL & 4) == 0) {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[0]), __builtin_bit_cast(bf16x8, xv[0]), c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[1]), __builtin_bit_cast(bf16x8, xv[1]), c, 0, 0, 0);
+      asm volatile("" : "+v"(c));
+    }
   };
   auto wait_block = [&](auto nc, pp_u32x4 (&blk)[2]) {
     constexpr int n = decltype(nc)::value;
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
   };
-
-  // ---- staging (everything by value: see KWalk in conv_gemm_pp_kernel) ----
-  struct Step { int tap, chunk; };             // the step being STAGED (weights) / the chunk whose halo is being staged
-  bool in_loop = false;
-  auto stage_w = [&](auto qc, int wslot, Step st, int live) {
-    constexpr int q = decltype(qc)::value;
-    if ((lab & 1) && in_loop) return;
-    if ((lab & 32) && !in_loop) return;
-    const unsigned k0b = (unsigned)(st.tap * p.Cin + st.chunk * 64) * 2u;
-    const unsigned a = live ? w_off[q] : 0xFFFFFFFFu;
-    lds_dma16(rs_w, smem + H::W_BASE + wslot * H::WBYTES + (wid + 8 * q) * 1024, a, k0b);
+  auto wait_block2 = [&](auto nc, pp_u32x4 (&b0)[2], pp_u32x4 (&b1)[2]) {   // (one s_waitcnt for two blocks)
+    constexpr int n = decltype(nc)::value;
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(b0[0]), "+v"(b0[1]), "+v"(b1[0]), "+v"(b1[1]) : "n"(n) : "memory");
   };
-  auto stage_h = [&](auto qc, int hbuf, int chunk, int live) {
-    constexpr int q = decltype(qc)::value;
-    if ((lab & 1) && in_loop) return;
-    if ((lab & 32) && !in_loop) return;
-    const unsigned a = live ? h_off[q] : 0xFFFFFFFFu;
-    lds_dma16(rs_x, smem + hbuf * H::HBUF + (wid + 8 * q) * 1024, a, (unsigned)chunk * 128u);
-  };
-  const int nchunks_all = p.Cin >> 6;
-  const int step_end = kt_begin + KT;          // first step (global index) that does not exist
-  const bool stg = p.pp_stagger != 0;
-
-  // one K step: compute (chunk, tap) from halo buffer hb and weight slot ws while staging the weights of step + 2 into
-  // slot ws2 and, during the first nhq taps, one halo piece of chunk + 1 into the other halo buffer
-  auto step = [&](int s_glob, int tap, int hb, int ws, int ws2, pp_u32x4 (&xc)[MI][2], pp_u32x4 (&xp)[MI][2]) {
-    constexpr int NB = NI + MI;
-    const int chunk = s_glob / 9;               // (scalar division by a constant)
-    // what this step stages
-    const int s2 = s_glob + 2;
-    Step st2;
-    st2.chunk = s2 / 9;
-    st2.tap = s2 - st2.chunk * 9;
-    const int live_w = s2 < step_end ? 1 : 0;
-    const int live_h = ((chunk + 1) * 9 < step_end && chunk + 1 < nchunks_all) ? 1 : 0;
-    // operand addresses of this tap
-    const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
-    const int tapoff = ky * HW + kx;
-    unsigned xa0[MI];
-#pragma unroll
-    for (int j = 0; j < MI; ++j) {
-      const unsigned hp = (unsigned)(xhp[j] + tapoff);
-      xa0[j] = lds0 + (unsigned)(hb * H::HBUF) + (hp << 7) + (((qsel ^ hp) & 7u) << 4);
-    }
-    const unsigned wb0 = lds0 + (unsigned)(H::W_BASE + ws * H::WBYTES) + w_base + fch0;
-    const unsigned wb1 = lds0 + (unsigned)(H::W_BASE + ws * H::WBYTES) + w_base + fch1;
-    auto rd_block = [&](auto bc) {
-      constexpr int bi = decltype(bc)::value;
-      if (lab & 2) return;
-      if constexpr (bi == 0) {
-        w8[0][0] = pp_lds_read128<0>(wb0);
-        w8[0][1] = pp_lds_read128<0>(wb1);
-      } else if constexpr (bi <= MI) {
-        xc[bi - 1][0] = pp_lds_read128<0>(xa0[bi - 1]);
-        xc[bi - 1][1] = pp_lds_read128<0>(xa0[bi - 1] ^ 64u);
-      } else {
-        w8[bi - MI][0] = pp_lds_read128<(bi - MI) * 2048>(wb0);
-        w8[bi - MI][1] = pp_lds_read128<(bi - MI) * 2048>(wb1);
-      }
-    };
-    rd_block(std::integral_constant<int, 0>{});
-    rd_block(std::integral_constant<int, 1>{});
-    __builtin_amdgcn_sched_barrier(0);
-    pp_static_for<0, MI * NI>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      if constexpr (m < MI) {
-        mfma2(acc[NI - 1][m], w8[NI - 1], xp[m]);          // held back from the previous step
-      } else {
-        constexpr int i = (m - MI) / MI, j = (m - MI) % MI;
-        constexpr int issued = (2 + m) < NB ? (2 + m) : NB;
-        constexpr int need = i == 0 ? 1 + j : (j == 0 ? MI + i : -1);
-        if constexpr (need >= 0) {
-          std::integral_constant<int, 2 * (issued - need - 1)> cnt;
-          if constexpr (i == 0) wait_block(cnt, xc[j]); else wait_block(cnt, w8[i]);
-          if constexpr (i == 0 && j == 0) wait_block(cnt, w8[0]);
-        }
-        mfma2(acc[i][j], w8[i], xc[j]);
-      }
-      if constexpr (2 + m < NB) rd_block(std::integral_constant<int, 2 + m>{});
-      // staging: weight pieces behind MFMAs 4, 6, (8) and one halo piece behind MFMA 10 for waves 0-3; their SIMD partners
-      // (waves 4-7) one MFMA later each, so that the two waves of a SIMD do not stall on their LDS-DMA issue together
-      if constexpr (m == MI) { if (g == 0 || !stg) stage_w(std::integral_constant<int, 0>{}, ws2, st2, live_w); }
-      if constexpr (m == MI + 1) { if (g == 1 && stg) stage_w(std::integral_constant<int, 0>{}, ws2, st2, live_w); }
-      if constexpr (m == MI + 2) { if (g == 0 || !stg) stage_w(std::integral_constant<int, 1>{}, ws2, st2, live_w); }
-      if constexpr (m == MI + 3) { if (g == 1 && stg) stage_w(std::integral_constant<int, 1>{}, ws2, st2, live_w); }
-      if constexpr (m == MI + 4) { if (g == 0) stage_w(std::integral_constant<int, 2>{}, ws2, st2, live_w); }
-      if constexpr (m == MI + 6 || m == MI + 7) {
-        if (tap < nhq && (stg ? g == (m - MI - 6) : m == MI + 6)) {
-          switch (tap) {
-            case 0: stage_h(std::integral_constant<int, 0>{}, hb ^ 1, chunk + 1, live_h); break;
-            case 1: stage_h(std::integral_constant<int, 1>{}, hb ^ 1, chunk + 1, live_h); break;
-            case 2: stage_h(std::integral_constant<int, 2>{}, hb ^ 1, chunk + 1, live_h); break;
-            case 3: stage_h(std::integral_constant<int, 3>{}, hb ^ 1, chunk + 1, live_h); break;
-            case 4: stage_h(std::integral_constant<int, 4>{}, hb ^ 1, chunk + 1, live_h); break;
-            case 5: stage_h(std::integral_constant<int, 5>{}, hb ^ 1, chunk + 1, live_h); break;
-            default: stage_h(std::integral_constant<int, 6>{}, hb ^ 1, chunk + 1, live_h); break;
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    pp_wait_lgkm0();
+  auto dma = [&](__amdgpu_buffer_rsrc_t rs, char* dst, unsigned voff, unsigned soff) {
+    if constexpr ((LABL & 1) == 0) lds_dma16(rs, dst, voff, soff);
   };
 
   // ---- prologue: halo of the first chunk, weights of steps 0 and 1 ----
-  pp_static_for<0, NHQ>([&](auto qc) {
-    if (decltype(qc)::value < nhq) stage_h(qc, 0, chunk0, 1);
-  });
-  {
-    Step s0{0, chunk0}, s1{1, chunk0};
-    stage_w(std::integral_constant<int, 0>{}, 0, s0, 1);
-    stage_w(std::integral_constant<int, 1>{}, 0, s0, 1);
-    if (g == 0) stage_w(std::integral_constant<int, 2>{}, 0, s0, 1);
-    stage_w(std::integral_constant<int, 0>{}, 1, s1, 1);
-    stage_w(std::integral_constant<int, 1>{}, 1, s1, 1);
-    if (g == 0) stage_w(std::integral_constant<int, 2>{}, 1, s1, 1);
+  if (!(lab & 32)) {
+    const unsigned kc = (unsigned)chunk0 * 128u;
+#pragma unroll
+    for (int q = 0; q < NHQ; ++q)
+      if (q < nhq) lds_dma16(rs_x, smem + (wid + 8 * q) * 1024, h_off[q], kc);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      char* const dst = smem + H::W_BASE + s * H::WBYTES + wid * 1024;
+      lds_dma16(rs_w, dst, w_off[0], s * cin2 + kc);
+      lds_dma16(rs_w, dst + 8 * 1024, w_off[1], s * cin2 + kc);
+      if (g == 0) lds_dma16(rs_w, dst + 16 * 1024, w_off[2], s * cin2 + kc);
+    }
   }
-  // vmcnt at the head of a step: everything but what the PREVIOUS step issued (its nwq weight pieces + its halo piece)
-  auto wait_head = [&](int prev_halo) {
-    const int n = nwq + prev_halo;
-    if (n == 2) pp_wait_vm<2>(); else if (n == 3) pp_wait_vm<3>(); else pp_wait_vm<4>();
-  };
-  int tap = 0, hb = 0, ws = 0, ws1 = 1, ws2 = 2, s_glob = kt_begin;
-  int prev_halo = 0;                            // the prologue's last issue is a weight set: keep nwq in flight
-  auto one = [&](pp_u32x4 (&xc)[MI][2], pp_u32x4 (&xp)[MI][2]) {
-    wait_head(prev_halo);
-    __builtin_amdgcn_s_barrier();
-    step(s_glob, tap, hb, ws, ws2, xc, xp);
-    prev_halo = tap < nhq ? 1 : 0;
-    ++s_glob;
-    if (++tap == 9) { tap = 0; hb ^= 1; }
-    const int t3 = ws; ws = ws1; ws1 = ws2; ws2 = t3;
-  };
-  int t = 0;
-  in_loop = true;
 #ifdef AF_LAB_ABLATE
   if (lab & 64) st1 = lab_now();
 #endif
-  for (; t + 1 < KT; t += 2) {
-    one(xa8, xb8);
-    one(xb8, xa8);
-  }
-  if (KT & 1) one(xa8, xb8);
+
+  // ---- K loop: chunk by chunk, the nine taps unrolled; one body per wave group ----
+  // Schedule of a step: the held-back MFMAs of the previous step first, the fragment reads two blocks ahead of their
+  // MFMAs; weight pieces of step + 2 behind MFMAs 4, 6, (8) and one halo piece of chunk + 1 (taps 0-6) behind MFMA 10 for
+  // waves 0-3, their SIMD partners (waves 4-7) one MFMA later each, so that the two waves of a SIMD do not stall on their
+  // LDS-DMA issue together.
+  auto chunk_loop = [&](auto gc) {
+    constexpr int G = decltype(gc)::value;
+    constexpr int NWQ = G == 0 ? 3 : 2;         // weight pieces a wave stages per step
+    constexpr int NHT = G == 0 ? 7 : 6;         // taps at which it stages a halo piece
+    char* const wdst = smem + H::W_BASE + wid * 1024;
+    for (int c = 0; c < nch; ++c) {
+      const unsigned kc = (unsigned)(chunk0 + c) * 128u;
+      const int nrec = c + 1 < nch ? (int)0xFFFFFFF0u : 0;          // the pieces of the next chunk: none after the last
+      const __amdgpu_buffer_rsrc_t rs_xn = __builtin_amdgcn_make_buffer_rsrc(xsrc, 0, nrec, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs_wn = __builtin_amdgcn_make_buffer_rsrc(wsrc, 0, nrec, 0x00020000);
+      const unsigned hrd8 = (lds0 + (unsigned)((c & 1) * H::HBUF)) >> 3;   // halo buffer read ...
+      char* const hdst = smem + ((c & 1) ^ 1) * H::HBUF + wid * 1024;       // ... and staged
+      pp_static_for<0, 9>([&](auto tc) {
+        constexpr int TAP = decltype(tc)::value;
+        constexpr int KY = TAP / 3, KX = TAP % 3, WS = TAP % 3, WS2 = (TAP + 2) % 3, T2 = TAP + 2;
+        constexpr int NB = NI + MI;
+        // vmcnt at the head of a step: everything but what the PREVIOUS step issued (its weight pieces + its halo piece)
+        pp_wait_vm<NWQ + (TAP >= 1 && TAP <= NHT ? 1 : 0)>();
+        __builtin_amdgcn_s_barrier();
+        const unsigned ut = hrd8 + KY * hw16 + KX * 16u;
+        unsigned xa0[MI];
+#pragma unroll
+        for (int j = 0; j < MI; ++j) {
+          const unsigned u = xh16[j] + ut;
+          xa0[j] = (u << 3) | ((u ^ qsel16) & 0x70u);
+        }
+        pp_u32x4 xc[MI][2];
+        if constexpr ((LABL & 2) != 0) {
+#pragma unroll
+          for (int j = 0; j < MI; ++j) xc[j][0] = xc[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+        }
+        auto rd_block = [&](auto bc) {
+          constexpr int bi = decltype(bc)::value;
+          if constexpr ((LABL & 2) != 0) {
+          } else if constexpr (bi == 0) {
+            w8[0][0] = pp_lds_read128<WS * H::WBYTES>(wrd0);
+            w8[0][1] = pp_lds_read128<WS * H::WBYTES>(wrd1);
+          } else if constexpr (bi <= MI) {
+            xc[bi - 1][0] = pp_lds_read128<0>(xa0[bi - 1]);
+            xc[bi - 1][1] = pp_lds_read128<0>(xa0[bi - 1] ^ 64u);
+          } else {
+            w8[bi - MI][0] = pp_lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd0);
+            w8[bi - MI][1] = pp_lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd1);
+          }
+        };
+        // weight piece q of step + 2 (the first two taps of the next chunk from tap 7 on)
+        auto stage_w = [&](auto qc) {
+          constexpr int q = decltype(qc)::value;
+          char* const dst = wdst + WS2 * H::WBYTES + 8 * q * 1024;
+          if constexpr (T2 < 9) dma(rs_w, dst, w_off[q], T2 * cin2 + kc);
+          else dma(rs_wn, dst, w_off[q], (T2 - 9) * cin2 + kc + 128u);
+        };
+        auto stage_h = [&]() {
+          if constexpr (TAP < NHT) {
+            if constexpr (TAP < NHQ - 1) dma(rs_xn, hdst + 8 * TAP * 1024, h_off[TAP], kc + 128u);
+            else dma(rs_xn, hdst + hl6, h_off[NHQ - 1], kc + 128u);
+          }
+        };
+        rd_block(std::integral_constant<int, 0>{});
+        rd_block(std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        pp_static_for<0, MI * NI>([&](auto mc) {
+          constexpr int m = decltype(mc)::value;
+          if constexpr (m < MI) {
+            mfma2(acc[NI - 1][m], w8[NI - 1], xp[m]);          // held back from the previous step
+          } else {
+            constexpr int i = (m - MI) / MI, j = (m - MI) % MI;
+            constexpr int issued = (2 + m) < NB ? (2 + m) : NB;
+            constexpr int need = i == 0 ? 1 + j : (j == 0 ? MI + i : -1);
+            if constexpr (need >= 0) {
+              std::integral_constant<int, 2 * (issued - need - 1)> cnt;
+              if constexpr (i == 0 && j == 0) wait_block2(cnt, xc[0], w8[0]);
+              else if constexpr (i == 0) wait_block(cnt, xc[j]);
+              else wait_block(cnt, w8[i]);
+            }
+            mfma2(acc[i][j], w8[i], xc[j]);
+          }
+          if constexpr (2 + m < NB) rd_block(std::integral_constant<int, 2 + m>{});
+          if constexpr (m == MI + G) stage_w(std::integral_constant<int, 0>{});
+          if constexpr (m == MI + 2 + G) stage_w(std::integral_constant<int, 1>{});
+          if constexpr (G == 0 && m == MI + 4) stage_w(std::integral_constant<int, 2>{});
+          if constexpr (m == MI + 6 + G) stage_h();
+          __builtin_amdgcn_sched_barrier(0);
+        });
+        pp_wait_lgkm0();
+#pragma unroll
+        for (int j = 0; j < MI; ++j) xp[j][0] = xc[j][0], xp[j][1] = xc[j][1];
+      });
+    }
+  };
+  if (g == 0) chunk_loop(std::integral_constant<int, 0>{});
+  else chunk_loop(std::integral_constant<int, 1>{});
   pp_wait_vm<0>();
-  if (KT & 1) {
 #pragma unroll
-    for (int j = 0; j < MI; ++j) mfma2(acc[NI - 1][j], w8[NI - 1], xa8[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < MI; ++j) mfma2(acc[NI - 1][j], w8[NI - 1], xb8[j]);
-  }
+  for (int j = 0; j < MI; ++j) mfma2(acc[NI - 1][j], w8[NI - 1], xp[j]);
   __builtin_amdgcn_s_barrier();
 #ifdef AF_LAB_ABLATE
   if (lab & 64) st2 = lab_now();
@@ -1663,7 +1663,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
     if (sum == 12345.678f) reinterpret_cast<float*>(p.out)[tid] = sum;
     return;
   }
-
   const int cl = 4 * (lane >> 4);
   float4 bias_r[NI];
 #pragma unroll
@@ -3092,13 +3091,33 @@ static int launch_conv_gemm_fp8(ConvGemmParams p, hipStream_t stream, const AfGe
   return 0;
 }
 
-static int launch_halo8(const ConvGemmParams& p, hipStream_t stream) {
+template <int LABL> static int launch_halo8_lab(const ConvGemmParams& p, hipStream_t stream) {
   static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv3x3_halo8_kernel), Halo8Cfg::LDS_BYTES)) return rc;
+  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv3x3_halo8_kernel<LABL>), Halo8Cfg::LDS_BYTES))
+    return rc;
   dim3 grid((p.M / 256) * (p.N / 160), 1, p.splitk > 1 ? p.splitk : 1);
-  hipLaunchKernelGGL(conv3x3_halo8_kernel, grid, dim3(512), Halo8Cfg::LDS_BYTES, stream, p);
+  hipLaunchKernelGGL(conv3x3_halo8_kernel<LABL>, grid, dim3(512), Halo8Cfg::LDS_BYTES, stream, p);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
+}
+static int launch_halo8(const ConvGemmParams& p, hipStream_t stream) {
+  if (p.Cin % 64 != 0 || (p.Cin / 64) % (p.splitk > 1 ? p.splitk : 1) != 0) {   // the K loop walks whole chunks
+    af_set_error_msg("conv_gemm: halo kernel needs K slices of whole 64-channel chunks (Cin=%d splitk=%d)", p.Cin, p.splitk);
+    return -1;
+  }
+#ifdef AF_LAB_ABLATE
+  switch ((p.fast_taps >> 4) & 7) {   // the in-loop phase removals are template bits of the lab kernel
+    case 1: return launch_halo8_lab<1>(p, stream);
+    case 2: return launch_halo8_lab<2>(p, stream);
+    case 3: return launch_halo8_lab<3>(p, stream);
+    case 4: return launch_halo8_lab<4>(p, stream);
+    case 5: return launch_halo8_lab<5>(p, stream);
+    case 6: return launch_halo8_lab<6>(p, stream);
+    case 7: return launch_halo8_lab<7>(p, stream);
+    default: break;
+  }
+#endif
+  return launch_halo8_lab<0>(p, stream);
 }
 
 template <typename T, int TW, int BN> static int launch_halo(const ConvGemmParams& p, hipStream_t stream) {

@@ -85,10 +85,8 @@ struct AfKnobs {
   int gemm_splitk;          // AF_GEMM_SPLITK          >= 1: force the number of K slices
   int gemm_groupm;          // AF_GEMM_GROUPM          >= 1: force the grouped tile order
   int gemm_dma;             // AF_GEMM_DMA             0 / 1: force register / LDS-DMA staging in the four-wave kernel
-  int pp_direct;            // AF_PP_DIRECT            0 / 1: force the LDS / direct epilogue of the ping-pong kernel
   int attn_ring;            // AF_ATTN_RING            bit 0: dh-40, bit 1: dh-80 (>= 256 keys; bit 2: any key count) bf16 attention on the eight-wave ring kernel
   int gn_small;             // AF_GN_SMALL             0 = no single-launch GroupNorm for small maps
-  int conv_tap_inner;       // AF_CONV_TAP_INNER       0 = ping-pong convs walk K tap-outermost (the round-1 order)
   int ln_fuse;              // AF_LN_FUSE              0 = stand-alone LayerNorm kernels in front of the transformer GEMMs
   int geglu_rowpanel;       // AF_GEGLU_ROWPANEL       row-panel kernel (K = 320, >= 32768 rows): 0 = never, 1 = GEGLU only, 2 = the plain
                             //                         GEMMs of the 64x64-level transformers too, 3 = and its K = 640 form (GEGLU and
@@ -96,12 +94,10 @@ struct AfKnobs {
                             //                         ([>= 4096, 1280] -> 1280 of the 16x16 level)
   int conv_halo8;           // AF_CONV_HALO8           bit 0: 3x3 / stride-1 convs of the 64x64 / 32x32 / 16x16 maps on conv3x3_halo8_kernel,
                             //                         bit 1: those of the 8x8 maps on conv3x3_s8_kernel; 0 = all on the gathering kernel
-  int conv_fast_taps;       // AF_CONV_FAST_TAPS       0 = ping-pong convs recompute every tap's bounds check in the staging phase
-  int pp_stagger;           // AF_PP_STAGGER           merged schedule: 1 = the two wave groups issue their LDS-DMA pieces behind alternate MFMAs (conv3x3_halo8_kernel always does)
+  int ablate;               // AF_ABLATE               lab builds only (-DAF_LAB_ABLATE, scripts/lab/ablate_conv.sh): timing ablations of the
+                            //                         eight-wave kernels, WRONG results; bits 4.. (16, 32, 64, ...) name the phase removed
   int gn_producer;          // AF_GN_PRODUCER          0 = GroupNorm always runs its own statistics pass (no sums from the producer convolution)
   int conv_up_phase4;       // AF_CONV_UP_PHASE4       0 = upsampled 3x3 convolutions gather all nine taps from the upsampled map
-  int pp_sched;             // AF_PP_SCHED             eight-wave kernel: 0 = round-1 compute phase (two K halves, a full LDS drain
-                            //                         after each), 1 = block-ordered compute phase, 2 = merged (no staging phase)
   int attn_short;           // AF_ATTN_SHORT           0 = cross-attention (<= 96 keys) stays on the flash kernels
   int gemm_m128;            // AF_GEMM_M128            0 = no 128 x 160 tile GEMM for the few-row plain GEMMs (16x16 level)
   int small_m_tile64;       // AF_SMALL_M_TILE64       0 = GEMMs with <= 1024 rows and K <= 2048 keep the cost model's tile / K slices
@@ -289,16 +285,14 @@ struct ConvGemmParams {
   // partial sums [ln_parts_n][M][2] and the kernel finalises (mu, rstd) of its rows itself: mu = sum * ln_inv_count, ...
   int ln_parts_n;
   float ln_inv_count, ln_eps;
-  int k_tap_inner;        // ping-pong kernel (set by the launcher): K walked as (channel chunk, tap) instead of (tap, chunk)
-  int pp_epilogue;        // ping-pong kernel (set by the launcher): 0 = direct for GEGLU / split-K slabs and LDS
-                          // otherwise, 1 = always through LDS, 2 = always direct
+  int epi_direct;         // eight-wave kernels (set by the launcher): 1 = always the direct epilogue (GroupNorm statistics,
+                          // phase-decomposed launches); 0 = direct for GEGLU / split-K slabs, through LDS otherwise
   // fp8 (OCP e4m3) operands on the block-scaled MFMA (ping-pong kernel only; bf16 in every other respect: bias,
   // residual, output).  src = fp8 NHWC (ldc, src_batch_stride in BYTES), W = fp8 [Wrows][ldw] with K laid out in 64-channel
   // UNITS, unit u = (channel chunk u / taps, tap u % taps), zero-padded to a multiple of 128 = K; Cin = real channel
   // count (multiple of 64).  Scales are powers of two applied by the MFMA itself (E8M0): w_scale[n] per output channel,
   // x_scale_e8 for the whole activation tensor (the producer multiplied by 2^(127 - x_scale_e8)).
-  int pp_stagger;         // merged schedule (set by the launcher): the wave groups stage behind alternate MFMAs
-  int fast_taps;          // ping-pong kernel (set by the launcher): per-piece tap validity masks instead of per-tap bounds arithmetic
+  int ablate;             // lab builds (set by the launcher from the ablate knob): timing ablation bits, 0 in the library
   int fp8;
   const unsigned char* w_scale;
   int x_scale_e8;

@@ -593,12 +593,13 @@ __device__ __forceinline__ void pp_epilogue(const ConvGemmParams& p, f32x4 (&acc
   const T* __restrict__ res = reinterpret_cast<const T*>(p.residual);
   const T* __restrict__ rowb = reinterpret_cast<const T*>(p.rowbias);
   float* slab = p.splitk > 1 ? reinterpret_cast<float*>(p.ws) + (long)zk * p.M * p.N : nullptr;
-  if (LNMODE == 2 || p.pp_epilogue == 2 || (p.pp_epilogue == 0 && (geglu || slab))) {
+  if (LNMODE == 2 || p.epi_direct || geglu || slab) {
     // Direct epilogue: every lane stores its 4 consecutive output channels of a pixel straight from the accumulator
     // (8-byte stores, four lanes covering a 32-byte run of the row; fp32 split-K slabs: 16-byte stores).  No LDS pass,
     // no workgroup barriers; the time-bias / residual quads of a row group are fetched before its first store.
     // Measured against the two-pass LDS transposition below: GEGLU -4...-6 %, split-K slabs -2...-5 %, everything else
-    // within +-1 %, so it is the default for those two and AF_PP_DIRECT = 0 / 1 forces either.
+    // within +-1 % (round 4, forcing either for every launch: UNet forward 14.694 / 14.709 ms against 14.689-14.723), so it
+    // is taken for those two and where the launcher asks for it (ConvGemmParams::epi_direct).
     const int nblk = geglu ? NI / 2 : NI;
     const int cbase = ncol0 + g * HNo + cl;
     // bf16 outputs leave through a WAVE-PRIVATE LDS tile (64 rows x HNo columns, no barriers) as 16-byte stores of whole
@@ -832,13 +833,17 @@ typedef __attribute__((ext_vector_type(4))) int pp_i32x4;
 // that channel counts that are multiples of 64 but not of 128 (320, 960) waste nothing: chunks 0-3 of an LDS row come
 // from unit 2t, chunks 4-7 from unit 2t + 1, each lane of the staging waves walks the units of ITS half.
 //
-// SCHED: 0 = the round-1 compute phase (two K halves, a full LDS drain after each); 1 = block-ordered compute phase (see
-// "FP8 fragments and compute phase" below), staging still in its own phase; 2 = MERGED: no staging phase at all -- every
-// wave stages its share of tile t + 2 (one LDS-DMA piece behind every other MFMA of tile t) while it computes, ONE barrier
-// per K tile, and both waves of a SIMD always have MFMAs to offer the matrix pipe.
+// SCHED: 0 = PHASED, the round-1 schedule: the two wave groups alternate between a staging phase and a compute phase (two
+// K halves, a full LDS drain after each); 2 = MERGED: no staging phase at all -- every wave stages its share of tile t + 2
+// (one LDS-DMA piece behind every other MFMA of tile t) while it computes, ONE barrier per K tile, and both waves of a SIMD
+// always have MFMAs to offer the matrix pipe.  (SCHED 1, a block-ordered phased schedule, was retired: DESIGN section 5.)
+// Gathers address their taps through per-pixel tap-validity masks on the merged schedule (no upsampling, at most 31 taps:
+// launch_pp) and through per-tap bounds arithmetic on the phased one.
 template <int BN, bool GATHER, int LNMODE = 0, bool FP8 = false, int SCHED = FP8 ? 2 : 0>
 __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams p) {
-  constexpr bool NS = SCHED >= 1, MG = SCHED == 2;
+  static_assert(SCHED == 0 || SCHED == 2, "schedules: 0 phased, 2 merged");
+  constexpr bool MG = SCHED == 2;
+  constexpr bool FT = GATHER && MG;        // tap masks
   static_assert(MG || !FP8, "fp8 operands exist on the merged schedule only");
   using C = PpCfg<BN>;
   typedef bf16 T;
@@ -886,9 +891,8 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
   const unsigned lchunk = (FP8 ? (dchunk & 3u) : dchunk) * 16u;     // ... its byte offset inside the 64-channel run
   const int HoWo = p.Ho * p.Wo;
   const unsigned ldcb = (unsigned)p.ldc * XE;
-  const bool fast_taps = GATHER && ((p.up == 0 && p.ks * p.ks <= 31 && (p.fast_taps & 1)) || MG);
   unsigned x_off[NXM];
-  int x_yx[GATHER ? NXM : 1];   // (iy0 << 16) | (ix0 & 0xffff): input coordinate of tap (0,0); fast taps: validity mask
+  int x_yx[GATHER ? NXM : 1];   // tap masks: validity mask; else (iy0 << 16) | (ix0 & 0xffff): input coordinate of tap (0,0)
   pp_static_for<0, NXM>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
     const int piece = g == 0 ? wq + 4 * q : XP0 + wq + 4 * q;
@@ -912,7 +916,7 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     unsigned off = (unsigned)((long)b * p.src_batch_stride * XE) + lchunk;
     if constexpr (GATHER) {
       const int y0 = oy * p.stride - pad_y, x0 = ox * p.stride - pad_x;
-      if (fast_taps) {
+      if constexpr (FT) {
         // no upsample: the address of tap (ky, kx) is the tap-(0,0) address plus a wave-uniform delta, and whether the tap
         // falls inside the image is one bit of a mask made here (row bits x column bits) -- the staging phase then spends
         // 4 vector instructions per piece instead of 12, issue slots it competes for with the partner wave's MFMAs
@@ -940,10 +944,10 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     const int n = n0 + ((g == 0 ? 0 : WP0) + wq + 4 * q) * 8 + srow;
     w_off[q] = n < p.Wrows ? (unsigned)(((long)ph4 * p.Wrows + n) * p.ldw * XE) + dchunk * 16u : 0xFFFFFFFFu;
   }
-  // K order.  The sum over (tap, channel chunk) can be walked either way; with the TAP innermost (k_tap_inner) the nine
-  // taps of a channel chunk re-read the same few input rows back to back, so eight of nine gathers hit the XCD's L2
-  // instead of each tap streaming the whole input slice again (PMC: 225 MB fetched per launch against ~50 MB of input
-  // with the tap outermost).  The weight tile of (tap, chunk) is the 128-byte run at column tap * Cin + c0 either way.
+  // K order: (channel chunk, tap), the TAP innermost.  The nine taps of a channel chunk re-read the same few input rows back
+  // to back, so eight of nine gathers hit the XCD's L2 instead of each tap streaming the whole input slice again (PMC: 225 MB
+  // fetched per launch against ~50 MB of input with the tap outermost, the round-1 order).  The weight tile of (tap, chunk)
+  // is the 128-byte run at column tap * Cin + c0.  (ks = 1: the plain K walk.)
   // K-walk state of the NEXT tile this wave stages: a plain struct handed around BY VALUE (as by-reference lambda captures
   // mutated inside the merged schedule's compute phase these scalars ended up in scratch, came back as VGPRs, and every
   // LDS-DMA grew a waterfall loop around its scalar offset)
@@ -954,20 +958,13 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
   KWalk kw;
   kw.ktile = kt_begin;
   kw.u_tap = 0; kw.u_c0 = 0;
-  if (p.k_tap_inner) {
-    const int taps = p.ks * p.ks;
-    const int cc = kt_begin / taps, tap = kt_begin - cc * taps;
+  const int taps8 = p.ks * p.ks;
+  {
+    const int cc = kt_begin / taps8, tap = kt_begin - cc * taps8;
     kw.c0 = cc * 64;
     kw.ky = tap / p.ks;
     kw.kx = tap - kw.ky * p.ks;
-  } else {
-    const int k0 = kt_begin * 64;
-    const int tap = k0 / p.Cin;
-    kw.c0 = k0 - tap * p.Cin;
-    kw.ky = tap / p.ks;
-    kw.kx = tap - kw.ky * p.ks;
   }
-  const int taps8 = p.ks * p.ks;
   const int adv_q = 2 / taps8, adv_r = 2 - adv_q * taps8;   // fp8: two units further = adv_q chunks + adv_r taps
   if constexpr (FP8) {
     const int u = 2 * kt_begin + (int)(dchunk >> 2);
@@ -981,28 +978,23 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     unsigned c0b, k0b;      // scalar byte offsets of the activation channel chunk / the weight K tile
     int live;               // merged schedule: the tile exists (pieces past the K range are issued out of bounds: no
                             // memory traffic, zeros into a slot nobody reads, the vmcnt counts stay fixed)
-    int tapbit;             // bf16 fast taps: mask bit of the tap, byte delta of its pixel
+    int tapbit;             // bf16 tap masks: mask bit of the tap, byte delta of its pixel
     unsigned delta;
-    int u_ok;               // fp8 fast taps (per lane): unit inside K, byte delta of its tap + channel offset
+    int u_ok;               // fp8 tap masks (per lane): unit inside K, byte delta of its tap + channel offset
     unsigned u_delta;
-    int ky, kx, u_tap, u_c0;  // copies for the generic (per-tap bounds arithmetic) address path
+    int ky, kx, u_tap, u_c0;  // copies for the per-tap bounds arithmetic (phased gathers) / the fp8 unit walk
   };
-  auto x_addr = [&](auto qc, auto ftc, const StageCtx& sc) -> unsigned {
+  auto x_addr = [&](auto qc, const StageCtx& sc) -> unsigned {
     constexpr int q = decltype(qc)::value;
-    constexpr bool FT = decltype(ftc)::value;   // fast taps (compile-time here: one uniform branch per stage() call, not per piece)
     if constexpr (FP8) {
       if constexpr (GATHER) {
-        if constexpr (FT) return ((x_yx[q] >> sc.u_tap) & sc.u_ok) ? x_off[q] + sc.u_delta : 0xFFFFFFFFu;
-        const int kyl = p.ks == 3 ? (sc.u_tap * 11) >> 5 : 0, kxl = p.ks == 3 ? sc.u_tap - 3 * kyl : 0;
-        const int iy = (x_yx[q] >> 16) + kyl, ix = ((x_yx[q] << 16) >> 16) + kxl;
-        const bool ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi && sc.u_c0 < p.Cin;
-        const unsigned pix = (unsigned)((iy >> p.up) * p.Ws + (ix >> p.up));
-        return ok ? x_off[q] + pix * ldcb + (unsigned)sc.u_c0 : 0xFFFFFFFFu;
+        return ((x_yx[q] >> sc.u_tap) & sc.u_ok) ? x_off[q] + sc.u_delta : 0xFFFFFFFFu;   // (fp8: merged, so tap masks)
       } else {
         return (sc.u_c0 < p.Cin && x_off[q] != 0xFFFFFFFFu) ? x_off[q] + (unsigned)sc.u_c0 : 0xFFFFFFFFu;
       }
+    } else if constexpr (FT) {
+      return (x_yx[q] & sc.tapbit) ? x_off[q] + sc.delta : 0xFFFFFFFFu;
     } else if constexpr (GATHER) {
-      if constexpr (FT) return (x_yx[q] & sc.tapbit) ? x_off[q] + sc.delta : 0xFFFFFFFFu;
       const int iy = (x_yx[q] >> 16) + sc.ky, ix = ((x_yx[q] << 16) >> 16) + sc.kx;
       const bool ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
       const unsigned pix = (unsigned)((iy >> p.up) * p.Ws + (ix >> p.up));
@@ -1012,13 +1004,13 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     }
   };
   // staging of one K tile = stage_begin (wave-uniform / per-lane tap state), one stage_piece per LDS-DMA piece, stage_end
-  // (advance to the next tile).  The phased schedules run the three back to back (stage); the merged one spreads the
+  // (advance to the next tile).  The phased schedule runs the three back to back (stage); the merged one spreads the
   // pieces over the compute phase.
   auto stage_begin = [&](const KWalk& k) -> StageCtx {
     StageCtx sc;
     sc.tapbit = 0; sc.delta = 0u; sc.u_ok = 0; sc.u_delta = 0u;
     sc.ky = k.ky; sc.kx = k.kx; sc.u_tap = k.u_tap; sc.u_c0 = k.u_c0;
-    if (fast_taps) {
+    if constexpr (FT) {
       if constexpr (FP8) {
         const int kyl = p.ks == 3 ? (k.u_tap * 11) >> 5 : 0, kxl = p.ks == 3 ? k.u_tap - 3 * kyl : 0;
         sc.u_ok = k.u_c0 < p.Cin ? 1 : 0;
@@ -1026,24 +1018,24 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
       } else {
         sc.tapbit = 1 << (k.ky * p.ks + k.kx);
 #ifdef AF_LAB_ABLATE
-        if ((p.fast_taps & 0x100) && (k.ky | k.kx)) sc.tapbit = 0;   // only tap (0,0) fetches activations
+        if ((p.ablate & 0x100) && (k.ky | k.kx)) sc.tapbit = 0;   // only tap (0,0) fetches activations
 #endif
         sc.delta = (unsigned)(k.ky * p.Ws + k.kx) * ldcb;
       }
     }
     sc.c0b = FP8 ? 0u : (unsigned)k.c0 * 2u;
-    sc.k0b = (!FP8 && p.k_tap_inner) ? (unsigned)((k.ky * p.ks + k.kx) * p.Cin + k.c0) * 2u : (unsigned)k.ktile * 128u;
+    sc.k0b = FP8 ? (unsigned)k.ktile * 128u : (unsigned)((k.ky * p.ks + k.kx) * p.Cin + k.c0) * 2u;
     sc.live = (!MG || k.ktile < kt_begin + KT) ? 1 : 0;
     return sc;
   };
-  auto stage_piece = [&](auto qc, auto ftc, char* base, const StageCtx& sc) {
+  auto stage_piece = [&](auto qc, char* base, const StageCtx& sc) {
     constexpr int q = decltype(qc)::value;
     auto fix = [&](unsigned a) -> unsigned { if constexpr (MG) return sc.live ? a : 0xFFFFFFFFu; else return a; };
     if (g == 0) {
-      if constexpr (q < NX0) lds_dma16(rs_x, base + (wq + 4 * q) * 1024, fix(x_addr(qc, ftc, sc)), sc.c0b);
+      if constexpr (q < NX0) lds_dma16(rs_x, base + (wq + 4 * q) * 1024, fix(x_addr(qc, sc)), sc.c0b);
       else if constexpr (q < NP0) lds_dma16(rs_w, base + XBYTES + (wq + 4 * (q - NX0)) * 1024, fix(w_off[q - NX0]), sc.k0b);
     } else {
-      if constexpr (q < NX1) lds_dma16(rs_x, base + (XP0 + wq + 4 * q) * 1024, fix(x_addr(qc, ftc, sc)), sc.c0b);
+      if constexpr (q < NX1) lds_dma16(rs_x, base + (XP0 + wq + 4 * q) * 1024, fix(x_addr(qc, sc)), sc.c0b);
       else if constexpr (q < NP1) lds_dma16(rs_w, base + XBYTES + (WP0 + wq + 4 * (q - NX1)) * 1024, fix(w_off[q - NX1]), sc.k0b);
     }
   };
@@ -1053,34 +1045,18 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
       k.u_tap += adv_r;
       k.u_c0 += 64 * adv_q;
       if (k.u_tap >= taps8) { k.u_tap -= taps8; k.u_c0 += 64; }
-    } else if (p.k_tap_inner) {
-      if (++k.kx >= p.ks) {
-        k.kx = 0;
-        if (++k.ky >= p.ks) { k.ky = 0; k.c0 += 64; }
-      }
-    } else {
-      k.c0 += 64;
-      if (k.c0 >= p.Cin) {
-        k.c0 = 0;
-        if (++k.kx >= p.ks) { k.kx = 0; ++k.ky; }
-      }
+    } else if (++k.kx >= p.ks) {
+      k.kx = 0;
+      if (++k.ky >= p.ks) { k.ky = 0; k.c0 += 64; }
     }
     return k;
   };
   auto stage = [&](int slot_off) {
     const StageCtx sc = stage_begin(kw);
     char* base = smem + slot_off;
-    auto issue = [&](auto ftc) { pp_static_for<0, NPMAX>([&](auto qc) { stage_piece(qc, ftc, base, sc); }); };
-    if constexpr (GATHER && MG) {
-      issue(std::true_type{});
-    } else if constexpr (GATHER) {
-      if (fast_taps) issue(std::true_type{}); else issue(std::false_type{});
-    } else {
-      issue(std::false_type{});
-    }
+    pp_static_for<0, NPMAX>([&](auto qc) { stage_piece(qc, base, sc); });
     kw = kw_next(kw);
   };
-  auto wait_keep1 = [&]() { if (g == 0) pp_wait_vm<NP0>(); else pp_wait_vm<NP1>(); };
 
   // ---- fragments: row (lane & 15) of a 16-row block, chunk ((lane >> 4) + 4 u) ^ (row & 7), u = K half ----
   const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)((__attribute__((address_space(3))) char*)smem);
@@ -1128,7 +1104,7 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
       if (p.bias && p.splitk <= 1) bias_r[i] = *reinterpret_cast<const float4*>(p.bias + n0 + g * C::HN + i * 16 + cl);
     }
   };
-  if constexpr (!NS) load_bias();   // (block-ordered schedule: 104 fragment registers in the loop; the bias is fetched after it)
+  if constexpr (!MG) load_bias();   // (merged schedule: 104 fragment registers in the loop; the bias is fetched after it)
 
   // LayerNorm consumer: column sums of W * gamma for this lane's channels and mu / rstd of its four rows
   float4 ln_cs[LNMODE == 1 ? NI : 1];
@@ -1146,17 +1122,17 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     }
   }
 
-  // ---- FP8 fragments and compute phase ----
+  // ---- merged schedule: fragments and compute phase (bf16 and fp8) ----
   // Order of a tile's 20 (16) MFMAs: weight block outermost, and the LAST weight block's four MFMAs are held back to the
   // head of the next tile's compute phase, where they cover the latency of that tile's first fragment reads (nothing of
   // a tile can be read before the barrier that opens its phase).  They need the previous tile's activation fragments, so
   // those are double-buffered (xa8 / xb8 alternate per tile).  Reads are issued in the order W0 X0 X1 X2 X3 W1 .. W(NI-1):
   // two blocks up front, then one block (two ds_read_b128) behind each MFMA; every MFMA waits with a counted lgkmcnt for
   // exactly the blocks it needs (LDS reads return in order).
-  pp_u32x4 w8[NS ? NI : 1][2], xa8[NS ? MI : 1][2], xb8[NS ? MI : 1][2];
+  pp_u32x4 w8[MG ? NI : 1][2], xa8[MG ? MI : 1][2], xb8[MG ? MI : 1][2];
   int wsc8[FP8 ? NI : 1];
   int xsc8 = p.x_scale_e8;
-  if constexpr (NS && !FP8) {
+  if constexpr (MG && !FP8) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
@@ -1191,17 +1167,17 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     constexpr int n = decltype(nc)::value;
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
   };
-  // (ftc / stage_off: merged schedule only -- the LDS-DMA pieces of tile t + 2 go out one behind every other MFMA)
+  // (stage_off: the LDS-DMA pieces of tile t + 2 go out one behind every other MFMA)
   // Timing ablations (a separate lab build with -DAF_LAB_ABLATE, scripts/lab/ablate_conv.sh; results are WRONG): bits
-  // 4.. of the conv_fast_taps knob: 0x10 no LDS-DMA in the loop, 0x20 no fragment reads, 0x40 no MFMAs, 0x100 see above
+  // 4.. of the ablate knob: 0x10 no LDS-DMA in the loop, 0x20 no fragment reads, 0x40 no MFMAs, 0x100 see above
 #ifdef AF_LAB_ABLATE
-  const int lab = p.fast_taps >> 4;
+  const int lab = p.ablate >> 4;
 #else
   constexpr int lab = 0;
 #endif
-  auto cphase8 = [&](int slot_off, pp_u32x4 (&xc)[NS ? MI : 1][2], pp_u32x4 (&xp)[NS ? MI : 1][2], auto ftc, int stage_off,
+  auto cphase8 = [&](int slot_off, pp_u32x4 (&xc)[MG ? MI : 1][2], pp_u32x4 (&xp)[MG ? MI : 1][2], int stage_off,
                      const StageCtx& sc) {
-    if constexpr (NS) {
+    if constexpr (MG) {
       constexpr int NB = NI + MI;
       char* sbase = smem + stage_off;
       const unsigned b0 = lds0 + (unsigned)slot_off + fch0, b1 = lds0 + (unsigned)slot_off + fch1;
@@ -1238,15 +1214,13 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
           if (!(lab & 4)) mfma8(acc[i][j], w8[i], xc[j], wsc8[FP8 ? i : 0]);
         }
         if constexpr (2 + m < NB) rd_block(std::integral_constant<int, 2 + m>{});
-        if constexpr (MG && m >= MI && (m - MI) / 2 < NPMAX) {
+        if constexpr (m >= MI && (m - MI) / 2 < NPMAX) {
           // (the two waves of a SIMD issue their pieces behind alternate MFMAs: group 0 behind the even ones, group 1 odd)
-          if (!(lab & 1) && (g == ((m - MI) & 1) || !p.pp_stagger)) {
-            if (p.pp_stagger || ((m - MI) & 1) == 0) stage_piece(std::integral_constant<int, (m - MI) / 2>{}, ftc, sbase, sc);
-          }
+          if (!(lab & 1) && g == ((m - MI) & 1)) stage_piece(std::integral_constant<int, (m - MI) / 2>{}, sbase, sc);
         }
         __builtin_amdgcn_sched_barrier(0);
       });
-      static_assert(!MG || MI + 2 * (NPMAX - 1) + 1 < MI * NI, "merged schedule: a staging slot behind an MFMA for every piece");
+      static_assert(MI + 2 * (NPMAX - 1) + 1 < MI * NI, "merged schedule: a staging slot behind an MFMA for every piece");
       pp_wait_lgkm0();       // every read of the tile is back (the last weight block included)
     }
   };
@@ -1261,9 +1235,9 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
     auto tile = [&](auto& xc, auto& xp) {
       if (g == 0) pp_wait_vm<NP0>(); else pp_wait_vm<NP1>();
       __builtin_amdgcn_s_barrier();
-      // (gathers: fast taps only -- the launcher sends upsampled convolutions to the phased schedule)
+      // (gathers: tap masks only -- the launcher sends upsampled convolutions to the phased schedule)
       const StageCtx sc = stage_begin(kw);
-      cphase8(rd, xc, xp, std::integral_constant<bool, GATHER>{}, w1, sc);
+      cphase8(rd, xc, xp, w1, sc);
       kw = kw_next(kw);
       const int tmp = rd; rd = w0; w0 = w1; w1 = tmp;
     };
@@ -1281,53 +1255,28 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
       for (int j = 0; j < MI; ++j) mfma8(acc[NI - 1][j], w8[NI - 1], xb8[j], wsc8[FP8 ? NI - 1 : 0]);
     }
     __builtin_amdgcn_s_barrier();
-  }
-  // ---- phased schedules, prologue: tile 0 (group 1 also tile 1) in flight; group 1's part of tile 0 landed ----
-  if constexpr (!MG) {
-  stage(0);
-  if (g == 1) {
-    if (KT > 1) { stage(SLOT); wait_keep1(); } else pp_wait_vm<0>();
-  }
-  __builtin_amdgcn_s_barrier();
-  if (g == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one interval behind
-  }
-  auto dphase = [&](int t) {
-    if (g == 0) {
-      if (t + 1 < KT) { stage(w0); wait_keep1(); } else pp_wait_vm<0>();   // own part of tile t landed
-    } else {
-      if (t + 2 < KT) stage(w1);
-    }
-    __builtin_amdgcn_s_barrier();
-  };
-  auto cend = [&](int t) {
-    if (g == 1) { if (t + 2 < KT) wait_keep1(); else pp_wait_vm<0>(); }    // own part of tile t+1 landed
-    __builtin_amdgcn_s_barrier();
-    const int tmp = rd; rd = w0; w0 = w1; w1 = tmp;
-  };
-  if constexpr (MG) {
-  } else if constexpr (NS) {
-    auto tile1 = [&](int t, auto& xc, auto& xp) {
-      dphase(t);
-      __builtin_amdgcn_s_setprio(1);   // (no priorities at all, or the staging phase raised instead: no difference, measured)
-      cphase8(rd, xc, xp, std::false_type{}, 0, StageCtx{});
-      __builtin_amdgcn_s_setprio(0);
-      cend(t);
-    };
-    int t = 0;
-    for (; t + 1 < KT; t += 2) {
-      tile1(t, xa8, xb8);
-      tile1(t + 1, xb8, xa8);
-    }
-    if (KT & 1) tile1(t, xa8, xb8);
-    // the last tile's held-back MFMAs
-    if (KT & 1) {
-#pragma unroll
-      for (int j = 0; j < MI; ++j) mfma8(acc[NI - 1][j], w8[NI - 1], xa8[j], wsc8[FP8 ? NI - 1 : 0]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < MI; ++j) mfma8(acc[NI - 1][j], w8[NI - 1], xb8[j], wsc8[FP8 ? NI - 1 : 0]);
-    }
   } else {
+    // ---- phased schedule, prologue: tile 0 (group 1 also tile 1) in flight; group 1's part of tile 0 landed ----
+    auto wait_keep1 = [&]() { if (g == 0) pp_wait_vm<NP0>(); else pp_wait_vm<NP1>(); };
+    stage(0);
+    if (g == 1) {
+      if (KT > 1) { stage(SLOT); wait_keep1(); } else pp_wait_vm<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+    if (g == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one interval behind
+    auto dphase = [&](int t) {
+      if (g == 0) {
+        if (t + 1 < KT) { stage(w0); wait_keep1(); } else pp_wait_vm<0>();   // own part of tile t landed
+      } else {
+        if (t + 2 < KT) stage(w1);
+      }
+      __builtin_amdgcn_s_barrier();
+    };
+    auto cend = [&](int t) {
+      if (g == 1) { if (t + 2 < KT) wait_keep1(); else pp_wait_vm<0>(); }    // own part of tile t+1 landed
+      __builtin_amdgcn_s_barrier();
+      const int tmp = rd; rd = w0; w0 = w1; w1 = tmp;
+    };
     for (int t = 0; t < KT; ++t) {
       // ---------------- D(t) ----------------
       dphase(t);
@@ -1347,9 +1296,9 @@ __global__ __launch_bounds__(512) void conv_gemm_pp_kernel(const ConvGemmParams 
       for (int j = 0; j < MI; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[i][1]),
                                                             __builtin_bit_cast(bf16x8, xf[j][1]), acc[i][j], 0, 0, 0);
+    if (g == 0) __builtin_amdgcn_s_barrier();
   }
-  if constexpr (!MG) { if (g == 0) __builtin_amdgcn_s_barrier(); }
-  if constexpr (NS) load_bias();
+  if constexpr (MG) load_bias();
 
   pp_epilogue<BN, LNMODE>(p, acc, bias_r, ln_cs, ln_mu, ln_rs, smem, tid, lane, g, wq, m0, n0, tn, zk);
 }
@@ -1428,9 +1377,9 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
   const int kt_per = (KT_all + p.splitk - 1) / p.splitk;
   const int kt_begin = zk * kt_per;
 #ifdef AF_LAB_ABLATE
-  // timing ablations (wrong results; scripts/lab/ablate_conv.sh halo): bits 4.. of the conv_fast_taps knob: 1 / 2 / 4 see
+  // timing ablations (wrong results; scripts/lab/ablate_conv.sh halo): bits 4.. of the ablate knob: 1 / 2 / 4 see
   // LABL, 8 no epilogue, 16 one chunk (nine K steps) only, 32 no prologue staging, 64 time stamps
-  const int lab = p.fast_taps >> 4;
+  const int lab = p.ablate >> 4;
   const int KT = (lab & 16) ? 9 : min(KT_all, kt_begin + kt_per) - kt_begin;
 #else
   constexpr int lab = 0;
@@ -1876,7 +1825,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
   const int cl = 4 * (lane >> 4);
 
 #ifdef AF_LAB_ABLATE
-  const int lab = p.fast_taps >> 4;   // timing ablations (wrong results): 1 no LDS-DMA, 2 no fragment reads, 4 no MFMAs, 8 no epilogue
+  const int lab = p.ablate >> 4;   // timing ablations (wrong results): 1 no LDS-DMA, 2 no fragment reads, 4 no MFMAs, 8 no epilogue
 #else
   constexpr int lab = 0;
 #endif
@@ -2947,7 +2896,7 @@ static void plan_group_m(AfGemmPlan& pl, const ConvGemmParams& p) {
     const int resident = pl.tile >= 4 ? 32 : 32 * ((tbm * tbn >= 128 * 128) ? 2 : 3);
     // activation bytes a column of tiles streams per unit of M: every tap re-reads the input unless the taps of a channel
     // chunk follow each other (LDS halo kernel; ping-pong kernel with the tap innermost: ~1.5x halo rows at stride 1)
-    const bool taps_reuse = pl.halo_tw || (pl.tile >= 4 && p.ks > 1 && (g_af_knobs.conv_tap_inner || p.fp8));
+    const bool taps_reuse = pl.halo_tw || (pl.tile >= 4 && p.ks > 1);
     const double xb = (double)p.M * (p.K / (p.ks * p.ks)) * (taps_reuse ? (p.stride == 1 ? 1.5 : 1.0) : (double)(p.ks * p.ks) / (p.stride * p.stride));
     const double wb = (double)p.N * p.K;
     double bestc = 1e300;
@@ -2985,6 +2934,29 @@ static int launch_cfg(const ConvGemmParams& p, int batch, hipStream_t stream) {
   return use_dma ? launch_cfg2<T, BM, BN, true>(p, batch, stream) : launch_cfg2<T, BM, BN, false>(p, batch, stream);
 }
 
+// The launch fields of ConvGemmParams the kernels read besides the operands, filled in one place once the plan is known:
+// power-of-two shifts of the output map (-1: the kernels divide), the grouped tile order, the forced direct epilogue of the
+// eight-wave kernels (GroupNorm statistics are summed from its transposition tile; the phase-decomposed launch's rows are
+// known to it only) and the lab ablation bits (the phase-decomposed launch is never ablated).
+static void set_launch_fields(ConvGemmParams& p, const AfGemmPlan& pl) {
+  auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
+  p.howo_shift = lg2(p.Ho * p.Wo);
+  p.wo_shift = lg2(p.Wo);
+  p.group_m = pl.group_m > 0 ? pl.group_m : 1;
+  p.epi_direct = (p.gn_stats_out || p.phase4) ? 1 : 0;
+  p.ablate = p.phase4 ? 0 : g_af_knobs.ablate;
+}
+
+// the reduce pass of a sliced-K launch (splitk_reduce_kernel strides over the output: at most 4096 workgroups)
+template <typename T> static int launch_splitk_reduce(const ConvGemmParams& p, hipStream_t stream) {
+  const long nq = (long)p.M * (p.N >> 2);
+  unsigned blocks = (unsigned)((nq + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, stream, p);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
 template <int BN, int LNMODE, bool GATHER, bool FP8, int SCHED>
 static int launch_pp_one(const ConvGemmParams& p, dim3 grid, hipStream_t stream) {
   using C = PpCfg<BN>;
@@ -2994,17 +2966,17 @@ static int launch_pp_one(const ConvGemmParams& p, dim3 grid, hipStream_t stream)
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
-template <int BN, int LNMODE, bool GATHER> static int launch_pp_sched(const ConvGemmParams& p, dim3 grid, hipStream_t stream) {
-  int sched = g_af_knobs.pp_sched;
-  if (sched >= 2 && GATHER && !(p.up == 0 && p.ks * p.ks <= 31)) sched = 1;   // merged gathers exist with tap masks only
-  // GEGLU launches (K = 320 .. 1280, an epilogue of ~1/3 of the workgroup's time that wants its bias and LayerNorm operands
-  // fetched before the loop): the round-1 schedule measures 3-5 % ahead of both newer ones there
-  if (p.epilogue == AF_EPI_GEGLU && g_af_knobs.pp_sched == 2) sched = 0;
-  switch (sched) {
-    case 0: return launch_pp_one<BN, LNMODE, GATHER, false, 0>(p, grid, stream);
-    case 1: return launch_pp_one<BN, LNMODE, GATHER, false, 1>(p, grid, stream);
-    default: return launch_pp_one<BN, LNMODE, GATHER, false, 2>(p, grid, stream);
-  }
+// The schedule, by rule: the phased one (SCHED 0) for GEGLU launches (K = 320 .. 1280, an epilogue of ~1/3 of the workgroup's
+// time that wants its bias and LayerNorm operands fetched before the loop: 3-5 % ahead of the merged one there) and for the
+// gathers the tap masks cannot describe (upsampled, or more than 31 taps: the nine-tap fallback of upsampled convolutions);
+// the merged one (SCHED 2) for everything else.  Only the combinations this reaches are instantiated: GEGLU is planned on
+// the 128-column tile only and never produces LayerNorm statistics.
+template <int BN, int LNMODE, bool GATHER> static int launch_pp_bf16(const ConvGemmParams& p, dim3 grid, hipStream_t stream) {
+  const bool phased = p.epilogue == AF_EPI_GEGLU || (GATHER && !(p.up == 0 && p.ks * p.ks <= 31));
+  if (!phased) return launch_pp_one<BN, LNMODE, GATHER, false, 2>(p, grid, stream);
+  if constexpr (GATHER || (BN == 128 && LNMODE != 2)) return launch_pp_one<BN, LNMODE, GATHER, false, 0>(p, grid, stream);
+  af_set_error_msg("conv_gemm: GEGLU on the ping-pong kernel needs the 128-column tile and no LayerNorm statistics");
+  return -1;
 }
 template <int BN> static int launch_pp(const ConvGemmParams& p, hipStream_t stream) {
   const bool gather = !(p.ks == 1 && p.pad == 0);
@@ -3015,9 +2987,9 @@ template <int BN> static int launch_pp(const ConvGemmParams& p, hipStream_t stre
       af_set_error_msg("conv_gemm: LayerNorm-fused launch needs a 1x1 GEMM without split-K");
       return -1;
     }
-    return p.ln_stats ? launch_pp_sched<BN, 1, false>(p, grid, stream) : launch_pp_sched<BN, 2, false>(p, grid, stream);
+    return p.ln_stats ? launch_pp_bf16<BN, 1, false>(p, grid, stream) : launch_pp_bf16<BN, 2, false>(p, grid, stream);
   }
-  return gather ? launch_pp_sched<BN, 0, true>(p, grid, stream) : launch_pp_sched<BN, 0, false>(p, grid, stream);
+  return gather ? launch_pp_bf16<BN, 0, true>(p, grid, stream) : launch_pp_bf16<BN, 0, false>(p, grid, stream);
 }
 
 template <int BN> static int launch_pp8(const ConvGemmParams& p, hipStream_t stream) {
@@ -3059,36 +3031,19 @@ static int launch_conv_gemm_fp8(ConvGemmParams p, hipStream_t stream, const AfGe
   af_set_last_plan(pl);
   g_af_plan_counts[10] += 1;
   if (pl.splitk > 1) g_af_plan_counts[7] += 1;
-  {
-    auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
-    p.howo_shift = lg2(p.Ho * p.Wo);
-    p.wo_shift = lg2(p.Wo);
-  }
-  p.group_m = pl.group_m > 0 ? pl.group_m : 1;
-  p.pp_epilogue = g_af_knobs.pp_direct < 0 ? 0 : (g_af_knobs.pp_direct ? 2 : 1);
+  set_launch_fields(p, pl);
   if (p.gn_stats_out) {
     if (!af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
       af_set_error_msg("conv_gemm fp8: GroupNorm partial sums asked of a launch that cannot write them");
       return -1;
     }
-    p.pp_epilogue = 2;
     g_af_plan_counts[14] += 1;
   }
-  p.k_tap_inner = 1;
-  p.fast_taps = g_af_knobs.conv_fast_taps;
-  p.pp_stagger = g_af_knobs.pp_stagger;
   AfProfScope prof(AF_K_PP_FP8, stream, 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K),
                    (double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N * 2.0);
   const int rc = pl.tile == 4 ? launch_pp8<128>(p, stream) : launch_pp8<160>(p, stream);
   if (rc) return rc;
-  if (p.splitk > 1) {
-    const long nq = (long)p.M * (p.N >> 2);
-    unsigned blocks = (unsigned)((nq + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((splitk_reduce_kernel<bf16>), dim3(blocks), dim3(256), 0, stream, p);
-    HIP_CHECK_RET(hipGetLastError());
-  }
-  return 0;
+  return p.splitk > 1 ? launch_splitk_reduce<bf16>(p, stream) : 0;
 }
 
 template <int LABL> static int launch_halo8_lab(const ConvGemmParams& p, hipStream_t stream) {
@@ -3106,7 +3061,7 @@ static int launch_halo8(const ConvGemmParams& p, hipStream_t stream) {
     return -1;
   }
 #ifdef AF_LAB_ABLATE
-  switch ((p.fast_taps >> 4) & 7) {   // the in-loop phase removals are template bits of the lab kernel
+  switch ((p.ablate >> 4) & 7) {   // the in-loop phase removals are template bits of the lab kernel
     case 1: return launch_halo8_lab<1>(p, stream);
     case 2: return launch_halo8_lab<2>(p, stream);
     case 3: return launch_halo8_lab<3>(p, stream);
@@ -3188,7 +3143,6 @@ static bool up_phase4_ok(const ConvGemmParams& p, int batch) {
          (double)4 * p.Wrows * 4 * p.Cin * 2 < 4294967280.0;
 }
 static int launch_up_phase4(ConvGemmParams p, hipStream_t stream) {
-  auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return s; };
   const int bn = p.N % 160 == 0 ? 160 : 128;
   p.W = p.W_up4;
   p.ks = 2; p.up = 0; p.pad = 1;               // (the kernel takes the padding of its phase: 1 - dy, 1 - dx)
@@ -3196,18 +3150,12 @@ static int launch_up_phase4(ConvGemmParams p, hipStream_t stream) {
   p.M /= 4;
   p.K = 4 * p.Cin; p.ldw = p.K;
   p.k_logical = p.K;                           // FLOPs actually spent (4/9 of the nine-tap form)
-  p.phase4 = 1;
+  p.phase4 = 1;                                // (direct epilogue: the wave-private transposition knows the phase's row map)
   p.splitk = 1; p.ws = nullptr;
-  p.howo_shift = lg2(p.Ho * p.Wo);
-  p.wo_shift = lg2(p.Wo);
-  p.pp_epilogue = 2;                           // wave-private transposition: the only epilogue that knows the phase's row map
-  p.k_tap_inner = 1;
-  p.fast_taps = 1;
-  p.pp_stagger = g_af_knobs.pp_stagger;
   AfGemmPlan pl;
   pl.tile = bn == 160 ? 5 : 4; pl.splitk = 1; pl.ws_bytes = 0; pl.halo_tw = 0; pl.group_m = 1;
   plan_group_m(pl, p);
-  p.group_m = pl.group_m > 0 ? pl.group_m : 1;
+  set_launch_fields(p, pl);
   af_set_last_plan(pl);
   g_af_plan_counts[13] += 1;
   AfProfScope prof(bn == 160 ? AF_K_PP160_GATHER : AF_K_PP128, stream, 2.0 * p.M * (double)p.N * p.K * 4,
@@ -3338,24 +3286,14 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
   if (pl.splitk > 1) g_af_plan_counts[7] += 1;
   if (p.ln_stats) g_af_plan_counts[8] += 1;
   if (p.ln_stats_out) g_af_plan_counts[9] += 1;
-  {
-    auto lg2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (v > 0 && (1 << s) == v) ? s : -1; };
-    p.howo_shift = lg2(p.Ho * p.Wo);
-    p.wo_shift = lg2(p.Wo);
-  }
-  p.group_m = pl.group_m > 0 ? pl.group_m : 1;
-  p.pp_epilogue = g_af_knobs.pp_direct < 0 ? 0 : (g_af_knobs.pp_direct ? 2 : 1);
+  set_launch_fields(p, pl);
   if (p.gn_stats_out) {
     if (sizeof(T) != 2 || batch != 1 || !af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
       af_set_error_msg("conv_gemm: GroupNorm partial sums asked of a launch that cannot write them (ask af_conv_gn_stats_ok first)");
       return -1;
     }
-    p.pp_epilogue = 2;   // they are summed from the wave-private transposition tile of the direct epilogue
     g_af_plan_counts[14] += 1;
   }
-  p.k_tap_inner = (p.ks > 1 && g_af_knobs.conv_tap_inner) ? 1 : 0;
-  p.fast_taps = g_af_knobs.conv_fast_taps;
-  p.pp_stagger = g_af_knobs.pp_stagger;
   const int prof_cls = pl.halo_tw == 256 ? AF_K_HALO8
                        : pl.tile == 5 ? ((p.ks == 1 && p.pad == 0) ? AF_K_PP160_PLAIN : AF_K_PP160_GATHER)
                                       : (pl.tile == 4 ? AF_K_PP128 : AF_K_CONV_GEMM);
@@ -3391,70 +3329,36 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
       default: break;
     }
   }
-  if (pl.halo_tw == 8) {
+  if (pl.halo_tw == 8 || pl.halo_tw == 256) {
     if constexpr (sizeof(T) == 2) {
-      rc = af_launch_conv_s8(p, stream);
+      rc = pl.halo_tw == 8 ? af_launch_conv_s8(p, stream) : launch_halo8(p, stream);
     } else {
-      af_set_error_msg("conv_gemm: the 8 x 8-map kernel is bf16 only");
+      af_set_error_msg(pl.halo_tw == 8 ? "conv_gemm: the 8 x 8-map kernel is bf16 only" : "conv_gemm: the eight-wave halo kernel is bf16 only");
       return -1;
     }
-    if (rc) return rc;
-    if (p.splitk > 1) {
-      const long nq = (long)p.M * (p.N >> 2);
-      unsigned blocks = (unsigned)((nq + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, stream, p);
-      HIP_CHECK_RET(hipGetLastError());
-    }
-    return 0;
-  }
-  if (pl.halo_tw == 256) {
-    if constexpr (sizeof(T) == 2) {
-      rc = launch_halo8(p, stream);
-    } else {
-      af_set_error_msg("conv_gemm: the eight-wave halo kernel is bf16 only");
-      return -1;
-    }
-    if (rc) return rc;
-    if (p.splitk > 1) {
-      const long nq = (long)p.M * (p.N >> 2);
-      unsigned blocks = (unsigned)((nq + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, stream, p);
-      HIP_CHECK_RET(hipGetLastError());
-    }
-    return 0;
-  }
-  if (pl.halo_tw) {
+  } else if (pl.halo_tw) {
     const bool bn128 = pl.tile == 0 || pl.tile == 1;
-    if (pl.halo_tw == 32) rc = bn128 ? launch_halo<T, 32, 128>(p, stream) : launch_halo<T, 32, 64>(p, stream);
-    else rc = bn128 ? launch_halo<T, 16, 128>(p, stream) : launch_halo<T, 16, 64>(p, stream);
-    return rc;
-  }
-  switch (pl.tile) {
-    case 4:
-    case 5:
-      if constexpr (sizeof(T) == 2) {
-        rc = pl.tile == 4 ? launch_pp<128>(p, stream) : launch_pp<160>(p, stream);
-      } else {
-        af_set_error_msg("conv_gemm: ping-pong tiles are bf16 only");
-        return -1;
-      }
-      break;
-    case 0: rc = launch_cfg<T, 128, 128>(p, batch, stream); break;
-    case 1: rc = launch_cfg<T, 64, 128>(p, batch, stream); break;
-    case 2: rc = launch_cfg<T, 128, 64>(p, batch, stream); break;
-    default: rc = launch_cfg<T, 64, 64>(p, batch, stream); break;
+    if (pl.halo_tw == 32) return bn128 ? launch_halo<T, 32, 128>(p, stream) : launch_halo<T, 32, 64>(p, stream);
+    return bn128 ? launch_halo<T, 16, 128>(p, stream) : launch_halo<T, 16, 64>(p, stream);
+  } else {
+    switch (pl.tile) {
+      case 4:
+      case 5:
+        if constexpr (sizeof(T) == 2) {
+          rc = pl.tile == 4 ? launch_pp<128>(p, stream) : launch_pp<160>(p, stream);
+        } else {
+          af_set_error_msg("conv_gemm: ping-pong tiles are bf16 only");
+          return -1;
+        }
+        break;
+      case 0: rc = launch_cfg<T, 128, 128>(p, batch, stream); break;
+      case 1: rc = launch_cfg<T, 64, 128>(p, batch, stream); break;
+      case 2: rc = launch_cfg<T, 128, 64>(p, batch, stream); break;
+      default: rc = launch_cfg<T, 64, 64>(p, batch, stream); break;
+    }
   }
   if (rc) return rc;
-  if (p.splitk > 1) {
-    const long nq = (long)p.M * (p.N >> 2);
-    unsigned blocks = (unsigned)((nq + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, stream, p);
-    HIP_CHECK_RET(hipGetLastError());
-  }
-  return 0;
+  return p.splitk > 1 ? launch_splitk_reduce<T>(p, stream) : 0;
 }
 
 template int af_launch_conv_gemm<bf16>(const ConvGemmParams&, int, hipStream_t, const AfGemmPlan*, void*);

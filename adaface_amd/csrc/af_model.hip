@@ -50,11 +50,9 @@ AfKnobs g_af_knobs = {
     knob_env("AF_SPLITK_TARGET", 320), knob_env("AF_CONV_HALO", 1),       knob_env("AF_GEMM_PP", 1),
     knob_env("AF_GEMM_PP_MINFILL", 50), knob_env("AF_GEMM_TILE", -1),
     knob_env("AF_GEMM_SPLITK", -1),    knob_env("AF_GEMM_GROUPM", -1),    knob_env("AF_GEMM_DMA", -1),
-    knob_env("AF_PP_DIRECT", -1),      knob_env("AF_ATTN_RING", 3),
-    knob_env("AF_GN_SMALL", 1),        knob_env("AF_CONV_TAP_INNER", 1),
-    knob_env("AF_LN_FUSE", 1),         knob_env("AF_GEGLU_ROWPANEL", 4), knob_env("AF_CONV_HALO8", 3), knob_env("AF_CONV_FAST_TAPS", 1),
-    knob_env("AF_PP_STAGGER", 1),      knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1),
-    knob_env("AF_PP_SCHED", 2),        knob_env("AF_ATTN_SHORT", 1),
+    knob_env("AF_ATTN_RING", 3),       knob_env("AF_GN_SMALL", 1),
+    knob_env("AF_LN_FUSE", 1),         knob_env("AF_GEGLU_ROWPANEL", 4), knob_env("AF_CONV_HALO8", 3), knob_env("AF_ABLATE", 0),
+    knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1), knob_env("AF_ATTN_SHORT", 1),
     knob_env("AF_GEMM_M128", 1),       knob_env("AF_SMALL_M_TILE64", 1),  knob_env("AF_GN_CONSUMER", 1),
     knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0)};
 static const AfKnobs g_af_knobs_initial = g_af_knobs;
@@ -63,9 +61,9 @@ static int* knob_slot(const char* name) {
       {"splitk_target", &AfKnobs::splitk_target}, {"conv_halo", &AfKnobs::conv_halo}, {"gemm_pp", &AfKnobs::gemm_pp},
       {"gemm_pp_minfill", &AfKnobs::gemm_pp_minfill},
       {"gemm_tile", &AfKnobs::gemm_tile}, {"gemm_splitk", &AfKnobs::gemm_splitk}, {"gemm_groupm", &AfKnobs::gemm_groupm},
-      {"gemm_dma", &AfKnobs::gemm_dma}, {"pp_direct", &AfKnobs::pp_direct}, {"attn_ring", &AfKnobs::attn_ring},
-      {"gn_small", &AfKnobs::gn_small}, {"conv_tap_inner", &AfKnobs::conv_tap_inner}, {"ln_fuse", &AfKnobs::ln_fuse},
-      {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"conv_fast_taps", &AfKnobs::conv_fast_taps}, {"pp_stagger", &AfKnobs::pp_stagger}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4}, {"pp_sched", &AfKnobs::pp_sched},
+      {"gemm_dma", &AfKnobs::gemm_dma}, {"attn_ring", &AfKnobs::attn_ring},
+      {"gn_small", &AfKnobs::gn_small}, {"ln_fuse", &AfKnobs::ln_fuse},
+      {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"ablate", &AfKnobs::ablate}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4},
       {"attn_short", &AfKnobs::attn_short},
       {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}};
   if (!name) return nullptr;

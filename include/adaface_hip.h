@@ -205,11 +205,12 @@ int af_gemm_plan_counts_reset(void);
  * AF_* environment variables when the library is loaded (AF_GEMM_PP_MINFILL -> "gemm_pp_minfill", ...); nothing on the
  * launch path reads the environment.  The parity tests use af_knob_set to reach a kernel variant regardless of the
  * planner's choice and af_knob_reset to restore the load-time values.  No knob changes results beyond the summation
- * order of the chosen tiling.  The 26 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
- * gemm_pp_minfill, gemm_tile, gemm_splitk, gemm_groupm, gemm_dma, pp_direct, attn_ring, gn_small,
- * conv_tap_inner, ln_fuse, geglu_rowpanel, conv_halo8, conv_fast_taps, pp_stagger, gn_producer, conv_up_phase4, pp_sched,
- * attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log.  Round 4 removed the six that selected a measured-neutral or
- * slower variant or nothing at all (gn_reduce, splitk_inlaunch, rowpanel_deep, gn_fold, attn_w4, gemm_pp_geglu_minkt; numbers in DESIGN.md section 5). */
+ * order of the chosen tiling.  The 22 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
+ * gemm_pp_minfill, gemm_tile, gemm_splitk, gemm_groupm, gemm_dma, attn_ring, gn_small, ln_fuse, geglu_rowpanel, conv_halo8,
+ * ablate (lab builds only), gn_producer, conv_up_phase4, attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log.
+ * Round 4 removed the six that selected a measured-neutral or slower variant or nothing at all (gn_reduce, splitk_inlaunch,
+ * rowpanel_deep, gn_fold, attn_w4, gemm_pp_geglu_minkt), and after it the four variant switches of the ping-pong kernel went
+ * the same way (schedule, K order, stagger, forced epilogue; its tap-mask switch became ablate); numbers in DESIGN.md section 5. */
 int af_knob_set(const char* name, int value);
 int af_knob_get(const char* name, int* value);
 int af_knob_reset(void);

@@ -35,7 +35,7 @@ ntile = (16 * args.hw * args.hw // 256) * (args.cout // 160)
 
 
 def bracketed(knob):
-    _lib.set_knob("conv_fast_taps", knob)
+    _lib.set_knob("ablate", knob)
     for _ in range(5):
         ops.conv2d(x, w, b, dtype="bf16")
     torch.cuda.synchronize()
@@ -54,7 +54,7 @@ def bracketed(knob):
 
 print(f"event-bracketed launch: plain {bracketed(1):.1f} us, stamped build {bracketed(1 + 16 * 64):.1f} us")
 for knob in (1 + 16 * 64,):
-    _lib.set_knob("conv_fast_taps", knob)
+    _lib.set_knob("ablate", knob)
     for _ in range(20):
         ops.conv2d(x, w, b, dtype="bf16")
     torch.cuda.synchronize()

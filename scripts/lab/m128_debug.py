@@ -7,9 +7,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from adaface_amd import _lib, ops
 _lib.load()
 dev = torch.device("cuda:0")
-import os
 M, K, N = 4096, 1280, 1280
-if os.environ.get("ST"): _lib.set_knob("pp_stagger", int(os.environ["ST"]))
 g = torch.Generator().manual_seed(1)
 x = torch.randn(M, K, generator=g).to(torch.bfloat16).float().to(dev)
 w = (torch.randn(N, K, generator=g) / math.sqrt(K)).to(torch.bfloat16).float().to(dev)

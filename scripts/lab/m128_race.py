@@ -1,15 +1,14 @@
 #!/usr/bin/env python
 """Lab: run the 128 x 160 tile GEMM repeatedly on one input and count launches whose output differs from the first / from
-torch (race screen).  --stagger 77 = full vmcnt drain per step (debug)."""
+torch (race screen)."""
 import argparse, math, sys
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from adaface_amd import _lib, ops
-ap = argparse.ArgumentParser(); ap.add_argument("--stagger", type=int, default=-1); ap.add_argument("--reps", type=int, default=30)
+ap = argparse.ArgumentParser(); ap.add_argument("--reps", type=int, default=30)
 a = ap.parse_args()
 _lib.load()
-if a.stagger >= 0: _lib.set_knob("pp_stagger", a.stagger)
 dev = torch.device("cuda:0")
 for (M, K, N, res) in [(4096, 1280, 1280, False), (2048, 1280, 1280, False), (4096, 1280, 1280, True), (8192, 640, 640, False), (4096, 5120, 1280, False)]:
     g = torch.Generator().manual_seed(M + K + N)

@@ -40,7 +40,7 @@ inline int rup(int a, int b) { return (a + b - 1) / b * b; }
   void* var = tmp.get((bytes), (zero));                          \
   if (!var) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
 
-// ---- device clock probe (bench.py stamps every line with it: devices of one pool hold different clocks under MFMA load, so
+// ---- device clock probe (bench.py --full stamps its line with it: devices of one pool hold different clocks under MFMA load, so
 // whole-path numbers from different boxes are only comparable through a number like this) ----
 // Every wave runs `iters` rounds of four independent v_mfma_f32_32x32x16_bf16 on pseudo-random register operands (no memory
 // traffic, no LDS) between two (s_memtime, s_memrealtime) stamp pairs: shader cycles / 100 MHz reference ticks = the clock

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: 512x512 images/sec @ 50 DDIM steps, batch 8 per GPU (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config1|config2|config3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config1|config2|config3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,12 @@ One "step" = one pass of the hot path over one batch: DDIMSampler.sample (50 ste
 at Bf=16 on 4x64x64 latents with a [256,77,768] layerwise context) + decode_first_stage to 8 uint8 512x512
 frames, through the drop-in classes (ldm.models.diffusion.ddim.DDIMSampler, LatentDiffusion.apply_model,
 AutoencoderKL.decode) and the C ABI underneath.  Inputs are resident in HBM before the timed region.
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the steps (with the sampled
+HIP-event brackets behind `kernels` / `roofline` unless --no-kernel-timing), writes --dump-outputs and prints the line.
+--full adds the legs that cost time of their own: the device clock probe before the warm-up, the untimed f32 parity
+leg with its bar (exit code 3 if exceeded) and the CPU baseline.  In a plain run their fields are null, and so is
+`roofline.frac_of_device_mfma_loop`, which divides by the clock probe.  The serving leg needs its own --serving-leg.
 
 Multi-GPU: independent samples, one process per GPU, ONE RCCL all-gather of the decoded uint8 frames
 per step.  `--gpus N` without a launcher (no WORLD_SIZE / RANK in the environment) starts the N ranks itself, as
@@ -65,10 +71,13 @@ def parse():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--dtype", default=None, choices=["bf16", "f32", "fp8"],
                     help="compute mode (default bf16; config4: fp8 = bf16 with e4m3 ResBlock convolutions)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the device clock probe, the untimed f32 parity leg "
+                         "(exit code 3 past its bar) and the CPU baseline (the serving leg still needs --serving-leg)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the HIP-event roofline leg")
     ap.add_argument("--no-parity-leg", action="store_true",
-                    help="skip the untimed f32-mode batch (f32-mode images/s and the bf16 final-latent deviation)")
+                    help="with --full: skip the untimed f32-mode batch (f32-mode images/s and the bf16 final-latent deviation)")
     ap.add_argument("--serving-leg", action="store_true",
                     help="after the timed region, also run the serving leg (two independent batch-8 requests in flight on two HIP "
                          "streams: a second 859 M-parameter model, ~10 s; never part of `value`).  Default off: BASELINE's metric is "
@@ -291,7 +300,7 @@ def main():
 
     # held-clock proxy of THIS device, taken before the warm-up: devices of one pool differ by +-5 % on MFMA-dense kernels
     clock = None
-    if lib is not None:
+    if lib is not None and args.full:
         mhz, tfl = C.c_double(0.0), C.c_double(0.0)
         _lib.check(lib.af_clock_probe(C.c_void_p(torch.cuda.current_stream().cuda_stream), 0, C.byref(mhz), C.byref(tfl)),
                    "af_clock_probe")
@@ -443,7 +452,7 @@ def main():
 
     # ---- untimed parity leg (rank 0, N = 1): the SAME batch in f32 parity mode ----
     parity = None
-    if rank == 0 and world == 1 and not stub and not args.no_parity_leg and args.dtype in ("bf16", "fp8"):
+    if rank == 0 and world == 1 and not stub and args.full and not args.no_parity_leg and args.dtype in ("bf16", "fp8"):
         lat16 = step_latents[-1].clone()
         model.set_compute_dtype("f32")
         run_micro(x_T_all[(n_micro - 1) * B:], conds[-1])          # engine build + weight upload + first call
@@ -495,13 +504,13 @@ def main():
             "device_clock_probe": clock,
             "distributed": dict(STATS, per_rank=per_rank),
             "roofline": roof, "kernels": kernels, "parity": parity, "two_requests_in_flight": inflight,
-            "dumped_outputs": dumped,
+            "dumped_outputs": dumped, "full": args.full,
         }
         if stub:
             res.update(metric="PLUMBING TEST - stub in place of the HIP path, nothing measured", value=None, dtype="none",
                        checksum=int(out.to(torch.int64).sum().item()),
                        frames_sha256=__import__("hashlib").sha256(out.contiguous().numpy().tobytes()).hexdigest())
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub:
             res["cpu_baseline"] = cpu_baseline(S)
         else:
             res["cpu_baseline"] = None

@@ -184,7 +184,7 @@ int af_prof_set_stride(int every);
 double af_flops_issued(int reset);
 /* Device clock probe: a register-only bf16 MFMA loop (`iters` rounds of four v_mfma_f32_32x32x16_bf16 per wave, two waves
  * per SIMD on every CU; <= 0: 40000 rounds, about 5 ms) stamped with s_memtime / s_memrealtime.  mfma_mhz = median in-kernel
- * clock the chip held under it, mfma_tflops = its rate.  bench.py stamps each line with both so that lines measured on
+ * clock the chip held under it, mfma_tflops = its rate.  bench.py --full stamps its line with both so that lines measured on
  * different devices of a pool can be compared. */
 int af_clock_probe(void* stream, int iters, double* mfma_mhz, double* mfma_tflops);
 int af_prof_collect(int n_classes, double* ms, int64_t* launches, double* flops, double* bytes);

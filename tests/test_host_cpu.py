@@ -269,6 +269,20 @@ def test_bench_dump_outputs_is_float32_and_repeatable(tmp_path):
     assert j["dumped_outputs"]["arrays"]["frames"]["shape"] == [4, 8, 8, 3]
 
 
+def test_bench_extra_legs_only_with_full():
+    """--full is accepted and echoed on the line, and a plain line carries the headline fields.  The stub runs none of the
+    legs --full gates in either case: that they stay off without --full, and run with it, is checked on the GPU
+    (tests/test_chained_gpu.py::test_bench_full_gates_its_legs)."""
+    common = ["--gpus", "1", "--plumbing-test", "--steps", "1", "--warmup", "0", "--batch", "2", "--global-batch", "2"]
+    r, j = _run_bench(common)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert j["full"] is False and j["cpu_baseline"] is None and j["parity"] is None and j["device_clock_probe"] is None
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(j)
+    r, j = _run_bench([*common, "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert j["full"] is True
+
+
 def test_adaprompt_context_differs_per_layer_only_in_subject_rows():
     from adaface_amd.synth import synth_context, synth_context_adaprompt
     c = synth_context_adaprompt(3, seed=100, device="cpu").reshape(3, 16, 77, 768)

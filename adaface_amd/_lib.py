@@ -91,6 +91,13 @@ _SIGS = [
     ("af_op_conv_gn", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P] + [C.c_int] * 5 + [_P]),
     ("af_set_fp8", C.c_int, [_P, C.c_int]),
     ("af_fp8_gemm_launches", C.c_int64, []),
+    ("af_fp8_num_sites", C.c_int, [_P]),
+    ("af_fp8_site_name", C.c_char_p, [_P, C.c_int]),
+    ("af_fp8_record", C.c_int, [_P, C.c_int, _P]),
+    ("af_fp8_read_record", C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64), _P]),
+    ("af_fp8_get_shifts", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("af_fp8_set_shifts", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("af_fp8_shift_for_amax", C.c_int, [C.c_float, C.c_int]),
     ("af_halo8_launches", C.c_int64, []),
     ("af_rowpanel_launches", C.c_int64, []),
     ("af_up_phase4_launches", C.c_int64, []),
@@ -102,6 +109,8 @@ _SIGS = [
     ("af_op_conv2d_fp8", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 10 + [_P]),
     ("af_op_groupnorm_fp8", C.c_int, [_P, _P, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("af_op_layernorm_fp8", C.c_int, [_P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, C.c_int, _P]),
+    ("af_op_groupnorm_fp8_rec", C.c_int, [_P, _P, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("af_op_layernorm_fp8_rec", C.c_int, [_P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     ("af_op_layernorm", C.c_int, [C.c_int, _P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, _P]),
     ("af_op_attention", C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     ("af_clip_embed_tokens", C.c_int, [_P, _P, C.c_int64, _P, _P]),

@@ -37,7 +37,8 @@ template <typename T>
 int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn, const float* gamma,
                         const float* beta, float eps, int silu, void* y, long y_bs, int ldy, void* workspace,
                         hipStream_t stream, float fp8_mul = 0.f,    // fp8_mul != 0: y is e4m3 bytes of result * fp8_mul
-                        const float* pre_partial = nullptr, int pre_npart = 0);   // statistics already summed by the producer
+                        const float* pre_partial = nullptr, int pre_npart = 0,    // statistics already summed by the producer
+                        unsigned* fp8_rec = nullptr);   // fp8 calibration record {amax bits, n saturated} to update (e4m3 output only)
 // GroupNorm reduced to its per-sample affine map ab_out [B][2][Cn] (scale, shift) for a consumer that applies it itself
 // (ConvGemmParams::gn_ab): statistics pass (unless pre_partial) + fold, no pass that writes the normalised tensor
 template <typename T>
@@ -53,7 +54,7 @@ int af_launch_conv_s8(const ConvGemmParams& p, hipStream_t stream);
 int af_conv_rowpanel_kind(const ConvGemmParams& p, int batch);   // 0 = not a row-panel launch (p.splitk as planned)
 template <typename T>
 int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* gamma, const float* beta,
-                        float eps, void* y, int ldy, hipStream_t stream, float fp8_mul = 0.f);
+                        float eps, void* y, int ldy, hipStream_t stream, float fp8_mul = 0.f, unsigned* fp8_rec = nullptr);
 
 template <typename T>
 int af_launch_nchw_to_nhwc(const float* x, void* y, int B, int Cn, int HW, int Cpad, float scale, hipStream_t s);

@@ -145,7 +145,9 @@ struct Act {  // NHWC activation view
   void* p = nullptr;
   int B = 0, H = 0, W = 0, C = 0;
   int ld = 0;  // elements between pixels
-  bool f8 = false;  // e4m3 bytes (value * 2^AF_FP8_ACT_SHIFT), consumed by an fp8 convolution only
+  bool f8 = false;  // e4m3 bytes (value * 2^f8_shift), consumed by an fp8 convolution only
+  int f8_shift = AF_FP8_SHIFT_DEFAULT;   // the shift of the fp8 site this tensor belongs to (af_fp8_set_shifts)
+  int f8_site = -1;                      // ... and its index in the handle's record table
   // GroupNorm partial sums [B][gn_npart][32][2] written by the convolution that produced this tensor (ConvGemmParams::
   // gn_stats_out); valid for exactly the B samples and C channels of this view
   const float* gn_part = nullptr;
@@ -165,11 +167,12 @@ struct Linear {  // conv or linear weight, repacked [rows_pad][ldw] in storage d
   void* w8 = nullptr;
   unsigned char* sc8 = nullptr;
   int k8 = 0;
+  int f8_site = -1;   // fp8 site (its producer -> this consumer): index into af_handle::fp8_shift / fp8_rec, -1 = never gets a twin
   // phase weights of an upsampled 3x3 convolution (ConvGemmParams::W_up4): bf16 [4][rows_pad][4 * cin_pad]
   void* w_up4 = nullptr;
 };
-// fp8 activations hold value * 2^3: SiLU(GroupNorm) outputs saturate at +-56 and keep e4m3's 3-bit mantissa down to 2^-9
-constexpr int AF_FP8_ACT_SHIFT = 3;
+// fp8 activations hold value * 2^s, s per site.  Uncalibrated s = AF_FP8_SHIFT_DEFAULT = 3: SiLU(GroupNorm) outputs saturate at
+// +-56 and keep e4m3's 3-bit mantissa down to 2^-9; af_fp8_set_shifts puts a calibrated s in its place.
 struct Norm {
   float* gamma = nullptr;
   float* beta = nullptr;
@@ -293,6 +296,12 @@ struct af_handle {
   bool ln_fold_dirty = true;   // folded LayerNorm twins must be recomputed (a UNet tensor was loaded since)
   bool fp8_on = false;         // af_set_fp8: ResBlock 3x3 convolutions of the UNet on the block-scaled fp8 MFMA
   bool fp8_dirty = true;       // fp8 weight twins must be (re)quantised
+  // fp8 sites (register_fp8_sites): activation shift per site, the checkpoint key of the consumer's weight, and the device
+  // record table [n][2] = {max |value| as float bits, saturated elements} the producers update while fp8_recording
+  std::vector<int> fp8_shift;
+  std::vector<std::string> fp8_site_names;
+  unsigned* fp8_rec = nullptr;
+  bool fp8_recording = false;
   bool up4_dirty = true;       // phase weights of the upsampled convolutions must be (re)summed
   // GroupNorm partial sums of a block OUTPUT (ResBlock conv2 -> the GroupNorm that opens the next layer): outlives the
   // arena scope of the producer; one such tensor is live at a time.  Sized by the dry run.
@@ -765,11 +774,13 @@ struct Runner {
     a.p = A.alloc((size_t)a.npix() * a.ld * esize(dt));
     return a;
   }
-  Act alloc_act8(int B, int H, int W, int C) {   // e4m3 bytes
+  Act alloc_act8(int B, int H, int W, int C, const Linear& consumer) {   // e4m3 bytes at the scale of the consumer's fp8 site
     Act a;
     a.B = B; a.H = H; a.W = W; a.C = C;
     a.ld = C;
     a.f8 = true;
+    a.f8_site = consumer.f8_site;
+    if (a.f8_site >= 0) a.f8_shift = h->fp8_shift[a.f8_site];
     a.p = A.alloc((size_t)a.npix() * a.ld);
     return a;
   }
@@ -832,12 +843,12 @@ struct Runner {
       p.fp8 = 1;
       p.W = L.w8; p.ldw = L.k8; p.K = L.k8;
       p.w_scale = L.sc8;
-      p.x_scale_e8 = 127 - AF_FP8_ACT_SHIFT;
+      p.x_scale_e8 = 127 - x.f8_shift;
     }
   }
   // would this convolution run on the fp8 ping-pong kernel?  (asked BEFORE its input is produced as e4m3)
   bool fp8_capable(const Linear& L, const Act& x, const Act& out, int stride = 1, int up = 0) const {
-    if (!h->fp8_on || dt != AF_DTYPE_BF16 || !L.w8 || x.C != L.cin || L.cin != L.cin_pad) return false;
+    if (!h->fp8_on || dt != AF_DTYPE_BF16 || !L.w8 || L.f8_site < 0 || x.C != L.cin || L.cin != L.cin_pad) return false;
     Act x8 = x;
     x8.f8 = true; x8.ld = x.C;
     ConvGemmParams p;
@@ -957,6 +968,8 @@ struct Runner {
     if (dry) return 0;
     return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, batch, s), af_launch_conv_gemm<float>(p, batch, s));
   }
+  // the record slot of an e4m3 output while af_fp8_record is on
+  unsigned* fp8_rec_of(const Act& y) const { return h->fp8_recording && y.f8_site >= 0 ? h->fp8_rec + 2 * y.f8_site : nullptr; }
   int groupnorm(const Norm& N, const Act& x, Act& y, int silu) {
     AF_TRY(check(y));
     const int HW = x.H * x.W;
@@ -968,7 +981,7 @@ struct Runner {
     const float* pre = g_af_knobs.gn_producer ? x.gn_part : nullptr;
     if (y.f8)
       return af_launch_groupnorm<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu, y.p,
-                                       (long)HW * y.ld, y.ld, ws, s, (float)(1 << AF_FP8_ACT_SHIFT), pre, x.gn_npart);
+                                       (long)HW * y.ld, y.ld, ws, s, ldexpf(1.f, y.f8_shift), pre, x.gn_npart, fp8_rec_of(y));
     return DISPATCH(dt,
                     af_launch_groupnorm<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
                                               y.p, (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart),
@@ -979,7 +992,8 @@ struct Runner {
     AF_TRY(check(y));
     if (dry) return 0;
     if (y.f8)
-      return af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s, (float)(1 << AF_FP8_ACT_SHIFT));
+      return af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s, ldexpf(1.f, y.f8_shift),
+                                       fp8_rec_of(y));
     return DISPATCH(dt, af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s),
                     af_launch_layernorm<float>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s));
   }
@@ -1015,12 +1029,12 @@ static int run_resblock(Runner& R, const ResBlockW& w, const Act& x, Act& out, c
   const size_t mk = R.A.mark();
   // (fp8 mode: GroupNorm + SiLU writes e4m3 where the convolution that reads it runs on the fp8 kernel)
   Act t2 = R.alloc_act(x.B, x.H, x.W, w.cout);
-  Act t1 = R.fp8_capable(w.c1, x, t2) ? R.alloc_act8(x.B, x.H, x.W, x.C) : R.alloc_act(x.B, x.H, x.W, x.C);
+  Act t1 = R.fp8_capable(w.c1, x, t2) ? R.alloc_act8(x.B, x.H, x.W, x.C, w.c1) : R.alloc_act(x.B, x.H, x.W, x.C);
   AF_TRY(R.groupnorm(w.n1, x, t1, 1));
   const void* rb = (emb_all && w.emb_off >= 0) ? R.elem_ptr(const_cast<void*>(emb_all), w.emb_off) : nullptr;
   // (conv1 also sums the GroupNorm statistics of its output where its kernel can: n2 then makes no pass for them)
   AF_TRY(R.conv(w.c1, t1, t2, 1, 0, nullptr, rb, emb_ld, -1, -1, nullptr, 1));
-  Act t3 = R.fp8_capable(w.c2, t2, out) ? R.alloc_act8(x.B, x.H, x.W, w.cout) : R.alloc_act(x.B, x.H, x.W, w.cout);
+  Act t3 = R.fp8_capable(w.c2, t2, out) ? R.alloc_act8(x.B, x.H, x.W, w.cout, w.c2) : R.alloc_act(x.B, x.H, x.W, w.cout);
   AF_TRY(R.groupnorm(w.n2, t2, t3, 1));
   Act sk = x;
   if (w.has_skip) {
@@ -1130,7 +1144,7 @@ static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin
       if (R.fp8_capable(blk.qkv1, tp, qkvp)) {
         // fp8 mode: LayerNorm writes e4m3 and the q / k / v projection multiplies on the block-scaled fp8 MFMA (the
         // un-folded weights: its producer's row statistics, if any, simply go unused)
-        Act n8 = R.alloc_act8(Bp, H, W, C);
+        Act n8 = R.alloc_act8(Bp, H, W, C, blk.qkv1);
         AF_TRY(R.layernorm(blk.ln1, tp, n8));
         AF_TRY(R.conv(blk.qkv1, n8, qkvp, 1, 0, nullptr, nullptr, 0));
       } else if (ln_parts) {
@@ -1300,17 +1314,44 @@ static int fold_layernorms(af_handle* h, hipStream_t s) {
   return 0;
 }
 
-// fp8 twins of the UNet ResBlock convolutions (allocated on first use, re-quantised after weight loads)
-static int ensure_fp8_twins(af_handle* h, hipStream_t s) {
-  if (!h->fp8_on || !h->fp8_dirty) return 0;
-  if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("fp8 convolutions need the bf16 storage mode"); return AF_ERR_STATE; }
+// the weights that get an fp8 twin: the UNet ResBlock convolutions and the self-attention q / k / v projections
+static std::vector<Linear*> fp8_twin_list(af_handle* h) {
   std::vector<Linear*> twins;
   for (auto& r : h->res) { twins.push_back(&r.c1); twins.push_back(&r.c2); }
   for (auto& x : h->xf)      // "fp8 MFMA QKV": the self-attention q / k / v projection (attention.py:195-196, fused qkv1)
     for (auto& t : x.blocks) twins.push_back(&t.qkv1);
-  for (Linear* L : twins) {
+  std::vector<Linear*> ok;
+  for (Linear* L : twins)
+    if (L->cin_pad % 64 == 0 && (L->ks == 1 || L->ks == 3)) ok.push_back(L);
+  return ok;
+}
+
+// one fp8 site per such weight (bf16 handles): its shift, its name (the slot that fills row 0 of the weight) and its slot in
+// the record table
+static int register_fp8_sites(Builder& b) {
+  af_handle* h = b.h;
+  if (h->dtype != AF_DTYPE_BF16) return 0;
+  for (Linear* L : fp8_twin_list(h)) {
+    std::string name;
+    for (const std::string& n : h->slot_names) {
+      const Slot& sl = h->slots[n];
+      if (sl.kind == Slot::WEIGHT && sl.dst == L->w && sl.row_off == 0) { name = n; break; }
+    }
+    if (name.empty()) { af_set_error_msg("fp8 site without a weight slot"); return AF_ERR_STATE; }
+    L->f8_site = (int)h->fp8_shift.size();
+    h->fp8_shift.push_back(AF_FP8_SHIFT_DEFAULT);
+    h->fp8_site_names.push_back(name);
+  }
+  if (!h->fp8_shift.empty()) h->fp8_rec = reinterpret_cast<unsigned*>(b.dmalloc(h->fp8_shift.size() * 2 * sizeof(unsigned)));
+  return b.rc;
+}
+
+// fp8 twins of these weights (allocated on first use, re-quantised after weight loads)
+static int ensure_fp8_twins(af_handle* h, hipStream_t s) {
+  if (!h->fp8_on || !h->fp8_dirty) return 0;
+  if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("fp8 convolutions need the bf16 storage mode"); return AF_ERR_STATE; }
+  for (Linear* L : fp8_twin_list(h)) {
     {
-      if (L->cin_pad % 64 != 0 || (L->ks != 1 && L->ks != 3)) continue;
       if (!L->w8) {
         const int units = L->ks * L->ks * (L->cin_pad / 64);
         L->k8 = round_up(units * 64, 128);
@@ -1824,6 +1865,7 @@ int af_create(int device_id, const af_config* cfg, af_handle** out) {
       return AF_ERR_INVALID;
     }
     int rc = build_unet(b);
+    if (!rc) rc = register_fp8_sites(b);
     if (rc) { af_destroy(h.release()); return rc; }
   }
   if (cfg->build_vae) {
@@ -2335,6 +2377,74 @@ int af_set_fp8(af_handle* h, int on) {
   if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is f32)"); return AF_ERR_STATE; }
   h->fp8_on = on != 0;
   return AF_OK;
+}
+int af_fp8_num_sites(af_handle* h) { return h ? (int)h->fp8_shift.size() : 0; }
+const char* af_fp8_site_name(af_handle* h, int i) {
+  if (!h || i < 0 || i >= (int)h->fp8_site_names.size()) return nullptr;
+  return h->fp8_site_names[i].c_str();
+}
+static int fp8_sites_arg(af_handle* h, int n, const char* who) {
+  if (!h) { af_set_error_msg("%s: null handle", who); return AF_ERR_INVALID; }
+  if (n != (int)h->fp8_shift.size()) { af_set_error_msg("%s: n = %d, the handle has %d fp8 sites", who, n, (int)h->fp8_shift.size()); return AF_ERR_INVALID; }
+  return AF_OK;
+}
+int af_fp8_record(af_handle* h, int on, void* stream) {
+  if (!h) { af_set_error_msg("af_fp8_record: null handle"); return AF_ERR_INVALID; }
+  if (on && !h->fp8_rec) { af_set_error_msg("af_fp8_record: the handle has no fp8 sites (f32 handle, or no UNet)"); return AF_ERR_STATE; }
+  if (on) {
+    HIP_CHECK_RET(hipSetDevice(h->device));
+    HIP_CHECK_RET(hipMemsetAsync(h->fp8_rec, 0, h->fp8_shift.size() * 2 * sizeof(unsigned), reinterpret_cast<hipStream_t>(stream)));
+  }
+  h->fp8_recording = on != 0;
+  return AF_OK;
+}
+int af_fp8_read_record(af_handle* h, int n, float* amax, int64_t* nsat, void* stream) {
+  AF_TRY(fp8_sites_arg(h, n, "af_fp8_read_record"));
+  if (n == 0) return AF_OK;
+  if (!amax || !nsat) { af_set_error_msg("af_fp8_read_record: null output"); return AF_ERR_INVALID; }
+  std::vector<unsigned> host(2 * (size_t)n);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  HIP_CHECK_RET(hipMemcpyAsync(host.data(), h->fp8_rec, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  HIP_CHECK_RET(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) {
+    memcpy(&amax[i], &host[2 * i], sizeof(float));
+    nsat[i] = (int64_t)host[2 * i + 1];
+  }
+  return AF_OK;
+}
+int af_fp8_get_shifts(af_handle* h, int n, int* shifts) {
+  AF_TRY(fp8_sites_arg(h, n, "af_fp8_get_shifts"));
+  if (n && !shifts) { af_set_error_msg("af_fp8_get_shifts: null output"); return AF_ERR_INVALID; }
+  for (int i = 0; i < n; ++i) shifts[i] = h->fp8_shift[i];
+  return AF_OK;
+}
+int af_fp8_set_shifts(af_handle* h, int n, const int* shifts) {
+  if (!h) { af_set_error_msg("af_fp8_set_shifts: null handle"); return AF_ERR_INVALID; }
+  if (!shifts) {
+    for (int& v : h->fp8_shift) v = AF_FP8_SHIFT_DEFAULT;
+    return AF_OK;
+  }
+  AF_TRY(fp8_sites_arg(h, n, "af_fp8_set_shifts"));
+  for (int i = 0; i < n; ++i)
+    if (shifts[i] < AF_FP8_SHIFT_MIN || shifts[i] > AF_FP8_SHIFT_MAX) {
+      af_set_error_msg("af_fp8_set_shifts: shift %d of site %d (%s) outside [%d, %d]", shifts[i], i, h->fp8_site_names[i].c_str(),
+                       AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX);
+      return AF_ERR_INVALID;
+    }
+  for (int i = 0; i < n; ++i) h->fp8_shift[i] = shifts[i];
+  return AF_OK;
+}
+int af_fp8_shift_for_amax(float amax, int headroom) {
+  if (!(amax > 0.f) || std::isinf(amax)) return AF_FP8_SHIFT_DEFAULT;
+  // amax = m * 2^e with m in [0.5, 1), 448 = 0.875 * 2^9: floor(log2(448 / amax)) = 9 - e, one less when m > 0.875 (exact:
+  // no logarithm is rounded -- 56.0 gives 3, the next float above it 2)
+  int e = 0;
+  const float m = frexpf(amax, &e);
+  long sft = 9L - e - (m > 0.875f ? 1 : 0) - headroom;
+  if (sft < AF_FP8_SHIFT_MIN) sft = AF_FP8_SHIFT_MIN;
+  if (sft > AF_FP8_SHIFT_MAX) sft = AF_FP8_SHIFT_MAX;
+  return (int)sft;
 }
 double af_prof_event_overhead_us(void* stream, int n) {
   // what an event pair with NOTHING between its two records measures on this stream (the cost the bracket itself adds to

@@ -148,7 +148,34 @@ __device__ __forceinline__ unsigned gn_pack4_e4m3(float a, float b, float c, flo
   return (unsigned)v;
 }
 
-template <typename T>
+// fp8 calibration record (af_fp8_record): what a producer saw at one fp8 site, {max |f| as float bits, elements with
+// |f * mul| > 448}.  f is the fp32 value BEFORE the multiplication and the clamp.  Non-negative floats order like
+// unsigned integers, and integer max / add do not depend on arrival order: the record is bit-reproducible run to run.
+__device__ __forceinline__ void fp8_rec_note4(float a, float b, float c, float d, float mul, float& amax, unsigned& nsat) {
+  a = fabsf(a); b = fabsf(b); c = fabsf(c); d = fabsf(d);
+  amax = fmaxf(fmaxf(amax, fmaxf(a, b)), fmaxf(c, d));
+  nsat += (unsigned)(a * mul > 448.f) + (unsigned)(b * mul > 448.f) + (unsigned)(c * mul > 448.f) + (unsigned)(d * mul > 448.f);
+}
+// every thread of the 256-thread workgroup calls this once: wave shuffles, four wave partials through LDS, then ONE atomic
+// max and ONE atomic add per workgroup
+__device__ __forceinline__ void fp8_rec_commit(float amax, unsigned nsat, unsigned* __restrict__ rec) {
+  __shared__ unsigned s_rec[8];
+  unsigned m = __float_as_uint(amax);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    nsat += (unsigned)__shfl_xor((int)nsat, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { s_rec[wave] = m; s_rec[4 + wave] = nsat; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMax(rec, max(max(s_rec[0], s_rec[1]), max(s_rec[2], s_rec[3])));
+    atomicAdd(rec + 1, s_rec[4] + s_rec[5] + s_rec[6] + s_rec[7]);
+  }
+}
+
+template <typename T, bool REC = false>   // REC: also fill the fp8 calibration record (a variant of its own: the plain path pays nothing)
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, long batch_stride, int ldc,
                                                         int HW, int Cn, int P,
                                                         const float* __restrict__ stats,
@@ -156,8 +183,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                                                         const float* __restrict__ beta, int silu,
                                                         T* __restrict__ y, long y_batch_stride, int ldy,
                                                         const float* __restrict__ partial, int nchunk, double count,
-                                                        float eps, float fp8_mul, int npart) {
+                                                        float eps, float fp8_mul, int npart, unsigned* __restrict__ rec) {
   constexpr int EPC = 16 / sizeof(T);
+  float r_amax = 0.f;
+  unsigned r_nsat = 0;
   __shared__ __attribute__((aligned(16))) float s_a[GN_MAX_C];
   __shared__ __attribute__((aligned(16))) float s_b[GN_MAX_C];
   __shared__ double s_ra[256], s_rq[256];
@@ -247,28 +276,38 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
       if (fp8_mul != 0.f) {   // (y_batch_stride, ldy in bytes)
         unsigned char* y8 = reinterpret_cast<unsigned char*>(y) + (long)b * y_batch_stride + (long)pixs[u] * ldy + vs[u] * EPC;
 #pragma unroll
-        for (int e = 0; e < EPC; e += 4) *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+        for (int e = 0; e < EPC; e += 4) {
+          *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+          if constexpr (REC) fp8_rec_note4(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul, r_amax, r_nsat);
+        }
       } else {
         *reinterpret_cast<uint4*>(yb + (long)pixs[u] * ldy + vs[u] * EPC) = oo.u;
       }
     }
   }
+  if constexpr (REC) fp8_rec_commit(r_amax, r_nsat, rec);
 }
 
 // ---------------------------------------------------------------------------
 // LayerNorm: one wave per row; C*sizeof(T)/16 <= 64*LN_MAXV vectors.
 // ---------------------------------------------------------------------------
 #define LN_MAXV 5
-template <typename T>
+template <typename T, bool REC = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, int ldx, long rows, int Cn,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float eps,
-                                                         T* __restrict__ y, int ldy, float fp8_mul) {
+                                                         T* __restrict__ y, int ldy, float fp8_mul,
+                                                         unsigned* __restrict__ rec) {
   constexpr int EPC = 16 / sizeof(T);
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int NV = Cn / EPC;
+  if constexpr (!REC) {
+    if (row >= rows) return;
+  }
+  // (REC: the waves past the last row stay for the workgroup reduction and own no vector)
+  const int NV = (REC && row >= rows) ? 0 : Cn / EPC;
+  float r_amax = 0.f;
+  unsigned r_nsat = 0;
   Vec16<T> v[LN_MAXV];
   float s = 0.f;
 #pragma unroll
@@ -313,12 +352,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
       if (fp8_mul != 0.f) {   // e4m3 output (ldy in bytes)
         unsigned char* y8 = reinterpret_cast<unsigned char*>(y) + row * ldy + vi * EPC;
 #pragma unroll
-        for (int e = 0; e < EPC; e += 4) *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+        for (int e = 0; e < EPC; e += 4) {
+          *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+          if constexpr (REC) fp8_rec_note4(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul, r_amax, r_nsat);
+        }
       } else {
         *reinterpret_cast<uint4*>(y + row * ldy + vi * EPC) = o.u;
       }
     }
   }
+  if constexpr (REC) fp8_rec_commit(r_amax, r_nsat, rec);
 }
 
 // Small feature maps (16x16, 8x8): one workgroup per (sample, group) holds the group's HW x C/32 elements in
@@ -326,12 +369,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
 // ~7-9 us each, both launch-latency bound at these sizes).  Sums in fp32 per lane, wave shuffles, the four wave
 // partials combined in fp64 in a fixed order (bitwise reproducible).
 #define GNS_MAXV 10
-template <typename T>
+template <typename T, bool REC = false>
 __global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x, long batch_stride, int ldc, int HW,
                                                         int Cn, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, int silu,
-                                                        T* __restrict__ y, long y_batch_stride, int ldy, float fp8_mul) {
+                                                        T* __restrict__ y, long y_batch_stride, int ldy, float fp8_mul,
+                                                        unsigned* __restrict__ rec) {
   constexpr int EPC = 16 / sizeof(T);
+  float r_amax = 0.f;
+  unsigned r_nsat = 0;
   __shared__ float s_ra[4], s_rq[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = blockIdx.x, b = blockIdx.y;
@@ -393,12 +439,16 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x, 
       if (fp8_mul != 0.f) {   // (y_batch_stride, ldy in bytes)
         unsigned char* y8 = reinterpret_cast<unsigned char*>(y) + (long)b * y_batch_stride + (long)g * cpg + (long)pix * ldy + vv * EPC;
 #pragma unroll
-        for (int e = 0; e < EPC; e += 4) *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+        for (int e = 0; e < EPC; e += 4) {
+          *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+          if constexpr (REC) fp8_rec_note4(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul, r_amax, r_nsat);
+        }
       } else {
         *reinterpret_cast<uint4*>(yb + (long)pix * ldy + vv * EPC) = o.u;
       }
     }
   }
+  if constexpr (REC) fp8_rec_commit(r_amax, r_nsat, rec);
 }
 
 // Row-group LayerNorm: RL lanes share a row (RL = 8 for bf16, 16 for f32), lane j holding vectors j, j+RL, ... of the
@@ -406,13 +456,16 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const T* __restrict__ x, 
 // fetches gamma / beta with 16 scalar loads per vector; here they sit in LDS and are read as 16-byte vectors).
 // One load instruction covers 64/RL rows x 128 contiguous bytes.  Same two-pass variance in fp32.
 #define LNG_MAXV 10
-template <typename T, int RL>
+template <typename T, int RL, bool REC = false>
 __global__ __launch_bounds__(256) void layernorm_rowgroup_kernel(const T* __restrict__ x, int ldx, long rows, int Cn,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
-                                                                  T* __restrict__ y, int ldy, float fp8_mul) {
+                                                                  T* __restrict__ y, int ldy, float fp8_mul,
+                                                                  unsigned* __restrict__ rec) {
   constexpr int EPC = 16 / sizeof(T);
   constexpr int RPB = 256 / RL;   // rows per block
+  float r_amax = 0.f;
+  unsigned r_nsat = 0;
   __shared__ __attribute__((aligned(16))) float s_g[1280 * 2];
   float* s_b = s_g + Cn;
   for (int c = threadIdx.x; c < Cn; c += 256) { s_g[c] = gamma[c]; s_b[c] = beta[c]; }
@@ -446,10 +499,13 @@ __global__ __launch_bounds__(256) void layernorm_rowgroup_kernel(const T* __rest
 #pragma unroll
   for (int o = RL / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
   const float rstd = rsqrtf(q / (float)Cn + eps);
-  if (!live) return;
+  if constexpr (!REC) {
+    if (!live) return;
+  }
+  // (REC: the lanes past the last row stay for the workgroup reduction and write nothing)
 #pragma unroll
   for (int i = 0; i < LNG_MAXV; ++i)
-    if (i < nv) {
+    if (i < nv && (!REC || live)) {
       const int c0 = (j + i * RL) * EPC;
       float g[EPC], bb[EPC];
 #pragma unroll
@@ -467,11 +523,15 @@ __global__ __launch_bounds__(256) void layernorm_rowgroup_kernel(const T* __rest
       if (fp8_mul != 0.f) {   // e4m3 output (ldy in bytes)
         unsigned char* y8 = reinterpret_cast<unsigned char*>(y) + row * ldy + c0;
 #pragma unroll
-        for (int e = 0; e < EPC; e += 4) *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+        for (int e = 0; e < EPC; e += 4) {
+          *reinterpret_cast<unsigned*>(y8 + e) = gn_pack4_e4m3(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul);
+          if constexpr (REC) fp8_rec_note4(ff[e], ff[e + 1], ff[e + 2], ff[e + 3], fp8_mul, r_amax, r_nsat);
+        }
       } else {
         *reinterpret_cast<uint4*>(y + row * ldy + c0) = o.u;
       }
     }
+  if constexpr (REC) fp8_rec_commit(r_amax, r_nsat, rec);
 }
 
 // ---------------------------------------------------------------------------
@@ -497,9 +557,10 @@ size_t af_gn_workspace_bytes(int B, int HW) {
 template <typename T>
 int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn, const float* gamma,
                         const float* beta, float eps, int silu, void* y, long y_bs, int ldy, void* workspace,
-                        hipStream_t stream, float fp8_mul, const float* pre_partial, int pre_npart) {
+                        hipStream_t stream, float fp8_mul, const float* pre_partial, int pre_npart, unsigned* fp8_rec) {
   constexpr int EPC = 16 / sizeof(T);
   if (fp8_mul != 0.f && sizeof(T) != 2) { af_set_error_msg("groupnorm: fp8 output needs the bf16 storage mode"); return -1; }
+  if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("groupnorm: an fp8 record needs the fp8 output"); return -1; }
   if (Cn % GN_GROUPS != 0 || Cn % EPC != 0 || Cn > GN_MAX_C || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("groupnorm: unsupported C=%d (need C%%32==0, C%%%d==0, C<=%d)", Cn, EPC, GN_MAX_C);
     return -1;
@@ -510,8 +571,13 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
     const int cpg = Cn / GN_GROUPS;
     const bool small_ok = g_af_knobs.gn_small != 0;
     if (small_ok && cpg % EPC == 0 && (long)HW * (cpg / EPC) <= 256 * GNS_MAXV && Cn % 4 == 0) {
-      hipLaunchKernelGGL((gn_small_kernel<T>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
-                         x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul);
+      if (fp8_rec) {   // (e4m3 output exists for bf16 only: no recording variant of the f32 kernels)
+        if constexpr (sizeof(T) == 2)
+          hipLaunchKernelGGL((gn_small_kernel<T, true>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
+                             x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
+      } else
+        hipLaunchKernelGGL((gn_small_kernel<T>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
+                           x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
       HIP_CHECK_RET(hipGetLastError());
       return 0;
     }
@@ -533,9 +599,15 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
   const double count = (double)HW * (double)(Cn / GN_GROUPS);
   const bool fold = npart <= 64;  // few chunks: the apply blocks finalize the statistics themselves
   if (!fold) hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, stream, partial, npart, count, eps, stats);
-  hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(nchunk, B), dim3(256), 0, stream,
-                     reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, stats, gamma, beta, silu,
-                     reinterpret_cast<T*>(y), y_bs, ldy, fold ? partial : nullptr, nchunk, count, eps, fp8_mul, npart);
+  if (fp8_rec) {
+    if constexpr (sizeof(T) == 2)
+      hipLaunchKernelGGL((gn_apply_kernel<T, true>), dim3(nchunk, B), dim3(256), 0, stream,
+                         reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, stats, gamma, beta, silu,
+                         reinterpret_cast<T*>(y), y_bs, ldy, fold ? partial : nullptr, nchunk, count, eps, fp8_mul, npart, fp8_rec);
+  } else
+    hipLaunchKernelGGL((gn_apply_kernel<T>), dim3(nchunk, B), dim3(256), 0, stream,
+                       reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, stats, gamma, beta, silu,
+                       reinterpret_cast<T*>(y), y_bs, ldy, fold ? partial : nullptr, nchunk, count, eps, fp8_mul, npart, fp8_rec);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -607,9 +679,10 @@ int af_launch_groupnorm_fold(const void* x, long x_bs, int ldx, int B, int HW, i
 
 template <typename T>
 int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* gamma, const float* beta,
-                        float eps, void* y, int ldy, hipStream_t stream, float fp8_mul) {
+                        float eps, void* y, int ldy, hipStream_t stream, float fp8_mul, unsigned* fp8_rec) {
   constexpr int EPC = 16 / sizeof(T);
   if (fp8_mul != 0.f && sizeof(T) != 2) { af_set_error_msg("layernorm: fp8 output needs the bf16 storage mode"); return -1; }
+  if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("layernorm: an fp8 record needs the fp8 output"); return -1; }
   if (Cn % EPC != 0 || Cn / EPC > 64 * LN_MAXV || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("layernorm: unsupported C=%d", Cn);
     return -1;
@@ -621,27 +694,38 @@ int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* 
   constexpr int RPB = 256 / RL;
   // (few rows of many vectors -- [4096, 1280] -- fill the chip better with one wave per row: measured 10 vs 19 us)
   if (NV % RL == 0 && NV / RL <= 10 && Cn <= 1280 && Cn % 4 == 0 && rows / RPB >= 256) {
-    hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
-                       reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul);
+    if (fp8_rec) {
+      if constexpr (sizeof(T) == 2)
+        hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL, true>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
+                           reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
+    } else
+      hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
+                         reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
     HIP_CHECK_RET(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL((layernorm_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
-                     reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
-                     reinterpret_cast<T*>(y), ldy, fp8_mul);
+  if (fp8_rec) {
+    if constexpr (sizeof(T) == 2)
+      hipLaunchKernelGGL((layernorm_kernel<T, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
+                         reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
+                         reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
+  } else
+    hipLaunchKernelGGL((layernorm_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
+                       reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
+                       reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
 
 template int af_launch_groupnorm<bf16>(const void*, long, int, int, int, int, const float*, const float*, float,
-                                       int, void*, long, int, void*, hipStream_t, float, const float*, int);
+                                       int, void*, long, int, void*, hipStream_t, float, const float*, int, unsigned*);
 template int af_launch_groupnorm<float>(const void*, long, int, int, int, int, const float*, const float*, float,
-                                        int, void*, long, int, void*, hipStream_t, float, const float*, int);
+                                        int, void*, long, int, void*, hipStream_t, float, const float*, int, unsigned*);
 template int af_launch_groupnorm_fold<bf16>(const void*, long, int, int, int, int, const float*, const float*, float, void*,
                                             hipStream_t, const float*, int, float*);
 template int af_launch_groupnorm_fold<float>(const void*, long, int, int, int, int, const float*, const float*, float, void*,
                                              hipStream_t, const float*, int, float*);
 template int af_launch_layernorm<bf16>(const void*, int, long, int, const float*, const float*, float, void*, int,
-                                       hipStream_t, float);
+                                       hipStream_t, float, unsigned*);
 template int af_launch_layernorm<float>(const void*, int, long, int, const float*, const float*, float, void*,
-                                        int, hipStream_t, float);
+                                        int, hipStream_t, float, unsigned*);

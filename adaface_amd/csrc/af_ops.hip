@@ -173,6 +173,13 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
   return 0;
 }
 
+// activation shifts of the fp8 mode: e4m3 of value * 2^s, s in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX] (adaface_hip.h)
+static bool act_shift_ok(int act_shift, const char* who) {
+  if (act_shift >= AF_FP8_SHIFT_MIN && act_shift <= AF_FP8_SHIFT_MAX) return true;
+  af_set_error_msg("%s: act_shift %d outside [%d, %d]", who, act_shift, AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX);
+  return false;
+}
+
 // fp8 convolution as the UNet's fp8 mode runs it (bf16 storage): x is cast to bf16, multiplied by 2^act_shift and stored
 // as e4m3 (what the GroupNorm kernels write), the weight is repacked to bf16 and quantised per output row
 // (af_launch_quant_weight_fp8), the ping-pong kernel multiplies on the block-scaled fp8 MFMA; bias / residual / output bf16.
@@ -181,6 +188,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
                      int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int upsample, int act_shift,
                      void* stream) {
   if ((ks != 1 && ks != 3) || pad != ks / 2 || Cin % 64 != 0) { af_set_error_msg("af_op_conv2d_fp8: ks 1|3, pad ks/2, Cin%%64==0"); return AF_ERR_INVALID; }
+  if (!act_shift_ok(act_shift, "af_op_conv2d_fp8")) return AF_ERR_INVALID;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int Hi = H << upsample, Wi = W << upsample;
@@ -196,7 +204,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   void* rn = nullptr;
   float* bn = nullptr;
   OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, Cin, 1.f, s));
-  OP_TRY(af_launch_cast_fp8(xn, x8, (long)nx, (float)(1 << act_shift), s));
+  OP_TRY(af_launch_cast_fp8(xn, x8, (long)nx, ldexpf(1.f, act_shift), s));
   OP_TRY(af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, Cin, ks, ldw, 0, 0, s));
   OP_TRY(af_launch_quant_weight_fp8(wn, rows_pad, ldw, Cin, ks, w8, k8, sc, s));
   if (bias_dev) {
@@ -229,28 +237,51 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
 }
 
 // GroupNorm (+SiLU) with the e4m3 output the fp8 convolutions read: y8_dev [B][H*W][C] bytes of result * 2^act_shift
-int af_op_groupnorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
-                        unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, void* stream) {
+// rec_out_dev (af_op_groupnorm_fp8_rec): two 32-bit words, {max |result| as a float, number of elements with |result * 2^act_shift| > 448}
+static int op_groupnorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
+                            unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, unsigned* rec_out_dev, void* stream) {
+  if (!act_shift_ok(act_shift, "af_op_groupnorm_fp8")) return AF_ERR_INVALID;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int HW = H * W;
   OP_ALLOC(xn, (size_t)B * HW * C * 2, false);
   OP_ALLOC(ws, af_gn_workspace_bytes(B, HW), false);
+  if (rec_out_dev && hipMemsetAsync(rec_out_dev, 0, 2 * sizeof(unsigned), s) != hipSuccess) return AF_ERR_HIP;
   OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s));
   OP_TRY(af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, y8_dev, (long)HW * C, C, ws, s,
-                                   (float)(1 << act_shift)));
+                                   ldexpf(1.f, act_shift), nullptr, 0, rec_out_dev));
   return 0;
+}
+int af_op_groupnorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
+                        unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, void* stream) {
+  return op_groupnorm_fp8(x_dev, gamma_dev, beta_dev, eps, silu, y8_dev, B, C, H, W, act_shift, nullptr, stream);
+}
+int af_op_groupnorm_fp8_rec(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
+                            unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, void* rec_out_dev, void* stream) {
+  if (!rec_out_dev) { af_set_error_msg("af_op_groupnorm_fp8_rec: null record"); return AF_ERR_INVALID; }
+  return op_groupnorm_fp8(x_dev, gamma_dev, beta_dev, eps, silu, y8_dev, B, C, H, W, act_shift, reinterpret_cast<unsigned*>(rec_out_dev), stream);
 }
 
 // LayerNorm with the e4m3 output the fp8 q / k / v projection reads: y8_dev [rows][C] bytes of result * 2^act_shift
-int af_op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
-                        int64_t rows, int C, int act_shift, void* stream) {
+static int op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
+                            int64_t rows, int C, int act_shift, unsigned* rec_out_dev, void* stream) {
+  if (!act_shift_ok(act_shift, "af_op_layernorm_fp8")) return AF_ERR_INVALID;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   OP_ALLOC(xn, (size_t)rows * C * 2, false);
+  if (rec_out_dev && hipMemsetAsync(rec_out_dev, 0, 2 * sizeof(unsigned), s) != hipSuccess) return AF_ERR_HIP;
   OP_TRY(af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s));
-  OP_TRY(af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, y8_dev, C, s, (float)(1 << act_shift)));
+  OP_TRY(af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, y8_dev, C, s, ldexpf(1.f, act_shift), rec_out_dev));
   return 0;
+}
+int af_op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
+                        int64_t rows, int C, int act_shift, void* stream) {
+  return op_layernorm_fp8(x_dev, gamma_dev, beta_dev, eps, y8_dev, rows, C, act_shift, nullptr, stream);
+}
+int af_op_layernorm_fp8_rec(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
+                            int64_t rows, int C, int act_shift, void* rec_out_dev, void* stream) {
+  if (!rec_out_dev) { af_set_error_msg("af_op_layernorm_fp8_rec: null record"); return AF_ERR_INVALID; }
+  return op_layernorm_fp8(x_dev, gamma_dev, beta_dev, eps, y8_dev, rows, C, act_shift, reinterpret_cast<unsigned*>(rec_out_dev), stream);
 }
 
 int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,

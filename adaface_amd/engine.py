@@ -6,6 +6,7 @@ current torch HIP stream.  PyTorch is used only for device memory and streams.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Iterable, Optional, Sequence
 
@@ -252,9 +253,76 @@ class Engine:
         return out
 
     def set_fp8(self, on: bool = True):
-        """af_set_fp8: the UNet's ResBlock 3x3 convolutions read e4m3 activations / weights (bf16 engines only)."""
+        """af_set_fp8: the UNet's ResBlock 3x3 convolutions and self-attention q / k / v projections read e4m3 activations /
+        weights (bf16 engines only).  Activation scales: 2^3 per site until calibrate_fp8 / set_fp8_shifts."""
         check(self._lib.af_set_fp8(self._h, 1 if on else 0), "af_set_fp8")
         self.fp8 = bool(on)
+
+    # -- fp8 mode: calibrated per-site activation scales (adaface_hip.h, af_fp8_*) ----------------
+    def fp8_site_names(self):
+        n = self._lib.af_fp8_num_sites(self._h)
+        return [self._lib.af_fp8_site_name(self._h, i).decode() for i in range(n)]
+
+    def fp8_shifts(self) -> Dict[str, int]:
+        names = self.fp8_site_names()
+        buf = (C.c_int * max(len(names), 1))()
+        check(self._lib.af_fp8_get_shifts(self._h, len(names), buf), "af_fp8_get_shifts")
+        return {n: int(buf[i]) for i, n in enumerate(names)}
+
+    def set_fp8_shifts(self, shifts: Optional[Dict[str, int]]):
+        """{site name: shift} for every site (unknown or missing names are refused); None: every site back to 2^3."""
+        if shifts is None:
+            check(self._lib.af_fp8_set_shifts(self._h, 0, None), "af_fp8_set_shifts")
+            return
+        from .fp8_calib import check_shifts
+        names = self.fp8_site_names()
+        shifts = check_shifts(shifts, names)
+        buf = (C.c_int * max(len(names), 1))(*[shifts[n] for n in names])
+        check(self._lib.af_fp8_set_shifts(self._h, len(names), buf), "af_fp8_set_shifts")
+
+    @contextlib.contextmanager
+    def fp8_record(self):
+        """Within the block every fp8-mode forward also records, per site, the largest |activation| its producer wrote and
+        how many elements saturated (fp8_read_record).  Entering zeroes the table; what the forwards write is unchanged."""
+        check(self._lib.af_fp8_record(self._h, 1, stream_ptr()), "af_fp8_record")
+        try:
+            yield self
+        except BaseException:
+            self._lib.af_fp8_record(self._h, 0, stream_ptr())      # (the exception under way is the one to report)
+            raise
+        check(self._lib.af_fp8_record(self._h, 0, stream_ptr()), "af_fp8_record")
+
+    def fp8_read_record(self) -> Dict[str, tuple]:
+        """{site name: (amax, nsat)} of the last recording (synchronises the current stream)."""
+        names = self.fp8_site_names()
+        amax = (C.c_float * max(len(names), 1))()
+        nsat = (C.c_int64 * max(len(names), 1))()
+        check(self._lib.af_fp8_read_record(self._h, len(names), amax, nsat, stream_ptr()), "af_fp8_read_record")
+        return {n: (float(amax[i]), int(nsat[i])) for i, n in enumerate(names)}
+
+    def calibrate_fp8(self, run, passes: int = 2, headroom: int = 1) -> Dict[str, tuple]:
+        """Static activation scales from a calibration run.  `run` drives this engine (forwards, or a whole sampler run) in
+        fp8 mode.  Per pass: record, run(), read, derive every site's shift from its recorded maximum, set the shifts.  The
+        second pass runs on the first pass's scales, so a trajectory that clipping distorted in pass one is measured again.
+        A site no forward reached keeps its shift.  Returns {site name: (amax, shift, nsat)} of the last pass -- nsat is what
+        saturated DURING that pass (on the previous pass's scales); nothing runs after it."""
+        from .fp8_calib import shift_for_amax
+        if not getattr(self, "fp8", False):
+            raise _lib.AfError("calibrate_fp8: switch the fp8 mode on first (set_fp8)")
+        if passes < 1:
+            raise ValueError("calibrate_fp8: at least one pass")
+        out = {}
+        for _ in range(passes):
+            with self.fp8_record():
+                run()
+                rec = self.fp8_read_record()
+            shifts = self.fp8_shifts()
+            for name, (amax, _n) in rec.items():
+                if amax > 0.0:
+                    shifts[name] = shift_for_amax(amax, headroom)
+            self.set_fp8_shifts(shifts)
+            out = {name: (amax, shifts[name], nsat) for name, (amax, nsat) in rec.items()}
+        return out
 
     def arena_bytes(self) -> int:
         return int(self._lib.af_arena_bytes(self._h))

@@ -53,11 +53,18 @@ class HipModule(nn.Module):
         super().__init__()
         object.__setattr__(self, "_engine", None)
         object.__setattr__(self, "_weights_dirty", True)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
+        # calibrated fp8 activation shifts {site name: shift} (None: the fixed 2^3).  They live here, not on the engine: the
+        # engine is rebuilt when the compute dtype or the device changes, and every fp8 engine gets them again
+        object.__setattr__(self, "_fp8_shifts", None)
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
     def _mark_dirty(self):
         object.__setattr__(self, "_weights_dirty", True)
+
+    def _after_load_state_dict(self):
+        self._mark_dirty()
+        self.set_fp8_shifts(None)      # a calibration belongs to the checkpoint it was made with
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
@@ -95,10 +102,64 @@ class HipModule(nn.Module):
                                                        **self._engine_kwargs()))
             if fp8:
                 self._engine.set_fp8(True)
+                if self._fp8_shifts is not None:
+                    try:
+                        self._engine.set_fp8_shifts(self._fp8_shifts)
+                    except KeyError as e:
+                        raise KeyError(f"{type(self).__name__}: the shifts given to set_fp8_shifts / load_fp8_scales do not "
+                                       f"name this model's fp8 sites ({e.args[0]})") from None
             self._mark_dirty()
         if self._weights_dirty:
             self.sync_weights()
         return self._engine
+
+    # ---- fp8 mode: calibrated activation scales --------------------------------------------
+    def _fp8_engine(self, device):
+        if self.compute_dtype != "fp8":
+            raise RuntimeError(f"{type(self).__name__}: set_compute_dtype('fp8') first (compute dtype is {self.compute_dtype})")
+        return self.engine(torch.device(device))
+
+    def fp8_shifts(self):
+        """The calibrated shifts {site name: shift}, or None while the fp8 mode runs on the fixed 2^3."""
+        return None if self._fp8_shifts is None else dict(self._fp8_shifts)
+
+    def set_fp8_shifts(self, shifts):
+        """Keep `shifts` ({site name: shift} for every fp8 site; None = back to 2^3) and apply them to the live engine.  A
+        load_state_dict clears them: a calibration belongs to a checkpoint, so load scales after weights.
+        Every value must be an integer in [-16, 8] (checked here).  The site NAMES are only known to an engine: with a
+        live fp8 engine they are checked here too, otherwise when the next fp8 engine is built (engine() then raises a
+        KeyError that names this call)."""
+        if shifts is not None:
+            from adaface_amd.fp8_calib import check_shifts
+            shifts = check_shifts(shifts, list(shifts))          # (values; the names against themselves)
+        eng = self._engine if self.compute_dtype == "fp8" else None
+        if eng is not None:
+            eng.set_fp8_shifts(shifts)          # (validates the names against the engine's sites)
+        object.__setattr__(self, "_fp8_shifts", shifts)
+        return self
+
+    def calibrate_fp8(self, run, device, passes: int = 2, headroom: int = 1):
+        """Engine.calibrate_fp8 on this module's fp8 engine; the shifts are kept for every later engine.  `run` drives the
+        module (forwards or a sampler run).  Returns {site name: (amax, shift, nsat of the last pass)}."""
+        eng = self._fp8_engine(device)
+        out = eng.calibrate_fp8(run, passes=passes, headroom=headroom)
+        if self._engine is not eng:
+            raise RuntimeError("calibrate_fp8: `run` rebuilt the engine (compute dtype or device changed during calibration)")
+        object.__setattr__(self, "_fp8_shifts", eng.fp8_shifts())
+        return out
+
+    def save_fp8_scales(self, path):
+        """Write the calibrated shifts as JSON keyed by site name (adaface_amd.fp8_calib.save_scales)."""
+        from adaface_amd.fp8_calib import save_scales
+        if self._fp8_shifts is None:
+            raise RuntimeError("save_fp8_scales: nothing calibrated or loaded")
+        save_scales(path, self._fp8_shifts)
+
+    def load_fp8_scales(self, path, device):
+        """Read a scale file; a file whose site names are not exactly this model's fp8 sites is refused."""
+        from adaface_amd.fp8_calib import load_scales
+        eng = self._fp8_engine(device)
+        return self.set_fp8_shifts(load_scales(path, eng.fp8_site_names()))
 
     def sync_weights(self):
         """Upload (repack) every parameter into the engine."""

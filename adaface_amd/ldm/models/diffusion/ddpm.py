@@ -248,6 +248,36 @@ class LatentDiffusion(DDPM):
             return self.scale_factor * encoder_posterior
         raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
 
+    # ---- fp8 mode: calibrated activation scales (adaface_hip.h, af_fp8_*) --------------------------
+    @torch.no_grad()
+    def calibrate_fp8(self, conditioning, unconditional_conditioning=None, shape=None, batch_size=1, S=10,
+                      guidance_scale=7.5, x_T=None, passes=2, headroom=1):
+        """Static per-site activation scales for the fp8 mode from a short DDIM sample (S steps, eta 0) with the caller's
+        conditioning (as get_learned_conditioning returns it).  Needs set_compute_dtype('fp8') and weights loaded.  The
+        sample is run `passes` times, each on the scales the one before derived.  Returns {site name: (amax, shift, nsat
+        of the last pass)}; the shifts stay with the UNet module (save_fp8_scales) until the next load_state_dict."""
+        from adaface_amd.ldm.models.diffusion.ddim import DDIMSampler
+        unet = self.model.diffusion_model
+        if shape is None:
+            shape = [unet.in_channels, unet.image_size, unet.image_size]
+        if x_T is None:
+            x_T = torch.randn(batch_size, *shape, generator=torch.Generator().manual_seed(0)).to(self.device)
+        sampler = DDIMSampler(self)
+
+        def run():
+            sampler.sample(S=S, conditioning=conditioning, batch_size=batch_size, shape=list(shape), verbose=False,
+                           guidance_scale=guidance_scale, unconditional_conditioning=unconditional_conditioning, eta=0.0,
+                           x_T=x_T)
+        return unet.calibrate_fp8(run, self.device, passes=passes, headroom=headroom)
+
+    def save_fp8_scales(self, path):
+        self.model.diffusion_model.save_fp8_scales(path)
+
+    def load_fp8_scales(self, path):
+        """Load scales AFTER the weights (load_state_dict clears them) and with the compute dtype at 'fp8'."""
+        self.model.diffusion_model.load_fp8_scales(path, self.device)
+        return self
+
     def set_compute_dtype(self, dtype: str):
         """'bf16' | 'f32' | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16)."""
         rest = "bf16" if dtype == "fp8" else dtype

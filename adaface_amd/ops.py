@@ -42,7 +42,13 @@ def conv2d(x, weight, bias=None, stride=1, padding=None, upsample=False, residua
     return y
 
 
-FP8_ACT_SHIFT = 3   # fp8 activations hold value * 2^3 (AF_FP8_ACT_SHIFT in csrc/af_model.hip)
+FP8_ACT_SHIFT = 3   # fp8 activations hold value * 2^s; s = 3 until a site is calibrated (AF_FP8_SHIFT_DEFAULT, adaface_hip.h)
+
+
+def _fp8_record(rec):
+    """The two 32-bit words an af_op_*_fp8_rec call wrote -> (amax: float, nsat: int)."""
+    words = rec.cpu()
+    return float(words.view(torch.float32)[0]), int(words[1]) & 0xFFFFFFFF
 
 
 def conv2d_fp8(x, weight, bias=None, stride=1, upsample=False, residual=None, act_shift=FP8_ACT_SHIFT):
@@ -65,24 +71,37 @@ def conv2d_fp8(x, weight, bias=None, stride=1, upsample=False, residual=None, ac
     return y
 
 
-def group_norm_fp8(x, weight, bias, eps=1e-5, silu=False, act_shift=FP8_ACT_SHIFT):
-    """GroupNorm(32) [+ SiLU] written as e4m3 bytes of result * 2^act_shift: uint8 [B, H*W, C] (NHWC)."""
+def group_norm_fp8(x, weight, bias, eps=1e-5, silu=False, act_shift=FP8_ACT_SHIFT, record=False):
+    """GroupNorm(32) [+ SiLU] written as e4m3 bytes of result * 2^act_shift: uint8 [B, H*W, C] (NHWC).
+    record=True: returns (bytes, (amax, nsat)), the calibration record of the call: the largest |result| the kernel saw and
+    the number of elements with |result * 2^act_shift| > 448."""
     lib = _lib.load()
     x = _dev_f32(x)
     B, Cn, H, W = x.shape
     y = torch.empty(B, H * W, Cn, device=x.device, dtype=torch.uint8)
+    if record:
+        rec = torch.zeros(2, device=x.device, dtype=torch.int32)
+        check(lib.af_op_groupnorm_fp8_rec(ptr(x), ptr(_dev_f32(weight)), ptr(_dev_f32(bias)), eps, 1 if silu else 0, ptr(y), B,
+                                          Cn, H, W, act_shift, ptr(rec), stream_ptr()), "af_op_groupnorm_fp8_rec")
+        return y, _fp8_record(rec)
     check(lib.af_op_groupnorm_fp8(ptr(x), ptr(_dev_f32(weight)), ptr(_dev_f32(bias)), eps, 1 if silu else 0, ptr(y), B, Cn,
                                   H, W, act_shift, stream_ptr()), "af_op_groupnorm_fp8")
     return y
 
 
-def layer_norm_fp8(x, weight, bias, eps=1e-5, act_shift=FP8_ACT_SHIFT):
-    """LayerNorm over the last dim written as e4m3 bytes of result * 2^act_shift: uint8, same shape as x."""
+def layer_norm_fp8(x, weight, bias, eps=1e-5, act_shift=FP8_ACT_SHIFT, record=False):
+    """LayerNorm over the last dim written as e4m3 bytes of result * 2^act_shift: uint8, same shape as x.
+    record=True: returns (bytes, (amax, nsat)) as group_norm_fp8."""
     lib = _lib.load()
     x = _dev_f32(x)
     Cn = x.shape[-1]
     rows = x.numel() // Cn
     y = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    if record:
+        rec = torch.zeros(2, device=x.device, dtype=torch.int32)
+        check(lib.af_op_layernorm_fp8_rec(ptr(x), ptr(_dev_f32(weight)), ptr(_dev_f32(bias)), eps, ptr(y), rows, Cn, act_shift,
+                                          ptr(rec), stream_ptr()), "af_op_layernorm_fp8_rec")
+        return y, _fp8_record(rec)
     check(lib.af_op_layernorm_fp8(ptr(x), ptr(_dev_f32(weight)), ptr(_dev_f32(bias)), eps, ptr(y), rows, Cn, act_shift,
                                   stream_ptr()), "af_op_layernorm_fp8")
     return y

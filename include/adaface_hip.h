@@ -238,10 +238,34 @@ int af_op_groupnorm(int dtype, const float* x_dev, const float* gamma_dev, const
 /* fp8 (OCP e4m3) operand variant of the UNet's ResBlock convolutions (BASELINE config 4: "fp8 MFMA QKV/conv"; the
  * reference has no fp8 path: torch autocast fp16 at most, scripts/stable_txt2img.py:711).  af_set_fp8(h, 1) on a bf16
  * handle: GroupNorm + SiLU (openaimodel.py:259-263, in_layers / out_layers) writes e4m3 and the 3x3 convolutions that read
- * it multiply on v_mfma_scale_f32_16x16x128_f8f6f4 with power-of-two scales (per output channel for the weights, 2^3 for
- * the activations); likewise norm1 -> to_q / to_k / to_v of every BasicTransformerBlock's self-attention
- * (attention.py:195-196, 275-285); everything else stays bf16.  Tolerance: tests/test_fp8_gpu.py. */
+ * it multiply on v_mfma_scale_f32_16x16x128_f8f6f4 with power-of-two scales (per output channel for the weights, one
+ * static 2^s per fp8 site for the activations: s = 3 unless calibrated, see af_fp8_record / af_fp8_set_shifts below);
+ * likewise norm1 -> to_q / to_k / to_v of every BasicTransformerBlock's self-attention (attention.py:195-196, 275-285);
+ * everything else stays bf16.  Tolerance: tests/test_fp8_gpu.py, tests/test_fp8_calib_gpu.py.  PARITY UNPINNED. */
 int af_set_fp8(af_handle* h, int on);
+/* Calibrated activation scales of the fp8 mode.  An fp8 SITE is one (producer -> fp8 consumer) pair of the UNet: ResBlock
+ * in_layers.0 -> in_layers.2, out_layers.0 -> out_layers.3, and norm1 -> attn1.to_q|k|v of every transformer block (every
+ * weight that gets an fp8 twin, whether or not today's shape is planned onto the fp8 kernel).  The producer writes e4m3 of
+ * value * 2^s, the consumer's activation scale is 2^-s; s is a per-site integer in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX],
+ * AF_FP8_SHIFT_DEFAULT (values beyond +-56 saturate) until set.  The scales are STATIC: an input whose activations exceed
+ * 448 / 2^s still saturates (a clamp: finite); recording is how a caller sees that.  f32 handles have no sites. */
+#define AF_FP8_SHIFT_MIN (-16)
+#define AF_FP8_SHIFT_MAX 8
+#define AF_FP8_SHIFT_DEFAULT 3
+int af_fp8_num_sites(af_handle* h);
+const char* af_fp8_site_name(af_handle* h, int i); /* checkpoint key of the consumer's weight (attn1: its to_q.weight) */
+/* on = 1: zero the record table; the fp8-mode forwards that follow also record, per site, the largest |value| the producer
+ * wrote (before scaling and clamping) and how many elements saturated.  on = 0: stop.  Recording never changes what a
+ * forward writes; the table is bit-reproducible (integer atomic max / add, one of each per workgroup). */
+int af_fp8_record(af_handle* h, int on, void* stream);
+/* synchronises `stream` and copies the table back: amax[n], nsat[n] (n = af_fp8_num_sites; a site no forward reached: 0, 0;
+ * nsat counts modulo 2^32) */
+int af_fp8_read_record(af_handle* h, int n, float* amax, int64_t* nsat, void* stream);
+int af_fp8_get_shifts(af_handle* h, int n, int* shifts);
+int af_fp8_set_shifts(af_handle* h, int n, const int* shifts); /* shifts = NULL: every site back to AF_FP8_SHIFT_DEFAULT */
+/* pure host function (no GPU, no handle): the largest s in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX] with
+ * amax * 2^(s + headroom) <= 448; amax <= 0, infinite or NaN -> AF_FP8_SHIFT_DEFAULT */
+int af_fp8_shift_for_amax(float amax, int headroom);
 int64_t af_fp8_gemm_launches(void); /* launches on the fp8 kernel since af_gemm_plan_counts_reset */
 int64_t af_halo8_launches(void);    /* launches of the eight-wave LDS-halo 3x3 kernel (also counted under tile 5) */
 int64_t af_gn_producer_launches(void); /* convolutions that also wrote the GroupNorm partial sums of their output (no statistics pass in the consumer) */
@@ -268,6 +292,12 @@ int af_op_groupnorm_fp8(const float* x_dev, const float* gamma_dev, const float*
                         unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, void* stream);
 int af_op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
                         int64_t rows, int C, int act_shift, void* stream);
+/* the two producers with the calibration record of the call: rec_out_dev = two 32-bit device words, {max |result| as a
+ * float, number of elements with |result * 2^act_shift| > 448 as an unsigned}.  act_shift of every fp8 op: [-16, 8]. */
+int af_op_groupnorm_fp8_rec(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
+                            unsigned char* y8_dev, int B, int C, int H, int W, int act_shift, void* rec_out_dev, void* stream);
+int af_op_layernorm_fp8_rec(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
+                            int64_t rows, int C, int act_shift, void* rec_out_dev, void* stream);
 /* GroupNorm(32) (no SiLU) + 1x1 convolution (SpatialTransformer.norm + proj_in, attention.py:325-326) on the same bf16
  * operands both ways: y_plain = apply pass + GEMM, y_fused = row-panel GEMM that normalises its rows in its prologue.
  * x [B,C,H,W], w [N,C], outputs [B,N,H,W] fp32; fails when the shape has no row-panel launch. */

@@ -53,7 +53,13 @@ def parse_args():
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
                     help="data-parallel ranks (one process per GPU); without a launcher the ranks are started here")
-    ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
+    ap.add_argument("--dtype", choices=["bf16", "f32", "fp8"], default="bf16",
+                    help="fp8: bf16 with the UNet's ResBlock convolutions and self-attention q/k/v on e4m3 operands (PARITY UNPINNED)")
+    ap.add_argument("--fp8_calib_steps", type=int, default=10,
+                    help="--dtype fp8: DDIM steps of the calibration sample that sets the per-layer activation scales "
+                         "(two passes, with this run's conditioning); 0 = keep the fixed 2^3, which clips beyond +-56")
+    ap.add_argument("--fp8_scales", type=str, default=None,
+                    help="--dtype fp8: JSON file of calibrated scales: loaded if present, else written after the calibration")
     return ap.parse_args()
 
 
@@ -125,6 +131,44 @@ def main():
         raise SystemExit("give --prompt_emb (pre-computed CLIP/AdaFace embedding) or --synthetic")
     c = model.get_learned_conditioning(shard_batch(c_all, rank, world, per_sample=16).to(device))
     uc = model.get_learned_conditioning(shard_batch(uc_all, rank, world, per_sample=16).to(device))
+    if opt.dtype == "fp8":
+        # static activation scales: from the file when it exists, else from a short calibration sample with this run's
+        # conditioning.  With several ranks and a file to write, rank 0 calibrates on its shard and the others load what it
+        # wrote; without a file every rank calibrates on its own shard
+        def calibrate():
+            lat = [opt.C, opt.H // opt.f, opt.W // opt.f]
+            x_cal = torch.randn([b] + lat, generator=torch.Generator().manual_seed(opt.seed + 3))
+            cal = model.calibrate_fp8(c, uc, shape=lat, batch_size=b, S=opt.fp8_calib_steps,
+                                      guidance_scale=opt.scale if len(opt.scale) > 1 else opt.scale[0], x_T=x_cal.to(device))
+            shifts = sorted(set(s for _, s, _ in cal.values()))
+            print(f"[rank {rank}] fp8 calibration: {len(cal)} sites, shifts {shifts[0]} .. {shifts[-1]}, largest |activation| "
+                  f"{max(a for a, _, _ in cal.values()):.1f}, {sum(k for _, _, k in cal.values())} elements saturated in the last pass")
+            if opt.fp8_scales:
+                model.save_fp8_scales(opt.fp8_scales)
+
+        def agreed(flag):     # rank 0's answer on every rank (each rank looking for itself could disagree while rank 0 writes)
+            if world == 1:
+                return bool(flag)
+            t = torch.tensor([int(bool(flag))], device=device)
+            dist.broadcast(t, 0)
+            return bool(t.item())
+
+        if agreed(bool(opt.fp8_scales) and os.path.exists(opt.fp8_scales)):
+            model.load_fp8_scales(opt.fp8_scales)
+        elif opt.fp8_calib_steps > 0:
+            if opt.fp8_scales and world > 1:
+                err = None
+                if rank == 0:
+                    try:
+                        calibrate()
+                    except Exception as e:      # the others wait in the broadcast below: tell them before leaving
+                        err = e
+                if not agreed(err is None):
+                    raise SystemExit(f"[rank {rank}] fp8 calibration failed on rank 0" + (f": {err!r}" if err is not None else ""))
+                if rank != 0:
+                    model.load_fp8_scales(opt.fp8_scales)
+            else:
+                calibrate()
     if opt.plms:
         from ldm.models.diffusion.plms import PLMSSampler
         sampler = PLMSSampler(model)

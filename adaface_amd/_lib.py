@@ -91,6 +91,10 @@ _SIGS = [
     ("af_op_conv_gn", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P] + [C.c_int] * 5 + [_P]),
     ("af_set_fp8", C.c_int, [_P, C.c_int]),
     ("af_fp8_gemm_launches", C.c_int64, []),
+    ("af_set_fp8_scope", C.c_int, [_P, C.c_int]),
+    ("af_get_fp8_scope", C.c_int, [_P]),
+    ("af_ff8_launches", C.c_int64, []),
+    ("af_op_ff_fp8", C.c_int, [_P] * 4 + [C.c_float] + [_P] * 5 + [C.c_int64] + [C.c_int] * 5 + [_P, _P, _P, C.POINTER(C.c_int), _P]),
     ("af_fp8_num_sites", C.c_int, [_P]),
     ("af_fp8_site_name", C.c_char_p, [_P, C.c_int]),
     ("af_fp8_record", C.c_int, [_P, C.c_int, _P]),
@@ -163,6 +167,7 @@ def plan_counts(reset: bool = False) -> dict:
     out = {f"tile{i}": int(c[i]) for i in range(6)}
     out["halo"], out["splitk"], out["ln_consumer"], out["ln_producer"] = int(c[6]), int(c[7]), int(c[8]), int(c[9])
     out["fp8"] = int(lib.af_fp8_gemm_launches())
+    out["ff8"] = int(lib.af_ff8_launches())
     out["halo8"] = int(lib.af_halo8_launches())
     out["rowpanel"] = int(lib.af_rowpanel_launches())
     out["up_phase4"] = int(lib.af_up_phase4_launches())

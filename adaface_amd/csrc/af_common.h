@@ -106,6 +106,12 @@ struct AfKnobs {
   int xattn_fused;          // AF_XATTN_FUSED          0 = cross-attention of the 64x64-level transformers as three launches (to_q,
                             //                         short-key attention, to_out + residual) instead of xattn_fused_kernel
   int plan_log;             // AF_PLAN_LOG             1 = one stderr line per GEMM / convolution launch: shape, tile, K slices (lab)
+  // fp8 mode, FeedForward scope: the level rule.  A transformer block keeps its FeedForward on bf16 when its
+  // width C (the K of the GEGLU GEMM) is below ff8_min_k or its rows (B * H * W) are below ff8_min_rows
+  int ff8_min_k;            // AF_FF8_MIN_K            512: four K tiles of 128 at least.  At C = 320 (64x64 level) the e4m3 GEGLU has
+                            //                         2.5 K tiles, is bound by its GELU epilogue, and the fp8 pair with its LayerNorm
+                            //                         pass measured 223 us against 192 us for the bf16 pair
+  int ff8_min_rows;         // AF_FF8_MIN_ROWS         0: no floor (16x16 and 8x8 levels measured 1.47x / 1.32x)
 };
 extern AfKnobs g_af_knobs;
 
@@ -197,6 +203,54 @@ __device__ __forceinline__ f32x2 gelu_bf16out_f2(f32x2 x) {
   q = q * s + 3.97883296e-01f;
   const f32x2 ph = xc * q + 0.5f;
   return x * ph;
+}
+
+// fp8 output (the consumer is a convolution on the block-scaled fp8 MFMA): OCP e4m3 bytes of value * mul, saturating
+__device__ __forceinline__ unsigned gn_pack4_e4m3(float a, float b, float c, float d, float mul) {
+  a = __builtin_amdgcn_fmed3f(a * mul, -448.f, 448.f);
+  b = __builtin_amdgcn_fmed3f(b * mul, -448.f, 448.f);
+  c = __builtin_amdgcn_fmed3f(c * mul, -448.f, 448.f);
+  d = __builtin_amdgcn_fmed3f(d * mul, -448.f, 448.f);
+  int v = 0;
+  v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
+  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
+  return (unsigned)v;
+}
+
+// fp8 calibration record (af_fp8_record): what a producer saw at one fp8 site, {max |f| as float bits, elements with
+// |f * mul| > 448}.  f is the fp32 value BEFORE the multiplication and the clamp.  Non-negative floats order like
+// unsigned integers, and integer max / add do not depend on arrival order: the record is bit-reproducible run to run.
+__device__ __forceinline__ void fp8_rec_note4(float a, float b, float c, float d, float mul, float& amax, unsigned& nsat) {
+  a = fabsf(a); b = fabsf(b); c = fabsf(c); d = fabsf(d);
+  amax = fmaxf(fmaxf(amax, fmaxf(a, b)), fmaxf(c, d));
+  nsat += (unsigned)(a * mul > 448.f) + (unsigned)(b * mul > 448.f) + (unsigned)(c * mul > 448.f) + (unsigned)(d * mul > 448.f);
+}
+// every thread of the workgroup (WAVES waves of 64) calls this once: wave shuffles, the wave partials through LDS, then ONE
+// atomic max and ONE atomic add per workgroup
+template <int WAVES = 4>
+__device__ __forceinline__ void fp8_rec_commit(float amax, unsigned nsat, unsigned* __restrict__ rec) {
+  __shared__ unsigned s_rec[2 * WAVES];
+  unsigned m = __float_as_uint(amax);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    nsat += (unsigned)__shfl_xor((int)nsat, o, 64);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { s_rec[wave] = m; s_rec[WAVES + wave] = nsat; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if constexpr (WAVES == 4) {   // (written out: the code of the four-wave producers stays what it was)
+      atomicMax(rec, max(max(s_rec[0], s_rec[1]), max(s_rec[2], s_rec[3])));
+      atomicAdd(rec + 1, s_rec[4] + s_rec[5] + s_rec[6] + s_rec[7]);
+    } else {
+      unsigned mm = s_rec[0], nn = s_rec[WAVES];
+#pragma unroll
+      for (int w = 1; w < WAVES; ++w) { mm = max(mm, s_rec[w]); nn += s_rec[WAVES + w]; }
+      atomicMax(rec, mm);
+      atomicAdd(rec + 1, nn);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------

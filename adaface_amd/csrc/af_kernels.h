@@ -32,6 +32,12 @@ int af_launch_xattn_fused_permute_wo(const void* w, int ldw, int rows, void* wp,
 int af_launch_xattn_fused(const AfXattnFusedParams& a, hipStream_t stream);
 extern std::atomic<long> g_af_xattn_fused_launches;
 
+// FeedForward scope of the fp8 mode (ff_geglu_fp8_kernel, af_conv_gemm.hip): e4m3 x [M][K] times the e4m3 twin of a GEGLU
+// projection -> e4m3 bytes of value * gelu(gate) * out_mul, p.out [M][p.ldo >= N / 2]; rec: optional fp8 calibration record
+bool af_ff_geglu_fp8_ok(const ConvGemmParams& p);
+int af_launch_ff_geglu_fp8(ConvGemmParams p, float out_mul, unsigned* rec, hipStream_t stream);
+extern std::atomic<long> g_af_ff8_launches;
+
 size_t af_gn_workspace_bytes(int B, int HW);
 template <typename T>
 int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn, const float* gamma,

@@ -54,7 +54,7 @@ AfKnobs g_af_knobs = {
     knob_env("AF_LN_FUSE", 1),         knob_env("AF_GEGLU_ROWPANEL", 4), knob_env("AF_CONV_HALO8", 3), knob_env("AF_ABLATE", 0),
     knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1), knob_env("AF_ATTN_SHORT", 1),
     knob_env("AF_GEMM_M128", 1),       knob_env("AF_SMALL_M_TILE64", 1),  knob_env("AF_GN_CONSUMER", 1),
-    knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0)};
+    knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0),      knob_env("AF_FF8_MIN_K", 512),   knob_env("AF_FF8_MIN_ROWS", 0)};
 static const AfKnobs g_af_knobs_initial = g_af_knobs;
 static int* knob_slot(const char* name) {
   static const struct { const char* n; int AfKnobs::*m; } tab[] = {
@@ -65,7 +65,7 @@ static int* knob_slot(const char* name) {
       {"gn_small", &AfKnobs::gn_small}, {"ln_fuse", &AfKnobs::ln_fuse},
       {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"ablate", &AfKnobs::ablate}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4},
       {"attn_short", &AfKnobs::attn_short},
-      {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}};
+      {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}, {"ff8_min_k", &AfKnobs::ff8_min_k}, {"ff8_min_rows", &AfKnobs::ff8_min_rows}};
   if (!name) return nullptr;
   for (auto& t : tab)
     if (strcmp(t.n, name) == 0) return &(g_af_knobs.*(t.m));
@@ -296,6 +296,12 @@ struct af_handle {
   bool ln_fold_dirty = true;   // folded LayerNorm twins must be recomputed (a UNet tensor was loaded since)
   bool fp8_on = false;         // af_set_fp8: ResBlock 3x3 convolutions of the UNet on the block-scaled fp8 MFMA
   bool fp8_dirty = true;       // fp8 weight twins must be (re)quantised
+  // af_set_fp8_scope: AF_FP8_SCOPE_BASE (the ResBlock convolutions and self-attention q / k / v) | AF_FP8_SCOPE_FF (GEGLU +
+  // ff.net.2 of the transformer blocks).  The FF sites follow the fp8_nbase base sites in the tables below; the ABI shows them
+  // (and their twins exist) only while the scope holds them.
+  int fp8_scope = AF_FP8_SCOPE_BASE;
+  int fp8_nbase = 0;
+  int fp8_nsites() const { return (fp8_scope & AF_FP8_SCOPE_FF) ? (int)fp8_shift.size() : fp8_nbase; }
   // fp8 sites (register_fp8_sites): activation shift per site, the checkpoint key of the consumer's weight, and the device
   // record table [n][2] = {max |value| as float bits, saturated elements} the producers update while fp8_recording
   std::vector<int> fp8_shift;
@@ -855,6 +861,30 @@ struct Runner {
     conv_params(p, L, x8, out, stride, up, nullptr, nullptr, 0, -1, -1);
     return af_plan_conv_gemm(p, 1, 2).tile >= 4;
   }
+  // FeedForward scope: would BOTH GEMMs of a transformer block's FeedForward run on fp8 operands -- ff1 (GEGLU, e4m3 output,
+  // ff_geglu_fp8_kernel) on e4m3(norm3 x) and ff2 on its bytes?  From the scope, the shapes and the twins alone.
+  bool ff8_capable(const Linear& ff1, const Linear& ff2, const Act& x, const Act& out) const {
+    if (!h->fp8_on || !(h->fp8_scope & AF_FP8_SCOPE_FF) || dt != AF_DTYPE_BF16 || !ff1.w8 || !ff2.w8 || ff1.f8_site < 0 ||
+        ff2.f8_site < 0 || !ff1.geglu || ff1.ks != 1 || x.C != ff1.cin || ff1.cin != ff1.cin_pad || ff1.cout != 2 * ff2.cin ||
+        x.C < g_af_knobs.ff8_min_k || x.npix() < (long)g_af_knobs.ff8_min_rows)   // (the level rule: AfKnobs)
+      return false;
+    Act x8 = x;
+    x8.f8 = true; x8.ld = x.C;
+    Act f8 = x8;
+    f8.C = f8.ld = ff2.cin;
+    ConvGemmParams p;
+    conv_params(p, ff1, x8, f8, 1, 0, nullptr, nullptr, 0, ff1.cout, -1);
+    return af_ff_geglu_fp8_ok(p) && fp8_capable(ff2, f8, out);
+  }
+  // y8 = e4m3(geglu(ff1 x8) * 2^shift of y8's site)
+  int ff_geglu8(const Linear& L, const Act& x8, Act& y8) {
+    AF_TRY(check(y8));
+    if (!x8.f8 || !y8.f8 || !L.w8) { af_set_error_msg("ff_geglu8: e4m3 operands and an fp8 weight twin needed"); return AF_ERR_STATE; }
+    ConvGemmParams p;
+    conv_params(p, L, x8, y8, 1, 0, nullptr, nullptr, 0, L.cout, -1);
+    if (dry) return 0;
+    return af_launch_ff_geglu_fp8(p, ldexpf(1.f, y8.f8_shift), fp8_rec_of(y8), s);
+  }
   // would this 1x1 GEMM run on the ping-pong kernel in one K slice (the only place the LayerNorm epilogues exist)?
   // returns the number of 80-column statistics slabs its output rows would be cut into (0 = no)
   int ln_capable(const Linear& L, const Act& x, const Act& out, int n_valid = -1) const {
@@ -1271,6 +1301,18 @@ static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin
     }
     }
     // --- x = ff(norm3(x)) + x ---
+    // FeedForward scope of the fp8 mode: LayerNorm writes e4m3, GEGLU multiplies on the fp8 MFMA and writes e4m3 at the scale
+    // of ff.net.2's site, ff.net.2 (residual, bf16 output) runs on the plain fp8 launch.  Both GEMMs or neither; not where a
+    // following block of this transformer expects ff.net.2's LayerNorm partial sums (an fp8 launch does not write them).
+    if (!(ln_parts && d + 1 < w.blocks.size()) && R.ff8_capable(blk.ff1, blk.ff2, t2, t)) {
+      Act n8 = R.alloc_act8(B, H, W, C, blk.ff1);
+      AF_TRY(R.layernorm(blk.ln3, t2, n8));
+      Act f8 = R.alloc_act8(B, H, W, 4 * C, blk.ff2);
+      AF_TRY(R.ff_geglu8(blk.ff1, n8, f8));
+      AF_TRY(R.conv(blk.ff2, f8, t, 1, 0, &t2, nullptr, 0));
+      R.A.release(mk2);
+      continue;
+    }
     Act f = R.alloc_act(B, H, W, 4 * C);
     if (ln_parts) {
       const Runner::LnArgs ca = consumer(st_2, blk.ff1_cs, blk.ln3);
@@ -1314,12 +1356,22 @@ static int fold_layernorms(af_handle* h, hipStream_t s) {
   return 0;
 }
 
-// the weights that get an fp8 twin: the UNet ResBlock convolutions and the self-attention q / k / v projections
-static std::vector<Linear*> fp8_twin_list(af_handle* h) {
+// the weights that get an fp8 twin: the UNet ResBlock convolutions and the self-attention q / k / v projections (scope BASE),
+// then -- scope FF -- ff.net.0.proj and ff.net.2 of every transformer block
+static std::vector<Linear*> fp8_twin_list(af_handle* h, int scope) {
   std::vector<Linear*> twins;
-  for (auto& r : h->res) { twins.push_back(&r.c1); twins.push_back(&r.c2); }
-  for (auto& x : h->xf)      // "fp8 MFMA QKV": the self-attention q / k / v projection (attention.py:195-196, fused qkv1)
-    for (auto& t : x.blocks) twins.push_back(&t.qkv1);
+  if (scope & AF_FP8_SCOPE_BASE) {
+    for (auto& r : h->res) { twins.push_back(&r.c1); twins.push_back(&r.c2); }
+    for (auto& x : h->xf)      // "fp8 MFMA QKV": the self-attention q / k / v projection (attention.py:195-196, fused qkv1)
+      for (auto& t : x.blocks) twins.push_back(&t.qkv1);
+  }
+  if (scope & AF_FP8_SCOPE_FF)
+    for (auto& x : h->xf)
+      for (auto& t : x.blocks) {
+        if (t.ff1.cin_pad % 64 != 0 || t.ff2.cin_pad % 64 != 0) continue;   // (a block gets both sites or none)
+        twins.push_back(&t.ff1);
+        twins.push_back(&t.ff2);
+      }
   std::vector<Linear*> ok;
   for (Linear* L : twins)
     if (L->cin_pad % 64 == 0 && (L->ks == 1 || L->ks == 3)) ok.push_back(L);
@@ -1331,7 +1383,8 @@ static std::vector<Linear*> fp8_twin_list(af_handle* h) {
 static int register_fp8_sites(Builder& b) {
   af_handle* h = b.h;
   if (h->dtype != AF_DTYPE_BF16) return 0;
-  for (Linear* L : fp8_twin_list(h)) {
+  h->fp8_nbase = (int)fp8_twin_list(h, AF_FP8_SCOPE_BASE).size();
+  for (Linear* L : fp8_twin_list(h, AF_FP8_SCOPE_BASE | AF_FP8_SCOPE_FF)) {   // (the FF sites follow the base sites)
     std::string name;
     for (const std::string& n : h->slot_names) {
       const Slot& sl = h->slots[n];
@@ -1350,7 +1403,7 @@ static int register_fp8_sites(Builder& b) {
 static int ensure_fp8_twins(af_handle* h, hipStream_t s) {
   if (!h->fp8_on || !h->fp8_dirty) return 0;
   if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("fp8 convolutions need the bf16 storage mode"); return AF_ERR_STATE; }
-  for (Linear* L : fp8_twin_list(h)) {
+  for (Linear* L : fp8_twin_list(h, h->fp8_scope)) {
     {
       if (!L->w8) {
         const int units = L->ks * L->ks * (L->cin_pad / 64);
@@ -2361,10 +2414,12 @@ int af_gemm_plan_counts_reset(void) {
   g_af_attn_short_launches = 0;
   g_af_xattn_fused_launches = 0;
   g_af_gn_consumer_launches = 0;
+  g_af_ff8_launches = 0;
   for (int i = 0; i < 15; ++i) g_af_plan_counts[i] = 0;
   return AF_OK;
 }
 int64_t af_fp8_gemm_launches(void) { return g_af_plan_counts[10]; }
+int64_t af_ff8_launches(void) { return g_af_ff8_launches; }
 int64_t af_halo8_launches(void) { return g_af_plan_counts[11]; }
 int64_t af_rowpanel_launches(void) { return g_af_plan_counts[12]; }
 int64_t af_up_phase4_launches(void) { return g_af_plan_counts[13]; }
@@ -2378,14 +2433,26 @@ int af_set_fp8(af_handle* h, int on) {
   h->fp8_on = on != 0;
   return AF_OK;
 }
-int af_fp8_num_sites(af_handle* h) { return h ? (int)h->fp8_shift.size() : 0; }
+int af_set_fp8_scope(af_handle* h, int mask) {
+  if (!h) { af_set_error_msg("af_set_fp8_scope: null handle"); return AF_ERR_INVALID; }
+  if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8_scope: the fp8 mode extends the bf16 mode (handle is f32)"); return AF_ERR_STATE; }
+  if (!(mask & AF_FP8_SCOPE_BASE) || (mask & ~(AF_FP8_SCOPE_BASE | AF_FP8_SCOPE_FF))) {
+    af_set_error_msg("af_set_fp8_scope: mask %d (AF_FP8_SCOPE_BASE is always part of the scope, AF_FP8_SCOPE_FF may be added)", mask);
+    return AF_ERR_INVALID;
+  }
+  if (mask != h->fp8_scope) h->fp8_dirty = true;   // twins of the sites that joined are quantised before the next forward
+  h->fp8_scope = mask;
+  return AF_OK;
+}
+int af_get_fp8_scope(af_handle* h) { return h ? h->fp8_scope : 0; }
+int af_fp8_num_sites(af_handle* h) { return h ? h->fp8_nsites() : 0; }
 const char* af_fp8_site_name(af_handle* h, int i) {
-  if (!h || i < 0 || i >= (int)h->fp8_site_names.size()) return nullptr;
+  if (!h || i < 0 || i >= h->fp8_nsites()) return nullptr;
   return h->fp8_site_names[i].c_str();
 }
 static int fp8_sites_arg(af_handle* h, int n, const char* who) {
   if (!h) { af_set_error_msg("%s: null handle", who); return AF_ERR_INVALID; }
-  if (n != (int)h->fp8_shift.size()) { af_set_error_msg("%s: n = %d, the handle has %d fp8 sites", who, n, (int)h->fp8_shift.size()); return AF_ERR_INVALID; }
+  if (n != h->fp8_nsites()) { af_set_error_msg("%s: n = %d, the handle has %d fp8 sites in its scope", who, n, h->fp8_nsites()); return AF_ERR_INVALID; }
   return AF_OK;
 }
 int af_fp8_record(af_handle* h, int on, void* stream) {

@@ -136,45 +136,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   }
 }
 
-// fp8 output (the consumer is a convolution on the block-scaled fp8 MFMA): OCP e4m3 bytes of value * mul, saturating
-__device__ __forceinline__ unsigned gn_pack4_e4m3(float a, float b, float c, float d, float mul) {
-  a = __builtin_amdgcn_fmed3f(a * mul, -448.f, 448.f);
-  b = __builtin_amdgcn_fmed3f(b * mul, -448.f, 448.f);
-  c = __builtin_amdgcn_fmed3f(c * mul, -448.f, 448.f);
-  d = __builtin_amdgcn_fmed3f(d * mul, -448.f, 448.f);
-  int v = 0;
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
-  v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-  return (unsigned)v;
-}
-
-// fp8 calibration record (af_fp8_record): what a producer saw at one fp8 site, {max |f| as float bits, elements with
-// |f * mul| > 448}.  f is the fp32 value BEFORE the multiplication and the clamp.  Non-negative floats order like
-// unsigned integers, and integer max / add do not depend on arrival order: the record is bit-reproducible run to run.
-__device__ __forceinline__ void fp8_rec_note4(float a, float b, float c, float d, float mul, float& amax, unsigned& nsat) {
-  a = fabsf(a); b = fabsf(b); c = fabsf(c); d = fabsf(d);
-  amax = fmaxf(fmaxf(amax, fmaxf(a, b)), fmaxf(c, d));
-  nsat += (unsigned)(a * mul > 448.f) + (unsigned)(b * mul > 448.f) + (unsigned)(c * mul > 448.f) + (unsigned)(d * mul > 448.f);
-}
-// every thread of the 256-thread workgroup calls this once: wave shuffles, four wave partials through LDS, then ONE atomic
-// max and ONE atomic add per workgroup
-__device__ __forceinline__ void fp8_rec_commit(float amax, unsigned nsat, unsigned* __restrict__ rec) {
-  __shared__ unsigned s_rec[8];
-  unsigned m = __float_as_uint(amax);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-    nsat += (unsigned)__shfl_xor((int)nsat, o, 64);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { s_rec[wave] = m; s_rec[4 + wave] = nsat; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomicMax(rec, max(max(s_rec[0], s_rec[1]), max(s_rec[2], s_rec[3])));
-    atomicAdd(rec + 1, s_rec[4] + s_rec[5] + s_rec[6] + s_rec[7]);
-  }
-}
-
+// (gn_pack4_e4m3, fp8_rec_note4, fp8_rec_commit: af_common.h, shared with the e4m3 GEGLU epilogue of af_conv_gemm.hip)
 template <typename T, bool REC = false>   // REC: also fill the fp8 calibration record (a variant of its own: the plain path pays nothing)
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, long batch_stride, int ldc,
                                                         int HW, int Cn, int P,

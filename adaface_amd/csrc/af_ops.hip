@@ -284,6 +284,88 @@ int af_op_layernorm_fp8_rec(const float* x_dev, const float* gamma_dev, const fl
   return op_layernorm_fp8(x_dev, gamma_dev, beta_dev, eps, y8_dev, rows, C, act_shift, reinterpret_cast<unsigned*>(rec_out_dev), stream);
 }
 
+// One FeedForward as the FF scope of the fp8 mode runs it (af_model.hip run_xfmr): e4m3 LayerNorm (or the caller's raw e4m3
+// bytes) -> ff_geglu_fp8_kernel -> e4m3 -> the plain fp8 launch with bias / residual / bf16 output.  Weights are repacked to bf16
+// and quantised per output row as the model's twins are (af_launch_quant_weight_fp8).
+int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* gamma_dev, const float* beta_dev, float eps,
+                 const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev, const float* residual_dev,
+                 int64_t M, int C, int F, int Cout, int shift1, int shift2, void* rec_out_dev, float* y_dev,
+                 unsigned char* mid8_dev, int* plan_out, void* stream) {
+  if (!act_shift_ok(shift1, "af_op_ff_fp8") || !act_shift_ok(shift2, "af_op_ff_fp8")) return AF_ERR_INVALID;
+  if (M <= 0 || M > (1 << 24) || C % 64 != 0 || F % 64 != 0 || Cout % 4 != 0 || !w1_dev || !w2_dev || !y_dev || (!x8_dev && (!x_dev || !gamma_dev || !beta_dev))) {
+    af_set_error_msg("af_op_ff_fp8: M=%lld C=%d F=%d Cout=%d (need C%%64==0, F%%64==0, Cout%%4==0, weights, an input)", (long long)M, C, F, Cout);
+    return AF_ERR_INVALID;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  const int Mi = (int)M;
+  const int rows1 = rup(2 * F, 128), k1 = rup(C, 128), rows2 = rup(Cout, 160), k2 = rup(F, 128);
+  OP_ALLOC(n8, (size_t)M * C, false);
+  OP_ALLOC(f8, (size_t)M * F, true);
+  OP_ALLOC(w1n, (size_t)rows1 * C * 2, true);
+  OP_ALLOC(w18, (size_t)rows1 * k1 + rows1, true);
+  OP_ALLOC(w2n, (size_t)rows2 * F * 2, true);
+  OP_ALLOC(w28, (size_t)rows2 * k2 + rows2, true);
+  OP_ALLOC(yn, (size_t)M * Cout * 2, true);
+  OP_ALLOC(b1n, (size_t)rows1 * 4, true);
+  OP_ALLOC(b2n, (size_t)rows2 * 4, true);
+  unsigned char* sc1 = reinterpret_cast<unsigned char*>(w18) + (size_t)rows1 * k1;
+  unsigned char* sc2 = reinterpret_cast<unsigned char*>(w28) + (size_t)rows2 * k2;
+  unsigned* rec = reinterpret_cast<unsigned*>(rec_out_dev);
+  if (rec && hipMemsetAsync(rec, 0, 2 * sizeof(unsigned), s) != hipSuccess) return AF_ERR_HIP;
+  if (x8_dev) {
+    if (hipMemcpyAsync(n8, x8_dev, (size_t)M * C, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
+  } else {
+    OP_ALLOC(xn, (size_t)M * C * 2, false);
+    OP_TRY(af_launch_cast_f32<bf16>(x_dev, xn, M * C, s));
+    OP_TRY(af_launch_layernorm<bf16>(xn, C, M, C, gamma_dev, beta_dev, eps, n8, C, s, ldexpf(1.f, shift1), nullptr));
+  }
+  OP_TRY(af_launch_repack_weight<bf16>(w1_dev, w1n, 2 * F, C, C, 1, C, 0, 1, s));
+  OP_TRY(af_launch_quant_weight_fp8(w1n, rows1, C, C, 1, w18, k1, sc1, s));
+  OP_TRY(af_launch_repack_weight<bf16>(w2_dev, w2n, Cout, F, F, 1, F, 0, 0, s));
+  OP_TRY(af_launch_quant_weight_fp8(w2n, rows2, F, F, 1, w28, k2, sc2, s));
+  if (b1_dev) OP_TRY(af_launch_permute_bias(b1_dev, reinterpret_cast<float*>(b1n), 2 * F, 1, s));
+  if (b2_dev && hipMemcpyAsync(b2n, b2_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
+  void* rn = nullptr;
+  if (residual_dev) {
+    rn = tmp.get((size_t)M * Cout * 2, false);
+    if (!rn) return AF_ERR_HIP;
+    OP_TRY(af_launch_cast_f32<bf16>(residual_dev, rn, M * Cout, s));
+  }
+  ConvGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.src = n8; p.src_batch_stride = (long)M * C; p.ldc = C; p.Cin = C;
+  p.Hs = 1; p.Ws = Mi; p.Hi = 1; p.Wi = Mi; p.Ho = 1; p.Wo = Mi;
+  p.ks = 1; p.stride = 1; p.pad = 0;
+  p.W = w18; p.ldw = k1; p.Wrows = rows1;
+  p.M = Mi; p.N = 2 * F; p.K = k1; p.k_logical = C;
+  p.bias = b1_dev ? reinterpret_cast<float*>(b1n) : nullptr;
+  p.out = f8; p.ldo = F; p.alpha = 1.f;
+  p.epilogue = AF_EPI_GEGLU;
+  p.fp8 = 1; p.w_scale = sc1; p.x_scale_e8 = 127 - shift1;
+  if (!af_ff_geglu_fp8_ok(p)) { af_set_error_msg("af_op_ff_fp8: no e4m3 GEGLU launch for M=%d C=%d F=%d", Mi, C, F); return AF_ERR_INVALID; }
+  OP_TRY(af_launch_ff_geglu_fp8(p, ldexpf(1.f, shift2), rec, s));
+  if (mid8_dev && hipMemcpyAsync(mid8_dev, f8, (size_t)M * F, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
+  ConvGemmParams q;
+  memset(&q, 0, sizeof(q));
+  q.src = f8; q.src_batch_stride = (long)M * F; q.ldc = F; q.Cin = F;
+  q.Hs = 1; q.Ws = Mi; q.Hi = 1; q.Wi = Mi; q.Ho = 1; q.Wo = Mi;
+  q.ks = 1; q.stride = 1; q.pad = 0;
+  q.W = w28; q.ldw = k2; q.Wrows = rows2;
+  q.M = Mi; q.N = Cout; q.K = k2; q.k_logical = F;
+  q.bias = b2_dev ? reinterpret_cast<float*>(b2n) : nullptr;
+  q.residual = rn; q.ldr = Cout; q.out = yn; q.ldo = Cout; q.alpha = 1.f;
+  q.fp8 = 1; q.w_scale = sc2; q.x_scale_e8 = 127 - shift2;
+  const AfGemmPlan pl = af_plan_conv_gemm(q, 1, 2);
+  if (pl.tile < 4) { af_set_error_msg("af_op_ff_fp8: no fp8 plan for ff.net.2 M=%d N=%d K=%d", q.M, q.N, q.K); return AF_ERR_INVALID; }
+  if (plan_out) { plan_out[0] = pl.tile; plan_out[1] = pl.splitk; }
+  void* ws = nullptr;
+  if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
+  OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, ws));
+  OP_TRY(af_launch_cast_to_f32<bf16>(yn, y_dev, M * Cout, s));
+  return 0;
+}
+
 int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
                  float* y_dev, int64_t M, int K, int N, int geglu, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -252,11 +252,22 @@ class Engine:
                                               stream_ptr()), "af_clip_text_forward3")
         return out
 
-    def set_fp8(self, on: bool = True):
+    def set_fp8(self, on: bool = True, scope=("base",)):
         """af_set_fp8: the UNet's ResBlock 3x3 convolutions and self-attention q / k / v projections read e4m3 activations /
-        weights (bf16 engines only).  Activation scales: 2^3 per site until calibrate_fp8 / set_fp8_shifts."""
+        weights (bf16 engines only).  Activation scales: 2^3 per site until calibrate_fp8 / set_fp8_shifts.
+        scope: ("base",) or ("base", "ff") / "base+ff" -- the latter adds the transformer blocks' FeedForward (af_set_fp8_scope):
+        32 more sites behind the base ones; shifts set before the scope changed keep their sites."""
+        from .fp8_calib import parse_fp8_scope
+        mask = parse_fp8_scope(scope)
+        if on:
+            check(self._lib.af_set_fp8_scope(self._h, mask), "af_set_fp8_scope")
         check(self._lib.af_set_fp8(self._h, 1 if on else 0), "af_set_fp8")
         self.fp8 = bool(on)
+
+    @property
+    def fp8_scope(self) -> tuple:
+        from .fp8_calib import fp8_scope_names
+        return fp8_scope_names(int(self._lib.af_get_fp8_scope(self._h)))
 
     # -- fp8 mode: calibrated per-site activation scales (adaface_hip.h, af_fp8_*) ----------------
     def fp8_site_names(self):

@@ -14,6 +14,32 @@ from typing import Dict, Iterable
 FP8_SHIFT_MIN, FP8_SHIFT_MAX, FP8_SHIFT_DEFAULT = -16, 8, 3
 FP8_DEFAULT_HEADROOM = 1      # binades the recorded maximum may grow before anything clips
 SCALES_FORMAT = "adaface_amd.fp8_scales/1"
+# scope of the fp8 mode (AF_FP8_SCOPE_*, adaface_hip.h): "base" = ResBlock convolutions + self-attention q / k / v (always
+# part of it), "ff" = the transformer blocks' FeedForward (GEGLU + ff.net.2) on top
+FP8_SCOPE_BASE, FP8_SCOPE_FF = 1, 2
+_SCOPE_BITS = {"base": FP8_SCOPE_BASE, "ff": FP8_SCOPE_FF}
+
+
+def parse_fp8_scope(scope) -> int:
+    """'base' | 'base+ff' | ('base', 'ff') | a mask -> the AF_FP8_SCOPE_* mask.  'base' must be part of it."""
+    if isinstance(scope, bool):
+        raise ValueError(f"fp8 scope: {scope!r}")
+    if isinstance(scope, int):
+        mask = scope
+    else:
+        parts = scope.split("+") if isinstance(scope, str) else list(scope)
+        mask = 0
+        for part in parts:
+            if not isinstance(part, str) or part.strip() not in _SCOPE_BITS:
+                raise ValueError(f"fp8 scope: unknown part {part!r} (known: {sorted(_SCOPE_BITS)})")
+            mask |= _SCOPE_BITS[part.strip()]
+    if not (mask & FP8_SCOPE_BASE) or (mask & ~(FP8_SCOPE_BASE | FP8_SCOPE_FF)):
+        raise ValueError(f"fp8 scope {scope!r}: 'base' is always part of the scope, 'ff' may be added")
+    return mask
+
+
+def fp8_scope_names(mask: int) -> tuple:
+    return tuple(n for n, b in _SCOPE_BITS.items() if mask & b)
 
 
 def shift_for_amax(amax: float, headroom: int = FP8_DEFAULT_HEADROOM) -> int:

@@ -56,6 +56,7 @@ class HipModule(nn.Module):
         # calibrated fp8 activation shifts {site name: shift} (None: the fixed 2^3).  They live here, not on the engine: the
         # engine is rebuilt when the compute dtype or the device changes, and every fp8 engine gets them again
         object.__setattr__(self, "_fp8_shifts", None)
+        object.__setattr__(self, "_fp8_scope", ("base",))     # kept here like the shifts: every fp8 engine gets it again
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
@@ -84,6 +85,24 @@ class HipModule(nn.Module):
             self._mark_dirty()
         return self
 
+    @property
+    def fp8_scope(self) -> tuple:
+        return self._fp8_scope
+
+    def set_fp8_scope(self, scope):
+        """("base",) | ("base", "ff") | "base+ff": which layers the fp8 mode covers (adaface_hip.h, AF_FP8_SCOPE_*).  Kept for
+        every later fp8 engine; a live one is switched now.  Calibrated shifts name the sites of the scope they were made
+        under, so a scope change drops them (calibrate or load_fp8_scales again)."""
+        from adaface_amd.fp8_calib import fp8_scope_names, parse_fp8_scope
+        names = fp8_scope_names(parse_fp8_scope(scope))
+        if names != self._fp8_scope:
+            object.__setattr__(self, "_fp8_scope", names)
+            object.__setattr__(self, "_fp8_shifts", None)
+            if self._engine is not None and self.compute_dtype == "fp8":
+                self._engine.set_fp8_shifts(None)
+                self._engine.set_fp8(True, scope=names)
+        return self
+
     def _engine_kwargs(self) -> dict:  # pragma: no cover - abstract
         raise NotImplementedError
 
@@ -101,7 +120,7 @@ class HipModule(nn.Module):
             object.__setattr__(self, "_engine", Engine(dtype="bf16" if fp8 else self.compute_dtype, device=idx,
                                                        **self._engine_kwargs()))
             if fp8:
-                self._engine.set_fp8(True)
+                self._engine.set_fp8(True, scope=self._fp8_scope)
                 if self._fp8_shifts is not None:
                     try:
                         self._engine.set_fp8_shifts(self._fp8_shifts)

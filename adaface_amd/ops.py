@@ -107,6 +107,43 @@ def layer_norm_fp8(x, weight, bias, eps=1e-5, act_shift=FP8_ACT_SHIFT, record=Fa
     return y
 
 
+def ff_fp8(x, ln_weight, ln_bias, w1, b1, w2, b2, residual=None, shift1=FP8_ACT_SHIFT, shift2=FP8_ACT_SHIFT, eps=1e-5,
+           x8=None, record=False):
+    """One FeedForward as the fp8 mode's FF scope runs it (af_op_ff_fp8): LayerNorm -> e4m3 * 2^shift1 -> GEGLU (w1 [2F, C]:
+    value rows then gate rows, b1) on the fp8 MFMA -> e4m3 * 2^shift2 -> w2 [Cout, F], b2, + residual -> bf16.
+    x8: uint8 [M, C] of raw e4m3 bytes that replace the LayerNorm output (x / ln_weight / ln_bias may then be None).
+    Returns {"y": fp32 [M, Cout] (bf16 values), "mid8": uint8 [M, F] (the GEGLU bytes), "plan": (tile, splitk) of the second
+    GEMM, "record": (amax, nsat) of the GEGLU output when record=True}."""
+    import ctypes as C
+    lib = _lib.load()
+    w1, w2 = _dev_f32(w1), _dev_f32(w2)
+    F2, Cn = w1.shape
+    Cout, Fn = w2.shape
+    if F2 != 2 * Fn:
+        raise ValueError(f"ff_fp8: w1 {tuple(w1.shape)} / w2 {tuple(w2.shape)}")
+    if x8 is not None:
+        x8 = x8.contiguous()
+        assert x8.dtype == torch.uint8 and x8.shape[-1] == Cn
+        M, dev = x8.numel() // Cn, x8.device
+        xf = g = b = None
+    else:
+        xf, g, b = _dev_f32(x), _dev_f32(ln_weight), _dev_f32(ln_bias)
+        M, dev = xf.numel() // Cn, xf.device
+    b1 = None if b1 is None else _dev_f32(b1)
+    b2 = None if b2 is None else _dev_f32(b2)
+    r = None if residual is None else _dev_f32(residual)
+    y = torch.empty(M, Cout, device=dev, dtype=torch.float32)
+    mid = torch.empty(M, Fn, device=dev, dtype=torch.uint8)
+    rec = torch.zeros(2, device=dev, dtype=torch.int32) if record else None
+    plan = (C.c_int * 2)()
+    check(lib.af_op_ff_fp8(ptr(xf), ptr(x8), ptr(g), ptr(b), eps, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(r), M, Cn, Fn, Cout,
+                           shift1, shift2, ptr(rec), ptr(y), ptr(mid), plan, stream_ptr()), "af_op_ff_fp8")
+    out = {"y": y, "mid8": mid, "plan": (int(plan[0]), int(plan[1]))}
+    if record:
+        out["record"] = _fp8_record(rec)
+    return out
+
+
 def linear(x, weight, bias=None, residual=None, geglu=False, dtype="bf16"):
     """F.linear over the last dim; geglu=True applies GEGLU (attention.py:32-45) to the projection."""
     lib = _lib.load()

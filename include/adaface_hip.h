@@ -205,9 +205,10 @@ int af_gemm_plan_counts_reset(void);
  * AF_* environment variables when the library is loaded (AF_GEMM_PP_MINFILL -> "gemm_pp_minfill", ...); nothing on the
  * launch path reads the environment.  The parity tests use af_knob_set to reach a kernel variant regardless of the
  * planner's choice and af_knob_reset to restore the load-time values.  No knob changes results beyond the summation
- * order of the chosen tiling.  The 22 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
+ * order of the chosen tiling (ff8_min_k / ff8_min_rows: which transformer blocks the fp8 mode's FeedForward scope covers).  The 24 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
  * gemm_pp_minfill, gemm_tile, gemm_splitk, gemm_groupm, gemm_dma, attn_ring, gn_small, ln_fuse, geglu_rowpanel, conv_halo8,
- * ablate (lab builds only), gn_producer, conv_up_phase4, attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log.
+ * ablate (lab builds only), gn_producer, conv_up_phase4, attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log,
+ * ff8_min_k, ff8_min_rows.
  * Round 4 removed the six that selected a measured-neutral or slower variant or nothing at all (gn_reduce, splitk_inlaunch,
  * rowpanel_deep, gn_fold, attn_w4, gemm_pp_geglu_minkt), and after it the four variant switches of the ping-pong kernel went
  * the same way (schedule, K order, stagger, forced epilogue; its tap-mask switch became ablate); numbers in DESIGN.md section 5. */
@@ -266,6 +267,30 @@ int af_fp8_set_shifts(af_handle* h, int n, const int* shifts); /* shifts = NULL:
 /* pure host function (no GPU, no handle): the largest s in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX] with
  * amax * 2^(s + headroom) <= 448; amax <= 0, infinite or NaN -> AF_FP8_SHIFT_DEFAULT */
 int af_fp8_shift_for_amax(float amax, int headroom);
+/* Scope of the fp8 mode (a mask).  AF_FP8_SCOPE_BASE, the default: the sites above.  AF_FP8_SCOPE_FF, opt-in on top of it:
+ * the FeedForward of every BasicTransformerBlock (attention.py:32-59, 286): norm3 writes e4m3, ff.net.0.proj (GEGLU)
+ * multiplies on the fp8 MFMA and writes e4m3 of value * gelu(gate) * 2^s for ff.net.2, which runs on the plain fp8 launch
+ * (residual, bf16 output).  Two more sites per transformer block, named by ...ff.net.0.proj.weight (norm3 -> GEGLU) and
+ * ...ff.net.2.weight (GEGLU -> ff.net.2), appended AFTER the base sites: af_fp8_num_sites / _site_name / _get_shifts /
+ * _set_shifts / _read_record cover the base sites while the scope is BASE and base + FF sites while it holds FF.  A block
+ * takes the FeedForward path as a unit (both GEMMs plannable on fp8, width C >= 512: the 32x32, 16x16 and 8x8 levels of SD-1.5;
+ * at C = 320 the pair measured slower than bf16) or stays on bf16; its two sites exist either way.  Masks without BASE and f32 handles
+ * are refused.  af_set_fp8 switches the mode on and off; the scope is kept across it.  PARITY UNPINNED, as the base scope. */
+#define AF_FP8_SCOPE_BASE 1
+#define AF_FP8_SCOPE_FF 2
+int af_set_fp8_scope(af_handle* h, int mask);
+int af_get_fp8_scope(af_handle* h);
+int64_t af_ff8_launches(void); /* GEGLU launches with e4m3 output since af_gemm_plan_counts_reset (also counted by af_fp8_gemm_launches) */
+/* One FeedForward as the FF scope runs it (kernel tests): x [M, C] fp32 -> LayerNorm(gamma, beta, eps) -> e4m3 at 2^shift1
+ * (x8_dev != NULL: these [M, C] e4m3 bytes are the GEGLU's operand instead, x / gamma / beta unused) -> GEGLU with w1 [2 F, C]
+ * (value rows, then gate rows, as the checkpoint stores ff.net.0.proj), b1 [2 F] or NULL -> e4m3 at 2^shift2 (copied to
+ * mid8_dev [M, F] when not NULL) -> w2 [Cout, F], b2 [Cout] or NULL, + residual [M, Cout] or NULL -> y_dev [M, Cout] (bf16
+ * values as fp32).  rec_out_dev: NULL or two 32-bit words, the calibration record of the GEGLU output.  plan_out: NULL or
+ * {tile, splitk} of the ff.net.2 launch.  Fails when the shapes have no fp8 launch. */
+int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* gamma_dev, const float* beta_dev, float eps,
+                 const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev, const float* residual_dev,
+                 int64_t M, int C, int F, int Cout, int shift1, int shift2, void* rec_out_dev, float* y_dev,
+                 unsigned char* mid8_dev, int* plan_out, void* stream);
 int64_t af_fp8_gemm_launches(void); /* launches on the fp8 kernel since af_gemm_plan_counts_reset */
 int64_t af_halo8_launches(void);    /* launches of the eight-wave LDS-halo 3x3 kernel (also counted under tile 5) */
 int64_t af_gn_producer_launches(void); /* convolutions that also wrote the GroupNorm partial sums of their output (no statistics pass in the consumer) */

@@ -2,8 +2,10 @@
 """Per-shape kernel microbenchmark at the SD-1.5 / Bf=16 shapes (kernel-only time from the library's HIP-event
 profiler, so the layout conversions of the op-level API are excluded).  Prints TFLOP/s or GB/s per shape.
 
-    python scripts/bench_shapes.py [--dtype bf16] [--reps 5] [--only conv|linear|attn|norm|conv8]
+    python scripts/bench_shapes.py [--dtype bf16] [--reps 5] [--only conv|linear|attn|norm|conv8|ff8]
     (conv8: the ResBlock convolutions with e4m3 operands next to their bf16 form, same process)
+    (ff8: the FeedForward of a transformer block per UNet level, bf16 pair against the fp8 mode's FF scope -- e4m3
+     LayerNorm + GEGLU with e4m3 output + ff.net.2 on fp8 operands)
 """
 import argparse
 import ctypes as C
@@ -95,6 +97,50 @@ if args.only == "conv8":
         tot += ms * cnt
         tot8 += ms8 * cnt
     print(f"  ResBlock conv weighted total per forward: bf16 {tot:.2f} ms, e4m3 {tot8:.2f} ms")
+
+if args.only == "ff8":
+    def total(classes, fn):
+        """kernel time of ONE call of fn summed over its launches of these profiler classes, ms"""
+        fn()
+        torch.cuda.synchronize()
+        lib.af_prof_reset()
+        lib.af_prof_enable(sum(1 << c for c in classes))
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        lib.af_prof_enable(0)
+        n = 10
+        ms = (C.c_double * n)(); la = (C.c_int64 * n)(); fl = (C.c_double * n)(); by = (C.c_double * n)()
+        lib.af_prof_collect(n, ms, la, fl, by)
+        return {c: ms[c] / args.reps for c in classes}
+
+    # (level, rows at Bf, C, transformer blocks of that level per forward, bf16 model path has a stand-alone LayerNorm?)
+    # 64x64 / 32x32: the bf16 mode folds norm3 into the GEGLU GEMM (no LayerNorm pass); 16x16 / 8x8: it runs the pass
+    levels = [(64, Bf * 4096, 320, 5, False), (32, Bf * 1024, 640, 5, False), (16, Bf * 256, 1280, 5, True), (8, Bf * 64, 1280, 1, True)]
+    print(f"FeedForward per transformer block, Bf = {Bf}: bf16 = GEGLU + ff.net.2 (+ LayerNorm pass where the bf16 mode runs one); "
+          "fp8 = e4m3 LayerNorm pass + e4m3 GEGLU + ff.net.2")
+    tot = tot8 = 0.0
+    for lvl, M, Cn, cnt, ln_pass in levels:
+        x = rn(M, Cn) * 2 + 0.3; gam = rn(Cn) * 0.3 + 1; bet = rn(Cn) * 0.2
+        w1 = rn(8 * Cn, Cn) * Cn ** -0.5; b1 = rn(8 * Cn) * 0.1
+        w2 = rn(Cn, 4 * Cn) * (4 * Cn) ** -0.5; b2 = rn(Cn) * 0.1
+        f = rn(M, 4 * Cn); r = rn(M, Cn)
+        t_ln = total((3,), lambda: ops.layer_norm(x, gam, bet, dtype="bf16"))[3]
+        t_g = sum(total(GEMM_CLASSES, lambda: ops.linear(x, w1, b1, geglu=True, dtype="bf16")).values())
+        t_2 = sum(total(GEMM_CLASSES, lambda: ops.linear(f, w2, b2, residual=r, dtype="bf16")).values())
+        try:
+            t8 = total((3, 8), lambda: ops.ff_fp8(x, gam, bet, w1, b1, w2, b2, residual=r))
+        except _lib.AfError as e:
+            print(f"  {lvl}x{lvl} [{M},{Cn}]: no fp8 launch ({e})")
+            continue
+        bf = t_g + t_2 + (t_ln if ln_pass else 0.0)
+        f8 = t8[3] + t8[8]
+        print(f"  {lvl:2d}x{lvl:<2d} [{M},{Cn}] (x{cnt}): bf16 GEGLU {t_g * 1e3:7.1f} + ff.net.2 {t_2 * 1e3:7.1f}"
+              f"{f' + LayerNorm {t_ln * 1e3:6.1f}' if ln_pass else ' (LayerNorm folded)   '} = {bf * 1e3:7.1f} us | fp8 LayerNorm {t8[3] * 1e3:6.1f} + "
+              f"GEGLU + ff.net.2 {t8[8] * 1e3:7.1f} = {f8 * 1e3:7.1f} us  [{bf / f8:.2f}x]", flush=True)
+        tot += bf * cnt
+        tot8 += f8 * cnt
+    print(f"  FeedForward weighted total per forward: bf16 {tot:.3f} ms, fp8 scope {tot8:.3f} ms")
 
 if args.only in ("", "linear"):
     lins = [  # M, K, N, geglu, count

@@ -18,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--lib", default="")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--fp8", action="store_true")
+ap.add_argument("--fp8-scope", dest="fp8_scope", default="base", help="with --fp8: base | base+ff (the FeedForward scope)")
 ap.add_argument("--knob", action="append", default=[])
 ap.add_argument("--twin", action="store_true", help="af_unet_forward_twin on x[:8] (the CFG batch [x; x]) instead of af_unet_forward")
 args = ap.parse_args()
@@ -41,7 +42,10 @@ kw = dict(in_channels=cfg.in_channels, model_channels=cfg.model_channels, out_ch
 eng = Engine(dtype="bf16", unet=kw)
 synth_weights_into(eng, O.unet_param_shapes(cfg), seed=1, device=dev)
 if args.fp8:
-    eng.set_fp8(True)
+    if args.fp8_scope != "base" or hasattr(eng._lib, "af_set_fp8_scope"):
+        eng.set_fp8(True, scope=args.fp8_scope)
+    else:                      # (--lib with a build from before the scopes: the base scope is all it has)
+        _lib.check(eng._lib.af_set_fp8(eng._h, 1), "af_set_fp8")
 g = torch.Generator().manual_seed(3)
 x = torch.randn(16, 4, 64, 64, generator=g).to(dev)
 t = torch.full((16,), 500, dtype=torch.long, device=dev)
@@ -76,4 +80,4 @@ lib.af_prof_collect(n, ms, la, fl, by)
 names = ["gemm_other", "attention", "groupnorm", "layernorm", "other", "pp160_gather", "pp160_plain", "pp128", "fp8", "halo8"]
 print("   per-class ms per forward: " + ", ".join(f"{names[i]} {ms[i]:.2f} ({la[i]})" for i in range(n) if la[i])
       + f" | gemm total {ms[0] + ms[5] + ms[6] + ms[7] + ms[8] + ms[9]:.2f}")
-print(f"{args.lib or 'HEAD'}{' fp8' if args.fp8 else ''}{' twin' if args.twin else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")
+print(f"{args.lib or 'HEAD'}{(' fp8 ' + args.fp8_scope) if args.fp8 else ''}{' twin' if args.twin else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")

@@ -55,6 +55,9 @@ def parse_args():
                     help="data-parallel ranks (one process per GPU); without a launcher the ranks are started here")
     ap.add_argument("--dtype", choices=["bf16", "f32", "fp8"], default="bf16",
                     help="fp8: bf16 with the UNet's ResBlock convolutions and self-attention q/k/v on e4m3 operands (PARITY UNPINNED)")
+    ap.add_argument("--fp8-scope", dest="fp8_scope", choices=["base", "base+ff"], default="base",
+                    help="--dtype fp8: base = ResBlock convolutions + self-attention q/k/v; base+ff = also the transformer "
+                         "blocks' FeedForward (GEGLU + ff.net.2).  A scale file belongs to the scope it was calibrated under")
     ap.add_argument("--fp8_calib_steps", type=int, default=10,
                     help="--dtype fp8: DDIM steps of the calibration sample that sets the per-layer activation scales "
                          "(two passes, with this run's conditioning); 0 = keep the fixed 2^3, which clips beyond +-56")
@@ -105,7 +108,8 @@ def main():
         model = load_model_from_config(config, opt.ckpt)
     else:
         model = instantiate_from_config(config["model"]).eval()
-    model = model.to(device).set_compute_dtype(opt.dtype)
+    model = model.to(device)
+    model = model.set_compute_dtype(opt.dtype, fp8_scope=opt.fp8_scope) if opt.dtype == "fp8" else model.set_compute_dtype(opt.dtype)
     if not opt.ckpt:  # seeded synthetic weights (identical on every rank)
         g = torch.Generator(device=device).manual_seed(1234)
         with torch.no_grad():

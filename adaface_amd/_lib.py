@@ -109,6 +109,8 @@ _SIGS = [
     ("af_attn_short_launches", C.c_int64, []),
     ("af_gn_consumer_launches", C.c_int64, []),
     ("af_xattn_fused_launches", C.c_int64, []),
+    ("af_conv_attn_short_launches", C.c_int64, []),
+    ("af_op_conv_attention", C.c_int, [C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3 + [_P]),
     ("af_op_xattn_fused", C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p]),
     ("af_op_conv2d_fp8", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 10 + [_P]),
     ("af_op_groupnorm_fp8", C.c_int, [_P, _P, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -175,6 +177,7 @@ def plan_counts(reset: bool = False) -> dict:
     out["attn_short"] = int(lib.af_attn_short_launches())
     out["gn_consumer"] = int(lib.af_gn_consumer_launches())
     out["xattn_fused"] = int(lib.af_xattn_fused_launches())
+    out["conv_attn_short"] = int(lib.af_conv_attn_short_launches())
     if reset:
         lib.af_gemm_plan_counts_reset()
     return out

@@ -804,135 +804,31 @@ __global__ __launch_bounds__(256) void pack_vt_kernel(const bf16* __restrict__ v
   }
 }
 
+// Subject-token conv attention in the same pass (xattn_short_conv_kernel = the body with CONV): af_set_context moves the
+// ks^2 tokens of every subject string to the END of the key list, so the score rows [tok0, tok0 + nsub) of S^T are the
+// reference's "rows replaced by conv attention" (ldm/util.py:701-879 replace_rows_by_conv_attn).  The conv map
+// amap[g][b][head][pixel] (conv_attn_map_kernel, fp32, without the softmax scale) is gathered per lane: subject token
+// j = (key - tok0) % ks^2 of string g = (key - tok0) / ks^2 gets A_g(y - dy_j, x - dx_j), zero outside the map
+// (util.py:812-836), (dy_j, dx_j) = (j / ks - P0, j % ks - P0).  The rows enter the exact softmax like any other score.
+struct ConvCols {
+  const float* amap;
+  long gs;               // floats between two subject strings of amap (= samples of the launch * heads * pixels)
+  long zero;             // index of the map's zero word (behind the last string): what a shift outside the map reads
+  int tok0, nsub;        // first subject key row, number of subject rows (strings * ks^2)
+  int Hh, Ww;            // the query map (Hh * Ww = Nq)
+  int ks;                // conv kernel size 2 / 3 / 4
+};
+
 template <int DH>
 __global__ __launch_bounds__(256) void xattn_short_kernel(const AttnParams p, const bf16* __restrict__ vt, int bpw) {
-  using C = Cfg<DH>;
-  typedef bf16 T;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int h = lane >> 5, l31 = lane & 31;
-  const int head = blockIdx.y * 4 + wave, b = blockIdx.z;
-  if (head >= p.H) return;                                          // (wave-uniform; no barrier in this kernel)
-  const T* Q = reinterpret_cast<const T*>(p.q) + (long)b * p.bsq + head * DH;
-  const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.bsk + head * DH;
-  T* O = reinterpret_cast<T*>(p.o) + (long)b * p.bso + head * DH;
-  const float sl2 = p.scale * 1.44269504088896340736f;
-
-  // ---- resident operand fragments ----
-  uint4 kf[NKB][C::KS];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-    for (int s = 0; s < C::KS; ++s) {
-      const int key = 32 * kb + l31, d0 = 16 * s + 8 * h;
-      Vec16<T> v;
-      v.u = make_uint4(0, 0, 0, 0);
-      if (key < p.Nk && d0 < DH) v.u = *reinterpret_cast<const uint4*>(K + (long)key * p.ldk + d0);
-      // K and Q go into the MFMA as loaded (round 4: scale * log2(e) used to ride on these fragments, a second bf16 rounding
-      // of K); the factor enters in the fp32 fma in front of the exponential: softmax is exp2(s * sl2 - m * sl2)
-      kf[kb][s] = v.u;
-    }
-  uint4 vf[C::DB][C::VSTEPS];
-  {
-    const uint4* vp = reinterpret_cast<const uint4*>(vt + ((long)b * p.H + head) * C::PACK_ELEMS_PER_HEAD);
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db)
-#pragma unroll
-      for (int ks = 0; ks < C::VSTEPS; ++ks) vf[db][ks] = vp[((db * C::VSTEPS + ks) * 2 + h) * 32 + l31];
-  }
-  auto load_q = [&](int blk, uint4 (&qf)[C::KS]) {
-    const int q = blk * 32 + l31;
-#pragma unroll
-    for (int s = 0; s < C::KS; ++s) {
-      const int d0 = 16 * s + 8 * h;
-      qf[s] = make_uint4(0, 0, 0, 0);
-      if (q < p.Nq && d0 < DH) qf[s] = *reinterpret_cast<const uint4*>(Q + (long)q * p.ldq + d0);
-    }
-  };
-  const int nblk = (p.Nq + 31) / 32;
-  const int blk0 = blockIdx.x * bpw, blk1 = blk0 + bpw < nblk ? blk0 + bpw : nblk;
-  if (blk0 >= nblk) return;
-  // one block of 32 queries (fragments qraw, as loaded): S^T, softmax, O^T, store
-  auto body = [&](const uint4 (&qf)[C::KS], int blk) {
-    // ---- S^T = K Q^T ----
-    f32x16 sc[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sc[kb][r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < C::KS; ++s) Mma<T>::step(kf[kb][s], qf[s], sc[kb]);
-    }
-    // ---- exact softmax over the keys < Nk this lane's query column holds (rows split over the two lane halves) ----
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      if (32 * kb + 32 > p.Nk) {       // (wave-uniform) only a partial or empty key block has rows to mask
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (32 * kb + acc_row(r, h) >= p.Nk) sc[kb][r] = -INFINITY;
-      }
-      // (plain fmaxf: an inline-asm v_max3 reading MFMA results would need its own wait states, see the flash kernels)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[kb][r]);
-    }
-    mx = xhalf_max(mx);
-    const float msl = mx * sl2;
-    uint4 pb[NKB][2];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        Vec16<T> v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.e[j] = from_f32<T>(__builtin_amdgcn_exp2f(fmaf(sc[kb][8 * s2 + j], sl2, -msl)));
-        pb[kb][s2] = v.u;
-      }
-    // ---- O^T = V^T P^T (row DH = the softmax denominator) ----
-    f32x16 o[C::DB];
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) Mma<T>::step(vf[db][2 * kb + s2], pb[kb][s2], o[db]);
-    }
-    constexpr int rr = DH % 32, ob = DH / 32, oreg = (rr & 3) + 4 * (rr >> 3), oh = (rr >> 2) & 1;
-    const float l_tot = __shfl(o[ob][oreg], l31 + 32 * oh, 64);
-    const float inv = 1.0f / l_tot;
-    const int q = blk * 32 + l31;
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 32 * db + 8 * g + 4 * h;
-        if (dd < DH) {
-          Quad<T> ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov.e[e] = from_f32<T>(o[db][4 * g + e] * inv);
-          if (q < p.Nq) ov.store(O + (long)q * p.ldo + dd);
-        }
-      }
-  };
-  // Q fragments of THREE blocks in flight (a three-register ring, statically indexed): with one block ahead the wave had
-  // ~3 KB of loads outstanding and the launch ran at the memory latency (1.3 TB/s of Q + O traffic), not at its bandwidth
-  uint4 q0[C::KS], q1[C::KS], q2[C::KS];
-  load_q(blk0, q0);
-  load_q(blk0 + 1, q1);           // (blocks past the end load nothing: q >= Nq)
-  load_q(blk0 + 2, q2);
-  for (int blk = blk0; blk < blk1; blk += 3) {
-    body(q0, blk);
-    if (blk + 3 < blk1) load_q(blk + 3, q0);
-    if (blk + 1 < blk1) {
-      body(q1, blk + 1);
-      if (blk + 4 < blk1) load_q(blk + 4, q1);
-    }
-    if (blk + 2 < blk1) {
-      body(q2, blk + 2);
-      if (blk + 5 < blk1) load_q(blk + 5, q2);
-    }
-  }
+  constexpr bool CONV = false;
+  [[maybe_unused]] const ConvCols cv{};
+#include "af_xattn_short_body.h"
+}
+template <int DH>
+__global__ __launch_bounds__(256) void xattn_short_conv_kernel(const AttnParams p, const bf16* __restrict__ vt, int bpw, const ConvCols cv) {
+  constexpr bool CONV = true;
+#include "af_xattn_short_body.h"
 }
 }  // namespace xs
 
@@ -1018,6 +914,52 @@ template <int DH> static int launch_xattn_short(const AttnParams& p, int B, hipS
   HIP_CHECK_RET(hipGetLastError());
   ++g_af_attn_short_launches;
   return 0;
+}
+
+// ---- subject-token conv attention on the short-key kernel (xs::xattn_short_conv_kernel) ----
+std::atomic<long> g_af_conv_attn_short_launches{0};
+
+bool af_conv_attn_short_ok(bool is_bf16, int dh, int Nk, bool vt_pack, int ks, int groups) {
+  return is_bf16 && (dh == 40 || dh == 80) && Nk > 0 && Nk <= xs::SMAX && vt_pack && ks >= 2 && ks <= 4 &&
+         groups > 0 && groups * ks * ks < Nk;
+}
+
+template <int DH> static int launch_xattn_short_conv(const AttnParams& p, int B, const xs::ConvCols& cv, hipStream_t stream) {
+  const int nblk = (p.Nq + 31) / 32;
+  const long wave_blocks = (long)B * p.H * nblk;       // one round of workgroups, as launch_xattn_short
+  const long slots = 1024L * (DH == 40 ? 2 : 1);
+  int bpw = (int)((wave_blocks + slots - 1) / slots);
+  if (bpw < 1) bpw = 1;
+  if (bpw > 16) bpw = 16;
+  dim3 grid((nblk + bpw - 1) / bpw, (p.H + 3) / 4, B);
+  hipLaunchKernelGGL((xs::xattn_short_conv_kernel<DH>), grid, dim3(256), 0, stream, p, reinterpret_cast<const bf16*>(p.vt_pack), bpw, cv);
+  HIP_CHECK_RET(hipGetLastError());
+  ++g_af_conv_attn_short_launches;
+  return 0;
+}
+
+int af_launch_conv_attn_short(const AttnParams& p, int B, int dh, int ks, int groups, int Hh, int Ww, const float* amap,
+                              hipStream_t stream) {
+  if (!af_conv_attn_short_ok(true, dh, p.Nk, p.vt_pack != nullptr, ks, groups) || p.causal || p.lse || !amap ||
+      Hh <= 0 || Ww <= 0 || (long)Hh * Ww != p.Nq || p.ldq % 8 || p.ldk % 8 || p.ldo % 4 ||
+      (long)groups * B * p.H * p.Nq >= (1L << 26)) {   // (the kernel keeps map offsets in 27 bits of a table word)
+    af_set_error_msg("conv attention: no one-pass kernel for dh %d, %d keys, ks %d, %d subject strings, map %d x %d / %d queries",
+                     dh, p.Nk, ks, groups, Hh, Ww, p.Nq);
+    return -1;
+  }
+  if (B <= 0) return 0;
+  AfProfScope prof(AF_K_ATTENTION, stream, 4.0 * B * p.H * (double)p.Nq * p.Nk * dh,
+                   (2.0 * p.Nq + 2.0 * p.Nk) * B * p.H * dh * 2 + 4.0 * groups * B * p.H * p.Nq);
+  xs::ConvCols cv;
+  cv.amap = amap;
+  cv.gs = (long)B * p.H * p.Nq;
+  cv.zero = cv.gs * groups;
+  cv.nsub = groups * ks * ks;
+  cv.tok0 = p.Nk - cv.nsub;
+  cv.Hh = Hh;
+  cv.Ww = Ww;
+  cv.ks = ks;
+  return dh == 40 ? launch_xattn_short_conv<40>(p, B, cv, stream) : launch_xattn_short_conv<80>(p, B, cv, stream);
 }
 
 template <typename T> int af_launch_attention(const AttnParams& p, int B, int dh, hipStream_t stream) {

@@ -112,6 +112,9 @@ struct AfKnobs {
                             //                         2.5 K tiles, is bound by its GELU epilogue, and the fp8 pair with its LayerNorm
                             //                         pass measured 223 us against 192 us for the bf16 pair
   int ff8_min_rows;         // AF_FF8_MIN_ROWS         0: no floor (16x16 and 8x8 levels measured 1.47x / 1.32x)
+  int conv_attn_short;      // AF_CONV_ATTN_SHORT      0 = subject-token conv attention stays on the flash kernels + subj_scores / merge
+                            //                         (and its samples without a subject on the flash kernels too), as before the
+                            //                         one-pass xattn_short_conv_kernel: the A/B handle of that kernel
 };
 extern AfKnobs g_af_knobs;
 

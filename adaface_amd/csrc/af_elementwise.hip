@@ -94,6 +94,83 @@ __global__ __launch_bounds__(256) void subj_scores_kernel(const T* __restrict__ 
   for (int t = 0; t < NT; ++t) o[t] = acc[t] * scale;
 }
 
+// The conv map on its own, for the one-pass conv attention of the short-key kernel (xs::xattn_short_conv_kernel,
+// af_attention.hip): amap[g][b][h][p] = KS^-1.5 * sum_t q[b][p + off_t][h] . k[b][tok0 + g NT + t][h] for every subject
+// string g of the samples of the launch, off_t = (t / KS - P0, t % KS - P0), pixels outside the map contribute zero.
+// fp32 accumulation, no softmax scale (the attention kernel applies scale * log2 e to these rows as to every other score).
+// amap holds G * B * H * N floats and ONE more, written 0 (what the attention kernel reads for a shift outside the map).
+// One float per (string, pixel, head) instead of subj_scores_kernel's NT.
+// A thread owns one 16-byte chunk (EPC channels) of the q row across all heads: its NT K slices sit in registers (as loaded), the q rows
+// of the NT neighbouring pixels arrive in fully coalesced 16-byte loads (a pixel's heads are contiguous), and the dh / EPC
+// partial sums of a head meet in LDS.  A workgroup does CONV_MAP_NP * (256 / (C / EPC)) pixels in ONE step -- every load of
+// the workgroup is in flight at once, one barrier -- and the grid (pixel ranges, strings, samples) is thousands of
+// workgroups: a first form that walked eight steps per workgroup ran at its own latency chain (34 us at 64 x 64, and the
+// same 33 us at 32 x 32).
+constexpr int CONV_MAP_NP = 2;
+template <typename T, int KS>
+__global__ __launch_bounds__(256) void conv_attn_map_kernel(const T* __restrict__ q, int ldq, long bsq, const T* __restrict__ k,
+                                                            int ldk, long bsk, int tok0, float* __restrict__ amap, int H, int dh,
+                                                            int Hh, int Ww) {
+  constexpr int NT = KS * KS, P0 = KS == 2 ? 0 : 1, EPC = Vec16<T>::N, NP = CONV_MAP_NP;
+  __shared__ float part[NP][256];
+  const int g = blockIdx.y, b = blockIdx.z, G = gridDim.y, B = gridDim.z, N = Hh * Ww;
+  const int CP = H * dh / EPC, PB = 256 / CP, CPH = dh / EPC;   // chunks per pixel, pixels per group, chunks per head
+  const int tid = threadIdx.x, pl = tid / CP, c = tid - pl * CP;
+  const bool act = pl < PB;
+  if (tid == 0 && blockIdx.x == 0 && g == 0 && b == 0) amap[(long)G * B * H * N] = 0.f;
+  // Every load of the thread is issued before the first use (no branch around a load: a tap outside the map, a pixel past
+  // the end or an idle thread reads a valid row and its product is dropped), so a workgroup pays ONE memory latency.
+  const int cc = act ? c : 0;
+  uint4 kraw[NT], qraw[NP][NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    kraw[t] = *reinterpret_cast<const uint4*>(k + (long)b * bsk + (long)(tok0 + g * NT + t) * ldk + cc * EPC);
+  const T* qb = q + (long)b * bsq + cc * EPC;
+  const int p_base = blockIdx.x * (NP * PB);
+  unsigned inmask[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const int pp = min(p_base + i * PB + pl, N - 1);
+    const int y = pp / Ww, x = pp - y * Ww;
+    inmask[i] = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int y2 = y + t / KS - P0, x2 = x + t % KS - P0;
+      const bool in = (unsigned)y2 < (unsigned)Hh && (unsigned)x2 < (unsigned)Ww;
+      inmask[i] |= (in ? 1u : 0u) << t;
+      qraw[i][t] = *reinterpret_cast<const uint4*>(qb + (long)(in ? y2 * Ww + x2 : pp) * ldq);
+    }
+  }
+  const float inv_norm = KS == 2 ? 0.35355339059327373f : (KS == 3 ? 0.19245008972987526f : 0.125f);   // KS^-1.5
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      Vec16<T> kv, qv;
+      kv.u = kraw[t];
+      qv.u = qraw[i][t];
+      float d = 0.f;
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) d = fmaf(to_f32<T>(qv.e[e]), to_f32<T>(kv.e[e]), d);
+      acc += (inmask[i] >> t) & 1u ? d : 0.f;
+    }
+    part[i][tid] = acc;
+  }
+  __syncthreads();
+  const int ohd = tid / PB, opl = tid - ohd * PB;              // the (head, pixel of a group) this thread sums and writes
+  if (ohd >= H) return;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const int pp = p_base + i * PB + opl;
+    if (pp < N) {
+      float s = 0.f;
+      for (int j = 0; j < CPH; ++j) s += part[i][opl * CP + ohd * CPH + j];
+      amap[(((long)g * B + b) * H + ohd) * N + pp] = s * inv_norm;
+    }
+  }
+}
+
 // Step 2: conv scores A(y,x) = KS^-1.5 * sum_t sN[(y+ty-P0, x+tx-P0)][t] (zero outside the map), column j of the subject
 // = A shifted by (dy,dx) = (j/KS-P0, j%KS-P0) with zero fill, then the exact softmax merge of the NT replaced keys with
 // the flash result over the other S-NT keys:  out = (w_U O_U + sum_j e_j v_j) / (w_U + sum_j e_j),
@@ -413,6 +490,8 @@ static int launch_conv_attn_ks(const void* q, int ldq, long bsq, const void* kv,
                                float* lse, void* o, int ldo, long bso, int B, int N, int H, int dh, int Hh, int Ww,
                                float scale, hipStream_t s) {
   dim3 grid((N + 255) / 256, H, B);
+  const double px = (double)B * H * N;   // (both launches in one profiling bracket of the attention class)
+  AfProfScope prof(AF_K_ATTENTION, s, 4.0 * px * KS * KS * dh, px * (3.0 * dh * sizeof(T) + 8.0 * KS * KS + 8.0));
   hipLaunchKernelGGL((subj_scores_kernel<T, KS>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(q), ldq, bsq,
                      reinterpret_cast<const T*>(kv), ldk, bsk, tok0, sN, N, H, dh, scale);
   hipLaunchKernelGGL((conv_attn_merge_kernel<T, KS>), grid, dim3(256), 0, s, sN, lse, reinterpret_cast<const T*>(kv), ldk, bsk,
@@ -431,6 +510,30 @@ int af_launch_conv_attn(const void* q, int ldq, long bsq, const void* kv, int ld
     case 4: return launch_conv_attn_ks<T, 4>(q, ldq, bsq, kv, ldk, bsk, tok0, sN, lse, o, ldo, bso, B, N, H, dh, Hh, Ww, scale, s);
     default: return -1;
   }
+}
+template <typename T>
+int af_launch_conv_attn_map(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, int tok0, int groups,
+                            float* amap, int B, int H, int dh, int Hh, int Ww, int ks, hipStream_t s) {
+  constexpr int EPC = Vec16<T>::N;
+  if (ks < 2 || ks > 4 || groups <= 0 || tok0 < 0 || dh <= 0 || H <= 0 || dh % EPC || H * dh / EPC > 256 || ldq % EPC ||
+      bsq % EPC || ldk % EPC || bsk % EPC || Hh <= 0 || Ww <= 0 || !amap) {
+    af_set_error_msg("conv attention map: ks %d, %d subject strings, %d heads x %d, row stride %d: not supported", ks, groups, H, dh, ldq);
+    return -1;
+  }
+  if (B <= 0) return 0;
+  const int ppb = CONV_MAP_NP * (256 / (H * dh / EPC));        // pixels per workgroup
+  const double px = (double)B * H * Hh * Ww;
+  AfProfScope prof(AF_K_ATTENTION, s, 2.0 * groups * px * ks * ks * dh, px * dh * sizeof(T) + 4.0 * groups * px);
+  dim3 grid((Hh * Ww + ppb - 1) / ppb, groups, B);
+#define AF_MAP(KS_)                                                                                                        \
+  hipLaunchKernelGGL((conv_attn_map_kernel<T, KS_>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(q), ldq, bsq,       \
+                     reinterpret_cast<const T*>(k), ldk, bsk, tok0, amap, H, dh, Hh, Ww)
+  if (ks == 2) AF_MAP(2);
+  else if (ks == 3) AF_MAP(3);
+  else AF_MAP(4);
+#undef AF_MAP
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
 }
 template <typename T> int af_launch_cast_to_f32(const void* x, float* y, long n, hipStream_t s) {
   hipLaunchKernelGGL((cast_to_f32_kernel<T>), EW_GRID(n), dim3(256), 0, s, reinterpret_cast<const T*>(x), y, n);
@@ -543,6 +646,8 @@ int af_launch_nchw_to_uint8(const float* x, uint8_t* y, int B, int HW, hipStream
   template int af_launch_gather_rows_cast<T>(const float*, const int*, void*, long, int, hipStream_t);         \
   template int af_launch_conv_attn<T>(const void*, int, long, const void*, int, long, int, float*, float*, \
                                       void*, int, long, int, int, int, int, int, int, float, int, hipStream_t); \
+  template int af_launch_conv_attn_map<T>(const void*, int, long, const void*, int, long, int, int, float*, int, int, int, \
+                                          int, int, int, hipStream_t);                                        \
   template int af_launch_cast_to_f32<T>(const void*, float*, long, hipStream_t);                              \
   template int af_launch_timestep_embedding<T>(const long long*, void*, int, int, hipStream_t);               \
   template int af_launch_silu<T>(const void*, void*, long, hipStream_t);                                      \

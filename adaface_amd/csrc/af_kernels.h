@@ -13,6 +13,13 @@ template <typename T> long af_attn_short_pack_elems(int B, int H, int dh, int Nk
 template <typename T>
 int af_launch_attn_short_pack(const void* v, int ldv, long bsv, int Nk, int H, int dh, int B, void* vt, hipStream_t stream);
 extern std::atomic<long> g_af_attn_short_launches;
+// Subject-token conv attention in ONE pass of the short-key kernel (bf16, dh 40 / 80, <= 96 keys with their V^T pack, ks 2..4):
+// p covers ALL Nk keys, the groups * ks^2 subject rows at their end (af_set_context's order); amap = the conv maps
+// [groups][B][H][Hh * Ww] fp32 + the zero word of af_launch_conv_attn_map.  The predicate is the planner's and the launcher's.
+bool af_conv_attn_short_ok(bool is_bf16, int dh, int Nk, bool vt_pack, int ks, int groups);
+int af_launch_conv_attn_short(const AttnParams& p, int B, int dh, int ks, int groups, int Hh, int Ww, const float* amap,
+                              hipStream_t stream);
+extern std::atomic<long> g_af_conv_attn_short_launches;
 // ONE launch per cross-attention layer (bf16, C = 320, 8 heads x 40, <= 80 keys; af_xattn_fused.hip): LayerNorm-folded to_q,
 // attention over the packed context K / V, to_out + bias + residual, LayerNorm partial sums for the next consumer
 struct AfXattnFusedParams {
@@ -77,6 +84,14 @@ template <typename T>
 int af_launch_conv_attn(const void* q, int ldq, long bsq, const void* kv, int ldk, long bsk, int tok0, float* sN,
                         float* lse, void* o, int ldo, long bso, int B, int N, int H, int dh, int Hh, int Ww,
                         float scale, int ks, hipStream_t s);
+// conv maps of `groups` subject strings whose ks^2 keys are rows tok0 + g * ks^2 + t of k (tap order), for B samples:
+// amap[g][b][h][p] = ks^-1.5 * sum_t q[b][p + off_t][h] . k[b][tok0 + g ks^2 + t][h], off_t = (t / ks - P0, t % ks - P0),
+// zero outside the Hh x Ww map, fp32 accumulation, WITHOUT the softmax scale (oracle conv_attn_rows' A / scale).  amap holds
+// af_conv_attn_map_floats(...) floats: the maps and one zero word behind them (the zero fill of af_launch_conv_attn_short)
+inline size_t af_conv_attn_map_floats(int groups, int B, int H, int N) { return (size_t)groups * B * H * N + 1; }
+template <typename T>
+int af_launch_conv_attn_map(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, int tok0, int groups,
+                            float* amap, int B, int H, int dh, int Hh, int Ww, int ks, hipStream_t s);
 template <typename T> int af_launch_cast_to_f32(const void* x, float* y, long n, hipStream_t s);
 template <typename T> int af_launch_timestep_embedding(const long long* t, void* y, int B, int dim, hipStream_t s);
 template <typename T> int af_launch_silu(const void* x, void* y, long n, hipStream_t s);

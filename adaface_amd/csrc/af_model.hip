@@ -54,7 +54,8 @@ AfKnobs g_af_knobs = {
     knob_env("AF_LN_FUSE", 1),         knob_env("AF_GEGLU_ROWPANEL", 4), knob_env("AF_CONV_HALO8", 3), knob_env("AF_ABLATE", 0),
     knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1), knob_env("AF_ATTN_SHORT", 1),
     knob_env("AF_GEMM_M128", 1),       knob_env("AF_SMALL_M_TILE64", 1),  knob_env("AF_GN_CONSUMER", 1),
-    knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0),      knob_env("AF_FF8_MIN_K", 512),   knob_env("AF_FF8_MIN_ROWS", 0)};
+    knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0),      knob_env("AF_FF8_MIN_K", 512),   knob_env("AF_FF8_MIN_ROWS", 0),
+    knob_env("AF_CONV_ATTN_SHORT", 1)};
 static const AfKnobs g_af_knobs_initial = g_af_knobs;
 static int* knob_slot(const char* name) {
   static const struct { const char* n; int AfKnobs::*m; } tab[] = {
@@ -65,7 +66,8 @@ static int* knob_slot(const char* name) {
       {"gn_small", &AfKnobs::gn_small}, {"ln_fuse", &AfKnobs::ln_fuse},
       {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"ablate", &AfKnobs::ablate}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4},
       {"attn_short", &AfKnobs::attn_short},
-      {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}, {"ff8_min_k", &AfKnobs::ff8_min_k}, {"ff8_min_rows", &AfKnobs::ff8_min_rows}};
+      {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}, {"ff8_min_k", &AfKnobs::ff8_min_k}, {"ff8_min_rows", &AfKnobs::ff8_min_rows},
+      {"conv_attn_short", &AfKnobs::conv_attn_short}};
   if (!name) return nullptr;
   for (auto& t : tab)
     if (strcmp(t.n, name) == 0) return &(g_af_knobs.*(t.m));
@@ -1259,25 +1261,57 @@ static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin
       AF_TRY(R.attention(q.p, C, (long)N * C, kv.kv, 2 * C, (long)S * 2 * C, R.dry ? nullptr : R.elem_ptr(kv.kv, C),
                          2 * C, (long)S * 2 * C, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt, B > 0 ? kv.vt_bytes / (size_t)B : 0));
     } else {
-      // runs of consecutive samples with / without the subject: flash attention over all S keys, or over the first
-      // S-ks^2 (the subject's keys were moved to the end by af_set_context) followed by the exact softmax merge with
-      // the ks^2 convolutional score columns (af_launch_conv_attn)
+      // runs of consecutive samples that carry the same NUMBER of subject strings (their keys were moved to the end of the key
+      // list by af_set_context).  With a subject: the conv map launch + the short-key kernel over ALL S keys with the subject
+      // rows replaced in front of its exact softmax (af_launch_conv_attn_short: bf16, dh 40 / 80, <= 96 keys); where that kernel
+      // does not exist (f32 handles, dh 160, longer key lists) or knob conv_attn_short = 0: flash attention over the first
+      // S - ng ks^2 keys followed by the exact softmax merge with the ks^2 convolutional score columns of every string
+      // (af_launch_conv_attn).  Without a subject: plain attention over all S keys, on the short-key kernel where it exists.
       const size_t mk3 = R.A.mark();
       const int nt = h->conv_ks * h->conv_ks;
-      float* lse = reinterpret_cast<float*>(R.A.alloc((size_t)B * w.heads * N * sizeof(float)));
-      float* s9 = reinterpret_cast<float*>(R.A.alloc((size_t)B * w.heads * N * nt * sizeof(float)));
-      if (!lse || !s9) { af_set_error_msg("arena exhausted (conv attention scratch)"); return AF_ERR_STATE; }
-      void* vptr = R.dry ? nullptr : R.elem_ptr(kv.kv, C);
-      // runs of consecutive samples that carry the same NUMBER of subject strings (0 = plain attention over all S keys)
       auto groups = [&](int b) { return (int)std::count(h->conv_batch.begin(), h->conv_batch.end(), b); };
+      int ng_max = 0;
+      for (int b = 0; b < B; ++b) ng_max = std::max(ng_max, groups(b));
+      // one scratch serves either path (the larger of the two, whichever runs: the sizing pass does not depend on the choice):
+      // lse [B][heads][N] + s9 [B][heads][N][nt], or the conv maps [ng][B][heads][N] + their zero word
+      const size_t per = (size_t)B * w.heads * N * sizeof(float);
+      float* lse = reinterpret_cast<float*>(R.A.alloc(std::max(per * (size_t)(1 + nt),
+                                                               af_conv_attn_map_floats(ng_max, B, w.heads, N) * sizeof(float))));
+      if (!lse) { af_set_error_msg("arena exhausted (conv attention scratch)"); return AF_ERR_STATE; }
+      float* s9 = lse + (size_t)B * w.heads * N;
+      float* amap = lse;
+      void* vptr = R.dry ? nullptr : R.elem_ptr(kv.kv, C);
+      const size_t vt_sample = B > 0 ? kv.vt_bytes / (size_t)B : 0;
+      const bool one_pass_on = g_af_knobs.conv_attn_short != 0 && g_af_knobs.attn_short != 0;
       int b0 = 0;
       while (b0 < B) {
         const int ng = groups(b0);
         int b1 = b0 + 1;
         while (b1 < B && groups(b1) == ng) ++b1;
         const int nb = b1 - b0;
+        if (ng > 0 && one_pass_on && !R.dry && af_conv_attn_short_ok(R.dt == AF_DTYPE_BF16, w.dh, S, kv.vt != nullptr, h->conv_ks, ng)) {
+          AF_TRY(R.check(a));
+          const bf16* qrun = reinterpret_cast<const bf16*>(q.p) + (long)b0 * N * C;
+          const bf16* krun = reinterpret_cast<const bf16*>(kv.kv) + (long)b0 * S * 2 * C;
+          AF_TRY(af_launch_conv_attn_map<bf16>(qrun, C, (long)N * C, krun, 2 * C, (long)S * 2 * C, S - ng * nt, ng, amap, nb,
+                                               w.heads, w.dh, H, W, h->conv_ks, R.s));
+          AttnParams p;
+          p.q = qrun; p.k = krun; p.v = krun + C; p.o = R.elem_ptr(a.p, (long)b0 * N * a.ld);
+          p.ldq = C; p.ldk = 2 * C; p.ldv = 2 * C; p.ldo = a.ld;
+          p.bsq = (long)N * C; p.bsk = (long)S * 2 * C; p.bsv = (long)S * 2 * C; p.bso = (long)N * a.ld;
+          p.Nq = N; p.Nk = S; p.H = w.heads;
+          p.scale = 1.0f / sqrtf((float)w.dh);
+          p.lse = nullptr; p.causal = 0;
+          p.vt_pack = reinterpret_cast<const char*>(kv.vt) + (size_t)b0 * vt_sample;
+          AF_TRY(af_launch_conv_attn_short(p, nb, w.dh, h->conv_ks, ng, H, W, amap, R.s));
+          b0 = b1;
+          continue;
+        }
+        // (knob 0: the samples without a subject take the call they took before the one-pass kernel, without the V^T pack)
+        const bool plain_short = ng == 0 && g_af_knobs.conv_attn_short != 0;
         AF_TRY(R.attention(q.p, C, (long)N * C, kv.kv, 2 * C, (long)S * 2 * C, vptr, 2 * C, (long)S * 2 * C, a, N,
-                           S - ng * nt, w.heads, w.dh, b0, nb, ng ? lse : nullptr));
+                           S - ng * nt, w.heads, w.dh, b0, nb, ng ? lse : nullptr, 0, plain_short ? kv.vt : nullptr,
+                           plain_short ? vt_sample : 0));
         for (int gi = 0; gi < ng && !R.dry; ++gi) {
           const float scale = 1.0f / sqrtf((float)w.dh);
           const int tok0 = S - (ng - gi) * nt;
@@ -2413,6 +2447,7 @@ int af_gemm_plan_counts(int64_t* counts10) {
 int af_gemm_plan_counts_reset(void) {
   g_af_attn_short_launches = 0;
   g_af_xattn_fused_launches = 0;
+  g_af_conv_attn_short_launches = 0;
   g_af_gn_consumer_launches = 0;
   g_af_ff8_launches = 0;
   for (int i = 0; i < 15; ++i) g_af_plan_counts[i] = 0;
@@ -2426,6 +2461,7 @@ int64_t af_up_phase4_launches(void) { return g_af_plan_counts[13]; }
 int64_t af_gn_producer_launches(void) { return g_af_plan_counts[14]; }
 int64_t af_attn_short_launches(void) { return g_af_attn_short_launches; }
 int64_t af_xattn_fused_launches(void) { return g_af_xattn_fused_launches; }
+int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches; }
 int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }
 int af_set_fp8(af_handle* h, int on) {
   if (!h) { af_set_error_msg("af_set_fp8: null handle"); return AF_ERR_INVALID; }

@@ -601,6 +601,74 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
   return 0;
 }
 
+// Cross-attention with subject-token conv attention, on the launches transformer_forward (af_model.hip) makes for a run of
+// samples that all carry n_groups subject strings at the end of their key list.
+int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Hh,
+                         int Ww, int Nk, int heads, int dh, float scale, int ks, int n_groups, int path, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if (!q_dev || !k_dev || !v_dev || !o_dev || B <= 0 || Hh <= 0 || Ww <= 0 || heads <= 0 || dh <= 0 || dh > 160 || dh % 8 ||
+      ks < 2 || ks > 4 || n_groups <= 0 || n_groups * ks * ks >= Nk || path < 0 || path > 2) {
+    af_set_error_msg("af_op_conv_attention: B=%d map %dx%d Nk=%d heads=%d dh=%d ks=%d groups=%d path=%d", B, Hh, Ww, Nk, heads,
+                     dh, ks, n_groups, path);
+    return AF_ERR_INVALID;
+  }
+  const int C = heads * dh, N = Hh * Ww, nt = ks * ks;
+  const long nq = (long)B * N * C, nk = (long)B * Nk * C;
+  const bool bf = dtype == AF_DTYPE_BF16;
+  const long pe = bf ? af_attn_short_pack_elems<bf16>(B, heads, dh, Nk) : 0;
+  const bool can = af_conv_attn_short_ok(bf, dh, Nk, pe > 0, ks, n_groups);
+  if (path == 2 && !can) {
+    af_set_error_msg("af_op_conv_attention: no one-pass kernel for dtype %d, dh %d, %d keys, ks %d, %d subject strings (bf16, dh 40 / 80, "
+                     "<= 96 keys)", dtype, dh, Nk, ks, n_groups);
+    return AF_ERR_INVALID;
+  }
+  const bool one_pass = path == 2 || (path == 0 && can && g_af_knobs.conv_attn_short && g_af_knobs.attn_short);
+  OP_ALLOC(qn, (size_t)nq * esz(dtype), false);
+  OP_ALLOC(kn, (size_t)nk * esz(dtype), false);
+  OP_ALLOC(vn, (size_t)nk * esz(dtype), false);
+  OP_ALLOC(kvn, (size_t)2 * nk * esz(dtype), false);   // K | V rows, as the cached context
+  OP_ALLOC(on, (size_t)nq * esz(dtype), true);
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s),
+              af_launch_copy_channels<float>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s)));
+  OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s),
+              af_launch_copy_channels<float>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s)));
+  AttnParams p;
+  p.q = qn; p.k = kvn; p.v = (char*)kvn + (size_t)C * esz(dtype); p.o = on; p.lse = nullptr; p.causal = 0;
+  p.ldq = C; p.ldo = C; p.ldk = p.ldv = 2 * C;
+  p.bsq = p.bso = (long)N * C; p.bsk = p.bsv = (long)Nk * 2 * C;
+  p.Nq = N; p.Nk = Nk; p.H = heads; p.scale = scale;
+  p.vt_pack = nullptr;
+  if (one_pass) {
+    OP_ALLOC(vt, (size_t)pe * 2, false);
+    OP_ALLOC(amap, af_conv_attn_map_floats(n_groups, B, heads, N) * sizeof(float), false);
+    OP_TRY(af_launch_attn_short_pack<bf16>(p.v, 2 * C, (long)Nk * 2 * C, Nk, heads, dh, B, vt, s));
+    p.vt_pack = vt;
+    OP_TRY(af_launch_conv_attn_map<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, Nk - n_groups * nt, n_groups,
+                                         (float*)amap, B, heads, dh, Hh, Ww, ks, s));
+    OP_TRY(af_launch_conv_attn_short(p, B, dh, ks, n_groups, Hh, Ww, (const float*)amap, s));
+  } else {
+    OP_ALLOC(lse, (size_t)B * heads * N * sizeof(float), false);
+    OP_ALLOC(s9, (size_t)B * heads * N * nt * sizeof(float), false);
+    p.lse = (float*)lse;
+    p.Nk = Nk - n_groups * nt;
+    OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s)));
+    for (int g = 0; g < n_groups; ++g) {
+      const int tok0 = Nk - (n_groups - g) * nt;
+      OP_TRY(DISP(dtype,
+                  af_launch_conv_attn<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
+                                            (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s),
+                  af_launch_conv_attn<float>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
+                                             (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s)));
+    }
+  }
+  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s)));
+  return 0;
+}
+
 // One cross-attention layer through xattn_fused_kernel (bf16), prepared as the model prepares it: LayerNorm folded into to_q
 // (af_launch_ln_fold), K / V packed per head pair, to_out's K dimension permuted.  ln_parts_out_dev (optional): [4][B * N][2]
 // partial sums of the stored rows, as the next LayerNorm's consumer reads them.

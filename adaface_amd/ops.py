@@ -227,6 +227,54 @@ def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=
     return o
 
 
+CONV_ATTN_PATHS = {"auto": 0, "merge": 1, "one_pass": 2}
+
+
+def conv_attn_key_order(n_keys, token_idx, ks):
+    """Key order of conv attention, as af_set_context lays the cached key list out: the subject tokens at the tail, the other
+    tokens first in their own order, then string by string in the order given (each string's ks^2 positions in the
+    reference's tap order).  token_idx: list of strings, each ks^2 distinct positions in [0, n_keys); no position twice.
+    Returns the list `order` with new row r = old row order[r]."""
+    nt = ks * ks
+    groups = [[int(t) for t in g] for g in token_idx]
+    if ks not in (2, 3, 4):
+        raise ValueError(f"conv attention: kernel size {ks} (the reference has 2, 3 and 4)")
+    if not groups or any(len(g) != nt for g in groups):
+        raise ValueError(f"conv attention: every subject string needs ks^2 = {nt} token positions")
+    flat = [t for g in groups for t in g]
+    if any(t < 0 or t >= n_keys for t in flat):
+        raise ValueError(f"conv attention: token position outside [0, {n_keys})")
+    if len(set(flat)) != len(flat):
+        raise ValueError("conv attention: a token position appears twice")
+    if len(flat) >= n_keys:
+        raise ValueError("conv attention: no ordinary key left")
+    subj = set(flat)
+    return [t for t in range(n_keys) if t not in subj] + flat
+
+
+def conv_attention(q, k, v, heads, hw, ks, token_idx, scale=None, dtype="bf16", path="auto"):
+    """Cross-attention with subject-token convolutional attention (attention.py:208-216, ldm/util.py:701-879): the score
+    columns of the ks^2 tokens of every subject string in token_idx are replaced by the shifted ks x ks conv maps of q with
+    their keys, then softmax over all keys and the product with v.  q [B, H*W, heads*dh] with hw = (H, W), k / v
+    [B, S, heads*dh]; every sample carries all strings.  path: "auto" = the UNet planner's choice, "merge" = flash attention
+    + the subj_scores / merge kernels, "one_pass" = conv map + the short-key kernel (AfError where the shape has none)."""
+    lib = _lib.load()
+    q, k, v = _dev_f32(q), _dev_f32(k), _dev_f32(v)
+    B, N, Cn = q.shape
+    Nk = k.shape[1]
+    Hh, Ww = hw
+    if Hh * Ww != N:
+        raise ValueError(f"conv_attention: hw {hw} does not match {N} queries")
+    dh = Cn // heads
+    scale = dh ** -0.5 if scale is None else scale
+    order = torch.tensor(conv_attn_key_order(Nk, token_idx, ks), device=q.device)
+    k, v = k[:, order].contiguous(), v[:, order].contiguous()
+    o = torch.empty_like(q)
+    check(lib.af_op_conv_attention(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(o), B, Hh, Ww, Nk, heads, dh, scale, ks,
+                                   len(token_idx), CONV_ATTN_PATHS[path], stream_ptr()), "af_op_conv_attention")
+    return o
+
+
 def xattn_fused(x, gamma, beta, wq, kv, wo, bo, eps=1e-5):
     """One cross-attention layer of a 64x64-level BasicTransformerBlock in ONE kernel (bf16; attention.py:172-257, 279):
     y = x + to_out(softmax(to_q(LayerNorm(x)) K^T / sqrt(40)) V) with x [B, N, 320], kv [B, S, 640] = the context's K | V

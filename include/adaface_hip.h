@@ -205,10 +205,10 @@ int af_gemm_plan_counts_reset(void);
  * AF_* environment variables when the library is loaded (AF_GEMM_PP_MINFILL -> "gemm_pp_minfill", ...); nothing on the
  * launch path reads the environment.  The parity tests use af_knob_set to reach a kernel variant regardless of the
  * planner's choice and af_knob_reset to restore the load-time values.  No knob changes results beyond the summation
- * order of the chosen tiling (ff8_min_k / ff8_min_rows: which transformer blocks the fp8 mode's FeedForward scope covers).  The 24 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
+ * order of the chosen tiling (ff8_min_k / ff8_min_rows: which transformer blocks the fp8 mode's FeedForward scope covers).  The 25 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
  * gemm_pp_minfill, gemm_tile, gemm_splitk, gemm_groupm, gemm_dma, attn_ring, gn_small, ln_fuse, geglu_rowpanel, conv_halo8,
  * ablate (lab builds only), gn_producer, conv_up_phase4, attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log,
- * ff8_min_k, ff8_min_rows.
+ * ff8_min_k, ff8_min_rows, conv_attn_short.
  * Round 4 removed the six that selected a measured-neutral or slower variant or nothing at all (gn_reduce, splitk_inlaunch,
  * rowpanel_deep, gn_fold, attn_w4, gemm_pp_geglu_minkt), and after it the four variant switches of the ping-pong kernel went
  * the same way (schedule, K order, stagger, forced epilogue; its tap-mask switch became ablate); numbers in DESIGN.md section 5. */
@@ -300,6 +300,20 @@ int64_t af_attn_short_launches(void);
 /* launches of the one-kernel cross-attention layer (bf16, C = 320, 8 heads x 40, <= 80 keys: LayerNorm-folded to_q + attention +
  * to_out + residual; adaface_amd/csrc/af_xattn_fused.hip) since the last af_gemm_plan_counts_reset */
 int64_t af_xattn_fused_launches(void);
+/* launches of the one-pass subject-token conv attention kernel (xs::xattn_short_conv_kernel: the short-key kernel with the
+ * subject's score rows replaced by their conv columns in front of its softmax; bf16, dh 40 / 80, <= 96 keys) since the last
+ * af_gemm_plan_counts_reset.  Launches of this variant only: af_attn_short_launches does not count them. */
+int64_t af_conv_attn_short_launches(void);
+/* Cross-attention with subject-token convolutional attention as an operator (parity tests; attention.py:208-216 and
+ * ldm/util.py:701-879 replace_rows_by_conv_attn): q [B, Hh * Ww, heads * dh], k / v [B, Nk, heads * dh], o as q, fp32.
+ * The ks^2 tokens of subject string g are the key rows Nk - (n_groups - g) * ks^2 + t in tap order (t = ty * ks + tx), the
+ * layout af_set_context gives the cached key list; every sample of the call carries all n_groups strings.  Their score
+ * columns are replaced by the shifted ks x ks conv maps of q with their K rows (zero fill outside the map), then softmax
+ * over all Nk keys and the product with v.  ks = 2, 3 or 4.  path: 0 = what the UNet's planner runs for this shape,
+ * 1 = flash attention over the other keys + subj_scores / merge kernels (any dtype, dh <= 160), 2 = the conv map kernel + the
+ * one-pass short-key kernel (bf16, dh 40 / 80, Nk <= 96, n_groups * ks^2 < Nk; AF_ERR_INVALID with a message otherwise). */
+int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Hh,
+                         int Ww, int Nk, int heads, int dh, float scale, int ks, int n_groups, int path, void* stream);
 /* the same layer as an operator (parity tests; /root/reference/ldm/modules/attention.py:172-257, 279): x [B, N, 320] fp32,
  * ln_stats [B * N][2] = (mean, rstd) of the bf16-rounded rows, gamma / beta [320], wq [320, 320] (to_q, no bias), kv [B, S, 640]
  * = the context's K | V projections, wo [320, 320] + bo [320] (to_out); y = x + to_out(softmax(to_q(LN(x)) K^T / sqrt(40)) V) */

@@ -2,7 +2,7 @@
 """Per-shape kernel microbenchmark at the SD-1.5 / Bf=16 shapes (kernel-only time from the library's HIP-event
 profiler, so the layout conversions of the op-level API are excluded).  Prints TFLOP/s or GB/s per shape.
 
-    python scripts/bench_shapes.py [--dtype bf16] [--reps 5] [--only conv|linear|attn|norm|conv8|ff8]
+    python scripts/bench_shapes.py [--dtype bf16] [--reps 5] [--only conv|linear|attn|norm|conv8|ff8|convattn]
     (conv8: the ResBlock convolutions with e4m3 operands next to their bf16 form, same process)
     (ff8: the FeedForward of a transformer block per UNet level, bf16 pair against the fp8 mode's FF scope -- e4m3
      LayerNorm + GEGLU with e4m3 output + ff.net.2 on fp8 operands)
@@ -176,6 +176,39 @@ if args.only in ("", "attn", "xattn") and args.dtype == "bf16":
     bo = rn(Cn) * 0.1; kv = rn(Bf, S, 2 * Cn)
     ms, fl, by = timed(1, lambda: ops.xattn_fused(x, gamma, beta, wq, kv, wo, bo))
     show(f"cross-attention layer fused N{N} S{S} C{Cn} (x5)", ms, fl, by)
+
+if args.only == "convattn" and args.dtype == "bf16":
+    # subject-token conv attention of ONE cross-attention layer (to_q / to_out excluded), every sample carrying one 3 x 3 subject
+    # string: the conv map + one-pass short-key kernel against flash attention + subj_scores + merge, and the plain short-key
+    # kernel on the same shape.  Sum of the attention-class launches per call, five rounds of --reps calls: min / median / max.
+    def per_call(fn):
+        fn()
+        torch.cuda.synchronize()
+        rounds = []
+        for _ in range(5):
+            lib.af_prof_reset()
+            lib.af_prof_enable(1 << 1)
+            for _ in range(args.reps):
+                fn()
+            torch.cuda.synchronize()
+            lib.af_prof_enable(0)
+            n = 10
+            ms = (C.c_double * n)(); la = (C.c_int64 * n)(); fl = (C.c_double * n)(); by = (C.c_double * n)()
+            lib.af_prof_collect(n, ms, la, fl, by)
+            rounds.append((ms[1] / args.reps * 1e3, la[1] // args.reps))
+        us = sorted(r[0] for r in rounds)
+        return us[0], us[2], us[4], rounds[0][1]
+    for B_, Hh, dh in [(8, 64, 40), (8, 32, 80)]:
+        N, S = Hh * Hh, 77
+        q = rn(B_, N, 8 * dh); k = rn(B_, S, 8 * dh); v = rn(B_, S, 8 * dh)
+        toks = [list(range(5, 14))]
+        rows = [("plain short-key attention (no subject)", lambda: ops.attention(q, k, v, 8))]
+        if hasattr(lib, "af_op_conv_attention"):
+            rows += [("conv map + one-pass short-key kernel", lambda: ops.conv_attention(q, k, v, 8, (Hh, Hh), 3, toks, path="one_pass")),
+                     ("flash + subj_scores + merge", lambda: ops.conv_attention(q, k, v, 8, (Hh, Hh), 3, toks, path="merge"))]
+        for name, fn in rows:
+            lo, med, hi, nl = per_call(fn)
+            print(f"conv attention B{B_} N{N} S{S} d{dh} ks3: {name:42s} {med:8.1f} us  (min {lo:.1f}, max {hi:.1f}; {nl} bracket(s) per call)", flush=True)
 
 if args.only in ("", "norm"):
     gns = [(320, 64, 13), (640, 64, 2), (960, 64, 1), (320, 32, 1), (640, 32, 11), (1280, 32, 1), (1920, 32, 1),

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Lab: time the full SD-1.5 UNet forward at Bf = 16 (bf16, synthetic weights) with a given build of libadaface_hip.so,
 so that two builds (e.g. the round-1 library and HEAD) can be compared on ONE box:
-    python scripts/lab/ab_forward.py [--lib path/to/lib.so] [--reps 20] [--fp8]
+    python scripts/lab/ab_forward.py [--lib path/to/lib.so] [--reps 20] [--fp8] [--conv-attn KS [--ab-knob NAME]]
+--conv-attn KS: subject-token conv attention (kernel size KS) on the first half of the batch (the conditional half of a CFG
+batch).  --ab-knob NAME: time the forward with knob NAME = 1 and = 0 alternately in this one process (five rounds each).
 Older builds lack newer entry points: missing symbols are skipped when --lib is given (lab only)."""
 import argparse
 import ctypes as C
@@ -21,6 +23,8 @@ ap.add_argument("--fp8", action="store_true")
 ap.add_argument("--fp8-scope", dest="fp8_scope", default="base", help="with --fp8: base | base+ff (the FeedForward scope)")
 ap.add_argument("--knob", action="append", default=[])
 ap.add_argument("--twin", action="store_true", help="af_unet_forward_twin on x[:8] (the CFG batch [x; x]) instead of af_unet_forward")
+ap.add_argument("--conv-attn", dest="conv_attn", type=int, default=0, help="conv attention kernel size (2 / 3 / 4) on the first half of the batch")
+ap.add_argument("--ab-knob", dest="ab_knob", default="", help="alternate this knob between 1 and 0 in one process and report both")
 args = ap.parse_args()
 if args.lib:
     _lib._LIB_PATH = Path(args.lib).resolve()
@@ -50,6 +54,9 @@ g = torch.Generator().manual_seed(3)
 x = torch.randn(16, 4, 64, 64, generator=g).to(dev)
 t = torch.full((16,), 500, dtype=torch.long, device=dev)
 ctx = torch.randn(16 * 16, 77, 768, generator=g).to(dev)
+if args.conv_attn:
+    nt = args.conv_attn ** 2
+    eng.set_conv_attn(args.conv_attn, list(range(8)), [list(range(4, 4 + nt))] * 8)
 eng.set_context(ctx, 16, layerwise=True)
 out = torch.empty_like(x)
 if args.twin:
@@ -60,6 +67,28 @@ else:
 for _ in range(3):
     fwd(x, t, out)
 torch.cuda.synchronize()
+if args.ab_knob:
+    times = {1: [], 0: []}
+    for rnd in range(5):
+        for val in (1, 0):
+            _lib.set_knob(args.ab_knob, val)
+            fwd(x, t, out)
+            torch.cuda.synchronize()
+            _lib.plan_counts(reset=True)
+            t0 = time.perf_counter()
+            for _ in range(args.reps):
+                fwd(x, t, out)
+            torch.cuda.synchronize()
+            times[val].append((time.perf_counter() - t0) / args.reps * 1e3)
+            pc = _lib.plan_counts(reset=True)
+            if rnd == 0:
+                print(f"   {args.ab_knob}={val}: per forward conv_attn_short {pc.get('conv_attn_short', 0) // args.reps}, "
+                      f"attn_short {pc['attn_short'] // args.reps}, xattn_fused {pc['xattn_fused'] // args.reps}")
+    for val in (1, 0):
+        ts = sorted(times[val])
+        print(f"{args.lib or 'HEAD'}{' twin' if args.twin else ''} conv-attn {args.conv_attn} {args.ab_knob}={val}: UNet forward Bf=16: "
+              f"median {ts[2]:.3f} ms (min {ts[0]:.3f}, max {ts[4]:.3f}; five rounds of {args.reps})")
+    _lib.set_knob(args.ab_knob, 1)
 best = 1e9
 for rnd in range(3):
     t0 = time.perf_counter()
@@ -80,4 +109,4 @@ lib.af_prof_collect(n, ms, la, fl, by)
 names = ["gemm_other", "attention", "groupnorm", "layernorm", "other", "pp160_gather", "pp160_plain", "pp128", "fp8", "halo8"]
 print("   per-class ms per forward: " + ", ".join(f"{names[i]} {ms[i]:.2f} ({la[i]})" for i in range(n) if la[i])
       + f" | gemm total {ms[0] + ms[5] + ms[6] + ms[7] + ms[8] + ms[9]:.2f}")
-print(f"{args.lib or 'HEAD'}{(' fp8 ' + args.fp8_scope) if args.fp8 else ''}{' twin' if args.twin else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")
+print(f"{args.lib or 'HEAD'}{(' fp8 ' + args.fp8_scope) if args.fp8 else ''}{' twin' if args.twin else ''}{(' conv-attn ' + str(args.conv_attn)) if args.conv_attn else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")

@@ -11,8 +11,9 @@ from pathlib import Path
 
 AF_DTYPE_BF16 = 0
 AF_DTYPE_F32 = 1
+AF_DTYPE_F16 = 2
 DTYPES = {"bf16": AF_DTYPE_BF16, "bfloat16": AF_DTYPE_BF16, "f32": AF_DTYPE_F32, "fp32": AF_DTYPE_F32,
-          "float32": AF_DTYPE_F32}
+          "float32": AF_DTYPE_F32, "f16": AF_DTYPE_F16, "fp16": AF_DTYPE_F16, "float16": AF_DTYPE_F16}
 
 _LIB_PATH = Path(__file__).resolve().parent / "libadaface_hip.so"
 

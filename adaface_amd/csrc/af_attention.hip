@@ -33,7 +33,8 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 template <typename T, int DH> struct AttnCfg {
-  static constexpr bool BF = sizeof(T) == 2;
+  static constexpr bool BF = sizeof(T) == 2;      // 16-bit storage (bf16 or fp16): the LDS layout, double buffering, ds_read_b64_tr_b16
+  static constexpr bool IS_BF16 = std::is_same_v<T, bf16>;
   static constexpr int EPC = 16 / sizeof(T);
   static constexpr int FS = (DH * (int)sizeof(T) + 31) / 32;   // 32-byte steps along d
   static constexpr int KROW = FS * 32 + 16;                    // bytes
@@ -51,13 +52,17 @@ template <typename T, int DH> struct AttnCfg {
   static constexpr int NLD = (64 * CPR + 255) / 256;           // staged chunks per thread (K and V each)
   // a free padding column d = DH of the V tile holds 1.0 for valid keys: row DH of O^T is then the softmax
   // denominator, summed by the MFMA instead of 32 VALU adds per tile (bf16 only; needs DH % 32 != 0)
+  // (fp16: the column holds fp16 1.0; P is at most 1 there, the maximum being the running one, see MREF)
   static constexpr bool ONES = BF && (DH % 32) != 0;
+  static constexpr unsigned short ONE_BITS = IS_BF16 ? 0x3F80 : 0x3C00;   // 1.0 in the storage type
   // a free padding slot d = DH in the QK^T K-dimension (dh = 40: 80 -> 96 bytes) carries "1.0" on the K side and
   // "-m_ref" (the per-query running softmax reference, kept bf16-representable) on the Q side: the MFMA then returns
   // s - m_ref directly and the 32 v_sub per tile disappear; m_ref moves only on the first tile or when a score rises
   // 2^24 above it.  With ONE exp loop behind a rare "move the reference" fix-up the kernel needs 132 VGPRs (the first
   // version with two unrolled loops needed 190 and lost); dh = 40 self-attention 612 -> 539 us, 515 us at 4 waves/SIMD.
-  static constexpr bool MREF = BF && ((DH * 2) % 32) != 0;
+  // bf16 only: the trick lets exp2(s - m_ref) reach 2^24, which bf16's exponent holds and fp16's (65504) does not, and it
+  // rounds the pre-scaled Q a second time; fp16 takes the running-maximum VALU path of the f32 instantiation
+  static constexpr bool MREF = IS_BF16 && ((DH * 2) % 32) != 0;
   static constexpr int MREF_STEP = (DH * 2) / 32, MREF_HALF = ((DH * 2) % 32) / 16, MREF_ELEM = (((DH * 2) % 32) % 16) / 2;
 };
 
@@ -123,7 +128,7 @@ template <typename T, int DH> __device__ __forceinline__ void attn_body(const At
       }
       kreg[i] = kv;
       vreg[i] = vv;
-      ones_val[i] = (idx < 64 * CPR && key < p.Nk) ? (unsigned short)0x3F80 : (unsigned short)0;
+      ones_val[i] = (idx < 64 * CPR && key < p.Nk) ? C::ONE_BITS : (unsigned short)0;
     }
   };
   auto lstore = [&](int buf) {
@@ -844,8 +849,10 @@ template <typename T, int DH> static int launch_attn(const AttnParams& p, int B,
   using C = AttnCfg<T, DH>;
   static unsigned long long attr_done = 0, attr_done_w4 = 0;
   if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&attn_kernel<T, DH>), C::LDS_BYTES)) return rc;
-  if (int rc = af_ensure_dynamic_lds(attr_done_w4, reinterpret_cast<const void*>(&attn_kernel_w4<T, DH>), C::LDS_BYTES)) return rc;
-  if constexpr (C::BF && DH == 40) {
+  if constexpr (!std::is_same_v<T, f16>) {   // (the 128-VGPR cap was sized for the bf16 dh-40 body: fp16 has no such instantiation)
+    if (int rc = af_ensure_dynamic_lds(attr_done_w4, reinterpret_cast<const void*>(&attn_kernel_w4<T, DH>), C::LDS_BYTES)) return rc;
+  }
+  if constexpr (C::IS_BF16 && DH == 40) {
     if ((g_af_knobs.attn_ring & 1) && !p.causal) {   // eight-wave LDS-DMA ring kernel (the 64x64 level)
       static unsigned long long attr_done_ring = 0;
       if (int rc = af_ensure_dynamic_lds(attr_done_ring, reinterpret_cast<const void*>(&ring::attn_ring40_kernel), ring::Cfg<40>::LDS_BYTES)) return rc;
@@ -854,7 +861,7 @@ template <typename T, int DH> static int launch_attn(const AttnParams& p, int B,
       return 0;
     }
   }
-  if constexpr (C::BF && DH == 80) {
+  if constexpr (C::IS_BF16 && DH == 80) {
     if ((g_af_knobs.attn_ring & 2) && !p.causal && (p.Nk >= 256 || (g_af_knobs.attn_ring & 4))) {   // 80-wide heads (the 32x32 level; bit 2: tests force it for short key lists)
       static unsigned long long attr_done_ring = 0;
       constexpr int lds80 = ring::Cfg<80, 4>::LDS_BYTES;
@@ -865,7 +872,7 @@ template <typename T, int DH> static int launch_attn(const AttnParams& p, int B,
     }
   }
   dim3 grid((p.Nq + 127) / 128, p.H, B);
-  if (C::BF && DH == 40)
+  if constexpr (C::IS_BF16 && DH == 40)
     hipLaunchKernelGGL((attn_kernel_w4<T, DH>), grid, dim3(256), C::LDS_BYTES, stream, p);
   else
     hipLaunchKernelGGL((attn_kernel<T, DH>), grid, dim3(256), C::LDS_BYTES, stream, p);
@@ -875,14 +882,14 @@ template <typename T, int DH> static int launch_attn(const AttnParams& p, int B,
 
 // packed V^T fragments for xs::xattn_short_kernel (elements; 0 = this (dtype, dh, Nk) has no short-key kernel)
 template <typename T> long af_attn_short_pack_elems(int B, int H, int dh, int Nk) {
-  if (sizeof(T) != 2 || Nk <= 0 || Nk > xs::SMAX) return 0;
+  if (!std::is_same_v<T, bf16> || Nk <= 0 || Nk > xs::SMAX) return 0;
   if (dh == 40) return (long)B * H * xs::Cfg<40>::PACK_ELEMS_PER_HEAD;
   if (dh == 80) return (long)B * H * xs::Cfg<80>::PACK_ELEMS_PER_HEAD;
   return 0;
 }
 template <typename T>
 int af_launch_attn_short_pack(const void* v, int ldv, long bsv, int Nk, int H, int dh, int B, void* vt, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same_v<T, bf16>) {
     const long total = af_attn_short_pack_elems<T>(B, H, dh, Nk);
     if (total <= 0) { af_set_error_msg("attention: no short-key pack for dh %d, %d keys", dh, Nk); return -1; }
     unsigned blocks = (unsigned)((total + 255) / 256);
@@ -971,7 +978,7 @@ template <typename T> int af_launch_attention(const AttnParams& p, int B, int dh
   if (p.Nq <= 0 || B <= 0) return 0;
   AfProfScope prof(AF_K_ATTENTION, stream, 4.0 * B * p.H * (double)p.Nq * p.Nk * dh,
                    (2.0 * p.Nq + 2.0 * p.Nk) * B * p.H * dh * sizeof(T));
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same_v<T, bf16>) {
     // short key list with the V^T fragments packed by the caller: the register-resident cross-attention kernel
     if (p.vt_pack && g_af_knobs.attn_short && !p.causal && !p.lse && p.Nk <= xs::SMAX && (dh == 40 || dh == 80))
       return dh == 40 ? launch_xattn_short<40>(p, B, stream) : launch_xattn_short<80>(p, B, stream);
@@ -997,3 +1004,6 @@ template long af_attn_short_pack_elems<float>(int, int, int, int);
 template int af_launch_attn_short_pack<bf16>(const void*, int, long, int, int, int, int, void*, hipStream_t);
 template int af_launch_attn_short_pack<float>(const void*, int, long, int, int, int, int, void*, hipStream_t);
 template int af_launch_attention<float>(const AttnParams&, int, int, hipStream_t);
+template int af_launch_attention<f16>(const AttnParams&, int, int, hipStream_t);
+template long af_attn_short_pack_elems<f16>(int, int, int, int);
+template int af_launch_attn_short_pack<f16>(const void*, int, long, int, int, int, int, void*, hipStream_t);

@@ -1,6 +1,7 @@
 // adaface_amd — shared device/host definitions for the gfx950 (MI355X) kernels.
 //
-// Storage type T is either __bf16 (throughput mode) or float (parity mode).
+// Storage type T is __bf16 (throughput mode), float (parity mode) or _Float16 (fp16 mode: the four-wave kernels on the
+// F16 MFMA, the precision of the reference's autocast path).
 // All activations are NHWC ("token-major"): [B, H*W, C] with C contiguous, so
 // the reference's 'b c h w -> b (h w) c' rearranges (attention.py:327,335) are
 // no-ops and every 1x1 conv / Linear is a plain row-major GEMM.
@@ -11,6 +12,14 @@
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef _Float16 f16;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+// the storage type as a value (what the planner is told: bf16 and fp16 share the element size, not the kernels)
+enum AfStorage { AF_ST_BF16 = 0, AF_ST_F32 = 1, AF_ST_F16 = 2 };
+template <typename T> struct StorageOf;
+template <> struct StorageOf<__bf16> { static constexpr AfStorage value = AF_ST_BF16; };
+template <> struct StorageOf<float> { static constexpr AfStorage value = AF_ST_F32; };
+template <> struct StorageOf<_Float16> { static constexpr AfStorage value = AF_ST_F16; };
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -124,12 +133,15 @@ extern AfKnobs g_af_knobs;
 template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f32<bf16>(bf16 v) { return (float)v; }
+template <> __device__ __forceinline__ float to_f32<f16>(f16 v) { return (float)v; }
 
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16 from_f32<bf16>(float v) { return (bf16)v; }
+// IEEE round-to-nearest-even (v_cvt_f16_f32); beyond +-65504 the result is +-inf, as torch.Tensor.half(): no saturating clamp
+template <> __device__ __forceinline__ f16 from_f32<f16>(float v) { return (f16)v; }
 
-// 16-byte vector of storage elements (8 bf16 or 4 float)
+// 16-byte vector of storage elements (8 bf16 / fp16 or 4 float)
 template <typename T> struct Vec16 {
   static constexpr int N = 16 / sizeof(T);
   union {
@@ -147,6 +159,14 @@ template <> struct Quad<bf16> {
   };
   __device__ __forceinline__ void load(const bf16* p) { u = *reinterpret_cast<const uint2*>(p); }
   __device__ __forceinline__ void store(bf16* p) const { *reinterpret_cast<uint2*>(p) = u; }
+};
+template <> struct Quad<f16> {
+  union {
+    uint2 u;
+    f16 e[4];
+  };
+  __device__ __forceinline__ void load(const f16* p) { u = *reinterpret_cast<const uint2*>(p); }
+  __device__ __forceinline__ void store(f16* p) const { *reinterpret_cast<uint2*>(p) = u; }
 };
 template <> struct Quad<float> {
   union {
@@ -260,6 +280,7 @@ __device__ __forceinline__ void fp8_rec_commit(float amax, unsigned nsat, unsign
 // MFMA wrapper: one "fragment step" consumes a 16-byte fragment per lane from
 // each operand (= 32 bytes of K per row: 16 bf16 or 8 float).
 //   bf16 : one v_mfma_f32_32x32x16_bf16      (lane l: row l&31, k = 8*(l>>5)+j)
+//   fp16 : one v_mfma_f32_32x32x16_f16       (the same operand layout and the same 8 passes)
 //   float: four v_mfma_f32_32x32x2_f32, MFMA j taking element j of the
 //          fragment, i.e. k = 4*(l>>5)+j : a fixed permutation of K applied
 //          identically to both operands, so the sum is unchanged.
@@ -270,6 +291,11 @@ template <> struct Mma<bf16> {
   static __device__ __forceinline__ void step(const uint4& a, const uint4& b, f32x16& c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  }
+};
+template <> struct Mma<f16> {
+  static __device__ __forceinline__ void step(const uint4& a, const uint4& b, f32x16& c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   }
 };
 template <> struct Mma<float> {

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvGemmParams p) 
               float val = acc[ni][mi][4 * q + e] * p.alpha;
               float gat = acc[ni][mi][4 * (q + 2) + e] * p.alpha;
               if (p.bias) { val += p.bias[nv + e]; gat += p.bias[nv + 16 + e]; }
-              op[e] = val * (sizeof(T) == 2 ? gelu_bf16out_f(gat) : gelu_erf_f(gat));
+              op[e] = val * (std::is_same_v<T, bf16> ? gelu_bf16out_f(gat) : gelu_erf_f(gat));   // (fp16: the fit's 4e-4 is an fp16 step of the result)
             }
             *reinterpret_cast<float4*>(et + row * C::EPI_LD + wn * 32 + ni * 16 + j) = o;
           }
@@ -2371,7 +2371,11 @@ static AfGemmPlan plan_fp8(const ConvGemmParams& p, int batch) {
   return pl;
 }
 
-AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, int elem_size) {
+AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st) {
+  // fp16 plans like f32 with the 16-bit K tile: the four four-wave tiles, the LDS-halo kernel and split-K; every eight-wave
+  // kernel below is bf16
+  const int elem_size = st == AF_ST_F32 ? 4 : 2;
+  const bool is_bf16 = st == AF_ST_BF16;
   if (p.fp8) return plan_fp8(p, batch);
   AfGemmPlan pl;
   pl.tile = 0;
@@ -2432,7 +2436,7 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, int elem_size) 
   }
   // ping-pong 256 x {160,128} tiles (bf16): preferred wherever the grid fills the chip.  tile 5 = BN 160 (divides
   // every SD-1.5 channel count), tile 4 = BN 128 (GEGLU needs an even number of 16-column blocks per wave; VAE widths)
-  if (elem_size == 2 && batch == 1 && p.K % 64 == 0 && p.Cin % 64 == 0 && g_af_knobs.gemm_pp) {
+  if (is_bf16 && batch == 1 && p.K % 64 == 0 && p.Cin % 64 == 0 && g_af_knobs.gemm_pp) {
     int cand = -1;
     if (!geglu && p.N % 160 == 0) cand = 5;
     else if (p.N % 128 == 0) cand = 4;
@@ -2473,7 +2477,7 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, int elem_size) 
   // 8 x 8 maps (round 4): tiles of four whole images x 80 columns over four K slices, the images' halos resident in LDS
   // (conv3x3_s8_kernel, af_conv_s8.hip); halo_tw = 8 names it
   // ... and the 16 x 16 maps: one whole image x 80 columns per tile, ONE K slice (256 tiles at Bf = 16)
-  if (elem_size == 2 && (g_af_knobs.conv_halo8 & 2) && g_af_knobs.gemm_pp && af_conv_s8_ok(p, batch) && !p.gn_stats_out &&
+  if (is_bf16 && (g_af_knobs.conv_halo8 & 2) && g_af_knobs.gemm_pp && af_conv_s8_ok(p, batch) && !p.gn_stats_out &&
       (p.Wo <= 16 || (g_af_knobs.conv_halo8 & 4))) {
     pl.tile = 5;
     pl.halo_tw = 8;
@@ -2627,7 +2631,7 @@ static int launch_conv_gemm_fp8(ConvGemmParams p, hipStream_t stream, const AfGe
       return -1;
     }
   }
-  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, 1, 2);
+  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, 1, AF_ST_BF16);
   if (pl.tile != 4 && pl.tile != 5) {
     af_set_error_msg("conv_gemm fp8: shape M=%d N=%d K=%d has no fp8 plan (ask af_plan_conv_gemm first)", p.M, p.N, p.K);
     return -1;
@@ -2877,10 +2881,10 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
   constexpr int BK = 128 / sizeof(T);
   ConvGemmParams p = p_in;
   if (p.fp8) {
-    if constexpr (sizeof(T) == 2) return batch == 1 ? launch_conv_gemm_fp8(p, stream, plan, ws) : (af_set_error_msg("conv_gemm fp8: no batched form"), -1);
+    if constexpr (std::is_same_v<T, bf16>) return batch == 1 ? launch_conv_gemm_fp8(p, stream, plan, ws) : (af_set_error_msg("conv_gemm fp8: no batched form"), -1);
     else { af_set_error_msg("conv_gemm: fp8 operands need the bf16 storage mode"); return -1; }
   }
-  if (p.gn_ab && sizeof(T) != 2) { af_set_error_msg("conv_gemm: consumer-side GroupNorm exists on the bf16 row-panel kernels only"); return -1; }
+  if (p.gn_ab && !std::is_same_v<T, bf16>) { af_set_error_msg("conv_gemm: consumer-side GroupNorm exists on the bf16 row-panel kernels only"); return -1; }
   if (p.K % BK != 0 || p.Cin % BK != 0 || p.K != p.ks * p.ks * p.Cin) {
     af_set_error_msg("conv_gemm: K=%d Cin=%d ks=%d must satisfy K==ks*ks*Cin and Cin%%%d==0", p.K, p.Cin, p.ks, BK);
     return -1;
@@ -2907,12 +2911,12 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
       return -1;
     }
   }
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same_v<T, bf16>) {
     if (up_phase4_ok(p, batch)) return launch_up_phase4(p, stream);
   }
-  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, batch, (int)sizeof(T));
+  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, batch, StorageOf<T>::value);
   if (pl.splitk > 1 && !ws) pl.splitk = 1;  // no workspace supplied: fall back to one slice
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same_v<T, bf16>) {
     // the 128 x 160 tile GEMM fills the chip in one K slice where the 256-row tile was planned over two
     if (pl.splitk > 1) {
       ConvGemmParams q = p;
@@ -2934,7 +2938,7 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
   if (p.ln_stats_out) g_af_plan_counts[9] += 1;
   set_launch_fields(p, pl);
   if (p.gn_stats_out) {
-    if (sizeof(T) != 2 || batch != 1 || !af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
+    if (!std::is_same_v<T, bf16> || batch != 1 || !af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
       af_set_error_msg("conv_gemm: GroupNorm partial sums asked of a launch that cannot write them (ask af_conv_gn_stats_ok first)");
       return -1;
     }
@@ -2947,13 +2951,13 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
                    ((double)p.M * p.K / (p.ks * p.ks) + (double)p.N * p.K + (double)p.M * p.N) * batch * sizeof(T));
   int rc;
   int rk_pre = 0;
-  if constexpr (sizeof(T) == 2) rk_pre = af_conv_rowpanel_kind(p, batch);
+  if constexpr (std::is_same_v<T, bf16>) rk_pre = af_conv_rowpanel_kind(p, batch);
   if ((p.ln_stats || p.ln_stats_out) && rk_pre != 6 && !(pl.tile >= 4 && !pl.halo_tw)) {   // (the 128 x 160 GEMM has both epilogues whatever was planned)
     af_set_error_msg("conv_gemm: LayerNorm-fused launch planned on a kernel without that epilogue (tile %d)", pl.tile);
     return -1;
   }
   // the row-panel kernels (activation rows resident in registers): K = 320 / 640 / 1280 GEMMs with enough rows
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (std::is_same_v<T, bf16>) {
     const int rk = rk_pre;
     if (p.ln_parts_n > 0 && !rk) {
       af_set_error_msg("conv_gemm: un-finalised LayerNorm statistics handed to a launch that is not a row-panel one");
@@ -2976,7 +2980,7 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
     }
   }
   if (pl.halo_tw == 8 || pl.halo_tw == 256) {
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (std::is_same_v<T, bf16>) {
       rc = pl.halo_tw == 8 ? af_launch_conv_s8(p, stream) : launch_halo8(p, stream);
     } else {
       af_set_error_msg(pl.halo_tw == 8 ? "conv_gemm: the 8 x 8-map kernel is bf16 only" : "conv_gemm: the eight-wave halo kernel is bf16 only");
@@ -2990,7 +2994,7 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
     switch (pl.tile) {
       case 4:
       case 5:
-        if constexpr (sizeof(T) == 2) {
+        if constexpr (std::is_same_v<T, bf16>) {
           rc = pl.tile == 4 ? launch_pp<128>(p, stream) : launch_pp<160>(p, stream);
         } else {
           af_set_error_msg("conv_gemm: ping-pong tiles are bf16 only");
@@ -3009,3 +3013,4 @@ int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t strea
 
 template int af_launch_conv_gemm<bf16>(const ConvGemmParams&, int, hipStream_t, const AfGemmPlan*, void*);
 template int af_launch_conv_gemm<float>(const ConvGemmParams&, int, hipStream_t, const AfGemmPlan*, void*);
+template int af_launch_conv_gemm<f16>(const ConvGemmParams&, int, hipStream_t, const AfGemmPlan*, void*);

@@ -661,6 +661,7 @@ int af_launch_nchw_to_uint8(const float* x, uint8_t* y, int B, int HW, hipStream
   template int af_launch_to_uint8<T>(const void*, int, uint8_t*, long, hipStream_t);
 INST(bf16)
 INST(float)
+INST(f16)
 
 // ---------------------------------------------------------------------------
 // weight repack: [rows][cin][ks][ks] fp32 -> T [row_off + perm(n)][(ky,kx,c) with c padded to cin_pad]
@@ -736,3 +737,4 @@ int af_launch_permute_bias(const float* src, float* dst, int rows, int perm, hip
 }
 template int af_launch_repack_weight<bf16>(const float*, void*, int, int, int, int, int, int, int, hipStream_t);
 template int af_launch_repack_weight<float>(const float*, void*, int, int, int, int, int, int, int, hipStream_t);
+template int af_launch_repack_weight<f16>(const float*, void*, int, int, int, int, int, int, int, hipStream_t);

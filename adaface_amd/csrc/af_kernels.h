@@ -1,8 +1,8 @@
-// Internal launcher declarations (one template per storage type T = bf16 | float).
+// Internal launcher declarations (one template per storage type T = bf16 | float | f16).
 #pragma once
 #include "af_common.h"
 
-AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, int elem_size);
+AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st);
 template <typename T>
 int af_launch_conv_gemm(const ConvGemmParams& p, int batch, hipStream_t stream, const AfGemmPlan* plan = nullptr,
                         void* ws = nullptr);

@@ -117,11 +117,14 @@ void af_prof_end_impl(hipStream_t s) { hipEventRecord(g_prof_recs.back().stop, s
     if (_rc != 0) return _rc;   \
   } while (0)
 
-static inline size_t esize(int dtype) { return dtype == AF_DTYPE_BF16 ? 2 : 4; }
-static inline int bk_of(int dtype) { return dtype == AF_DTYPE_BF16 ? 64 : 32; }
+static inline size_t esize(int dtype) { return dtype == AF_DTYPE_F32 ? 4 : 2; }
+static inline int bk_of(int dtype) { return dtype == AF_DTYPE_F32 ? 32 : 64; }
+// the planner's name for a handle's storage type
+static inline AfStorage storage_of(int dtype) { return dtype == AF_DTYPE_BF16 ? AF_ST_BF16 : dtype == AF_DTYPE_F16 ? AF_ST_F16 : AF_ST_F32; }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
-#define DISPATCH(dtype, CALL_BF16, CALL_F32) ((dtype) == AF_DTYPE_BF16 ? (CALL_BF16) : (CALL_F32))
+#define DISPATCH(dtype, CALL_BF16, CALL_F32, CALL_F16) \
+  ((dtype) == AF_DTYPE_BF16 ? (CALL_BF16) : (dtype) == AF_DTYPE_F16 ? (CALL_F16) : (CALL_F32))
 
 // ----------------------------------------------------------------------------
 // activation arena (bump allocator with mark/release); dry mode only measures.
@@ -861,7 +864,7 @@ struct Runner {
     x8.f8 = true; x8.ld = x.C;
     ConvGemmParams p;
     conv_params(p, L, x8, out, stride, up, nullptr, nullptr, 0, -1, -1);
-    return af_plan_conv_gemm(p, 1, 2).tile >= 4;
+    return af_plan_conv_gemm(p, 1, AF_ST_BF16).tile >= 4;
   }
   // FeedForward scope: would BOTH GEMMs of a transformer block's FeedForward run on fp8 operands -- ff1 (GEGLU, e4m3 output,
   // ff_geglu_fp8_kernel) on e4m3(norm3 x) and ff2 on its bytes?  From the scope, the shapes and the twins alone.
@@ -893,7 +896,7 @@ struct Runner {
     if (dt != AF_DTYPE_BF16 || L.ks != 1) return 0;
     ConvGemmParams p;
     conv_params(p, L, x, out, 1, 0, nullptr, nullptr, 0, n_valid, -1);
-    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, (int)esize(dt));
+    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
     // (folding at the 16x16 level through the 128 x 160 tile GEMM's epilogues measured neutral in round 3 -- 15.834 vs 15.842 ms per
     // forward: a stand-alone LayerNorm over [4096, 1280] costs what the two epilogues and the statistics traffic cost -- and is not
     // planned; at the 32x32 level the same kernel's two-slot form carries the epilogues)
@@ -908,7 +911,7 @@ struct Runner {
     if (ln) { p.ln_stats = ln->stats; p.ln_colsum = ln->colsum; p.ln_stats_out = ln->stats_out; }
     p.gn_ab = reinterpret_cast<const float*>(1);   // (capability question only)
     p.gn_hw = gn_hw;
-    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, (int)esize(dt));
+    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
     p.splitk = pl.splitk;
     return af_conv_rowpanel_kind(p, 1) != 0;
   }
@@ -921,7 +924,8 @@ struct Runner {
     if (x.C != N.C) { af_set_error_msg("groupnorm: C mismatch %d vs %d", x.C, N.C); return AF_ERR_INVALID; }
     const float* pre = g_af_knobs.gn_producer ? x.gn_part : nullptr;
     return DISPATCH(dt, af_launch_groupnorm_fold<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab),
-                    af_launch_groupnorm_fold<float>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab));
+                    af_launch_groupnorm_fold<float>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab),
+                    af_launch_groupnorm_fold<f16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab));
   }
   // want_gn: 1 = also write the GroupNorm partial sums of `out` into the arena (consumer inside the caller's arena scope),
   // 2 = into the handle's carry buffer (consumer = the next layer); out.gn_part is set when the launch can do it
@@ -947,7 +951,7 @@ struct Runner {
       return AF_ERR_INVALID;
     }
     if (x.f8 && (!L.w8 || ln)) { af_set_error_msg("conv: e4m3 input without an fp8 weight twin"); return AF_ERR_STATE; }
-    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, (int)esize(dt));
+    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
     if (x.f8 && pl.tile < 4) { af_set_error_msg("conv: e4m3 input on a shape without an fp8 plan"); return AF_ERR_STATE; }
     if (ln_parts_pending) {
       ConvGemmParams q = p;
@@ -994,11 +998,11 @@ struct Runner {
       if (!ws) { af_set_error_msg("arena exhausted (split-K slabs)"); return AF_ERR_STATE; }
     }
     if (dry) return 0;
-    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws));
+    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws));
   }
   int gemm_raw(const ConvGemmParams& p, int batch) {
     if (dry) return 0;
-    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, batch, s), af_launch_conv_gemm<float>(p, batch, s));
+    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, batch, s), af_launch_conv_gemm<float>(p, batch, s), af_launch_conv_gemm<f16>(p, batch, s));
   }
   // the record slot of an e4m3 output while af_fp8_record is on
   unsigned* fp8_rec_of(const Act& y) const { return h->fp8_recording && y.f8_site >= 0 ? h->fp8_rec + 2 * y.f8_site : nullptr; }
@@ -1018,7 +1022,9 @@ struct Runner {
                     af_launch_groupnorm<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
                                               y.p, (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart),
                     af_launch_groupnorm<float>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
-                                               y.p, (long)HW * y.ld, y.ld, ws, s));
+                                               y.p, (long)HW * y.ld, y.ld, ws, s),
+                    af_launch_groupnorm<f16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
+                                              y.p, (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart));
   }
   int layernorm(const Norm& N, const Act& x, Act& y) {
     AF_TRY(check(y));
@@ -1027,7 +1033,8 @@ struct Runner {
       return af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s, ldexpf(1.f, y.f8_shift),
                                        fp8_rec_of(y));
     return DISPATCH(dt, af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s),
-                    af_launch_layernorm<float>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s));
+                    af_launch_layernorm<float>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s),
+                    af_launch_layernorm<f16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s));
   }
   // samples [b0, b0 + nb) of the batch (nb < 0: all of o.B); lse: optional [nb][heads][Nq] log-sum-exp output
   int attention(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, const void* v, int ldv, long bsv,
@@ -1046,12 +1053,13 @@ struct Runner {
     p.lse = lse;
     p.causal = causal;
     p.vt_pack = vt_pack ? reinterpret_cast<const char*>(vt_pack) + (size_t)b0 * vt_sample_bytes : nullptr;
-    return DISPATCH(dt, af_launch_attention<bf16>(p, nb, dh, s), af_launch_attention<float>(p, nb, dh, s));
+    return DISPATCH(dt, af_launch_attention<bf16>(p, nb, dh, s), af_launch_attention<float>(p, nb, dh, s), af_launch_attention<f16>(p, nb, dh, s));
   }
   int copy_channels(const Act& src, Act& dst, int off) {
     if (dry) return 0;
     return DISPATCH(dt, af_launch_copy_channels<bf16>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s),
-                    af_launch_copy_channels<float>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s));
+                    af_launch_copy_channels<float>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s),
+                    af_launch_copy_channels<f16>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s));
   }
   char* elem_ptr(void* p, long off) { return reinterpret_cast<char*>(p) + off * (long)esize(dt); }
 };
@@ -1323,7 +1331,11 @@ static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin
                           af_launch_conv_attn<float>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
                                                      R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0, s9, lse,
                                                      R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb, N, w.heads,
-                                                     w.dh, H, W, scale, h->conv_ks, R.s)));
+                                                     w.dh, H, W, scale, h->conv_ks, R.s),
+                          af_launch_conv_attn<f16>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
+                                                    R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0, s9, lse,
+                                                    R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb, N, w.heads,
+                                                    w.dh, H, W, scale, h->conv_ks, R.s)));
         }
         b0 = b1;
       }
@@ -1547,9 +1559,11 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   AF_TRY(R.check(emb_all));
   if (!R.dry) {
     AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s)));
+                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s),
+                    af_launch_nchw_to_nhwc<f16>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s)));
     AF_TRY(DISPATCH(dt, af_launch_timestep_embedding<bf16>((const long long*)t_dev, temb.p, Bin, mc, s),
-                    af_launch_timestep_embedding<float>((const long long*)t_dev, temb.p, Bin, mc, s)));
+                    af_launch_timestep_embedding<float>((const long long*)t_dev, temb.p, Bin, mc, s),
+                    af_launch_timestep_embedding<f16>((const long long*)t_dev, temb.p, Bin, mc, s)));
   }
   if (twin && !twin_prefix) AF_TRY(dup_half(x));   // other block structures: the whole network on [x; x]
   {
@@ -1557,9 +1571,9 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     Act tb = temb, e1b = e1, e2b = e2, eab = emb_all;
     tb.B = e1b.B = e2b.B = eab.B = Bin;
     AF_TRY(R.conv(h->time_embed0, tb, e1b, 1, 0, nullptr, nullptr, 0));
-    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e1.p, e1.p, (long)Bin * ted, s), af_launch_silu<float>(e1.p, e1.p, (long)Bin * ted, s)));
+    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e1.p, e1.p, (long)Bin * ted, s), af_launch_silu<float>(e1.p, e1.p, (long)Bin * ted, s), af_launch_silu<f16>(e1.p, e1.p, (long)Bin * ted, s)));
     AF_TRY(R.conv(h->time_embed2, e1b, e2b, 1, 0, nullptr, nullptr, 0));
-    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e2.p, e2.p, (long)Bin * ted, s), af_launch_silu<float>(e2.p, e2.p, (long)Bin * ted, s)));
+    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e2.p, e2.p, (long)Bin * ted, s), af_launch_silu<float>(e2.p, e2.p, (long)Bin * ted, s), af_launch_silu<f16>(e2.p, e2.p, (long)Bin * ted, s)));
     AF_TRY(R.conv(h->emb_all, e2b, eab, 1, 0, nullptr, nullptr, 0));
     if (twin) AF_TRY(dup_half(emb_all));
   }
@@ -1664,7 +1678,8 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   auto tap = [&](int idx, const Act& a) -> int {
     if (R.dry || idx != h->tap_index || !h->tap_out) return 0;
     return DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s),
-                    af_launch_nhwc_to_nchw<float>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
+                    af_launch_nhwc_to_nchw<float>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s),
+                    af_launch_nhwc_to_nchw<f16>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
   };
   Act hcur = x;
   for (int i = 0; i < n_in; ++i) {
@@ -1713,7 +1728,8 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   AF_TRY(R.conv(h->out_conv, g, e, 1, 0, nullptr, nullptr, 0));
   if (!R.dry)
     AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s),
-                    af_launch_nhwc_to_nchw<float>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s)));
+                    af_launch_nhwc_to_nchw<float>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s),
+                    af_launch_nhwc_to_nchw<f16>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s)));
   return 0;
 }
 
@@ -1745,9 +1761,11 @@ static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
     p.bs_src = (long)N * 3 * C; p.bs_w = (long)N * 3 * C; p.bs_out = (long)N * N;
     AF_TRY(R.gemm_raw(p, B));
     AF_TRY(DISPATCH(dt, af_launch_softmax_rows<bf16>(sc.p, N, N, (long)B * N, R.s),
-                    af_launch_softmax_rows<float>(sc.p, N, N, (long)B * N, R.s)));
+                    af_launch_softmax_rows<float>(sc.p, N, N, (long)B * N, R.s),
+                    af_launch_softmax_rows<f16>(sc.p, N, N, (long)B * N, R.s)));
     AF_TRY(DISPATCH(dt, af_launch_transpose<bf16>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s),
-                    af_launch_transpose<float>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s)));
+                    af_launch_transpose<float>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s),
+                    af_launch_transpose<f16>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s)));
     // h[b][i][c] = sum_j P[b][i][j] v[b][j][c]
     memset(&p, 0, sizeof(p));
     p.src = sc.p; p.src_batch_stride = 0; p.ldc = N; p.Cin = N;
@@ -1775,7 +1793,8 @@ static int vae_decode_impl(af_handle* h, hipStream_t s, const float* z_dev, floa
   AF_TRY(R.check(z2));
   if (!R.dry) {
     AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s),
-                    af_launch_nchw_to_nhwc<float>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s)));
+                    af_launch_nchw_to_nhwc<float>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s),
+                    af_launch_nchw_to_nhwc<f16>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s)));
     HIP_CHECK_RET(hipMemsetAsync(z2.p, 0, (size_t)z2.npix() * z2.ld * esize(dt), s));
   }
   AF_TRY(R.conv(h->post_quant, z, z2, 1, 0, nullptr, nullptr, 0));
@@ -1813,11 +1832,13 @@ static int vae_decode_impl(af_handle* h, hipStream_t s, const float* z_dev, floa
   if (!R.dry) {
     if (img_dev)
       AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s),
-                      af_launch_nhwc_to_nchw<float>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s)));
+                      af_launch_nhwc_to_nchw<float>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s),
+                      af_launch_nhwc_to_nchw<f16>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s)));
     if (u8_dev) {
       if (c.vae_out_ch != 3) { af_set_error_msg("uint8 output needs out_ch == 3"); return AF_ERR_INVALID; }
       AF_TRY(DISPATCH(dt, af_launch_to_uint8<bf16>(img.p, img.ld, u8_dev, img.npix(), s),
-                      af_launch_to_uint8<float>(img.p, img.ld, u8_dev, img.npix(), s)));
+                      af_launch_to_uint8<float>(img.p, img.ld, u8_dev, img.npix(), s),
+                      af_launch_to_uint8<f16>(img.p, img.ld, u8_dev, img.npix(), s)));
     }
   }
   return 0;
@@ -1833,7 +1854,8 @@ static int vae_encode_impl(af_handle* h, hipStream_t s, const float* x_dev, floa
   AF_TRY(R.check(x));
   if (!R.dry)
     AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s)));
+                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s),
+                    af_launch_nchw_to_nhwc<f16>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s)));
   Act hcur = R.alloc_act(B, H, W, h->enc_conv_in.cout);
   AF_TRY(R.conv(h->enc_conv_in, x, hcur, 1, 0, nullptr, nullptr, 0));
   auto res = [&](int ri) -> int {
@@ -1869,7 +1891,8 @@ static int vae_encode_impl(af_handle* h, hipStream_t s, const float* x_dev, floa
   AF_TRY(R.conv(h->quant_conv, m1, m2, 1, 0, nullptr, nullptr, 0));
   if (!R.dry)
     AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s),
-                    af_launch_nhwc_to_nchw<float>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s)));
+                    af_launch_nhwc_to_nchw<float>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s),
+                    af_launch_nhwc_to_nchw<f16>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s)));
   return 0;
 }
 
@@ -1895,7 +1918,8 @@ static int clip_forward_impl(af_handle* h, hipStream_t s, const float* emb_dev, 
   const long rows = (long)Bn * T;
   if (!R.dry)
     AF_TRY(DISPATCH(dt, af_launch_add_pos_cast<bf16>(emb_dev, h->clip_pos, T, D, x.p, rows, s),
-                    af_launch_add_pos_cast<float>(emb_dev, h->clip_pos, T, D, x.p, rows, s)));
+                    af_launch_add_pos_cast<float>(emb_dev, h->clip_pos, T, D, x.p, rows, s),
+                    af_launch_add_pos_cast<f16>(emb_dev, h->clip_pos, T, D, x.p, rows, s)));
   const int L = (int)h->clip_layers.size();
   for (int i = 0; i < L; ++i) {
     const ClipLayerW& w = h->clip_layers[i];
@@ -1911,20 +1935,22 @@ static int clip_forward_impl(af_handle* h, hipStream_t s, const float* emb_dev, 
     AF_TRY(R.layernorm(w.ln2, x1, n));
     AF_TRY(R.conv(w.fc1, n, f, 1, 0, nullptr, nullptr, 0));
     if (!R.dry)
-      AF_TRY(DISPATCH(dt, af_launch_quick_gelu<bf16>(f.p, f.p, rows * F, s), af_launch_quick_gelu<float>(f.p, f.p, rows * F, s)));
+      AF_TRY(DISPATCH(dt, af_launch_quick_gelu<bf16>(f.p, f.p, rows * F, s), af_launch_quick_gelu<float>(f.p, f.p, rows * F, s), af_launch_quick_gelu<f16>(f.p, f.p, rows * F, s)));
     AF_TRY(R.conv(w.fc2, f, x, 1, 0, &x1, nullptr, 0));
   }
   if (!R.dry) {
     if (L >= 1)
       AF_TRY(DISPATCH(dt, af_launch_blend2<bf16>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s),
-                      af_launch_blend2<float>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s)));
+                      af_launch_blend2<float>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s),
+                      af_launch_blend2<f16>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s)));
     if (L >= 2 && w_prev2 != 0.f)
       AF_TRY(DISPATCH(dt, af_launch_blend2<bf16>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s),
-                      af_launch_blend2<float>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s)));
+                      af_launch_blend2<float>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s),
+                      af_launch_blend2<f16>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s)));
   }
   AF_TRY(R.layernorm(h->clip_final_ln, L >= 1 ? n : x, a));
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_cast_to_f32<bf16>(a.p, out_dev, rows * D, s), af_launch_cast_to_f32<float>(a.p, out_dev, rows * D, s)));
+    AF_TRY(DISPATCH(dt, af_launch_cast_to_f32<bf16>(a.p, out_dev, rows * D, s), af_launch_cast_to_f32<float>(a.p, out_dev, rows * D, s), af_launch_cast_to_f32<f16>(a.p, out_dev, rows * D, s)));
   return 0;
 }
 
@@ -1938,7 +1964,7 @@ int af_version(void) { return 1; }
 
 int af_create(int device_id, const af_config* cfg, af_handle** out) {
   if (!cfg || !out) { af_set_error_msg("af_create: null argument"); return AF_ERR_INVALID; }
-  if (cfg->dtype != AF_DTYPE_BF16 && cfg->dtype != AF_DTYPE_F32) { af_set_error_msg("af_create: bad dtype"); return AF_ERR_INVALID; }
+  if (cfg->dtype != AF_DTYPE_BF16 && cfg->dtype != AF_DTYPE_F32 && cfg->dtype != AF_DTYPE_F16) { af_set_error_msg("af_create: bad dtype"); return AF_ERR_INVALID; }
   HIP_CHECK_RET(hipSetDevice(device_id));
   std::unique_ptr<af_handle> h(new af_handle());
   h->device = device_id;
@@ -2053,11 +2079,12 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
     srcp = h->stage;
   }
   if (s.kind == Slot::TABLE) {
-    AF_TRY(DISPATCH(h->dtype, af_launch_cast_f32<bf16>(srcp, s.dst, (long)n, 0), af_launch_cast_f32<float>(srcp, s.dst, (long)n, 0)));
+    AF_TRY(DISPATCH(h->dtype, af_launch_cast_f32<bf16>(srcp, s.dst, (long)n, 0), af_launch_cast_f32<float>(srcp, s.dst, (long)n, 0), af_launch_cast_f32<f16>(srcp, s.dst, (long)n, 0)));
   } else if (s.kind == Slot::WEIGHT) {
     AF_TRY(DISPATCH(h->dtype,
                     af_launch_repack_weight<bf16>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0),
-                    af_launch_repack_weight<float>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0)));
+                    af_launch_repack_weight<float>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0),
+                    af_launch_repack_weight<f16>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0)));
   } else {
     AF_TRY(af_launch_permute_bias(srcp, s.dst_f, s.rows, s.perm, 0));
   }
@@ -2183,9 +2210,10 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
     HIP_CHECK_RET(hipMemcpyAsync(h->ctx_rowmap, map.data(), rows * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_CHECK_RET(hipStreamSynchronize(s));   // `map` is a pageable host temporary
     AF_TRY(DISPATCH(dt, af_launch_gather_rows_cast<bf16>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s),
-                    af_launch_gather_rows_cast<float>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s)));
+                    af_launch_gather_rows_cast<float>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s),
+                    af_launch_gather_rows_cast<f16>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s)));
   } else {
-    AF_TRY(DISPATCH(dt, af_launch_cast_f32<bf16>(ctx_dev, h->ctx_cast, (long)n, s), af_launch_cast_f32<float>(ctx_dev, h->ctx_cast, (long)n, s)));
+    AF_TRY(DISPATCH(dt, af_launch_cast_f32<bf16>(ctx_dev, h->ctx_cast, (long)n, s), af_launch_cast_f32<float>(ctx_dev, h->ctx_cast, (long)n, s), af_launch_cast_f32<f16>(ctx_dev, h->ctx_cast, (long)n, s)));
   }
   for (size_t i = 0; i < h->ca_list.size(); ++i) {
     const XfmrW& x = h->xf[h->ca_list[i].first];
@@ -2204,7 +2232,7 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
     p.W = blk.kv2.w; p.ldw = blk.kv2.ldw; p.Wrows = blk.kv2.rows_pad;
     p.M = Bf * n_tokens; p.N = 2 * C; p.K = D;
     p.out = h->ctx_kv[i].kv; p.ldo = 2 * C; p.alpha = 1.0f;
-    AF_TRY(DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s), af_launch_conv_gemm<float>(p, 1, s)));
+    AF_TRY(DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s), af_launch_conv_gemm<float>(p, 1, s), af_launch_conv_gemm<f16>(p, 1, s)));
     if (h->ctx_kv[i].xf_pack)   // K and V of this layer as the operand fragments of xattn_fused_kernel
       AF_TRY(af_launch_xattn_fused_pack(h->ctx_kv[i].kv, 2 * C, (long)n_tokens * 2 * C, n_tokens, Bf,
                                         h->ctx_kv[i].xf_pack, s));
@@ -2293,7 +2321,8 @@ int af_clip_embed_tokens(af_handle* h, const int64_t* ids_dev, int64_t n, float*
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return DISPATCH(h->dtype,
                   af_launch_embed_rows<bf16>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s),
-                  af_launch_embed_rows<float>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s));
+                  af_launch_embed_rows<float>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s),
+                  af_launch_embed_rows<f16>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s));
 }
 
 int af_clip_text_forward(af_handle* h, const float* inputs_embeds_dev, int Bn, int T, float w_prev, float w_last,
@@ -2465,13 +2494,13 @@ int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches
 int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }
 int af_set_fp8(af_handle* h, int on) {
   if (!h) { af_set_error_msg("af_set_fp8: null handle"); return AF_ERR_INVALID; }
-  if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is f32)"); return AF_ERR_STATE; }
+  if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is %s)", h->dtype == AF_DTYPE_F16 ? "f16" : "f32"); return AF_ERR_STATE; }
   h->fp8_on = on != 0;
   return AF_OK;
 }
 int af_set_fp8_scope(af_handle* h, int mask) {
   if (!h) { af_set_error_msg("af_set_fp8_scope: null handle"); return AF_ERR_INVALID; }
-  if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8_scope: the fp8 mode extends the bf16 mode (handle is f32)"); return AF_ERR_STATE; }
+  if (h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8_scope: the fp8 mode extends the bf16 mode (handle is %s)", h->dtype == AF_DTYPE_F16 ? "f16" : "f32"); return AF_ERR_STATE; }
   if (!(mask & AF_FP8_SCOPE_BASE) || (mask & ~(AF_FP8_SCOPE_BASE | AF_FP8_SCOPE_FF))) {
     af_set_error_msg("af_set_fp8_scope: mask %d (AF_FP8_SCOPE_BASE is always part of the scope, AF_FP8_SCOPE_FF may be added)", mask);
     return AF_ERR_INVALID;
@@ -2493,7 +2522,7 @@ static int fp8_sites_arg(af_handle* h, int n, const char* who) {
 }
 int af_fp8_record(af_handle* h, int on, void* stream) {
   if (!h) { af_set_error_msg("af_fp8_record: null handle"); return AF_ERR_INVALID; }
-  if (on && !h->fp8_rec) { af_set_error_msg("af_fp8_record: the handle has no fp8 sites (f32 handle, or no UNet)"); return AF_ERR_STATE; }
+  if (on && !h->fp8_rec) { af_set_error_msg("af_fp8_record: the handle has no fp8 sites (f32 or fp16 handle, or no UNet)"); return AF_ERR_STATE; }
   if (on) {
     HIP_CHECK_RET(hipSetDevice(h->device));
     HIP_CHECK_RET(hipMemsetAsync(h->fp8_rec, 0, h->fp8_shift.size() * 2 * sizeof(unsigned), reinterpret_cast<hipStream_t>(stream)));

@@ -14,6 +14,7 @@
 //   layernorm   one wave per row, row held in registers, two-pass variance
 #include "af_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 #define GN_GROUPS 32
 #define GN_MAX_C 2560
@@ -521,7 +522,7 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
                         const float* beta, float eps, int silu, void* y, long y_bs, int ldy, void* workspace,
                         hipStream_t stream, float fp8_mul, const float* pre_partial, int pre_npart, unsigned* fp8_rec) {
   constexpr int EPC = 16 / sizeof(T);
-  if (fp8_mul != 0.f && sizeof(T) != 2) { af_set_error_msg("groupnorm: fp8 output needs the bf16 storage mode"); return -1; }
+  if (fp8_mul != 0.f && !std::is_same_v<T, bf16>) { af_set_error_msg("groupnorm: fp8 output needs the bf16 storage mode"); return -1; }
   if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("groupnorm: an fp8 record needs the fp8 output"); return -1; }
   if (Cn % GN_GROUPS != 0 || Cn % EPC != 0 || Cn > GN_MAX_C || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("groupnorm: unsupported C=%d (need C%%32==0, C%%%d==0, C<=%d)", Cn, EPC, GN_MAX_C);
@@ -534,7 +535,7 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
     const bool small_ok = g_af_knobs.gn_small != 0;
     if (small_ok && cpg % EPC == 0 && (long)HW * (cpg / EPC) <= 256 * GNS_MAXV && Cn % 4 == 0) {
       if (fp8_rec) {   // (e4m3 output exists for bf16 only: no recording variant of the f32 kernels)
-        if constexpr (sizeof(T) == 2)
+        if constexpr (std::is_same_v<T, bf16>)
           hipLaunchKernelGGL((gn_small_kernel<T, true>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
                              x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
       } else
@@ -562,7 +563,7 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
   const bool fold = npart <= 64;  // few chunks: the apply blocks finalize the statistics themselves
   if (!fold) hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, stream, partial, npart, count, eps, stats);
   if (fp8_rec) {
-    if constexpr (sizeof(T) == 2)
+    if constexpr (std::is_same_v<T, bf16>)
       hipLaunchKernelGGL((gn_apply_kernel<T, true>), dim3(nchunk, B), dim3(256), 0, stream,
                          reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, stats, gamma, beta, silu,
                          reinterpret_cast<T*>(y), y_bs, ldy, fold ? partial : nullptr, nchunk, count, eps, fp8_mul, npart, fp8_rec);
@@ -643,7 +644,7 @@ template <typename T>
 int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* gamma, const float* beta,
                         float eps, void* y, int ldy, hipStream_t stream, float fp8_mul, unsigned* fp8_rec) {
   constexpr int EPC = 16 / sizeof(T);
-  if (fp8_mul != 0.f && sizeof(T) != 2) { af_set_error_msg("layernorm: fp8 output needs the bf16 storage mode"); return -1; }
+  if (fp8_mul != 0.f && !std::is_same_v<T, bf16>) { af_set_error_msg("layernorm: fp8 output needs the bf16 storage mode"); return -1; }
   if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("layernorm: an fp8 record needs the fp8 output"); return -1; }
   if (Cn % EPC != 0 || Cn / EPC > 64 * LN_MAXV || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("layernorm: unsupported C=%d", Cn);
@@ -657,7 +658,7 @@ int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* 
   // (few rows of many vectors -- [4096, 1280] -- fill the chip better with one wave per row: measured 10 vs 19 us)
   if (NV % RL == 0 && NV / RL <= 10 && Cn <= 1280 && Cn % 4 == 0 && rows / RPB >= 256) {
     if (fp8_rec) {
-      if constexpr (sizeof(T) == 2)
+      if constexpr (std::is_same_v<T, bf16>)
         hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL, true>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
                            reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
     } else
@@ -667,7 +668,7 @@ int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* 
     return 0;
   }
   if (fp8_rec) {
-    if constexpr (sizeof(T) == 2)
+    if constexpr (std::is_same_v<T, bf16>)
       hipLaunchKernelGGL((layernorm_kernel<T, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
                          reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
                          reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
@@ -691,3 +692,9 @@ template int af_launch_layernorm<bf16>(const void*, int, long, int, const float*
                                        hipStream_t, float, unsigned*);
 template int af_launch_layernorm<float>(const void*, int, long, int, const float*, const float*, float, void*,
                                         int, hipStream_t, float, unsigned*);
+template int af_launch_groupnorm<f16>(const void*, long, int, int, int, int, const float*, const float*, float,
+                                      int, void*, long, int, void*, hipStream_t, float, const float*, int, unsigned*);
+template int af_launch_groupnorm_fold<f16>(const void*, long, int, int, int, int, const float*, const float*, float, void*,
+                                           hipStream_t, const float*, int, float*);
+template int af_launch_layernorm<f16>(const void*, int, long, int, const float*, const float*, float, void*, int,
+                                      hipStream_t, float, unsigned*);

@@ -25,8 +25,9 @@ struct Tmp {
     for (void* p : bufs) hipFree(p);
   }
 };
-inline size_t esz(int dtype) { return dtype == AF_DTYPE_BF16 ? 2 : 4; }
-inline int bk(int dtype) { return dtype == AF_DTYPE_BF16 ? 64 : 32; }
+inline size_t esz(int dtype) { return dtype == AF_DTYPE_F32 ? 4 : 2; }
+inline int bk(int dtype) { return dtype == AF_DTYPE_F32 ? 32 : 64; }
+inline AfStorage storage_of(int dtype) { return dtype == AF_DTYPE_BF16 ? AF_ST_BF16 : dtype == AF_DTYPE_F16 ? AF_ST_F16 : AF_ST_F32; }
 inline int rup(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace
 
@@ -35,7 +36,7 @@ inline int rup(int a, int b) { return (a + b - 1) / b * b; }
     int _rc = (expr);         \
     if (_rc != 0) return _rc; \
   } while (0)
-#define DISP(dtype, A, B) ((dtype) == AF_DTYPE_BF16 ? (A) : (B))
+#define DISP(dtype, A, B, C) ((dtype) == AF_DTYPE_BF16 ? (A) : (dtype) == AF_DTYPE_F16 ? (C) : (B))
 #define OP_ALLOC(var, bytes, zero)                               \
   void* var = tmp.get((bytes), (zero));                          \
   if (!var) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
@@ -135,9 +136,11 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
   void* rn = nullptr;
   float* bn = nullptr;
   OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s)));
+              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s),
+              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s)));
   OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
-              af_launch_repack_weight<float>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s)));
+              af_launch_repack_weight<float>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
+              af_launch_repack_weight<f16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s)));
   if (bias_dev) {
     bn = reinterpret_cast<float*>(tmp.get((size_t)rup(Cout, 128) * 4, true));
     if (!bn) return AF_ERR_HIP;
@@ -147,7 +150,8 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
     rn = tmp.get((size_t)B * Ho * Wo * co4 * esz(dtype), false);
     if (!rn) return AF_ERR_HIP;
     OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s)));
+                af_launch_nchw_to_nhwc<float>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s),
+                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s)));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -164,12 +168,13 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
     OP_TRY(af_launch_up_phase4_weights(wn, rows_pad, cin_pad, ldw, w4, s));
     p.W_up4 = w4;
   }
-  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, (int)esz(dtype));
+  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype));
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws)));
+  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
   OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, Cout, Ho * Wo, co4, s)));
+              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
+              af_launch_nhwc_to_nchw<f16>(yn, y_dev, B, Cout, Ho * Wo, co4, s)));
   return 0;
 }
 
@@ -227,7 +232,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   p.bias = bn; p.residual = rn; p.ldr = co4; p.out = yn; p.ldo = co4; p.alpha = 1.f;
   p.k_logical = ks * ks * Cin;
   p.fp8 = 1; p.w_scale = sc; p.x_scale_e8 = 127 - act_shift;
-  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, 2);
+  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, AF_ST_BF16);
   if (pl.tile < 4) { af_set_error_msg("af_op_conv2d_fp8: no fp8 plan for M=%d N=%d K=%d", p.M, p.N, p.K); return AF_ERR_INVALID; }
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
@@ -356,7 +361,7 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   q.bias = b2_dev ? reinterpret_cast<float*>(b2n) : nullptr;
   q.residual = rn; q.ldr = Cout; q.out = yn; q.ldo = Cout; q.alpha = 1.f;
   q.fp8 = 1; q.w_scale = sc2; q.x_scale_e8 = 127 - shift2;
-  const AfGemmPlan pl = af_plan_conv_gemm(q, 1, 2);
+  const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
   if (pl.tile < 4) { af_set_error_msg("af_op_ff_fp8: no fp8 plan for ff.net.2 M=%d N=%d K=%d", q.M, q.N, q.K); return AF_ERR_INVALID; }
   if (plan_out) { plan_out[0] = pl.tile; plan_out[1] = pl.splitk; }
   void* ws = nullptr;
@@ -381,9 +386,11 @@ int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float*
   void* rn = nullptr;
   // [M,K] rows == NCHW with C=K, HW=1 per "sample": reuse the NCHW converter with B=M, HW=1
   OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, (int)M, K, 1, kp, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, (int)M, K, 1, kp, 1.f, s)));
+              af_launch_nchw_to_nhwc<float>(x_dev, xn, (int)M, K, 1, kp, 1.f, s),
+              af_launch_nchw_to_nhwc<f16>(x_dev, xn, (int)M, K, 1, kp, 1.f, s)));
   OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
-              af_launch_repack_weight<float>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s)));
+              af_launch_repack_weight<float>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
+              af_launch_repack_weight<f16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s)));
   if (bias_dev) {
     bn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad * 4, true));
     if (!bn) return AF_ERR_HIP;
@@ -393,7 +400,8 @@ int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float*
     rn = tmp.get((size_t)M * no4 * esz(dtype), false);
     if (!rn) return AF_ERR_HIP;
     OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s)));
+                af_launch_nchw_to_nhwc<float>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s),
+                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s)));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -406,12 +414,13 @@ int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float*
   p.epilogue = geglu ? AF_EPI_GEGLU : AF_EPI_NONE;
   p.alpha = 1.f;
   p.k_logical = K;
-  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, (int)esz(dtype));
+  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype));
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws)));
+  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
   OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, (int)M, N, 1, no4, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, (int)M, N, 1, no4, s)));
+              af_launch_nhwc_to_nchw<float>(yn, y_dev, (int)M, N, 1, no4, s),
+              af_launch_nhwc_to_nchw<f16>(yn, y_dev, (int)M, N, 1, no4, s)));
   return 0;
 }
 
@@ -453,7 +462,7 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
   {
     ConvGemmParams q = p;
     q.src = gn; q.out = y0;
-    const AfGemmPlan pl = af_plan_conv_gemm(q, 1, 2);
+    const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
     void* wsk = nullptr;
     if (pl.splitk > 1) { wsk = tmp.get(pl.ws_bytes, false); if (!wsk) return AF_ERR_HIP; }
     OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, wsk));
@@ -464,7 +473,7 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
     ConvGemmParams q = p;
     q.src = xn; q.out = y1;
     q.gn_ab = (const float*)ab; q.gn_hw = HW;
-    AfGemmPlan pl = af_plan_conv_gemm(q, 1, 2);
+    AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
     q.splitk = pl.splitk;
     if (!af_conv_rowpanel_kind(q, 1)) { af_set_error_msg("af_op_gn_conv1x1: M=%d K=%d N=%d has no row-panel launch", q.M, q.K, q.N); return AF_ERR_INVALID; }
     q.splitk = 0;
@@ -484,12 +493,15 @@ int af_op_groupnorm(int dtype, const float* x_dev, const float* gamma_dev, const
   OP_ALLOC(yn, (size_t)B * HW * C * esz(dtype), false);
   OP_ALLOC(ws, af_gn_workspace_bytes(B, HW), false);
   OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, C, HW, C, 1.f, s)));
+              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, C, HW, C, 1.f, s),
+              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, C, HW, C, 1.f, s)));
   OP_TRY(DISP(dtype,
               af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s),
-              af_launch_groupnorm<float>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s)));
+              af_launch_groupnorm<float>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s),
+              af_launch_groupnorm<f16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s)));
   OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, C, HW, C, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, C, HW, C, s)));
+              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, C, HW, C, s),
+              af_launch_nhwc_to_nchw<f16>(yn, y_dev, B, C, HW, C, s)));
   return 0;
 }
 
@@ -532,7 +544,7 @@ int af_op_conv_gn(const float* x_dev, const float* w_dev, const float* bias_dev,
   p.M = B * HW; p.N = Cout; p.K = ldw;
   p.bias = bn; p.residual = rn; p.ldr = Cout; p.out = hn; p.ldo = Cout; p.alpha = 1.f;
   p.k_logical = 9 * Cin;
-  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, 2);
+  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, AF_ST_BF16);
   if (!af_conv_gn_stats_ok(p, pl, Cout / 32)) {
     af_set_error_msg("af_op_conv_gn: no GroupNorm-statistics producer plan for M=%d N=%d K=%d", p.M, p.N, p.K);
     return AF_ERR_INVALID;
@@ -553,10 +565,11 @@ int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const
   Tmp tmp;
   OP_ALLOC(xn, (size_t)rows * C * esz(dtype), false);
   OP_ALLOC(yn, (size_t)rows * C * esz(dtype), false);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s), af_launch_cast_f32<float>(x_dev, xn, rows * C, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s), af_launch_cast_f32<float>(x_dev, xn, rows * C, s), af_launch_cast_f32<f16>(x_dev, xn, rows * C, s)));
   OP_TRY(DISP(dtype, af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s),
-              af_launch_layernorm<float>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, rows * C, s), af_launch_cast_to_f32<float>(yn, y_dev, rows * C, s)));
+              af_launch_layernorm<float>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s),
+              af_launch_layernorm<f16>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, rows * C, s), af_launch_cast_to_f32<float>(yn, y_dev, rows * C, s), af_launch_cast_to_f32<f16>(yn, y_dev, rows * C, s)));
   return 0;
 }
 
@@ -579,9 +592,9 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
         hipMemsetAsync((char*)vn + (size_t)nk * esz(dtype), 0xFF, tail, s) != hipSuccess) return AF_ERR_HIP;
   }
   OP_ALLOC(on, (size_t)nq * esz(dtype), true);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s), af_launch_cast_f32<f16>(q_dev, qn, nq, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s), af_launch_cast_f32<f16>(k_dev, kn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s), af_launch_cast_f32<f16>(v_dev, vn, nk, s)));
   AttnParams p;
   p.q = qn; p.k = kn; p.v = vn; p.o = on; p.lse = nullptr; p.causal = causal;
   p.ldq = p.ldk = p.ldv = p.ldo = C;
@@ -596,8 +609,8 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
       p.vt_pack = vt;
     }
   }
-  OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s)));
+  OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s), af_launch_attention<f16>(p, B, dh, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s), af_launch_cast_to_f32<f16>(on, o_dev, nq, s)));
   return 0;
 }
 
@@ -629,13 +642,15 @@ int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, cons
   OP_ALLOC(vn, (size_t)nk * esz(dtype), false);
   OP_ALLOC(kvn, (size_t)2 * nk * esz(dtype), false);   // K | V rows, as the cached context
   OP_ALLOC(on, (size_t)nq * esz(dtype), true);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s), af_launch_cast_f32<f16>(q_dev, qn, nq, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s), af_launch_cast_f32<f16>(k_dev, kn, nk, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s), af_launch_cast_f32<f16>(v_dev, vn, nk, s)));
   OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s),
-              af_launch_copy_channels<float>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s)));
+              af_launch_copy_channels<float>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s),
+              af_launch_copy_channels<f16>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s)));
   OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s),
-              af_launch_copy_channels<float>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s)));
+              af_launch_copy_channels<float>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s),
+              af_launch_copy_channels<f16>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s)));
   AttnParams p;
   p.q = qn; p.k = kvn; p.v = (char*)kvn + (size_t)C * esz(dtype); p.o = on; p.lse = nullptr; p.causal = 0;
   p.ldq = C; p.ldo = C; p.ldk = p.ldv = 2 * C;
@@ -655,17 +670,19 @@ int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, cons
     OP_ALLOC(s9, (size_t)B * heads * N * nt * sizeof(float), false);
     p.lse = (float*)lse;
     p.Nk = Nk - n_groups * nt;
-    OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s)));
+    OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s), af_launch_attention<f16>(p, B, dh, s)));
     for (int g = 0; g < n_groups; ++g) {
       const int tok0 = Nk - (n_groups - g) * nt;
       OP_TRY(DISP(dtype,
                   af_launch_conv_attn<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
                                             (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s),
                   af_launch_conv_attn<float>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
-                                             (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s)));
+                                             (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s),
+                  af_launch_conv_attn<f16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
+                                            (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s)));
     }
   }
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s)));
+  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s), af_launch_cast_to_f32<f16>(on, o_dev, nq, s)));
   return 0;
 }
 
@@ -721,9 +738,11 @@ int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int 
   Tmp tmp;
   OP_ALLOC(yn, (size_t)B * dim * esz(dtype), false);
   OP_TRY(DISP(dtype, af_launch_timestep_embedding<bf16>((const long long*)t_dev, yn, B, dim, s),
-              af_launch_timestep_embedding<float>((const long long*)t_dev, yn, B, dim, s)));
+              af_launch_timestep_embedding<float>((const long long*)t_dev, yn, B, dim, s),
+              af_launch_timestep_embedding<f16>((const long long*)t_dev, yn, B, dim, s)));
   OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, (long)B * dim, s),
-              af_launch_cast_to_f32<float>(yn, y_dev, (long)B * dim, s)));
+              af_launch_cast_to_f32<float>(yn, y_dev, (long)B * dim, s),
+              af_launch_cast_to_f32<f16>(yn, y_dev, (long)B * dim, s)));
   return 0;
 }
 

@@ -47,7 +47,7 @@ class HipModule(nn.Module):
     """nn.Module facade over an Engine.  Subclasses set `_engine_kwargs()` and `_ckpt_prefix`."""
 
     _ckpt_prefix = ""          # prefix the C library expects in front of this module's keys
-    compute_dtype = "bf16"     # "bf16" (throughput), "f32" (parity mode) or "fp8" (bf16 + e4m3 ResBlock convolutions)
+    compute_dtype = "bf16"     # "bf16" (throughput), "f32" (parity mode), "f16" (the reference's autocast precision) or "fp8" (bf16 + e4m3 ResBlock convolutions)
 
     def __init__(self):
         super().__init__()
@@ -73,9 +73,12 @@ class HipModule(nn.Module):
         return out
 
     def set_compute_dtype(self, dtype: str):
-        """'bf16', 'f32' or 'fp8' (bf16 storage with the UNet's ResBlock 3x3 convolutions on the block-scaled fp8 MFMA;
-        modules without such layers run it as bf16); takes effect at the next forward (the engine is rebuilt)."""
-        if dtype not in ("bf16", "f32", "fp8"):
+        """'bf16', 'f32', 'f16' (alias 'fp16': fp16 storage on the f16 MFMA, fp32 accumulation) or 'fp8' (bf16 storage with the
+        UNet's ResBlock 3x3 convolutions on the block-scaled fp8 MFMA; modules without such layers run it as bf16); takes effect
+        at the next forward (the engine is rebuilt)."""
+        if dtype == "fp16":
+            dtype = "f16"
+        if dtype not in ("bf16", "f32", "f16", "fp8"):
             raise ValueError(dtype)
         if dtype != self.compute_dtype:
             self.compute_dtype = dtype

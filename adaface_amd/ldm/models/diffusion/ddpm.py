@@ -279,13 +279,15 @@ class LatentDiffusion(DDPM):
         return self
 
     def set_compute_dtype(self, dtype: str, fp8_scope: str = "base"):
-        """'bf16' | 'f32' | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).
+        """'bf16' | 'f32' | 'f16' (alias 'fp16') | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).
         fp8_scope: 'base' (ResBlock convolutions and self-attention q / k / v) or 'base+ff' (also the transformer blocks'
         FeedForward); only looked at with dtype 'fp8'."""
         from adaface_amd.fp8_calib import parse_fp8_scope
         parse_fp8_scope(fp8_scope)                  # (refuse a bad scope before anything changes)
         if dtype != "fp8" and fp8_scope != "base":
             raise ValueError(f"fp8_scope={fp8_scope!r} needs the compute dtype 'fp8' (got {dtype!r})")
+        if dtype == "fp16":
+            dtype = "f16"
         rest = "bf16" if dtype == "fp8" else dtype
         if dtype == "fp8":
             self.model.diffusion_model.set_fp8_scope(fp8_scope)

@@ -2,7 +2,7 @@
 
 Same names / argument meaning as the torch.nn.functional calls the reference makes on
 the hot path, operating on fp32 CUDA(HIP) tensors in the reference's
-layouts.  `dtype` selects the kernels' storage/MFMA type: "bf16" or "f32".
+layouts.  `dtype` selects the kernels' storage/MFMA type: "bf16", "f32" or "f16".
 Used by the parity tests and by nobody on the hot path (the model executors call the
 same kernels internally with no conversions).
 """

@@ -11,7 +11,7 @@
  *   - `*_dev` pointers are device (HBM) pointers owned by the caller (PyTorch);
  *     the library never frees or retains them past the call (stream-ordered)
  *   - tensors crossing the boundary use the REFERENCE's layout and dtype
- *     (NCHW float32, int64 timesteps); NHWC bf16/f32 is internal
+ *     (NCHW float32, int64 timesteps); NHWC bf16/f32/fp16 is internal
  *   - `stream` is a hipStream_t (0 = default stream); a HANDLE is not thread-safe (one host thread at a time per handle), but
  *     distinct handles may be driven from distinct host threads: the library's process-wide state (launch counters, the
  *     per-kernel LDS attribute masks, the last plan) is atomic / locked; the counters then count all threads' launches
@@ -25,7 +25,17 @@ extern "C" {
 
 typedef struct af_handle af_handle;
 
-enum { AF_DTYPE_BF16 = 0, AF_DTYPE_F32 = 1 };
+enum { AF_DTYPE_BF16 = 0, AF_DTYPE_F32 = 1, AF_DTYPE_F16 = 2 };
+/* AF_DTYPE_F16: the precision of the reference's own GPU path (torch autocast fp16, scripts/stable_txt2img.py:711).
+ * Activations and weights are stored as IEEE fp16 (NHWC), every product runs on v_mfma_f32_32x32x16_f16 with fp32
+ * accumulation, and every normalisation, softmax and epilogue computes in fp32, as in the other modes.  A stored value
+ * beyond +-65504 becomes +-inf, as torch.Tensor.half() and the reference's autocast do: no epilogue clamps.  The mode
+ * covers everything a handle runs (UNet plain / twin / taps / conv attention, VAE decoder and encoder, CLIP tower) on the
+ * four-wave kernels the f32 mode uses, with the 16-bit K tile of 64: the four conv_gemm_kernel tiles (register or LDS-DMA
+ * staging), the LDS-halo 3x3 kernel, split-K with its reduce pass, the flash attention kernel and the stand-alone
+ * GroupNorm / LayerNorm kernels.  The eight-wave bf16 kernels, the LayerNorm / GroupNorm fusions and the packed
+ * cross-attention operands are not built for such a handle.  fp8 is refused: af_set_fp8, af_set_fp8_scope and the fp8
+ * record calls return AF_ERR_STATE, af_fp8_num_sites is 0. */
 enum {
   AF_OK = 0,
   AF_ERR_INVALID = -1,   /* bad argument / unsupported shape */
@@ -38,7 +48,7 @@ enum {
  * and Decoder / AutoencoderKL (ldm/modules/diffusionmodules/model.py:502-507,
  * ldm/models/autoencoder.py:286-300) as used by configs/stable-diffusion/v1-inference-ada.yaml:35-76. */
 typedef struct af_config {
-  int dtype;                      /* AF_DTYPE_BF16 (throughput) or AF_DTYPE_F32 (parity) */
+  int dtype;                      /* AF_DTYPE_BF16 (throughput), AF_DTYPE_F32 (parity) or AF_DTYPE_F16 (the reference's autocast precision) */
   /* UNet */
   int build_unet;
   int in_channels, model_channels, out_channels, num_res_blocks;

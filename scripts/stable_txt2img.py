@@ -53,8 +53,9 @@ def parse_args():
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
                     help="data-parallel ranks (one process per GPU); without a launcher the ranks are started here")
-    ap.add_argument("--dtype", choices=["bf16", "f32", "fp8"], default="bf16",
-                    help="fp8: bf16 with the UNet's ResBlock convolutions and self-attention q/k/v on e4m3 operands (PARITY UNPINNED)")
+    ap.add_argument("--dtype", choices=["bf16", "f32", "fp16", "fp8"], default="bf16",
+                    help="fp16: fp16 storage on the f16 MFMA, the precision of the reference's autocast path; "
+                         "fp8: bf16 with the UNet's ResBlock convolutions and self-attention q/k/v on e4m3 operands (PARITY UNPINNED)")
     ap.add_argument("--fp8-scope", dest="fp8_scope", choices=["base", "base+ff"], default="base",
                     help="--dtype fp8: base = ResBlock convolutions + self-attention q/k/v; base+ff = also the transformer "
                          "blocks' FeedForward (GEGLU + ff.net.2).  A scale file belongs to the scope it was calibrated under")

@@ -83,6 +83,7 @@ _SIGS = [
     ("af_unet_set_tap", C.c_int, [_P, C.c_int, _P]),
     ("af_gemm_plan_counts", C.c_int, [C.POINTER(C.c_int64)]),
     ("af_gemm_plan_counts_reset", C.c_int, []),
+    ("af_gemm_plan_query", C.c_int, [C.c_int, C.c_int64] + [C.c_int] * 16 + [C.POINTER(C.c_int64)]),
     ("af_knob_set", C.c_int, [C.c_char_p, C.c_int]),
     ("af_knob_get", C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     ("af_knob_reset", C.c_int, []),
@@ -163,7 +164,11 @@ def reset_knobs() -> None:
 
 
 def plan_counts(reset: bool = False) -> dict:
-    """af_gemm_plan_counts as a dict: tile0..tile5, halo, splitk, ln_consumer, ln_producer."""
+    """The launch counters since the last reset.  Conv / linear launches, read off the plan's kernel (AfPlanCount, af_kernels.h):
+    tile0..tile5 by the plan's tile (row-panel and 128 x 160 GEMM launches under the tile of the tiled kernel they replace),
+    halo (four-wave LDS-halo, not under a tile), splitk (launches that ran more than one K slice), ln_consumer / ln_producer,
+    fp8 and up_phase4 (neither under a tile), ff8, halo8 (also under tile5), rowpanel (row-panel and 128 x 160 GEMM launches),
+    gn_producer / gn_consumer; attention: attn_short, xattn_fused, conv_attn_short."""
     lib = load()
     c = (C.c_int64 * 10)()
     check(lib.af_gemm_plan_counts(c), "af_gemm_plan_counts")
@@ -182,6 +187,19 @@ def plan_counts(reset: bool = False) -> dict:
     if reset:
         lib.af_gemm_plan_counts_reset()
     return out
+
+
+def gemm_plan_query(dtype, M, N, K, cin_pad, ks=1, stride=1, pad=0, up=0, Hs=1, Ws=None, Ho=1, Wo=None, ldc=None, ldo=None,
+                    gn_hw=0, gn_cpg=0, flags=0) -> tuple:
+    """af_gemm_plan_query: (kernel, row-panel kind, tile, splitk, halo_tw, group_m, ws_bytes) of the launch these integers
+    describe (flags: the AF_PQ_* bits of include/adaface_hip.h).  Host only: no GPU is needed.  A linear is ks = 1 on a 1 x M map."""
+    Ws = M if Ws is None else Ws
+    Wo = M if Wo is None else Wo
+    out = (C.c_int64 * 7)()
+    check(load().af_gemm_plan_query(int(dtype), int(M), N, K, cin_pad, ks, stride, pad, up, Hs, Ws, Ho, Wo,
+                                    cin_pad if ldc is None else ldc, N if ldo is None else ldo, gn_hw, gn_cpg, flags, out),
+          "af_gemm_plan_query")
+    return tuple(int(v) for v in out)
 
 
 def check(rc: int, what: str = "") -> None:

@@ -402,13 +402,39 @@ struct ConvGemmParams {
   int gn_hw;
 };
 
-struct AfGemmPlan {
-  int tile;         // 0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64
-  int splitk;       // >= 1
-  size_t ws_bytes;  // fp32 slab workspace needed when splitk > 1
-  int halo_tw;      // 0 = implicit-GEMM kernel; 16 / 32 = LDS-halo 3x3 kernel with that patch width
-  int group_m;      // grouped tile ordering: M tiles swept per N tile
+// the launch path of a conv / linear GEMM (AfGemmPlan::kernel; the values are part of af_gemm_plan_query's result)
+enum AfGemmKernel {
+  AF_GK_NONE = 0,        // fp8 operands on a shape without an fp8 plan: the caller keeps the layer on bf16
+  AF_GK_WAVE4 = 1,       // four-wave implicit GEMM (conv_gemm_kernel, tiles 0..3)
+  AF_GK_HALO4 = 2,       // four-wave LDS-halo 3x3 kernel (conv3x3_halo_kernel)
+  AF_GK_PP = 3,          // eight-wave ping-pong kernel, bf16 operands (tiles 4 / 5)
+  AF_GK_PP_FP8 = 4,      // ... fp8 operands
+  AF_GK_HALO8 = 5,       // eight-wave LDS-halo 3x3 kernel (conv3x3_halo8_kernel)
+  AF_GK_S8 = 6,          // small-map 3x3 kernel (conv3x3_s8_kernel, af_conv_s8.hip)
+  AF_GK_UP_PHASE4 = 7,   // nearest-2x upsample + 3x3 as four 2x2 phases on the ping-pong kernel
+  AF_GK_ROWPANEL = 8,    // row-panel kernels (AfGemmPlan::rowpanel names which)
+  AF_GK_M128 = 9         // 128 x 160 tile GEMM for few rows (gemm_m128_kernel)
 };
+
+// What af_plan_conv_gemm decides for one conv / linear launch.  tile / splitk / halo_tw are what af_last_gemm_plan reports.
+struct AfGemmPlan {
+  int kernel;       // AfGemmKernel: the launch path; everything below describes it
+  int rowpanel;     // AF_GK_ROWPANEL: which kernel -- 1 GEGLU K = 320, 2 plain K = 320, 3 plain K = 1280, 4 GEGLU K = 640,
+                    // 5 plain K = 640; 0 on every other path
+  int tile;         // four-wave tiles 0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64; eight-wave tiles 4 = 256x128, 5 = 256x160
+                    // (HALO8 and S8: 5; UP_PHASE4: 4 or 5 by its column tile; HALO4: 0 / 1 = 128 columns, else 64); -1 with NONE.
+                    // ROWPANEL and M128 launches keep the tile of the tiled kernel they replace: they are counted
+                    // (af_gemm_plan_counts) and profiled under it
+  int splitk;       // K slices the launch runs in, >= 1 (1 on ROWPANEL, M128, UP_PHASE4, HALO4)
+  size_t ws_bytes;  // fp32 slabs [splitk][M][N] the launch needs; 0 with one slice
+  int halo_tw;      // 0 = no LDS halo; 16 / 32 = HALO4 with that patch width; 256 = HALO8; 8 = S8
+  int group_m;      // grouped tile ordering: M tiles swept per N tile
+  int ln_slabs;     // LayerNorm epilogues are planned where the ping-pong tile takes the GEMM in ONE K slice (a ROWPANEL / M128
+                    // launch that replaces such a tile included; not one whose planned slices M128 dropped): the 80-column
+                    // statistics slabs a producer then writes per row, 2 per column tile.  0 = no LayerNorm epilogue here
+};
+// a one-slice plan on `kernel` / `tile` with nothing else decided
+inline AfGemmPlan af_empty_plan(int kernel, int tile) { return AfGemmPlan{kernel, 0, tile, 1, 0, 0, 1, 0}; }
 
 struct AttnParams {
   const void* q; const void* k; const void* v; void* o;  // T

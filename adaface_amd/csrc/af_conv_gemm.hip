@@ -2325,29 +2325,18 @@ int af_launch_cast_fp8(const void* x, void* y, long n, float mul, hipStream_t st
 }
 
 static std::mutex g_last_plan_mu;
-static AfGemmPlan g_af_last_plan = {0, 1, 0, 0, 1};
+static AfGemmPlan g_af_last_plan = af_empty_plan(AF_GK_WAVE4, 0);
 void af_set_last_plan(const AfGemmPlan& pl) { std::lock_guard<std::mutex> lk(g_last_plan_mu); g_af_last_plan = pl; }
 AfGemmPlan af_get_last_plan() { std::lock_guard<std::mutex> lk(g_last_plan_mu); return g_af_last_plan; }
 std::atomic<long> g_af_gn_consumer_launches{0};
-// launches since af_gemm_plan_counts_reset: [0..5] by tile (implicit-GEMM / ping-pong kernels), [6] LDS-halo kernel,
-// [7] launches that sliced K (counted in their tile's slot as well), [8] / [9] ping-pong launches with the LayerNorm
-// consumer / statistics-producer epilogue, [10] ping-pong launches with fp8 operands, [11] eight-wave halo launches
-// (counted under tile 5 as well), [12] row-panel GEGLU launches (counted under their planned tile as well)
 std::atomic<long> g_af_ff8_launches{0};
-std::atomic<long> g_af_plan_counts[15] = {};   // [13]: phase-decomposed upsampled convolutions, [14]: GroupNorm-statistics producers
+std::atomic<long> g_af_plan_counts[AF_PC_COUNT] = {};   // launches since af_gemm_plan_counts_reset (AfPlanCount, af_kernels.h)
 
-
-// tile: 0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64
 static void plan_group_m(AfGemmPlan& pl, const ConvGemmParams& p);
 
-// fp8 operands: the ping-pong kernel or nothing (tile -1: the caller keeps the layer on the bf16 path)
+// fp8 operands: the ping-pong kernel or nothing (AF_GK_NONE, tile -1: the caller keeps the layer on the bf16 path)
 static AfGemmPlan plan_fp8(const ConvGemmParams& p, int batch) {
-  AfGemmPlan pl;
-  pl.tile = -1;
-  pl.splitk = 1;
-  pl.ws_bytes = 0;
-  pl.halo_tw = 0;
-  pl.group_m = 1;
+  AfGemmPlan pl = af_empty_plan(AF_GK_NONE, -1);
   const int cand = p.N % 160 == 0 ? 5 : (p.N % 128 == 0 ? 4 : -1);
   if (batch != 1 || p.epilogue == AF_EPI_GEGLU || cand < 0 || p.K % 128 != 0 || p.Cin % 64 != 0 || (p.ks != 1 && p.ks != 3) ||
       p.up != 0 || p.M < 512 || !g_af_knobs.gemm_pp)
@@ -2364,23 +2353,21 @@ static AfGemmPlan plan_fp8(const ConvGemmParams& p, int batch) {
   const long nbs = nb * s;
   const double fill = (double)nbs / (double)(((nbs + 255) / 256) * 256);
   if (fill < g_af_knobs.gemm_pp_minfill * 0.01) return pl;
+  pl.kernel = AF_GK_PP_FP8;
   pl.tile = cand;
   pl.splitk = s;
-  if (s > 1) pl.ws_bytes = (size_t)s * p.M * p.N * sizeof(float);
   plan_group_m(pl, p);
   return pl;
 }
 
-AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st) {
+// tile, K slices and halo form among the tiled kernels (four-wave, ping-pong, the three LDS-halo kernels), forced knobs included.
+// tile: 0 = 128x128, 1 = 64x128, 2 = 128x64, 3 = 64x64, 4 / 5 = ping-pong 256x128 / 256x160
+static AfGemmPlan plan_tiled(const ConvGemmParams& p, int batch, AfStorage st) {
   // fp16 plans like f32 with the 16-bit K tile: the four four-wave tiles, the LDS-halo kernel and split-K; every eight-wave
   // kernel below is bf16
   const int elem_size = st == AF_ST_F32 ? 4 : 2;
   const bool is_bf16 = st == AF_ST_BF16;
-  if (p.fp8) return plan_fp8(p, batch);
-  AfGemmPlan pl;
-  pl.tile = 0;
-  pl.splitk = 1;
-  pl.ws_bytes = 0;
+  AfGemmPlan pl = af_empty_plan(AF_GK_WAVE4, 0);
   const bool geglu = p.epilogue == AF_EPI_GEGLU;
   const bool n128 = geglu || (p.N % 128) == 0 || p.N > 640;
   static const int bm[4] = {128, 64, 128, 64}, bn[4] = {128, 128, 64, 64};
@@ -2422,7 +2409,6 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st) {
     if (nb64 >= 64 && nb64 <= 1024) { pl.tile = 3; pl.splitk = 1; }
   }
   // 3x3 / stride 1 / no upsample on maps that tile by 4x32 or 8x16 pixels: LDS-halo kernel (tile 2 or 0 = BN 64 / 128)
-  pl.halo_tw = 0;
   if (p.ks == 3 && p.stride == 1 && p.up == 0 && p.pad == 1 && batch == 1 && !geglu && pl.splitk == 1 &&
       p.Ho == p.Hi && p.Wo == p.Wi && p.ldc >= p.Cin && g_af_knobs.conv_halo) {
     if (p.Wo % 32 == 0 && p.Ho % 4 == 0) pl.halo_tw = 32;
@@ -2477,7 +2463,7 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st) {
   // 8 x 8 maps (round 4): tiles of four whole images x 80 columns over four K slices, the images' halos resident in LDS
   // (conv3x3_s8_kernel, af_conv_s8.hip); halo_tw = 8 names it
   // ... and the 16 x 16 maps: one whole image x 80 columns per tile, ONE K slice (256 tiles at Bf = 16)
-  if (is_bf16 && (g_af_knobs.conv_halo8 & 2) && g_af_knobs.gemm_pp && af_conv_s8_ok(p, batch) && !p.gn_stats_out &&
+  if (is_bf16 && (g_af_knobs.conv_halo8 & 2) && g_af_knobs.gemm_pp && af_conv_s8_slices(p, batch) && !p.gn_stats_out &&
       (p.Wo <= 16 || (g_af_knobs.conv_halo8 & 4))) {
     pl.tile = 5;
     pl.halo_tw = 8;
@@ -2490,7 +2476,7 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st) {
   if (pl.halo_tw == 8 && (pl.tile != 5 || pl.splitk != af_conv_s8_slices(p, batch))) pl.halo_tw = 0;   // (a forced tile / slice count: the generic kernels)
   if (pl.splitk > 1 && pl.halo_tw != 256 && pl.halo_tw != 8) pl.halo_tw = 0;
   if (pl.halo_tw == 256 && (pl.tile != 5 || (p.Cin / 64) % pl.splitk != 0)) pl.halo_tw = 0;
-  if (pl.splitk > 1) pl.ws_bytes = (size_t)pl.splitk * p.M * p.N * sizeof(float);
+  pl.kernel = pl.halo_tw == 8 ? AF_GK_S8 : pl.halo_tw == 256 ? AF_GK_HALO8 : pl.halo_tw ? AF_GK_HALO4 : pl.tile >= 4 ? AF_GK_PP : AF_GK_WAVE4;
   plan_group_m(pl, p);
   return pl;
 }
@@ -2500,7 +2486,7 @@ static void plan_group_m(AfGemmPlan& pl, const ConvGemmParams& p) {
   {
     // grouped tile order: minimise  X_bytes * (NT / gn) + W_bytes * (MT / gm)  with gm * gn = workgroups resident
     // per XCD (32 CUs x blocks per CU)
-    const bool h4 = pl.halo_tw != 0 && pl.halo_tw != 256 && pl.halo_tw != 8;   // the four-wave halo kernel (128-pixel patches)
+    const bool h4 = pl.kernel == AF_GK_HALO4;   // (128-pixel patches)
     const int tbm = h4 ? 128 : (pl.tile >= 4 ? 256 : bm[pl.tile]);
     const int tbn = h4 ? ((pl.tile == 0 || pl.tile == 1) ? 128 : 64) : (pl.tile == 5 ? 160 : pl.tile == 4 ? 128 : bn[pl.tile]);
     const int MT = (p.M + tbm - 1) / tbm, NT = (p.N + tbn - 1) / tbn;
@@ -2610,51 +2596,15 @@ template <int BN> static int launch_pp8(const ConvGemmParams& p, hipStream_t str
   return gather ? launch_pp_one<BN, 0, true, true, 2>(p, grid, stream) : launch_pp_one<BN, 0, false, true, 2>(p, grid, stream);
 }
 
-// fp8-operand launch (bf16 everywhere else): validated apart from the bf16 / f32 path, ping-pong kernel only
-static int launch_conv_gemm_fp8(ConvGemmParams p, hipStream_t stream, const AfGemmPlan* plan, void* ws) {
+// fp8 operands (bf16 everywhere else): validated apart from the bf16 / f32 / f16 path
+static int validate_fp8(const ConvGemmParams& p) {
   if (p.K % 128 != 0 || p.Cin % 64 != 0 || (p.ks != 1 && p.ks != 3) || p.K < p.ks * p.ks * p.Cin || p.ldw < p.K ||
       p.ldw % 16 != 0 || p.ldc % 16 != 0 || p.ldc < p.Cin || !p.w_scale || p.epilogue == AF_EPI_GEGLU || p.ln_stats || p.ln_stats_out) {
     af_set_error_msg("conv_gemm fp8: K=%d Cin=%d ks=%d ldw=%d ldc=%d (need K%%128==0, Cin%%64==0, ks 1|3, 16-byte pitches, row scales)",
                      p.K, p.Cin, p.ks, p.ldw, p.ldc);
     return -1;
   }
-  if (p.N % 4 != 0 || p.ldo % 4 != 0 || (p.residual && p.ldr % 4 != 0) || (p.rowbias && p.ldrb % 4 != 0)) {
-    af_set_error_msg("conv_gemm fp8: N/ldo/ldr/ldrb must be multiples of 4 (N=%d ldo=%d)", p.N, p.ldo);
-    return -1;
-  }
-  if (p.M <= 0 || p.N <= 0) return 0;
-  {
-    const int HoWo = p.Ho * p.Wo > 0 ? p.Ho * p.Wo : 1;
-    const double nb = (double)((p.M + HoWo - 1) / HoWo);
-    if (nb * (double)p.src_batch_stride >= 4294967280.0 || (double)p.Wrows * p.ldw >= 4294967280.0) {
-      af_set_error_msg("conv_gemm fp8: operand exceeds the 4 GB range of the 32-bit gather offsets (split the batch)");
-      return -1;
-    }
-  }
-  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, 1, AF_ST_BF16);
-  if (pl.tile != 4 && pl.tile != 5) {
-    af_set_error_msg("conv_gemm fp8: shape M=%d N=%d K=%d has no fp8 plan (ask af_plan_conv_gemm first)", p.M, p.N, p.K);
-    return -1;
-  }
-  if (pl.splitk > 1 && !ws) pl.splitk = 1;
-  p.splitk = pl.splitk;
-  p.ws = ws;
-  af_set_last_plan(pl);
-  g_af_plan_counts[10] += 1;
-  if (pl.splitk > 1) g_af_plan_counts[7] += 1;
-  set_launch_fields(p, pl);
-  if (p.gn_stats_out) {
-    if (!af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
-      af_set_error_msg("conv_gemm fp8: GroupNorm partial sums asked of a launch that cannot write them");
-      return -1;
-    }
-    g_af_plan_counts[14] += 1;
-  }
-  AfProfScope prof(AF_K_PP_FP8, stream, 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K),
-                   (double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N * 2.0);
-  const int rc = pl.tile == 4 ? launch_pp8<128>(p, stream) : launch_pp8<160>(p, stream);
-  if (rc) return rc;
-  return p.splitk > 1 ? launch_splitk_reduce<bf16>(p, stream) : 0;
+  return 0;
 }
 
 // GEGLU on fp8 operands with e4m3 output (ff_geglu_fp8_kernel): can these (fp8, GEGLU) parameters be launched?  p.out / p.ldo
@@ -2672,14 +2622,13 @@ int af_launch_ff_geglu_fp8(ConvGemmParams p, float out_mul, unsigned* rec, hipSt
     return -1;
   }
   using C = PpCfg<128>;
-  AfGemmPlan pl;
-  pl.tile = 4; pl.splitk = 1; pl.ws_bytes = 0; pl.halo_tw = 0; pl.group_m = 1;
+  AfGemmPlan pl = af_empty_plan(AF_GK_PP_FP8, 4);
   plan_group_m(pl, p);
   p.splitk = 1;
   p.ws = nullptr;
   set_launch_fields(p, pl);
   af_set_last_plan(pl);
-  g_af_plan_counts[10] += 1;
+  g_af_plan_counts[AF_PC_FP8] += 1;
   g_af_ff8_launches += 1;
   AfProfScope prof(AF_K_PP_FP8, stream, 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K),
                    (double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N * 0.5);
@@ -2783,7 +2732,7 @@ int af_launch_up_phase4_weights(const void* w3, int rows, int cin, int ldw3, voi
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
-// does the launcher take the four-phase form for this (validated, bf16) upsampled convolution?
+// does a (bf16) upsampled convolution take the four-phase form?
 static bool up_phase4_ok(const ConvGemmParams& p, int batch) {
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   return p.W_up4 && g_af_knobs.conv_up_phase4 && g_af_knobs.gemm_pp && batch == 1 && p.up == 1 && p.ks == 3 && p.stride == 1 &&
@@ -2792,8 +2741,8 @@ static bool up_phase4_ok(const ConvGemmParams& p, int batch) {
          p.M / 4 >= 1024 && !p.residual && !p.rowbias && !p.ln_stats && !p.ln_stats_out && p.epilogue != AF_EPI_GEGLU &&
          (double)4 * p.Wrows * 4 * p.Cin * 2 < 4294967280.0;
 }
-static int launch_up_phase4(ConvGemmParams p, hipStream_t stream) {
-  const int bn = p.N % 160 == 0 ? 160 : 128;
+// the 2x2 convolution of one phase on the stored map, as the kernel (and the tile order) sees it
+static void up_phase4_params(ConvGemmParams& p) {
   p.W = p.W_up4;
   p.ks = 2; p.up = 0; p.pad = 1;               // (the kernel takes the padding of its phase: 1 - dy, 1 - dx)
   p.Hi = p.Ho = p.Hs; p.Wi = p.Wo = p.Ws;      // GEMM rows = pixels of the stored map
@@ -2802,14 +2751,9 @@ static int launch_up_phase4(ConvGemmParams p, hipStream_t stream) {
   p.k_logical = p.K;                           // FLOPs actually spent (4/9 of the nine-tap form)
   p.phase4 = 1;                                // (direct epilogue: the wave-private transposition knows the phase's row map)
   p.splitk = 1; p.ws = nullptr;
-  AfGemmPlan pl;
-  pl.tile = bn == 160 ? 5 : 4; pl.splitk = 1; pl.ws_bytes = 0; pl.halo_tw = 0; pl.group_m = 1;
-  plan_group_m(pl, p);
-  set_launch_fields(p, pl);
-  af_set_last_plan(pl);
-  g_af_plan_counts[13] += 1;
-  AfProfScope prof(bn == 160 ? AF_K_PP160_GATHER : AF_K_PP128, stream, 2.0 * p.M * (double)p.N * p.K * 4,
-                   ((double)p.M * p.Cin + 4.0 * p.N * p.K + 4.0 * p.M * p.N) * 2);
+}
+static int launch_up_phase4(const ConvGemmParams& p, int tile, hipStream_t stream) {
+  const int bn = tile == 5 ? 160 : 128;
   dim3 grid(((p.M + 255) / 256) * (p.N / bn), 4, 1);
   return bn == 160 ? launch_pp_one<160, 0, true, false, 2>(p, grid, stream) : launch_pp_one<128, 0, true, false, 2>(p, grid, stream);
 }
@@ -2820,18 +2764,18 @@ static int launch_up_phase4(ConvGemmParams p, hipStream_t stream) {
 bool af_conv_gn_stats_ok(const ConvGemmParams& p, const AfGemmPlan& pl, int cpg) {
   auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
   const int hn = pl.tile == 5 ? 80 : 64;
-  return g_af_knobs.gn_producer && pl.tile >= 4 && pl.splitk <= 1 && pl.halo_tw != 8 && p.ks == 3 && p.stride == 1 && p.up == 0 &&
+  const bool eight_wave = pl.kernel == AF_GK_PP || pl.kernel == AF_GK_PP_FP8 || pl.kernel == AF_GK_HALO8;
+  return g_af_knobs.gn_producer && eight_wave && pl.splitk <= 1 && p.ks == 3 && p.stride == 1 && p.up == 0 &&
          p.epilogue != AF_EPI_GEGLU && !p.ln_stats && !p.ln_stats_out && cpg >= 2 && cpg % 2 == 0 && hn % cpg == 0 &&
          p.N == 32 * cpg && pow2(p.Ho * p.Wo) && p.Ho * p.Wo >= 64 && p.M % 64 == 0;
 }
 
-// Which row-panel kernel a bf16 launch with these (validated) parameters takes in ONE K slice: 0 none, 1 GEGLU K = 320,
+// Which row-panel kernel a bf16 launch with these parameters takes when it runs in ONE K slice: 0 none, 1 GEGLU K = 320,
 // 2 plain K = 320 (LayerNorm consumer / producer, residual), 3 plain K = 1280 -> 1280, 4 GEGLU K = 640, 5 plain K = 640
-// (N >= 1920), 6 the 128 x 160 tile GEMM for few rows (not a row-panel kernel: LayerNorm / GroupNorm consumers never get it).
-// The model asks before it decides who finalises LayerNorm statistics (ConvGemmParams::ln_parts_n).
-int af_conv_rowpanel_kind(const ConvGemmParams& p, int batch) {
+// (N >= 1920), 6 the 128 x 160 tile GEMM for few rows (AF_GK_M128, not a row-panel kernel: GroupNorm consumers never get it).
+static int rowpanel_kind(const ConvGemmParams& p, int batch) {
   const int lvl = g_af_knobs.geglu_rowpanel;
-  if (!lvl || batch != 1 || p.ks != 1 || p.pad != 0 || p.stride != 1 || p.up != 0 || p.splitk > 1 || p.rowbias || p.fp8 ||
+  if (!lvl || batch != 1 || p.ks != 1 || p.pad != 0 || p.stride != 1 || p.up != 0 || p.rowbias || p.fp8 ||
       p.Cin != p.K || p.ldc < p.Cin)
     return 0;
   const bool geglu = p.epilogue == AF_EPI_GEGLU;
@@ -2876,136 +2820,186 @@ int af_conv_rowpanel_kind(const ConvGemmParams& p, int batch) {
   return 0;
 }
 
+// THE decision: which kernel runs a conv / linear launch, in how many K slices.  The rules, in the order they apply:
+//   1. fp8 operands: the fp8 ping-pong kernel or no plan;
+//   2. bf16 upsampled 3x3 with phase weights: the four-phase launch;
+//   3. tile / split-K / halo among the tiled kernels, forced knobs included (plan_tiled);
+//   (no workspace for K slabs: one slice, whatever was planned)
+//   4. bf16: the 128 x 160 tile GEMM where it fills the chip in ONE slice, dropping planned slices;
+//   5. bf16: a row-panel kernel, if the launch (still) has one slice.
+// 4 and 5 keep tile / halo_tw / group_m of the tiled kernel they replace: their launches are counted and profiled under it.
+AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st, bool have_ws) {
+  const bool is_bf16 = st == AF_ST_BF16;
+  AfGemmPlan pl;
+  if (p.fp8) {
+    pl = plan_fp8(p, batch);
+  } else if (is_bf16 && up_phase4_ok(p, batch)) {
+    ConvGemmParams q = p;
+    up_phase4_params(q);
+    pl = af_empty_plan(AF_GK_UP_PHASE4, p.N % 160 == 0 ? 5 : 4);
+    plan_group_m(pl, q);
+    return pl;
+  } else {
+    pl = plan_tiled(p, batch, st);
+    // (folding at the 16x16 level through the 128 x 160 tile GEMM's epilogues measured neutral in round 3 -- 15.834 vs 15.842 ms per
+    // forward: a stand-alone LayerNorm over [4096, 1280] costs what the two epilogues and the statistics traffic cost -- and is not
+    // planned; at the 32x32 level the same kernel's two-slot form carries the epilogues)
+    if (pl.kernel == AF_GK_PP && pl.splitk == 1) pl.ln_slabs = (p.N / (pl.tile == 5 ? 160 : 128)) * 2;
+  }
+  if (!have_ws) pl.splitk = 1;
+  if (const int rk = is_bf16 ? rowpanel_kind(p, batch) : 0; rk == 6 || (rk && pl.splitk == 1)) {
+    pl.kernel = rk == 6 ? AF_GK_M128 : AF_GK_ROWPANEL;
+    pl.rowpanel = rk == 6 ? 0 : rk;
+    pl.splitk = 1;
+  }
+  if (pl.splitk > 1) pl.ws_bytes = (size_t)pl.splitk * p.M * p.N * sizeof(float);
+  return pl;
+}
+
+// the kernels that exist for bf16 storage only
+static int launch_bf16_only(const ConvGemmParams& p, const AfGemmPlan& pl, hipStream_t stream) {
+  switch (pl.kernel) {
+    case AF_GK_PP: return pl.tile == 4 ? launch_pp<128>(p, stream) : launch_pp<160>(p, stream);
+    case AF_GK_PP_FP8: return pl.tile == 4 ? launch_pp8<128>(p, stream) : launch_pp8<160>(p, stream);
+    case AF_GK_HALO8: return launch_halo8(p, stream);
+    case AF_GK_S8: return af_launch_conv_s8(p, stream);
+    case AF_GK_UP_PHASE4: return launch_up_phase4(p, pl.tile, stream);
+    case AF_GK_M128: return launch_gemm_m128(p, stream);
+    case AF_GK_ROWPANEL:
+      switch (pl.rowpanel) {
+        case 1: return launch_geglu_rowpanel(p, stream);
+        case 2: return launch_plain_rowpanel(p, stream);
+        case 3: return launch_plain_rowpanel_k1280(p, stream);
+        case 4: return launch_geglu_rowpanel(p, stream, true);
+        case 5: return launch_plain_rowpanel(p, stream, true);
+        default: break;
+      }
+      break;
+    default: break;
+  }
+  af_set_error_msg("conv_gemm: plan names no kernel (kernel %d, row-panel kind %d)", pl.kernel, pl.rowpanel);
+  return -1;
+}
+
+// validate, take the caller's plan (or plan), dispatch on plan.kernel
 template <typename T>
 int af_launch_conv_gemm(const ConvGemmParams& p_in, int batch, hipStream_t stream, const AfGemmPlan* plan, void* ws) {
   constexpr int BK = 128 / sizeof(T);
+  constexpr bool kBf16 = std::is_same_v<T, bf16>;
   ConvGemmParams p = p_in;
   if (p.fp8) {
-    if constexpr (std::is_same_v<T, bf16>) return batch == 1 ? launch_conv_gemm_fp8(p, stream, plan, ws) : (af_set_error_msg("conv_gemm fp8: no batched form"), -1);
-    else { af_set_error_msg("conv_gemm: fp8 operands need the bf16 storage mode"); return -1; }
-  }
-  if (p.gn_ab && !std::is_same_v<T, bf16>) { af_set_error_msg("conv_gemm: consumer-side GroupNorm exists on the bf16 row-panel kernels only"); return -1; }
-  if (p.K % BK != 0 || p.Cin % BK != 0 || p.K != p.ks * p.ks * p.Cin) {
-    af_set_error_msg("conv_gemm: K=%d Cin=%d ks=%d must satisfy K==ks*ks*Cin and Cin%%%d==0", p.K, p.Cin, p.ks, BK);
-    return -1;
-  }
-  if (p.ldw % (16 / (int)sizeof(T)) != 0 || p.ldc % (16 / (int)sizeof(T)) != 0) {
-    af_set_error_msg("conv_gemm: ldw/ldc must be multiples of 16 bytes");
-    return -1;
+    if (!kBf16) { af_set_error_msg("conv_gemm: fp8 operands need the bf16 storage mode"); return -1; }
+    if (batch != 1) { af_set_error_msg("conv_gemm fp8: no batched form"); return -1; }
+    if (int rc = validate_fp8(p)) return rc;
+  } else {
+    if (p.gn_ab && !kBf16) { af_set_error_msg("conv_gemm: consumer-side GroupNorm exists on the bf16 row-panel kernels only"); return -1; }
+    if (p.K % BK != 0 || p.Cin % BK != 0 || p.K != p.ks * p.ks * p.Cin) {
+      af_set_error_msg("conv_gemm: K=%d Cin=%d ks=%d must satisfy K==ks*ks*Cin and Cin%%%d==0", p.K, p.Cin, p.ks, BK);
+      return -1;
+    }
+    if (p.ldw % (16 / (int)sizeof(T)) != 0 || p.ldc % (16 / (int)sizeof(T)) != 0) {
+      af_set_error_msg("conv_gemm: ldw/ldc must be multiples of 16 bytes");
+      return -1;
+    }
+    if (p.epilogue == AF_EPI_GEGLU && p.N % 64 != 0) { af_set_error_msg("conv_gemm: GEGLU needs N%%64==0"); return -1; }
   }
   if (p.N % 4 != 0 || p.ldo % 4 != 0 || (p.residual && p.ldr % 4 != 0) || (p.rowbias && p.ldrb % 4 != 0)) {
     af_set_error_msg("conv_gemm: N/ldo/ldr/ldrb must be multiples of 4 (N=%d ldo=%d)", p.N, p.ldo);
     return -1;
   }
-  if (p.epilogue == AF_EPI_GEGLU && p.N % 64 != 0) { af_set_error_msg("conv_gemm: GEGLU needs N%%64==0"); return -1; }
   if (p.M <= 0 || p.N <= 0) return 0;
   {
     // the gathers address activations and weights with 32-bit byte offsets from one buffer base: refuse operands that
     // do not fit instead of wrapping around silently (SD-1.5 at batch 8 is ~0.25 GB per activation, the VAE ~1.1 GB)
     const int HoWo = p.Ho * p.Wo > 0 ? p.Ho * p.Wo : 1;
-    const double nb = (double)((p.M + HoWo - 1) / HoWo);
-    const double src_bytes = nb * (double)p.src_batch_stride * sizeof(T), w_bytes = (double)p.Wrows * p.ldw * sizeof(T);
+    const double nb = (double)((p.M + HoWo - 1) / HoWo), esz = p.fp8 ? 1.0 : (double)sizeof(T);   // (e4m3 strides are bytes)
+    const double src_bytes = nb * (double)p.src_batch_stride * esz, w_bytes = (double)p.Wrows * p.ldw * esz;
     if (src_bytes >= 4294967280.0 || w_bytes >= 4294967280.0) {
       af_set_error_msg("conv_gemm: operand of %.2f GB exceeds the 4 GB range of the 32-bit gather offsets (split the batch)",
                        (src_bytes > w_bytes ? src_bytes : w_bytes) / 1e9);
       return -1;
     }
   }
-  if constexpr (std::is_same_v<T, bf16>) {
-    if (up_phase4_ok(p, batch)) return launch_up_phase4(p, stream);
+  // a caller's plan is trusted, unless it slices K and no workspace came with it: then the planner decides for one slice
+  const AfGemmPlan pl = (plan && (ws || plan->splitk <= 1)) ? *plan : af_plan_conv_gemm(p, batch, StorageOf<T>::value, ws != nullptr);
+  const int k = pl.kernel;
+  if ((k == AF_GK_PP_FP8) != (p.fp8 != 0)) {
+    af_set_error_msg("conv_gemm%s: shape M=%d N=%d K=%d has no %s plan (ask af_plan_conv_gemm first)", p.fp8 ? " fp8" : "", p.M, p.N, p.K,
+                     p.fp8 ? "fp8" : "bf16-operand");
+    return -1;
   }
-  AfGemmPlan pl = plan ? *plan : af_plan_conv_gemm(p, batch, StorageOf<T>::value);
-  if (pl.splitk > 1 && !ws) pl.splitk = 1;  // no workspace supplied: fall back to one slice
-  if constexpr (std::is_same_v<T, bf16>) {
-    // the 128 x 160 tile GEMM fills the chip in one K slice where the 256-row tile was planned over two
-    if (pl.splitk > 1) {
-      ConvGemmParams q = p;
-      q.splitk = 1;
-      if (af_conv_rowpanel_kind(q, batch) == 6) pl.splitk = 1;
-    }
-  }
+  if (!kBf16 && k != AF_GK_WAVE4 && k != AF_GK_HALO4) { af_set_error_msg("conv_gemm: kernel %d of the plan is bf16 only", k); return -1; }
   p.splitk = pl.splitk;
   p.ws = ws;
   af_set_last_plan(pl);
-  if (g_af_knobs.plan_log)
+  if (g_af_knobs.plan_log && k != AF_GK_PP_FP8 && k != AF_GK_UP_PHASE4)
     fprintf(stderr, "[af plan] M=%ld N=%d K=%d ks=%d stride=%d up=%d HoWo=%dx%d batch=%d tile=%d halo=%d splitk=%d rowpanel=%d res=%d geglu=%d ln=%d\n",
-            (long)p.M, p.N, p.K, p.ks, p.stride, p.up, p.Ho, p.Wo, batch, pl.tile, pl.halo_tw, pl.splitk, af_conv_rowpanel_kind(p, batch),
+            (long)p.M, p.N, p.K, p.ks, p.stride, p.up, p.Ho, p.Wo, batch, pl.tile, pl.halo_tw, pl.splitk, k == AF_GK_M128 ? 6 : pl.rowpanel,
             p.residual ? 1 : 0, p.epilogue == AF_EPI_GEGLU ? 1 : 0, (p.ln_stats || p.ln_stats_out) ? 1 : 0);
-  g_af_plan_counts[(pl.halo_tw && pl.halo_tw != 256 && pl.halo_tw != 8) ? 6 : (pl.tile >= 0 && pl.tile < 6 ? pl.tile : 0)] += 1;
-  if (pl.halo_tw == 256) g_af_plan_counts[11] += 1;
-  if (pl.splitk > 1) g_af_plan_counts[7] += 1;
-  if (p.ln_stats) g_af_plan_counts[8] += 1;
-  if (p.ln_stats_out) g_af_plan_counts[9] += 1;
-  set_launch_fields(p, pl);
+  // counters: fp8 and four-phase launches under their own slot, every other launch under the tile of its plan
+  if (k == AF_GK_PP_FP8 || k == AF_GK_UP_PHASE4) {
+    g_af_plan_counts[k == AF_GK_PP_FP8 ? AF_PC_FP8 : AF_PC_UP_PHASE4] += 1;
+  } else {
+    g_af_plan_counts[k == AF_GK_HALO4 ? AF_PC_HALO4 : AF_PC_TILE0 + (pl.tile >= 0 && pl.tile < 6 ? pl.tile : 0)] += 1;
+    if (k == AF_GK_HALO8) g_af_plan_counts[AF_PC_HALO8] += 1;
+    if (p.ln_stats) g_af_plan_counts[AF_PC_LN_CONSUMER] += 1;
+    if (p.ln_stats_out) g_af_plan_counts[AF_PC_LN_PRODUCER] += 1;
+  }
+  if (pl.splitk > 1) g_af_plan_counts[AF_PC_SPLITK] += 1;
+  // what the caller asked of the epilogue / prologue must exist on the planned kernel
   if (p.gn_stats_out) {
-    if (!std::is_same_v<T, bf16> || batch != 1 || !af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
+    if (!kBf16 || batch != 1 || !af_conv_gn_stats_ok(p, pl, p.gn_cpg)) {
       af_set_error_msg("conv_gemm: GroupNorm partial sums asked of a launch that cannot write them (ask af_conv_gn_stats_ok first)");
       return -1;
     }
-    g_af_plan_counts[14] += 1;
+    g_af_plan_counts[AF_PC_GN_PRODUCER] += 1;
   }
-  const int prof_cls = pl.halo_tw == 256 ? AF_K_HALO8
-                       : pl.tile == 5 ? ((p.ks == 1 && p.pad == 0) ? AF_K_PP160_PLAIN : AF_K_PP160_GATHER)
-                                      : (pl.tile == 4 ? AF_K_PP128 : AF_K_CONV_GEMM);
-  AfProfScope prof(prof_cls, stream, 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K) * batch,
-                   ((double)p.M * p.K / (p.ks * p.ks) + (double)p.N * p.K + (double)p.M * p.N) * batch * sizeof(T));
-  int rc;
-  int rk_pre = 0;
-  if constexpr (std::is_same_v<T, bf16>) rk_pre = af_conv_rowpanel_kind(p, batch);
-  if ((p.ln_stats || p.ln_stats_out) && rk_pre != 6 && !(pl.tile >= 4 && !pl.halo_tw)) {   // (the 128 x 160 GEMM has both epilogues whatever was planned)
-    af_set_error_msg("conv_gemm: LayerNorm-fused launch planned on a kernel without that epilogue (tile %d)", pl.tile);
+  const bool rows_resident = k == AF_GK_ROWPANEL || k == AF_GK_M128;
+  // (LayerNorm epilogues are planned on the ping-pong tile: a row-panel launch carries them in its place, the 128 x 160 GEMM whatever was planned)
+  if ((p.ln_stats || p.ln_stats_out) && k != AF_GK_PP && k != AF_GK_M128 && !(k == AF_GK_ROWPANEL && pl.tile >= 4)) {
+    af_set_error_msg("conv_gemm: LayerNorm-fused launch planned on a kernel without that epilogue (kernel %d, tile %d)", k, pl.tile);
     return -1;
   }
-  // the row-panel kernels (activation rows resident in registers): K = 320 / 640 / 1280 GEMMs with enough rows
-  if constexpr (std::is_same_v<T, bf16>) {
-    const int rk = rk_pre;
-    if (p.ln_parts_n > 0 && !rk) {
-      af_set_error_msg("conv_gemm: un-finalised LayerNorm statistics handed to a launch that is not a row-panel one");
-      return -1;
-    }
-    if (p.gn_ab && !rk) {
-      af_set_error_msg("conv_gemm: consumer-side GroupNorm asked of a launch that is not a row-panel one (ask af_conv_rowpanel_kind first)");
-      return -1;
-    }
-    if (p.gn_ab) g_af_gn_consumer_launches += 1;
-    if (rk) g_af_plan_counts[12] += 1;
-    switch (rk) {
-      case 1: return launch_geglu_rowpanel(p, stream);
-      case 2: return launch_plain_rowpanel(p, stream);
-      case 3: return launch_plain_rowpanel_k1280(p, stream);
-      case 4: return launch_geglu_rowpanel(p, stream, true);
-      case 5: return launch_plain_rowpanel(p, stream, true);
-      case 6: return launch_gemm_m128(p, stream);
-      default: break;
-    }
+  if (p.ln_parts_n > 0 && !rows_resident) {
+    af_set_error_msg("conv_gemm: un-finalised LayerNorm statistics handed to a launch that is not a row-panel one");
+    return -1;
   }
-  if (pl.halo_tw == 8 || pl.halo_tw == 256) {
-    if constexpr (std::is_same_v<T, bf16>) {
-      rc = pl.halo_tw == 8 ? af_launch_conv_s8(p, stream) : launch_halo8(p, stream);
-    } else {
-      af_set_error_msg(pl.halo_tw == 8 ? "conv_gemm: the 8 x 8-map kernel is bf16 only" : "conv_gemm: the eight-wave halo kernel is bf16 only");
-      return -1;
+  if (p.gn_ab && k != AF_GK_ROWPANEL) {
+    af_set_error_msg("conv_gemm: consumer-side GroupNorm asked of a launch that is not a row-panel one (ask af_plan_conv_gemm first)");
+    return -1;
+  }
+  if (p.gn_ab) g_af_gn_consumer_launches += 1;
+  if (rows_resident) g_af_plan_counts[AF_PC_ROWPANEL] += 1;
+  if (k == AF_GK_UP_PHASE4) up_phase4_params(p);
+  set_launch_fields(p, pl);
+  // profiler class and traffic model of the launch
+  int prof_cls = pl.tile == 5 ? ((p.ks == 1 && p.pad == 0) ? AF_K_PP160_PLAIN : AF_K_PP160_GATHER) : (pl.tile == 4 ? AF_K_PP128 : AF_K_CONV_GEMM);
+  double flops = 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K) * batch;
+  double bytes = ((double)p.M * p.K / (p.ks * p.ks) + (double)p.N * p.K + (double)p.M * p.N) * batch * sizeof(T);
+  if (k == AF_GK_HALO8) prof_cls = AF_K_HALO8;
+  if (k == AF_GK_PP_FP8) { prof_cls = AF_K_PP_FP8; bytes = (double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N * 2.0; }
+  if (k == AF_GK_UP_PHASE4) { flops *= 4; bytes = ((double)p.M * p.Cin + 4.0 * p.N * p.K + 4.0 * p.M * p.N) * 2; }   // (four phases)
+  AfProfScope prof(prof_cls, stream, flops, bytes);
+  int rc;
+  switch (k) {
+    case AF_GK_WAVE4:
+      switch (pl.tile) {
+        case 0: rc = launch_cfg<T, 128, 128>(p, batch, stream); break;
+        case 1: rc = launch_cfg<T, 64, 128>(p, batch, stream); break;
+        case 2: rc = launch_cfg<T, 128, 64>(p, batch, stream); break;
+        default: rc = launch_cfg<T, 64, 64>(p, batch, stream); break;
+      }
+      break;
+    case AF_GK_HALO4: {
+      const bool bn128 = pl.tile == 0 || pl.tile == 1;
+      if (pl.halo_tw == 32) rc = bn128 ? launch_halo<T, 32, 128>(p, stream) : launch_halo<T, 32, 64>(p, stream);
+      else rc = bn128 ? launch_halo<T, 16, 128>(p, stream) : launch_halo<T, 16, 64>(p, stream);
+      break;
     }
-  } else if (pl.halo_tw) {
-    const bool bn128 = pl.tile == 0 || pl.tile == 1;
-    if (pl.halo_tw == 32) return bn128 ? launch_halo<T, 32, 128>(p, stream) : launch_halo<T, 32, 64>(p, stream);
-    return bn128 ? launch_halo<T, 16, 128>(p, stream) : launch_halo<T, 16, 64>(p, stream);
-  } else {
-    switch (pl.tile) {
-      case 4:
-      case 5:
-        if constexpr (std::is_same_v<T, bf16>) {
-          rc = pl.tile == 4 ? launch_pp<128>(p, stream) : launch_pp<160>(p, stream);
-        } else {
-          af_set_error_msg("conv_gemm: ping-pong tiles are bf16 only");
-          return -1;
-        }
-        break;
-      case 0: rc = launch_cfg<T, 128, 128>(p, batch, stream); break;
-      case 1: rc = launch_cfg<T, 64, 128>(p, batch, stream); break;
-      case 2: rc = launch_cfg<T, 128, 64>(p, batch, stream); break;
-      default: rc = launch_cfg<T, 64, 64>(p, batch, stream); break;
-    }
+    default:
+      if constexpr (kBf16) rc = launch_bf16_only(p, pl, stream);
+      else rc = -1;   // (refused above)
+      break;
   }
   if (rc) return rc;
   return p.splitk > 1 ? launch_splitk_reduce<T>(p, stream) : 0;

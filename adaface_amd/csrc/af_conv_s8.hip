@@ -322,7 +322,6 @@ int af_conv_s8_slices(const ConvGemmParams& p, int batch) {
   return (p.Cin % 64 == 0 && p.ldo % 8 == 0 && (!p.residual || p.ldr % 4 == 0) && (!p.rowbias || p.ldrb % 4 == 0) && ((__UINTPTR_TYPE__)p.out & 15) == 0 &&
           (long)(p.M / cs8::BM) * (p.N / cs8::BN) >= 128) ? 1 : 0;
 }
-bool af_conv_s8_ok(const ConvGemmParams& p, int batch) { return af_conv_s8_slices(p, batch) != 0; }
 int af_launch_conv_s8(const ConvGemmParams& p, hipStream_t stream) {
   static unsigned long long attr_done4 = 0, attr_done1 = 0;
   const int sl = af_conv_s8_slices(p, 1);

@@ -2,7 +2,10 @@
 #pragma once
 #include "af_common.h"
 
-AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st);
+// The plan of a conv / linear launch: kernel, tile, K slices (AfGemmPlan, af_common.h).  have_ws = false: the launch gets no
+// workspace for K slabs.  A caller that needs to know what will run -- fp8 or not, row-panel or not, how much workspace -- asks
+// here and hands the plan to the launcher; the launcher plans itself when it gets none.
+AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st, bool have_ws = true);
 template <typename T>
 int af_launch_conv_gemm(const ConvGemmParams& p, int batch, hipStream_t stream, const AfGemmPlan* plan = nullptr,
                         void* ws = nullptr);
@@ -60,11 +63,10 @@ int af_launch_groupnorm_fold(const void* x, long x_bs, int ldx, int B, int HW, i
                              float* ab_out);
 // would a bf16 convolution with these parameters on this plan write GroupNorm partial sums (ConvGemmParams::gn_stats_out)?
 bool af_conv_gn_stats_ok(const ConvGemmParams& p, const AfGemmPlan& pl, int cpg);
-// the 8 x 8-map 3x3 convolution kernel (af_conv_s8.hip): four whole images x 80 columns per tile, always four K slices
-bool af_conv_s8_ok(const ConvGemmParams& p, int batch);
-int af_conv_s8_slices(const ConvGemmParams& p, int batch);    // K slices it runs in (8 x 8 maps: 4, 16 x 16 maps: 1), 0 = not taken
+// the small-map 3x3 convolution kernel (af_conv_s8.hip; planner and launcher only): K slices it runs in (8 x 8 maps: 4,
+// 16 x 16 maps: 1), 0 = not taken
+int af_conv_s8_slices(const ConvGemmParams& p, int batch);
 int af_launch_conv_s8(const ConvGemmParams& p, hipStream_t stream);
-int af_conv_rowpanel_kind(const ConvGemmParams& p, int batch);   // 0 = not a row-panel launch (p.splitk as planned)
 template <typename T>
 int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* gamma, const float* beta,
                         float eps, void* y, int ldy, hipStream_t stream, float fp8_mul = 0.f, unsigned* fp8_rec = nullptr);
@@ -134,7 +136,21 @@ int af_launch_ln_finalize(const float* part, int parts, int M, int count, float 
 // plan of the most recent af_launch_conv_gemm (diagnostics, af_last_gemm_plan)
 void af_set_last_plan(const AfGemmPlan& pl);
 AfGemmPlan af_get_last_plan();
-extern std::atomic<long> g_af_plan_counts[15];
+// launches since af_gemm_plan_counts_reset, read off the plan's kernel by af_launch_conv_gemm
+enum AfPlanCount {
+  AF_PC_TILE0 = 0,         // [0..5] by AfGemmPlan::tile: four-wave, ping-pong, eight-wave halo, small-map, row-panel and M128 launches
+  AF_PC_HALO4 = 6,         // four-wave LDS-halo launches (not counted under their tile)
+  AF_PC_SPLITK = 7,        // launches that ran more than one K slice (besides their own slot)
+  AF_PC_LN_CONSUMER = 8,   // launches with the LayerNorm consumer epilogue ...
+  AF_PC_LN_PRODUCER = 9,   // ... / the statistics-producer epilogue
+  AF_PC_FP8 = 10,          // fp8-operand launches (ff_geglu_fp8 included); not counted under a tile
+  AF_PC_HALO8 = 11,        // eight-wave halo launches (counted under tile 5 as well)
+  AF_PC_ROWPANEL = 12,     // row-panel and M128 launches (counted under their planned tile as well)
+  AF_PC_UP_PHASE4 = 13,    // four-phase upsample launches; not counted under a tile
+  AF_PC_GN_PRODUCER = 14,  // launches that wrote GroupNorm partial sums
+  AF_PC_COUNT = 15
+};
+extern std::atomic<long> g_af_plan_counts[AF_PC_COUNT];
 extern std::atomic<long> g_af_gn_consumer_launches;
 int af_launch_up_phase4_weights(const void* w3, int rows, int cin, int ldw3, void* w4, hipStream_t stream);
 // fp8 (e4m3) twin of a repacked bf16 weight (K in 64-channel units, power-of-two row scales) / saturating bf16 -> e4m3 cast

@@ -864,7 +864,7 @@ struct Runner {
     x8.f8 = true; x8.ld = x.C;
     ConvGemmParams p;
     conv_params(p, L, x8, out, stride, up, nullptr, nullptr, 0, -1, -1);
-    return af_plan_conv_gemm(p, 1, AF_ST_BF16).tile >= 4;
+    return af_plan_conv_gemm(p, 1, AF_ST_BF16).kernel == AF_GK_PP_FP8;
   }
   // FeedForward scope: would BOTH GEMMs of a transformer block's FeedForward run on fp8 operands -- ff1 (GEGLU, e4m3 output,
   // ff_geglu_fp8_kernel) on e4m3(norm3 x) and ff2 on its bytes?  From the scope, the shapes and the twins alone.
@@ -890,18 +890,13 @@ struct Runner {
     if (dry) return 0;
     return af_launch_ff_geglu_fp8(p, ldexpf(1.f, y8.f8_shift), fp8_rec_of(y8), s);
   }
-  // would this 1x1 GEMM run on the ping-pong kernel in one K slice (the only place the LayerNorm epilogues exist)?
-  // returns the number of 80-column statistics slabs its output rows would be cut into (0 = no)
+  // may this 1x1 GEMM carry a LayerNorm epilogue?  returns the number of 80-column statistics slabs its output rows would be cut
+  // into (AfGemmPlan::ln_slabs; 0 = no)
   int ln_capable(const Linear& L, const Act& x, const Act& out, int n_valid = -1) const {
     if (dt != AF_DTYPE_BF16 || L.ks != 1) return 0;
     ConvGemmParams p;
     conv_params(p, L, x, out, 1, 0, nullptr, nullptr, 0, n_valid, -1);
-    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
-    // (folding at the 16x16 level through the 128 x 160 tile GEMM's epilogues measured neutral in round 3 -- 15.834 vs 15.842 ms per
-    // forward: a stand-alone LayerNorm over [4096, 1280] costs what the two epilogues and the statistics traffic cost -- and is not
-    // planned; at the 32x32 level the same kernel's two-slot form carries the epilogues)
-    if (pl.tile < 4 || pl.splitk > 1 || pl.halo_tw) return 0;
-    return (p.N / (pl.tile == 5 ? 160 : 128)) * 2;
+    return af_plan_conv_gemm(p, 1, storage_of(dt)).ln_slabs;
   }
   // would conv(L, x, out, ..., ln) be a row-panel launch (the only kernels that can apply a GroupNorm of their input)?
   bool rowpanel_capable(const Linear& L, const Act& x, const Act& out, const LnArgs* ln, int gn_hw) const {
@@ -911,9 +906,7 @@ struct Runner {
     if (ln) { p.ln_stats = ln->stats; p.ln_colsum = ln->colsum; p.ln_stats_out = ln->stats_out; }
     p.gn_ab = reinterpret_cast<const float*>(1);   // (capability question only)
     p.gn_hw = gn_hw;
-    const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
-    p.splitk = pl.splitk;
-    return af_conv_rowpanel_kind(p, 1) != 0;
+    return af_plan_conv_gemm(p, 1, storage_of(dt)).kernel == AF_GK_ROWPANEL;
   }
   // GroupNorm reduced to its per-sample affine map [B][2][C] for such a consumer (statistics from the producer when it left them)
   int groupnorm_fold(const Norm& N, const Act& x, float* ab) {
@@ -952,16 +945,9 @@ struct Runner {
     }
     if (x.f8 && (!L.w8 || ln)) { af_set_error_msg("conv: e4m3 input without an fp8 weight twin"); return AF_ERR_STATE; }
     const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
-    if (x.f8 && pl.tile < 4) { af_set_error_msg("conv: e4m3 input on a shape without an fp8 plan"); return AF_ERR_STATE; }
+    if (x.f8 && pl.kernel != AF_GK_PP_FP8) { af_set_error_msg("conv: e4m3 input on a shape without an fp8 plan"); return AF_ERR_STATE; }
     if (ln_parts_pending) {
-      ConvGemmParams q = p;
-      q.splitk = pl.splitk;
-      int kind = dt == AF_DTYPE_BF16 ? af_conv_rowpanel_kind(q, 1) : 0;
-      if (!kind && dt == AF_DTYPE_BF16 && pl.splitk > 1) {   // (the launcher drops the K slices of a plan the 128 x 160 GEMM takes)
-        q.splitk = 1;
-        if (af_conv_rowpanel_kind(q, 1) == 6) kind = 6;
-      }
-      if (kind) {
+      if (pl.kernel == AF_GK_ROWPANEL || pl.kernel == AF_GK_M128) {   // (these sum the partial statistics of their rows themselves)
         p.ln_stats = ln->parts_in;
         p.ln_parts_n = ln->parts_n;
         p.ln_inv_count = 1.0f / (float)ln->count;
@@ -2479,15 +2465,15 @@ int af_gemm_plan_counts_reset(void) {
   g_af_conv_attn_short_launches = 0;
   g_af_gn_consumer_launches = 0;
   g_af_ff8_launches = 0;
-  for (int i = 0; i < 15; ++i) g_af_plan_counts[i] = 0;
+  for (int i = 0; i < AF_PC_COUNT; ++i) g_af_plan_counts[i] = 0;
   return AF_OK;
 }
-int64_t af_fp8_gemm_launches(void) { return g_af_plan_counts[10]; }
+int64_t af_fp8_gemm_launches(void) { return g_af_plan_counts[AF_PC_FP8]; }
 int64_t af_ff8_launches(void) { return g_af_ff8_launches; }
-int64_t af_halo8_launches(void) { return g_af_plan_counts[11]; }
-int64_t af_rowpanel_launches(void) { return g_af_plan_counts[12]; }
-int64_t af_up_phase4_launches(void) { return g_af_plan_counts[13]; }
-int64_t af_gn_producer_launches(void) { return g_af_plan_counts[14]; }
+int64_t af_halo8_launches(void) { return g_af_plan_counts[AF_PC_HALO8]; }
+int64_t af_rowpanel_launches(void) { return g_af_plan_counts[AF_PC_ROWPANEL]; }
+int64_t af_up_phase4_launches(void) { return g_af_plan_counts[AF_PC_UP_PHASE4]; }
+int64_t af_gn_producer_launches(void) { return g_af_plan_counts[AF_PC_GN_PRODUCER]; }
 int64_t af_attn_short_launches(void) { return g_af_attn_short_launches; }
 int64_t af_xattn_fused_launches(void) { return g_af_xattn_fused_launches; }
 int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches; }

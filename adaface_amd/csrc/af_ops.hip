@@ -178,6 +178,40 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
   return 0;
 }
 
+// Host-only diagnostic: the plan af_launch_conv_gemm would follow for a launch described by integers.  Parameters as af_op_conv2d
+// / af_op_linear build them (a linear: ks 1, the M rows as one 1 x M map), flagged operands as aligned dummies, alpha 1; no device
+// is touched.  out7 = {kernel (AfGemmKernel), row-panel kind, tile, splitk, halo_tw, group_m, ws_bytes}
+int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, int stride, int pad, int up, int Hs, int Ws, int Ho,
+                       int Wo, int ldc, int ldo, int gn_hw, int gn_cpg, int flags, int64_t* out7) {
+  if (!out7 || M <= 0 || M > 0x7fffffff || (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16)) {
+    af_set_error_msg("af_gemm_plan_query: bad argument");
+    return AF_ERR_INVALID;
+  }
+  alignas(16) static char dummy[16];
+  void* const d = dummy;
+  ConvGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.src = d; p.src_batch_stride = (long)Hs * Ws * ldc; p.ldc = ldc; p.Cin = cin_pad;
+  p.Hs = Hs; p.Ws = Ws; p.up = up; p.Hi = Hs << up; p.Wi = Ws << up; p.Ho = Ho; p.Wo = Wo;
+  p.ks = ks; p.stride = stride; p.pad = pad;
+  p.W = d; p.ldw = K; p.Wrows = rup(N, 128);
+  p.M = (int)M; p.N = N; p.K = K; p.k_logical = K;
+  p.out = d; p.ldo = ldo; p.alpha = 1.f;
+  if (flags & AF_PQ_GEGLU) p.epilogue = AF_EPI_GEGLU;
+  if (flags & AF_PQ_RESIDUAL) { p.residual = d; p.ldr = ldo; }
+  if (flags & AF_PQ_ROWBIAS) { p.rowbias = d; p.ldrb = N; }
+  if (flags & AF_PQ_LN_CONSUMER) { p.ln_stats = reinterpret_cast<const float*>(d); p.ln_colsum = reinterpret_cast<const float*>(d); }
+  if (flags & AF_PQ_LN_PRODUCER) p.ln_stats_out = reinterpret_cast<float*>(d);
+  if (flags & AF_PQ_GN_AB) { p.gn_ab = reinterpret_cast<const float*>(d); p.gn_hw = gn_hw; }
+  if (flags & AF_PQ_GN_STATS_OUT) { p.gn_stats_out = reinterpret_cast<float*>(d); p.gn_cpg = gn_cpg; }
+  if (flags & AF_PQ_FP8) { p.fp8 = 1; p.w_scale = reinterpret_cast<const unsigned char*>(d); p.x_scale_e8 = 127; }
+  if (flags & AF_PQ_PHASE_WEIGHTS) p.W_up4 = d;
+  const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype), (flags & AF_PQ_WORKSPACE) != 0);
+  const int64_t o[7] = {pl.kernel, pl.rowpanel, pl.tile, pl.splitk, pl.halo_tw, pl.group_m, (int64_t)pl.ws_bytes};
+  memcpy(out7, o, sizeof(o));
+  return AF_OK;
+}
+
 // activation shifts of the fp8 mode: e4m3 of value * 2^s, s in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX] (adaface_hip.h)
 static bool act_shift_ok(int act_shift, const char* who) {
   if (act_shift >= AF_FP8_SHIFT_MIN && act_shift <= AF_FP8_SHIFT_MAX) return true;
@@ -233,7 +267,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   p.k_logical = ks * ks * Cin;
   p.fp8 = 1; p.w_scale = sc; p.x_scale_e8 = 127 - act_shift;
   const AfGemmPlan pl = af_plan_conv_gemm(p, 1, AF_ST_BF16);
-  if (pl.tile < 4) { af_set_error_msg("af_op_conv2d_fp8: no fp8 plan for M=%d N=%d K=%d", p.M, p.N, p.K); return AF_ERR_INVALID; }
+  if (pl.kernel != AF_GK_PP_FP8) { af_set_error_msg("af_op_conv2d_fp8: no fp8 plan for M=%d N=%d K=%d", p.M, p.N, p.K); return AF_ERR_INVALID; }
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
   OP_TRY(af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws));
@@ -362,7 +396,7 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   q.residual = rn; q.ldr = Cout; q.out = yn; q.ldo = Cout; q.alpha = 1.f;
   q.fp8 = 1; q.w_scale = sc2; q.x_scale_e8 = 127 - shift2;
   const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
-  if (pl.tile < 4) { af_set_error_msg("af_op_ff_fp8: no fp8 plan for ff.net.2 M=%d N=%d K=%d", q.M, q.N, q.K); return AF_ERR_INVALID; }
+  if (pl.kernel != AF_GK_PP_FP8) { af_set_error_msg("af_op_ff_fp8: no fp8 plan for ff.net.2 M=%d N=%d K=%d", q.M, q.N, q.K); return AF_ERR_INVALID; }
   if (plan_out) { plan_out[0] = pl.tile; plan_out[1] = pl.splitk; }
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
@@ -473,10 +507,8 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
     ConvGemmParams q = p;
     q.src = xn; q.out = y1;
     q.gn_ab = (const float*)ab; q.gn_hw = HW;
-    AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
-    q.splitk = pl.splitk;
-    if (!af_conv_rowpanel_kind(q, 1)) { af_set_error_msg("af_op_gn_conv1x1: M=%d K=%d N=%d has no row-panel launch", q.M, q.K, q.N); return AF_ERR_INVALID; }
-    q.splitk = 0;
+    const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
+    if (pl.kernel != AF_GK_ROWPANEL) { af_set_error_msg("af_op_gn_conv1x1: M=%d K=%d N=%d has no row-panel launch", q.M, q.K, q.N); return AF_ERR_INVALID; }
     OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, nullptr));
   }
   OP_TRY(af_launch_nhwc_to_nchw<bf16>(y0, y_plain_dev, B, N, HW, N, s));

@@ -201,14 +201,29 @@ int af_prof_collect(int n_classes, double* ms, int64_t* launches, double* flops,
 /* microseconds an EMPTY event pair measures on `stream` (mean of n): the bracket's own cost inside every timed launch */
 double af_prof_event_overhead_us(void* stream, int n);
 /* diagnostics: the tiling the most recent conv / linear launch of this process used.
- * tile: 0-3 = 128x128 / 64x128 / 128x64 / 64x64 four-wave tiles, 4 / 5 = 256x128 / 256x160 eight-wave ping-pong tiles;
- * halo_tw != 0: LDS-halo 3x3 kernel.  The parity tests use it to assert which kernel they exercised. */
+ * tile: 0-3 = 128x128 / 64x128 / 128x64 / 64x64 four-wave tiles, 4 / 5 = 256x128 / 256x160 eight-wave tiles (a row-panel or
+ * 128 x 160 GEMM launch reports the tile of the tiled kernel it replaced); halo_tw: 0 none, 16 / 32 four-wave LDS-halo 3x3
+ * kernel, 256 eight-wave halo kernel, 8 small-map kernel.  The parity tests use it to assert which kernel they exercised. */
 int af_last_gemm_plan(int* tile, int* splitk, int* halo_tw);
 /* launches per tiling since the last reset: counts10[0..5] by tile (as af_last_gemm_plan), [6] LDS-halo 3x3 kernel,
  * [7] launches that sliced K (also counted under their tile), [8] / [9] ping-pong launches whose epilogue applied a
  * folded LayerNorm / produced LayerNorm row statistics.  Lets a whole-model test assert which kernels it ran. */
 int af_gemm_plan_counts(int64_t* counts10);
 int af_gemm_plan_counts_reset(void);
+/* Host-only diagnostic: the plan a conv / linear launch described by integers would follow (no device is touched; honours
+ * af_knob_set).  The launch is built as af_op_conv2d / af_op_linear build it: M = GEMM rows, N = valid columns (GEGLU: both
+ * halves), K = padded reduction length (fp8: the twin's, a multiple of 128), cin_pad = padded input channels, stored map
+ * Hs x Ws (a linear: 1 x M), output map Ho x Wo, pitches ldc / ldo; gn_hw / gn_cpg go with AF_PQ_GN_AB / AF_PQ_GN_STATS_OUT.
+ * out7 = {kernel, row-panel kind, tile, splitk, halo_tw, group_m, ws_bytes}; tile / splitk / halo_tw as af_last_gemm_plan
+ * reports them after the launch.  kernel: 0 none (fp8 operands without an fp8 plan), 1 four-wave implicit GEMM, 2 four-wave
+ * LDS-halo, 3 ping-pong bf16, 4 ping-pong fp8, 5 eight-wave halo, 6 small-map 3x3, 7 four-phase upsample, 8 row-panel
+ * (kind 1..5: GEGLU K=320, plain K=320, plain K=1280, GEGLU K=640, plain K=640), 9 the 128 x 160 tile GEMM. */
+enum {
+  AF_PQ_GEGLU = 1, AF_PQ_RESIDUAL = 2, AF_PQ_ROWBIAS = 4, AF_PQ_LN_CONSUMER = 8, AF_PQ_LN_PRODUCER = 16, AF_PQ_GN_AB = 32,
+  AF_PQ_GN_STATS_OUT = 64, AF_PQ_FP8 = 128, AF_PQ_PHASE_WEIGHTS = 256, AF_PQ_WORKSPACE = 512
+};
+int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, int stride, int pad, int up, int Hs, int Ws, int Ho,
+                       int Wo, int ldc, int ldo, int gn_hw, int gn_cpg, int flags, int64_t* out7);
 
 /* ---- tuning / diagnostic knobs ----
  * The planner thresholds and "force this kernel variant" switches live in one struct that is filled once from the

@@ -140,6 +140,69 @@ def _last_plan():
     return t.value, s.value, h.value
 
 
+# one smallest launch per AfGemmKernel value: (what runs, knob, the launch as ops.* takes it).  conv: B, Cin, H, W, Cout, ks, stride, up;
+# linear: M, K, N, residual
+_PLAN_QUERY_LAUNCHES = [
+    ("four-wave", None, "bf16", "linear", (333, 128, 4, False)),
+    ("four-wave halo", None, "f32", "conv", (1, 4, 64, 64, 320, 3, 1, False)),
+    ("ping-pong", ("gemm_pp_minfill", 0), "bf16", "linear", (512, 64, 160, False)),
+    ("eight-wave halo", ("gemm_pp_minfill", 0), "bf16", "conv", (1, 64, 64, 64, 160, 3, 1, False)),
+    ("small-map", None, "bf16", "conv", (4, 256, 8, 8, 80, 3, 1, False)),
+    ("four-phase upsample", None, "bf16", "conv", (4, 128, 16, 16, 320, 3, 1, True)),
+    ("row-panel", None, "bf16", "linear", (32768, 320, 320, True)),
+    ("m128", None, "bf16", "linear", (4096, 1280, 1280, False)),
+    ("ping-pong fp8", ("gemm_pp_minfill", 0), "bf16", "conv_fp8", (2, 64, 32, 32, 160, 3, 2, False)),
+]
+
+
+@pytest.mark.parametrize("kernel,knob,dtype,op,shape", _PLAN_QUERY_LAUNCHES, ids=[c[0] for c in _PLAN_QUERY_LAUNCHES])
+def test_plan_query_matches_launch(gpu, knobs, kernel, knob, dtype, op, shape):
+    """af_gemm_plan_query (host only; tests/test_gemm_plan_cpu.py pins it against the golden table) describes what a real
+    launch does: for one smallest shape per kernel, af_last_gemm_plan and the launch counters after the op equal what the
+    query says for the same integers."""
+    from adaface_amd import _lib, ops
+    from tests import gemm_plan_cases as G
+    want_kernel = {"four-wave": G.K_WAVE4, "four-wave halo": G.K_HALO4, "ping-pong": G.K_PP, "eight-wave halo": G.K_HALO8,
+                   "small-map": G.K_S8, "four-phase upsample": G.K_UP_PHASE4, "row-panel": G.K_ROWPANEL, "m128": G.K_M128,
+                   "ping-pong fp8": G.K_PP_FP8}[kernel]
+    if knob:
+        knobs(*knob)
+    dt = {"bf16": G.BF16, "f32": G.F32}[dtype]
+    g = torch.Generator().manual_seed(3)
+    if op == "linear":
+        M, K, N, res = shape
+        args = G.linear_args(dt, M, K, N, residual=res)
+        x, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / math.sqrt(K)
+        run = lambda: ops.linear(x.to(gpu), w.to(gpu), None, torch.randn(M, N, generator=g).to(gpu) if res else None, dtype=dtype)  # noqa: E731
+    else:
+        B, Cin, H, W, Cout, ks, stride, up = shape
+        args = G.conv_fp8_args(B, Cin, H, W, Cout, ks, stride, up) if op == "conv_fp8" else G.conv_args(dt, B, Cin, H, W, Cout, ks, stride, up)
+        x, w = torch.randn(B, Cin, H, W, generator=g), torch.randn(Cout, Cin, ks, ks, generator=g) / math.sqrt(Cin * ks * ks)
+        if op == "conv_fp8":
+            run = lambda: ops.conv2d_fp8(x.to(gpu), w.to(gpu), None, stride=stride, upsample=up)  # noqa: E731
+        else:
+            run = lambda: ops.conv2d(x.to(gpu), w.to(gpu), None, stride=stride, upsample=up, dtype=dtype)  # noqa: E731
+    k, rowpanel, tile, splitk, halo, _, ws_bytes = _lib.gemm_plan_query(*args)
+    assert k == want_kernel and (rowpanel == 2) == (kernel == "row-panel"), (k, rowpanel)
+    assert (ws_bytes > 0) == (splitk > 1)
+    want = dict.fromkeys(["halo", "splitk", "ln_consumer", "ln_producer", "fp8", "halo8", "rowpanel", "up_phase4", "gn_producer"]
+                         + [f"tile{i}" for i in range(6)], 0)
+    if k in (G.K_PP_FP8, G.K_UP_PHASE4):
+        want["fp8" if k == G.K_PP_FP8 else "up_phase4"] = 1          # (not counted under a tile)
+    else:
+        want["halo" if k == G.K_HALO4 else f"tile{tile}"] = 1
+        want["halo8"] = int(k == G.K_HALO8)
+        want["rowpanel"] = int(k in (G.K_ROWPANEL, G.K_M128))
+    want["splitk"] = int(splitk > 1)
+    _lib.plan_counts(reset=True)
+    out = run()
+    torch.cuda.synchronize()
+    pc = _lib.plan_counts(reset=True)
+    assert torch.isfinite(out).all()
+    assert _last_plan() == (tile, splitk, halo), (_last_plan(), (tile, splitk, halo))
+    assert {n: pc[n] for n in want} == want, (pc, want)
+
+
 @pytest.mark.parametrize("B,Cin,H,W,Cout,ks,stride,up,bias,res,splitk", [
     (2, 320, 32, 32, 320, 3, 1, False, True, True, 1),    # gather, 2 N tiles of 160, residual
     (1, 128, 24, 24, 160, 3, 1, False, True, False, 1),   # M = 576: ragged last M tile (rows >= M read as zero)

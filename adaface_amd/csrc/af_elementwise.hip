@@ -368,6 +368,68 @@ __global__ void lincomb_kernel(float* __restrict__ out, long n, const float* __r
   }
 }
 
+// Fused classifier-free guidance + one DPM-Solver++(2M) step (Lu et al. 2022, "DPM-Solver++", Algorithm 2; the multistep
+// data-prediction update of the CompVis dpm_solver sampler), fp32, n elements:
+//   e  = e_u + g (e_c - e_u)                      (the guidance form of ddim_step_kernel; CFG = false: e = e_c)
+//   x0 = (x - sigma_t e) / alpha_t                (data prediction; written to x0_out, the next step's x0_prev)
+//   D  = w_cur x0 + w_prev x0_prev                (MS = false, a first-order step: D = x0)
+//   x' = c_x x + c_d D                            (c_x = sigma_prev / sigma_t, c_d = -alpha_prev expm1(-h): af_dpmpp_coeffs)
+// fp32 roundings on an output's longest path, FMA contraction not counted on (a fused multiply-add rounds once where two are
+// counted): e 3 (sub, mul, add), x - sigma_t e +2, the IEEE division +1 => x0_out 6 (3 without CFG); D +2 (mul, add; none
+// when MS = false); x' +2 => x_next 10 (8 / 7 / 5 without MS / CFG / both).
+// One work item is four consecutive elements (16-byte loads and stores) while it < n4 and the single element
+// 4 n4 + (it - n4) after that: n4 = n / 4 when every pointer is 16-byte aligned (the items past n4 are the n % 4 tail), n4 = 0
+// for the all-scalar path.  Every load of an item is issued before its first use, and every store comes after them, so x_next
+// may be x itself (no __restrict__ on that pair); x0_out aliases no input (af_dpmpp_step refuses it).
+struct DpmppArgs {
+  const float* x;
+  const float* eps_c;
+  const float* eps_u;
+  const float* x0_prev;
+  float* x_next;
+  float* x0_out;
+  long n, n4;
+  float guidance, alpha_t, sigma_t, c_x, c_d, w_cur, w_prev;
+};
+template <bool CFG, bool MS>
+__device__ __forceinline__ void dpmpp_update(const DpmppArgs& a, float xv, float ec, float eu, float xp, float& xn, float& p0) {
+  float e = ec;
+  if (CFG) e = eu + a.guidance * (ec - eu);
+  p0 = (xv - a.sigma_t * e) / a.alpha_t;
+  float d = p0;
+  if (MS) d = a.w_cur * p0 + a.w_prev * xp;
+  xn = a.c_x * xv + a.c_d * d;
+}
+template <bool CFG, bool MS>
+__global__ void __launch_bounds__(128) dpmpp_step_kernel(const DpmppArgs a) {
+  const long it = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (it < a.n4) {
+    const float4 xv = reinterpret_cast<const float4*>(a.x)[it];
+    const float4 ec = reinterpret_cast<const float4*>(a.eps_c)[it];
+    float4 eu = make_float4(0.f, 0.f, 0.f, 0.f), xp = eu;
+    if (CFG) eu = reinterpret_cast<const float4*>(a.eps_u)[it];
+    if (MS) xp = reinterpret_cast<const float4*>(a.x0_prev)[it];
+    float4 xn, p0;
+    dpmpp_update<CFG, MS>(a, xv.x, ec.x, eu.x, xp.x, xn.x, p0.x);
+    dpmpp_update<CFG, MS>(a, xv.y, ec.y, eu.y, xp.y, xn.y, p0.y);
+    dpmpp_update<CFG, MS>(a, xv.z, ec.z, eu.z, xp.z, xn.z, p0.z);
+    dpmpp_update<CFG, MS>(a, xv.w, ec.w, eu.w, xp.w, xn.w, p0.w);
+    reinterpret_cast<float4*>(a.x_next)[it] = xn;
+    if (a.x0_out) reinterpret_cast<float4*>(a.x0_out)[it] = p0;
+    return;
+  }
+  const long i = 4 * a.n4 + (it - a.n4);
+  if (i >= a.n) return;
+  const float xv = a.x[i], ec = a.eps_c[i];
+  float eu = 0.f, xp = 0.f;
+  if (CFG) eu = a.eps_u[i];
+  if (MS) xp = a.x0_prev[i];
+  float xn, p0;
+  dpmpp_update<CFG, MS>(a, xv, ec, eu, xp, xn, p0);
+  a.x_next[i] = xn;
+  if (a.x0_out) a.x0_out[i] = p0;
+}
+
 // DiagonalGaussianDistribution.sample (distributions.py:27-37) + the scale_factor of get_first_stage_encoding
 __global__ void posterior_sample_kernel(const float* __restrict__ mom, const float* __restrict__ noise, float scale,
                                         float* __restrict__ z, int Cn, long HW, long total) {
@@ -603,6 +665,26 @@ int af_launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, 
 int af_launch_lincomb(float* out, long n, const float* x0, float w0, const float* x1, float w1, const float* x2, float w2,
                       const float* x3, float w3, int mode, hipStream_t s) {
   hipLaunchKernelGGL(lincomb_kernel, EW_GRID(n), dim3(256), 0, s, out, n, x0, w0, x1, w1, x2, w2, x3, w3, mode);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int af_launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, long n, float guidance,
+                         float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev, float* x_next,
+                         float* x0_out, hipStream_t s) {
+  // 16-byte path only when every pointer in use allows it (the samplers pass e[:b] / e[b:] views of one tensor)
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)x0_prev | (uintptr_t)x_next |
+                         (uintptr_t)x0_out;
+  DpmppArgs a{x, eps_c, eps_u, x0_prev, x_next, x0_out, n, (bits & 15) ? 0 : n / 4,
+              guidance, alpha_t, sigma_t, c_x, c_d, w_cur, w_prev};
+  // the grid follows n: 128 items per workgroup, so the 8 x 4 x 64 x 64 latent is 256 workgroups of four-element items
+  const long items = a.n4 + (n - 4 * a.n4);
+  const long blocks = (items + 127) / 128;
+  if (blocks > 0x7fffffffL) { af_set_error_msg("dpmpp_step: n = %ld is too large for one launch", n); return -1; }
+  const dim3 grid((unsigned)blocks), block(128);
+  if (eps_u && x0_prev) hipLaunchKernelGGL((dpmpp_step_kernel<true, true>), grid, block, 0, s, a);
+  else if (eps_u) hipLaunchKernelGGL((dpmpp_step_kernel<true, false>), grid, block, 0, s, a);
+  else if (x0_prev) hipLaunchKernelGGL((dpmpp_step_kernel<false, true>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((dpmpp_step_kernel<false, false>), grid, block, 0, s, a);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

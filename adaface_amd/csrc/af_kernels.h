@@ -109,6 +109,9 @@ int af_launch_copy_channels(const void* src, int lds_, void* dst, int ldd, int o
 int af_launch_ddim_step(const float* x, const float* eps_c, const float* eps_u, const float* noise, long n,
                         float guidance, float a_t, float a_prev, float sqrt_one_minus_at, float sigma_t,
                         float temperature, float* x_prev, float* pred_x0, hipStream_t s);
+int af_launch_dpmpp_step(const float* x, const float* eps_c, const float* eps_u, const float* x0_prev, long n, float guidance,
+                         float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev, float* x_next,
+                         float* x0_out, hipStream_t s);
 int af_launch_posterior_sample(const float* mom, const float* noise, float scale, float* z, int B, int Cn, long HW,
                                hipStream_t s);
 int af_launch_lincomb(float* out, long n, const float* x0, float w0, const float* x1, float w1, const float* x2, float w2,

@@ -317,6 +317,40 @@ def ddim_step(x, e_cond, e_uncond, guidance, a_t, a_prev, sqrt_one_minus_at, sig
     return x_prev, pred_x0
 
 
+def dpmpp_coeffs(acp_t, acp_prev, h_last=0.0):
+    """af_dpmpp_coeffs (host only, no GPU): the eight doubles (alpha_t, sigma_t, c_x, c_d, w_cur, w_prev, h, r) of one
+    DPM-Solver++(2M) step from alphas_cumprod acp_t to acp_prev; h_last <= 0: a first-order step."""
+    import ctypes
+    out = (ctypes.c_double * 8)()
+    check(_lib.load().af_dpmpp_coeffs(float(acp_t), float(acp_prev), float(h_last), out), "af_dpmpp_coeffs")
+    return tuple(float(v) for v in out)
+
+
+def dpmpp_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x, c_d, w_cur=1.0, w_prev=0.0, x_next=None,
+               x0_out=None, want_x0=True):
+    """CFG combine + one DPM-Solver++(2M) step (af_dpmpp_step); returns (x_next, x0).  e_uncond None: no guidance; x0_prev
+    None: a first-order step.  x_next / x0_out: fp32 contiguous tensors to write into (x_next may be x itself), allocated when
+    None; want_x0=False with x0_out None skips the x0 write and returns (x_next, None)."""
+    lib = _lib.load()
+    x, e_cond = _dev_f32(x), _dev_f32(e_cond)
+    eu = None if e_uncond is None else _dev_f32(e_uncond)
+    xp = None if x0_prev is None else _dev_f32(x0_prev)
+    for name, t in (("e_cond", e_cond), ("e_uncond", eu), ("x0_prev", xp)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f"dpmpp_step: {name} has {t.numel()} elements, x has {x.numel()}")
+    for name, t in (("x_next", x_next), ("x0_out", x0_out)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x.numel()):
+            raise ValueError(f"dpmpp_step: {name} must be a contiguous fp32 GPU tensor of x's size")
+    if x_next is None:
+        x_next = torch.empty_like(x)
+    if x0_out is None and want_x0:
+        x0_out = torch.empty_like(x)
+    check(lib.af_dpmpp_step(ptr(x), ptr(e_cond), ptr(eu), ptr(xp), x.numel(), float(guidance), float(alpha_t), float(sigma_t),
+                            float(c_x), float(c_d), float(w_cur), float(w_prev), ptr(x_next), ptr(x0_out), stream_ptr()),
+          "af_dpmpp_step")
+    return x_next, x0_out
+
+
 def lincomb(terms, cfg=False):
     """sum_i w_i * x_i over up to four (tensor, weight) pairs; cfg=True: terms = [(e_cond, g), (e_uncond, _)] ->
     e_uncond + g * (e_cond - e_uncond)."""

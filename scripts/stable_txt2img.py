@@ -3,7 +3,7 @@
 
 Keeps the reference's flag names for everything that reaches the denoising path
 (stable_txt2img.py:38-310): --config --ckpt --n_samples --n_repeat --ddim_steps --ddim_eta --scale --H --W --C --f
---seed --outdir --skip_save --fixed_code --gpu --bs --plms --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
+--seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
 
@@ -48,7 +48,12 @@ def parse_args():
     ap.add_argument("--init_img_paths", type=str, nargs="+", default=None,
                     help="initial image(s): encoded by the VAE encoder, averaged, blended with noise into the start code")
     ap.add_argument("--init_img_weight", type=float, default=0.1, help="w: start = w*enc(img) + (1-w)*noise")
-    ap.add_argument("--plms", action="store_true", help="PLMS sampler instead of DDIM (scalar --scale)")
+    smp = ap.add_mutually_exclusive_group()
+    smp.add_argument("--plms", action="store_true", help="PLMS sampler instead of DDIM (scalar --scale)")
+    smp.add_argument("--dpm_solver", action="store_true",
+                     help="DPM-Solver++(2M) sampler instead of DDIM: made for 15-25 --ddim_steps (eta must be 0)")
+    ap.add_argument("--dpm_skip", choices=["time_uniform", "logSNR"], default="time_uniform",
+                    help="--dpm_solver: the timestep grid; time_uniform = DDIM's, logSNR = uniform in log(alpha / sigma)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -177,6 +182,9 @@ def main():
     if opt.plms:
         from ldm.models.diffusion.plms import PLMSSampler
         sampler = PLMSSampler(model)
+    elif opt.dpm_solver:
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        sampler = DPMSolverSampler(model)
     else:
         sampler = DDIMSampler(model)
     shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
@@ -206,6 +214,10 @@ def main():
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
                                             eta=opt.ddim_eta, x_T=x_T)
+            elif opt.dpm_solver:
+                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
+                                            skip_type=opt.dpm_skip)
             else:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T)
@@ -219,7 +231,7 @@ def main():
     toc = time.time()
     if rank == 0:
         n_img = B * opt.n_repeat
-        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} DDIM steps in {toc - tic:.2f} s "
+        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M)' if opt.dpm_solver else 'DDIM'} steps in {toc - tic:.2f} s "
               f"({n_img / (toc - tic):.2f} images/s incl. first-call warm-up) on {world} GPU(s); outputs: {opt.outdir}")
     if dist.is_initialized():
         dist.destroy_process_group()

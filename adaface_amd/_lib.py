@@ -66,6 +66,11 @@ _SIGS = [
                                C.c_float, _P, _P, _P]),
     ("af_dpmpp_coeffs", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     ("af_dpmpp_step", C.c_int, [_P, _P, _P, _P, C.c_int64] + [C.c_float] * 7 + [_P, _P, _P]),
+    ("af_philox4x32_10", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("af_philox_randn", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    ("af_dpmpp_sde_coeffs", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    ("af_dpmpp_sde_step", C.c_int, [_P, _P, _P, _P, C.c_int64] + [C.c_float] * 7 + [_P, _P, C.c_float, _P, C.c_int64, _P, C.c_int64,
+                                    C.c_uint64, C.c_uint32, _P]),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

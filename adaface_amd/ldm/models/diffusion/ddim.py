@@ -17,6 +17,13 @@ import torch
 from adaface_amd import ops
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
                                                            make_ddim_timesteps, noise_like)
+from adaface_amd.noise import STREAM_QSAMPLE, STREAM_STEP, STREAM_XT
+
+
+def _check_noise_source(noise_source, noise_dropout):
+    if noise_source is not None and noise_dropout > 0.:
+        raise NotImplementedError("noise_dropout with a noise_source: the dropout mask would come from torch's generator, and "
+                                  "the result would again depend on the batch split")
 
 
 class DDIMSampler(object):
@@ -65,8 +72,10 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
-               unconditional_conditioning=None, **kwargs):
-        """ddim.py:71-132."""
+               unconditional_conditioning=None, noise_source=None, **kwargs):
+        """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
+        adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step)."""
+        _check_noise_source(noise_source, noise_dropout)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -77,17 +86,26 @@ class DDIMSampler(object):
                                   noise_dropout=noise_dropout, temperature=temperature,
                                   score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, x_T=x_T,
                                   log_every_t=log_every_t, guidance_scale=guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, verbose=verbose, **kwargs)
+                                  unconditional_conditioning=unconditional_conditioning, verbose=verbose,
+                                  noise_source=noise_source, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      guidance_scale=1., unconditional_conditioning=None, verbose=False, **kwargs):
-        """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218)."""
+                      guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None, **kwargs):
+        """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
+        code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
+        step = the loop index."""
+        _check_noise_source(noise_source, noise_dropout)
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
+        if x_T is not None:
+            img = x_T
+        elif noise_source is None:
+            img = torch.randn(shape, device=device)
+        else:
+            img = noise_source.randn(shape, STREAM_XT, 0, device)
         if timesteps is None:
             timesteps = self.ddpm_num_timesteps if ddim_use_original_steps else self.ddim_timesteps
         elif not ddim_use_original_steps:
@@ -113,13 +131,17 @@ class DDIMSampler(object):
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
                 assert x0 is not None
-                img_orig = self.model.q_sample(x0, ts)
+                if noise_source is None:
+                    img_orig = self.model.q_sample(x0, ts)
+                else:
+                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
                 img = img_orig * mask + (1. - mask) * img
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, use_original_steps=ddim_use_original_steps,
                                               quantize_denoised=quantize_denoised, temperature=temperature,
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
                                               corrector_kwargs=corrector_kwargs, guidance_scale=guide_scale,
-                                              unconditional_conditioning=unconditional_conditioning)
+                                              unconditional_conditioning=unconditional_conditioning,
+                                              noise_source=noise_source, noise_step=i)
             if callback:
                 callback(i)
             if img_callback:
@@ -148,8 +170,10 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      guidance_scale=1., unconditional_conditioning=None):
-        """ddim.py:222-296."""
+                      guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0):
+        """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
+        torch.randn; repeat_noise then gives every sample the first sample's id."""
+        _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
         if unconditional_conditioning is None or guidance_scale == 1.:
             e_c, e_u = self.model.apply_model(x, t, c), None
@@ -171,11 +195,17 @@ class DDIMSampler(object):
         sigma_t = f32(sigmas[index])
         # drawn every step like the reference (ddim.py:286) so the generator state advances identically,
         # even though sigma_t = 0 (eta = 0) makes the term vanish
-        noise = noise_like(x.shape, device, repeat_noise)
-        if noise_dropout > 0.:
-            noise = torch.nn.functional.dropout(noise, p=noise_dropout)
-        if sigma_t == 0.:
-            noise = None
+        if noise_source is None:
+            noise = noise_like(x.shape, device, repeat_noise)
+            if noise_dropout > 0.:
+                noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+            if sigma_t == 0.:
+                noise = None
+        elif sigma_t == 0.:
+            noise = None        # a keyed draw advances no generator state: nothing to draw where the term vanishes
+        else:
+            src = noise_source.repeated(b) if repeat_noise else noise_source
+            noise = src.randn(x.shape, STREAM_STEP, noise_step, device)
         if score_corrector is not None:
             # ddim.py:262-264: the corrector sees the COMBINED score; combine first (af_lincomb, the kernel's own CFG form),
             # then hand its result to the update as a plain eps

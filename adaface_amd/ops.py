@@ -351,6 +351,73 @@ def dpmpp_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x, c_
     return x_next, x0_out
 
 
+def philox4x32_10(ctr, key):
+    """af_philox4x32_10 (host only, no GPU): the four output words of Philox4x32-10 for a 4-word counter and a 2-word key."""
+    import ctypes
+    c = (ctypes.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
+    k = (ctypes.c_uint32 * 2)(*[int(v) & 0xFFFFFFFF for v in key])
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().af_philox4x32_10(c, k, out), "af_philox4x32_10")
+    return tuple(int(v) for v in out)
+
+
+def philox_randn(n_samples, per_sample, seed, stream, step, sample_ids=None, first_id=0, device=None, out=None):
+    """af_philox_randn: fp32 normals [n_samples, per_sample] of the samples sample_ids (an int64 GPU tensor; None:
+    first_id + i) under the keying contract of csrc/af_philox.h.  out: a contiguous fp32 GPU tensor (or view) of
+    n_samples * per_sample elements to write into."""
+    n_samples, per_sample = int(n_samples), int(per_sample)
+    if out is None:
+        out = torch.empty(n_samples, per_sample, device=device, dtype=torch.float32)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n_samples * per_sample):
+        raise ValueError("philox_randn: out must be a contiguous fp32 GPU tensor of n_samples * per_sample elements")
+    if sample_ids is not None and not (sample_ids.is_cuda and sample_ids.dtype == torch.int64 and sample_ids.is_contiguous()
+                                       and sample_ids.numel() >= n_samples):
+        raise ValueError("philox_randn: sample_ids must be a contiguous int64 GPU tensor of at least n_samples elements")
+    check(_lib.load().af_philox_randn(ptr(out), n_samples, per_sample, ptr(sample_ids), int(first_id),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(step), stream_ptr()), "af_philox_randn")
+    return out
+
+
+def dpmpp_sde_coeffs(acp_t, acp_prev, h_last=0.0):
+    """af_dpmpp_sde_coeffs (host only, no GPU): the nine doubles (alpha_t, sigma_t, c_x, c_d, c_n, w_cur, w_prev, h, r) of one
+    DPM-Solver++(2M) SDE step from alphas_cumprod acp_t to acp_prev; h_last <= 0: a first-order step."""
+    import ctypes
+    out = (ctypes.c_double * 9)()
+    check(_lib.load().af_dpmpp_sde_coeffs(float(acp_t), float(acp_prev), float(h_last), out), "af_dpmpp_sde_coeffs")
+    return tuple(float(v) for v in out)
+
+
+def dpmpp_sde_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x, c_d, c_n, w_cur=1.0, w_prev=0.0, noise=None,
+                   seed=0, step=0, sample_ids=None, first_id=0, x_next=None, x0_out=None, want_x0=True):
+    """CFG combine + one DPM-Solver++(2M) SDE step (af_dpmpp_sde_step); returns (x_next, x0).  noise: the z to use (x's
+    size); None: z is generated inside the kernel from (seed, sample id, stream 1, step, element), x's dim 0 being the
+    samples (ids: sample_ids, an int64 GPU tensor, or first_id + i).  The other arguments as dpmpp_step."""
+    lib = _lib.load()
+    x, e_cond = _dev_f32(x), _dev_f32(e_cond)
+    eu = None if e_uncond is None else _dev_f32(e_uncond)
+    xp = None if x0_prev is None else _dev_f32(x0_prev)
+    nz = None if noise is None else _dev_f32(noise)
+    for name, t in (("e_cond", e_cond), ("e_uncond", eu), ("x0_prev", xp), ("noise", nz)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f"dpmpp_sde_step: {name} has {t.numel()} elements, x has {x.numel()}")
+    for name, t in (("x_next", x_next), ("x0_out", x0_out)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x.numel()):
+            raise ValueError(f"dpmpp_sde_step: {name} must be a contiguous fp32 GPU tensor of x's size")
+    n_samples = x.shape[0] if x.dim() > 0 else 1
+    if sample_ids is not None and not (sample_ids.is_cuda and sample_ids.dtype == torch.int64 and sample_ids.is_contiguous()
+                                       and sample_ids.numel() >= n_samples):
+        raise ValueError("dpmpp_sde_step: sample_ids must be a contiguous int64 GPU tensor of at least x.shape[0] elements")
+    if x_next is None:
+        x_next = torch.empty_like(x)
+    if x0_out is None and want_x0:
+        x0_out = torch.empty_like(x)
+    check(lib.af_dpmpp_sde_step(ptr(x), ptr(e_cond), ptr(eu), ptr(xp), x.numel(), float(guidance), float(alpha_t), float(sigma_t),
+                                float(c_x), float(c_d), float(w_cur), float(w_prev), ptr(x_next), ptr(x0_out), float(c_n), ptr(nz),
+                                x.numel() // n_samples, ptr(sample_ids), int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step),
+                                stream_ptr()), "af_dpmpp_sde_step")
+    return x_next, x0_out
+
+
 def lincomb(terms, cfg=False):
     """sum_i w_i * x_i over up to four (tensor, weight) pairs; cfg=True: terms = [(e_cond, g), (e_uncond, _)] ->
     e_uncond + g * (e_cond - e_uncond)."""

@@ -100,6 +100,13 @@ def shard_range(global_batch: int, rank: Optional[int] = None, world_size: Optio
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def sample_ids(global_batch: int, rank: Optional[int] = None, world_size: Optional[int] = None) -> List[int]:
+    """The global sample indices of `rank`'s shard, in shard order: what shard_range slices, and what keys a sample's noise
+    (adaface_amd.noise.PhiloxNoise) so that it does not depend on the world size."""
+    lo, hi = shard_range(global_batch, rank, world_size)
+    return list(range(lo, hi))
+
+
 def shard_batch(t: torch.Tensor, rank: Optional[int] = None, world_size: Optional[int] = None,
                 per_sample: int = 1) -> torch.Tensor:
     """Slice dim 0 of a globally generated tensor; `per_sample` = rows per sample (16 for the layerwise context

@@ -171,6 +171,37 @@ int af_dpmpp_step(const float* x_dev, const float* eps_cond_dev, const float* ep
                   float guidance, float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev,
                   float* x_next_dev, float* x0_out_dev, void* stream);
 
+/* Seed-stable noise: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), keyed so that a sample's noise is a pure function of
+ * its identity, never of the rank, the batch position or the launch (the contract, stated in csrc/af_philox.h):
+ *     key = (seed lo32, seed hi32),  counter = (g, (step << 8) | stream, id lo32, id hi32),
+ *     id = the sample's GLOBAL index (>= 0), g = e / 4 for element e of the sample (lane e % 4), step < 2^24, stream < 256;
+ *     streams: 0 = start code x_T, 1 = sampler step noise, 2 = q_sample noise of the inpainting blend.
+ * Bits -> normals by Box-Muller in fp32 on the pairs (r0, r1), (r2, r3): u = ((r_even >> 9) + 0.5) 2^-23,
+ * v = (r_odd >> 8) 2^-24, rho = sqrtf(-2 logf(u)), (rho cospi(2v), rho sinpi(2v)); |z| <= 5.77.
+ *
+ * The generator's block function on the host (no GPU): out = Philox4x32-10(ctr, key). */
+int af_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* out_dev [n_samples][per_sample] fp32 = the normals of samples sample_ids_dev[i] (NULL: first_id + i), one launch.  Any
+ * alignment and any per_sample >= 1 (<= 2^34) are accepted.  An element's bits do not depend on what else is in the launch. */
+int af_philox_randn(float* out_dev, int64_t n_samples, int64_t per_sample, const int64_t* sample_ids_dev, int64_t first_id,
+                    uint64_t seed, uint32_t stream_id, uint32_t step, void* stream);
+/* DPM-Solver++(2M) SDE (the "sde-dpmsolver++" multistep update of Lu et al.'s code) on the schedule of the deterministic
+ * coefficients above:  x_next = c_x x + c_d D + c_n z,  z ~ N(0, 1),
+ *     c_x = (sigma_prev / sigma_t) e^-h,  c_d = -alpha_prev expm1(-2h),  c_n = sigma_prev sqrt(-expm1(-2h)),
+ * x0, D, w_cur, w_prev as the deterministic step.  c_x alpha_t + c_d = alpha_prev, (c_x sigma_t)^2 + c_n^2 = sigma_prev^2,
+ * and a first-order step is the DDIM step with eta = 1.  Host only, double; arguments and errors as the deterministic
+ * function; out = { alpha_t, sigma_t, c_x, c_d, c_n, w_cur, w_prev, h, r }. */
+int af_dpmpp_sde_coeffs(double acp_t, double acp_prev, double h_last, double out[9]);
+/* One launch per sampler step: the deterministic step's CFG combine, x0, blend and x0 history write, and the update above.
+ * noise_dev non-NULL: z is read from it (n elements) and the key arguments are ignored.  noise_dev NULL: z is generated in
+ * registers from (seed, id, stream 1, step, element), the bits af_philox_randn gives; n = n_samples * per_sample, ids from
+ * sample_ids_dev (NULL: first_id + i); no noise tensor is written or read.  A temperature is folded into c_n by the caller.
+ * Aliasing and alignment as the deterministic step; the wide and the scalar path give the same bits for an element. */
+int af_dpmpp_sde_step(const float* x_dev, const float* eps_cond_dev, const float* eps_uncond_dev, const float* x0_prev_dev, int64_t n,
+                      float guidance, float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev,
+                      float* x_next_dev, float* x0_out_dev, float c_n, const float* noise_dev, int64_t per_sample,
+                      const int64_t* sample_ids_dev, int64_t first_id, uint64_t seed, uint32_t step, void* stream);
+
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */
 int af_lincomb(float* out_dev, int64_t n, const float* x0_dev, float w0, const float* x1_dev, float w1,

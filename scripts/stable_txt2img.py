@@ -3,7 +3,7 @@
 
 Keeps the reference's flag names for everything that reaches the denoising path
 (stable_txt2img.py:38-310): --config --ckpt --n_samples --n_repeat --ddim_steps --ddim_eta --scale --H --W --C --f
---seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
+--seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --noise --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
 
@@ -26,7 +26,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default=None, help="reference yaml (v1-inference-ada.yaml); default: built-in SD-1.5")
     ap.add_argument("--ckpt", type=str, default=None, help="SD checkpoint (.ckpt / .safetensors); default: seeded synthetic weights")
@@ -54,6 +54,13 @@ def parse_args():
                      help="DPM-Solver++(2M) sampler instead of DDIM: made for 15-25 --ddim_steps (eta must be 0)")
     ap.add_argument("--dpm_skip", choices=["time_uniform", "logSNR"], default="time_uniform",
                     help="--dpm_solver: the timestep grid; time_uniform = DDIM's, logSNR = uniform in log(alpha / sigma)")
+    ap.add_argument("--dpm_sde", action="store_true",
+                    help="--dpm_solver: the stochastic variant, DPM-Solver++(2M) SDE (one noise draw per step, in the step kernel)")
+    ap.add_argument("--noise", choices=["torch", "philox"], default="torch",
+                    help="where the start code and the samplers' noise come from.  torch: the start code from the seeded host "
+                         "generator, step noise (--ddim_eta > 0, --dpm_sde) from the device's default generator, which --seed "
+                         "does not reach.  philox: all of it keyed by (--seed, global sample index, step): --seed names an image "
+                         "whatever the batch split or --gpus")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -69,7 +76,12 @@ def parse_args():
                          "(two passes, with this run's conditioning); 0 = keep the fixed 2^3, which clips beyond +-56")
     ap.add_argument("--fp8_scales", type=str, default=None,
                     help="--dtype fp8: JSON file of calibrated scales: loaded if present, else written after the calibration")
-    return ap.parse_args()
+    opt = ap.parse_args(argv)
+    if opt.dpm_sde and not opt.dpm_solver:
+        ap.error("--dpm_sde is a variant of --dpm_solver: give both")
+    if opt.noise == "philox" and opt.plms:
+        ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
+    return opt
 
 
 def load_img(path, h, w):
@@ -191,6 +203,11 @@ def main():
     gs = opt.scale if len(opt.scale) > 1 else opt.scale[0]
     gen = torch.Generator().manual_seed(opt.seed)  # host RNG: the start code does not depend on the world size
     start_code = torch.randn([B] + shape, generator=gen) if opt.fixed_code else None
+    noise_source = None
+    if opt.noise == "philox":
+        # this rank's samples carry their GLOBAL indices lo .. hi - 1: their noise does not depend on the world size
+        from adaface_amd.noise import STREAM_XT, PhiloxNoise
+        noise_source = PhiloxNoise(opt.seed, first_id=lo)
     if opt.init_img_paths:
         # stable_txt2img.py:594-625: encode each init image, average (divide by sqrt(N)), blend with noise
         avg = torch.zeros([B] + shape)
@@ -202,14 +219,23 @@ def main():
             dist.all_reduce(avg_dev := avg.to(device))
             avg = avg_dev.cpu()
         avg /= np.sqrt(len(opt.init_img_paths))
-        start_code = avg * opt.init_img_weight + torch.randn([B] + shape, generator=gen) * (1.0 - opt.init_img_weight)
+        start_code = avg * opt.init_img_weight
+        if noise_source is None:
+            start_code = start_code + torch.randn([B] + shape, generator=gen) * (1.0 - opt.init_img_weight)
     os.makedirs(opt.outdir, exist_ok=True)
     tic = time.time()
     count = 0
     with torch.no_grad(), model.ema_scope():
         for n in range(opt.n_repeat):
-            x_T_all = start_code if start_code is not None else torch.randn([B] + shape, generator=gen)
-            x_T = shard_batch(x_T_all, rank, world).to(device)
+            if noise_source is None:
+                x_T_all = start_code if start_code is not None else torch.randn([B] + shape, generator=gen)
+                x_T = shard_batch(x_T_all, rank, world).to(device)
+            else:
+                # stream 0; step = the repeat index, or 0 for every repeat under --fixed_code
+                x_T = noise_source.randn([b] + shape, STREAM_XT, 0 if opt.fixed_code else n, device)
+                if opt.init_img_paths:
+                    x_T = shard_batch(start_code, rank, world).to(device) + x_T * (1.0 - opt.init_img_weight)
+            kw = {} if noise_source is None else dict(noise_source=noise_source)
             if opt.plms:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
@@ -217,10 +243,11 @@ def main():
             elif opt.dpm_solver:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
-                                            skip_type=opt.dpm_skip)
+                                            skip_type=opt.dpm_skip, algorithm="sde-dpmsolver++" if opt.dpm_sde else "dpmsolver++",
+                                            **kw)
             else:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
-                                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T)
+                                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T, **kw)
             frames = gather_frames(model.decode_first_stage_uint8(samples), global_batch=B)
             if rank == 0 and not opt.skip_save:
                 from PIL import Image
@@ -231,7 +258,7 @@ def main():
     toc = time.time()
     if rank == 0:
         n_img = B * opt.n_repeat
-        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M)' if opt.dpm_solver else 'DDIM'} steps in {toc - tic:.2f} s "
+        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M) SDE' if opt.dpm_sde else 'DPM-Solver++(2M)' if opt.dpm_solver else 'DDIM'} steps in {toc - tic:.2f} s "
               f"({n_img / (toc - tic):.2f} images/s incl. first-call warm-up) on {world} GPU(s); outputs: {opt.outdir}")
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -96,6 +96,8 @@ _SIGS = [
     ("af_knob_reset", C.c_int, []),
     ("af_op_conv2d", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     ("af_op_linear", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_op_conv2d_ex", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_float, _P] + [C.c_int] * 10 + [_P]),
+    ("af_op_linear_ex", C.c_int, [C.c_int, _P, _P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("af_op_groupnorm", C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("af_op_conv_gn", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_int, _P, _P] + [C.c_int] * 5 + [_P]),
     ("af_set_fp8", C.c_int, [_P, C.c_int]),

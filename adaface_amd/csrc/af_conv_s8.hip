@@ -250,10 +250,10 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
     for (int j = 0; j < MI; ++j) {
       const int m = m0 + wid * 32 + j * 16 + l15;
 #pragma unroll
-      for (int i = 0; i < NI; ++i) *reinterpret_cast<f32x4*>(slab + (long)m * p.N + n0 + i * 16 + 4 * g) = acc[i][j];
+      for (int i = 0; i < NI; ++i) *reinterpret_cast<f32x4*>(slab + (long)m * p.N + n0 + i * 16 + 4 * g) = acc[i][j] * p.alpha;   // (the reduce adds, it does not scale)
     }
   } else {
-    // ---- one K slice: bias + time-embedding row + residual on the accumulators, bf16 through a wave-private transposition tile
+    // ---- one K slice: alpha, bias + time-embedding row + residual on the accumulators, bf16 through a wave-private transposition tile
     // (where the halo buffers were: every wave is past its last fragment read) into 16-byte row stores ----
     __builtin_amdgcn_s_barrier();
     constexpr int OPITCH = BN * 2 + 16, OCH = BN / 8, NST = 32 * OCH / 64;     // 176-byte rows, 10 chunks per row, 5 stores per lane
@@ -266,7 +266,8 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       bvec[i] = p.bias ? *reinterpret_cast<const float4*>(p.bias + n0 + i * 16 + cl) : float4{0.f, 0.f, 0.f, 0.f};
-      if (rowb) bq[i].load(rowb + (long)(m0 >> p.howo_shift) * p.ldrb + n0 + i * 16 + cl);   // (a tile lies inside one sample)
+      // (a tile holds up to four samples -- 4 x 16, 16 x 8, 8 x 16 maps -- but a wave's 32 rows lie inside one: a sample has >= 64 rows)
+      if (rowb) bq[i].load(rowb + (long)((m0 + wid * 32) >> p.howo_shift) * p.ldrb + n0 + i * 16 + cl);
     }
 #pragma unroll
     for (int j = 0; j < MI; ++j) {
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
         Quad<T> o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float v = acc[i][j][e] + bp[e];
+          float v = acc[i][j][e] * p.alpha + bp[e];
           if (rowb) v += to_f32<T>(bq[i].e[e]);
           if (res) v += to_f32<T>(rq[i].e[e]);
           o.e[e] = from_f32<T>(v);
@@ -317,7 +318,8 @@ int af_conv_s8_slices(const ConvGemmParams& p, int batch) {
     return 0;
   // the tile's halo must fit the buffer: whole images (Ho * Wo <= 256) or 256 / Wo whole rows of one image
   const int R = p.Ho < 256 / p.Wo ? p.Ho : 256 / p.Wo;
-  if (256 % (R * p.Wo) != 0 || (256 / (R * p.Wo)) * (R + 2) * (p.Wo + 2) > cs8::HSLOTS || (p.Ho * p.Wo > 256 && p.Ho % R != 0)) return 0;
+  // (... and a sample is whole 32-row wave slabs: the one-slice epilogue takes the time-embedding row per wave)
+  if (256 % (R * p.Wo) != 0 || (256 / (R * p.Wo)) * (R + 2) * (p.Wo + 2) > cs8::HSLOTS || (p.Ho * p.Wo > 256 && p.Ho % R != 0) || (p.Ho * p.Wo) % 32 != 0) return 0;
   if (p.Wo == 8 && p.Ho == 8) return p.Cin % (64 * cs8::SPLITK) == 0 ? cs8::SPLITK : 0;
   return (p.Cin % 64 == 0 && p.ldo % 8 == 0 && (!p.residual || p.ldr % 4 == 0) && (!p.rowbias || p.ldrb % 4 == 0) && ((__UINTPTR_TYPE__)p.out & 15) == 0 &&
           (long)(p.M / cs8::BM) * (p.N / cs8::BN) >= 128) ? 1 : 0;

@@ -31,6 +31,32 @@ inline AfStorage storage_of(int dtype) { return dtype == AF_DTYPE_BF16 ? AF_ST_B
 inline int rup(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace
 
+// columns [c0, ld) of every row of a [rows][ld] buffer of T become v (slack columns of a wide-row test buffer; c0 = 0: the whole buffer)
+template <typename T> __global__ __launch_bounds__(256) void fill_cols_kernel(T* __restrict__ y, long rows, int ld, int c0, float v) {
+  const int w = ld - c0;
+  const long n = rows * w;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / w;
+    y[r * ld + c0 + (int)(i - r * w)] = from_f32<T>(v);
+  }
+}
+template <typename T> static int fill_cols(void* y, long rows, int ld, int c0, float v, hipStream_t s) {
+  const long n = rows * (ld - c0);
+  if (n <= 0) return 0;
+  const long nb = (n + 255) / 256;
+  hipLaunchKernelGGL((fill_cols_kernel<T>), dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, s, reinterpret_cast<T*>(y), rows, ld, c0, v);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+static int fill_cols_dt(int dtype, void* y, long rows, int ld, int c0, float v, hipStream_t s) {
+  return dtype == AF_DTYPE_BF16 ? fill_cols<bf16>(y, rows, ld, c0, v, s) : dtype == AF_DTYPE_F16 ? fill_cols<f16>(y, rows, ld, c0, v, s)
+                                                                                                 : fill_cols<float>(y, rows, ld, c0, v, s);
+}
+// what af_op_conv2d_ex / af_op_linear_ex put into the output buffer before the launch (exact in bf16 / fp16, above any result of
+// the tests) and into the slack columns of the operands
+static const float OP_SENTINEL = 49152.f;   // 3 * 2^14
+static const float OP_NAN = __builtin_nanf("");
+
 #define OP_TRY(expr)          \
   do {                        \
     int _rc = (expr);         \
@@ -120,24 +146,43 @@ int af_clock_probe(void* stream, int iters, double* mfma_mhz, double* mfma_tflop
   return AF_OK;
 }
 
-int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
-                 float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int upsample,
-                 void* stream) {
-  if ((ks != 1 && ks != 3) || pad != ks / 2) { af_set_error_msg("af_op_conv2d: ks must be 1 or 3 with pad ks/2"); return AF_ERR_INVALID; }
+// af_op_conv2d with the launch forms only the model states (Runner::conv_params, af_model.hip): a per-sample bias row
+// (rowbias_dev: float [B][Cout], cast to the storage type), alpha on the accumulator, the VAE encoder's bottom / right-only
+// padding (pad 0: 3x3, stride 2, even maps; pad -1: ks / 2) and row pitches wider than the channel count (ld_slack elements,
+// a multiple of 8, added to ldc / ldo / ldr / ldrb).  The slack of the source, the residual and the bias row holds NaN, the
+// whole output buffer the sentinel before the launch.  ld_slack > 0: y_dev receives the whole rows, float [B * Ho * Wo][ldo]
+// with ldo = rup(Cout, 4) + ld_slack; otherwise NCHW as af_op_conv2d.
+int af_op_conv2d_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
+                    const float* rowbias_dev, float alpha, float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride,
+                    int pad, int upsample, int ld_slack, void* stream) {
+  if (pad < 0) pad = ks / 2;
+  const bool br_pad = pad == 0 && ks == 3 && stride == 2 && !upsample && H % 2 == 0 && W % 2 == 0;   // bottom / right only
+  if ((ks != 1 && ks != 3) || (pad != ks / 2 && !br_pad)) {
+    af_set_error_msg("af_op_conv2d_ex: ks must be 1 or 3 with pad ks/2 (pad 0: 3x3, stride 2, even maps, no upsampling)");
+    return AF_ERR_INVALID;
+  }
+  if (ld_slack < 0 || ld_slack % 8 != 0) { af_set_error_msg("af_op_conv2d_ex: ld_slack must be a non-negative multiple of 8"); return AF_ERR_INVALID; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int cin_pad = rup(Cin, bk(dtype));
   const int Hi = H << upsample, Wi = W << upsample;
-  const int Ho = (Hi + 2 * pad - ks) / stride + 1, Wo = (Wi + 2 * pad - ks) / stride + 1;
+  // (pad 0: one row / column of zeros below and to the right, as the model's (H + 1 - 3) / 2 + 1)
+  const int Ho = br_pad ? (Hi + 1 - ks) / stride + 1 : (Hi + 2 * pad - ks) / stride + 1;
+  const int Wo = br_pad ? (Wi + 1 - ks) / stride + 1 : (Wi + 2 * pad - ks) / stride + 1;
   const int co4 = rup(Cout, 4), rows_pad = rup(Cout, 128), ldw = ks * ks * cin_pad;
-  OP_ALLOC(xn, (size_t)B * H * W * cin_pad * esz(dtype), false);
+  const int ldc = cin_pad + ld_slack, ldo = co4 + ld_slack;
+  const long M = (long)B * Ho * Wo;
+  OP_ALLOC(xn, (size_t)B * H * W * ldc * esz(dtype), false);
   OP_ALLOC(wn, (size_t)rows_pad * ldw * esz(dtype), true);
-  OP_ALLOC(yn, (size_t)B * Ho * Wo * co4 * esz(dtype), true);
+  OP_ALLOC(yn, (size_t)M * ldo * esz(dtype), false);
   void* rn = nullptr;
+  void* rbn = nullptr;
   float* bn = nullptr;
-  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s),
-              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, Cin, H * W, cin_pad, 1.f, s)));
+  OP_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
+  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s),
+              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s),
+              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s)));
+  OP_TRY(fill_cols_dt(dtype, xn, (long)B * H * W, ldc, cin_pad, OP_NAN, s));
   OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
               af_launch_repack_weight<float>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
               af_launch_repack_weight<f16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s)));
@@ -147,20 +192,30 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
     if (hipMemcpyAsync(bn, bias_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   }
   if (residual_dev) {
-    rn = tmp.get((size_t)B * Ho * Wo * co4 * esz(dtype), false);
+    rn = tmp.get((size_t)M * ldo * esz(dtype), false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s),
-                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s)));
+    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<float>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s)));
+    OP_TRY(fill_cols_dt(dtype, rn, M, ldo, co4, OP_NAN, s));
+  }
+  if (rowbias_dev) {   // [B][Cout] rows = NCHW with one pixel per sample
+    rbn = tmp.get((size_t)B * ldo * esz(dtype), false);
+    if (!rbn) return AF_ERR_HIP;
+    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<float>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<f16>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s)));
+    OP_TRY(fill_cols_dt(dtype, rbn, B, ldo, co4, OP_NAN, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
-  p.src = xn; p.src_batch_stride = (long)H * W * cin_pad; p.ldc = cin_pad; p.Cin = cin_pad;
+  p.src = xn; p.src_batch_stride = (long)H * W * ldc; p.ldc = ldc; p.Cin = cin_pad;
   p.Hs = H; p.Ws = W; p.up = upsample; p.Hi = Hi; p.Wi = Wi; p.Ho = Ho; p.Wo = Wo;
   p.ks = ks; p.stride = stride; p.pad = pad;
   p.W = wn; p.ldw = ldw; p.Wrows = rows_pad;
-  p.M = B * Ho * Wo; p.N = co4; p.K = ldw;
-  p.bias = bn; p.residual = rn; p.ldr = co4; p.out = yn; p.ldo = co4; p.alpha = 1.f;
+  p.M = (int)M; p.N = co4; p.K = ldw;
+  p.bias = bn; p.residual = rn; p.ldr = ldo; p.out = yn; p.ldo = ldo; p.alpha = alpha;
+  p.rowbias = rbn; p.ldrb = ldo;
   p.k_logical = ks * ks * Cin;
   if (upsample && ks == 3 && dtype == AF_DTYPE_BF16 && cin_pad % 64 == 0) {
     // as the model does for its Upsample layers: phase weights next to the 3x3 ones, the launcher decides (AF_CONV_UP_PHASE4)
@@ -172,10 +227,21 @@ int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float*
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
   OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
+  if (ld_slack > 0) {
+    OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, M * ldo, s), af_launch_cast_to_f32<float>(yn, y_dev, M * ldo, s),
+                af_launch_cast_to_f32<f16>(yn, y_dev, M * ldo, s)));
+    return 0;
+  }
   OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
               af_launch_nhwc_to_nchw<float>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
               af_launch_nhwc_to_nchw<f16>(yn, y_dev, B, Cout, Ho * Wo, co4, s)));
   return 0;
+}
+int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
+                 float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int upsample,
+                 void* stream) {
+  if ((ks != 1 && ks != 3) || pad != ks / 2) { af_set_error_msg("af_op_conv2d: ks must be 1 or 3 with pad ks/2"); return AF_ERR_INVALID; }
+  return af_op_conv2d_ex(dtype, x_dev, w_dev, bias_dev, residual_dev, nullptr, 1.f, y_dev, B, Cin, H, W, Cout, ks, stride, pad, upsample, 0, stream);
 }
 
 // Host-only diagnostic: the plan af_launch_conv_gemm would follow for a launch described by integers.  Parameters as af_op_conv2d
@@ -405,23 +471,30 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   return 0;
 }
 
-int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
-                 float* y_dev, int64_t M, int K, int N, int geglu, void* stream) {
+// af_op_linear with alpha on the accumulator and row pitches wider than K / N (ld_slack elements, a multiple of 8, added to
+// ldc / ldo / ldr; NaN in the slack of the source and the residual, the sentinel in the whole output buffer before the launch).
+// ld_slack > 0: y_dev receives the whole rows, float [M][rup(N, 4) + ld_slack].
+int af_op_linear_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev, float alpha,
+                    float* y_dev, int64_t M, int K, int N, int geglu, int ld_slack, void* stream) {
+  if (ld_slack < 0 || ld_slack % 8 != 0) { af_set_error_msg("af_op_linear_ex: ld_slack must be a non-negative multiple of 8"); return AF_ERR_INVALID; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int kp = rup(K, bk(dtype));
   const int rows = geglu ? 2 * N : N;  // weight rows
   const int rows_pad = rup(rows, 128);
   const int no4 = rup(N, 4);
-  OP_ALLOC(xn, (size_t)M * kp * esz(dtype), false);
+  const int ldc = kp + ld_slack, ldo = no4 + ld_slack;
+  OP_ALLOC(xn, (size_t)M * ldc * esz(dtype), false);
   OP_ALLOC(wn, (size_t)rows_pad * kp * esz(dtype), true);
-  OP_ALLOC(yn, (size_t)M * no4 * esz(dtype), true);
+  OP_ALLOC(yn, (size_t)M * ldo * esz(dtype), false);
   float* bn = nullptr;
   void* rn = nullptr;
+  OP_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
   // [M,K] rows == NCHW with C=K, HW=1 per "sample": reuse the NCHW converter with B=M, HW=1
-  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, (int)M, K, 1, kp, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, (int)M, K, 1, kp, 1.f, s),
-              af_launch_nchw_to_nhwc<f16>(x_dev, xn, (int)M, K, 1, kp, 1.f, s)));
+  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s),
+              af_launch_nchw_to_nhwc<float>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s),
+              af_launch_nchw_to_nhwc<f16>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s)));
+  OP_TRY(fill_cols_dt(dtype, xn, M, ldc, kp, OP_NAN, s));
   OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
               af_launch_repack_weight<float>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
               af_launch_repack_weight<f16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s)));
@@ -431,31 +504,41 @@ int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float*
     OP_TRY(af_launch_permute_bias(bias_dev, bn, rows, geglu ? 1 : 0, s));
   }
   if (residual_dev) {
-    rn = tmp.get((size_t)M * no4 * esz(dtype), false);
+    rn = tmp.get((size_t)M * ldo * esz(dtype), false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s),
-                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, (int)M, N, 1, no4, 1.f, s)));
+    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<float>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s),
+                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s)));
+    OP_TRY(fill_cols_dt(dtype, rn, M, ldo, no4, OP_NAN, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
-  p.src = xn; p.src_batch_stride = (long)M * kp; p.ldc = kp; p.Cin = kp;
+  p.src = xn; p.src_batch_stride = (long)M * ldc; p.ldc = ldc; p.Cin = kp;
   p.Hs = 1; p.Ws = (int)M; p.Hi = 1; p.Wi = (int)M; p.Ho = 1; p.Wo = (int)M;
   p.ks = 1; p.stride = 1; p.pad = 0;
   p.W = wn; p.ldw = kp; p.Wrows = rows_pad;
   p.M = (int)M; p.N = geglu ? 2 * N : no4; p.K = kp;
-  p.bias = bn; p.residual = rn; p.ldr = no4; p.out = yn; p.ldo = no4;
+  p.bias = bn; p.residual = rn; p.ldr = ldo; p.out = yn; p.ldo = ldo;
   p.epilogue = geglu ? AF_EPI_GEGLU : AF_EPI_NONE;
-  p.alpha = 1.f;
+  p.alpha = alpha;
   p.k_logical = K;
   const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype));
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
   OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
+  if (ld_slack > 0) {
+    OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, M * ldo, s), af_launch_cast_to_f32<float>(yn, y_dev, M * ldo, s),
+                af_launch_cast_to_f32<f16>(yn, y_dev, M * ldo, s)));
+    return 0;
+  }
   OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, (int)M, N, 1, no4, s),
               af_launch_nhwc_to_nchw<float>(yn, y_dev, (int)M, N, 1, no4, s),
               af_launch_nhwc_to_nchw<f16>(yn, y_dev, (int)M, N, 1, no4, s)));
   return 0;
+}
+int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
+                 float* y_dev, int64_t M, int K, int N, int geglu, void* stream) {
+  return af_op_linear_ex(dtype, x_dev, w_dev, bias_dev, residual_dev, 1.f, y_dev, M, K, N, geglu, 0, stream);
 }
 
 // GroupNorm (no SiLU) followed by a 1x1 convolution -- SpatialTransformer.norm + proj_in (attention.py:325-326) -- both ways

@@ -22,8 +22,14 @@ def _dev_f32(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().float()
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=None, upsample=False, residual=None, dtype="bf16"):
-    """F.conv2d(F.interpolate(x, 2, 'nearest') if upsample else x, weight, bias, stride, padding) [+ residual]."""
+def conv2d(x, weight, bias=None, stride=1, padding=None, upsample=False, residual=None, dtype="bf16", rowbias=None, alpha=1.0,
+           ld_slack=0):
+    """alpha * F.conv2d(F.interpolate(x, 2, 'nearest') if upsample else x, weight, None, stride, padding) + bias
+    [+ rowbias[b]] [+ residual].  padding=0 on a 3x3 / stride-2 convolution of an even map pads below and to the right only
+    (F.pad(x, (0, 1, 0, 1)), the VAE encoder's Downsample).  rowbias: [B, Cout], the per-sample row the ResBlocks add.
+    ld_slack > 0 (a multiple of 8) widens every row pitch by that many elements (NaN in the operands' slack, a sentinel in the
+    output buffer before the launch) and returns (y, slack): slack [B * Ho * Wo, ld_slack] is what the output buffer's slack
+    columns hold after the launch (OUTPUT_SENTINEL if nothing wrote there)."""
     lib = _lib.load()
     x, weight = _dev_f32(x), _dev_f32(weight)
     B, Cin, H, W = x.shape
@@ -33,13 +39,30 @@ def conv2d(x, weight, bias=None, stride=1, padding=None, upsample=False, residua
     pad = ks // 2 if padding is None else padding
     up = 1 if upsample else 0
     Hi, Wi = H << up, W << up
-    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
-    y = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=torch.float32)
+    if pad == 0 and ks == 3:   # bottom / right only
+        Ho, Wo = (Hi + 1 - ks) // stride + 1, (Wi + 1 - ks) // stride + 1
+    else:
+        Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
     b = None if bias is None else _dev_f32(bias)
     r = None if residual is None else _dev_f32(residual)
-    check(lib.af_op_conv2d(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), ptr(y), B, Cin, H, W, Cout, ks, stride,
-                           pad, up, stream_ptr()), "af_op_conv2d")
-    return y
+    if rowbias is None and alpha == 1.0 and ld_slack == 0 and pad == ks // 2:
+        y = torch.empty(B, Cout, Ho, Wo, device=x.device, dtype=torch.float32)
+        check(lib.af_op_conv2d(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), ptr(y), B, Cin, H, W, Cout, ks, stride,
+                               pad, up, stream_ptr()), "af_op_conv2d")
+        return y
+    rb = None if rowbias is None else _dev_f32(rowbias)
+    if rb is not None and tuple(rb.shape) != (B, Cout):
+        raise ValueError(f"conv2d: rowbias {tuple(rb.shape)} is not [{B}, {Cout}]")
+    co4 = (Cout + 3) // 4 * 4
+    y = torch.empty((B * Ho * Wo, co4 + ld_slack) if ld_slack else (B, Cout, Ho, Wo), device=x.device, dtype=torch.float32)
+    check(lib.af_op_conv2d_ex(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), ptr(rb), float(alpha), ptr(y), B, Cin, H, W, Cout,
+                              ks, stride, pad, up, ld_slack, stream_ptr()), "af_op_conv2d_ex")
+    if not ld_slack:
+        return y
+    return y[:, :Cout].reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2).contiguous(), y[:, co4:].contiguous()
+
+
+OUTPUT_SENTINEL = 49152.0   # 3 * 2^14: what conv2d / linear leave in the output buffer before the launch (af_ops.hip)
 
 
 FP8_ACT_SHIFT = 3   # fp8 activations hold value * 2^s; s = 3 until a site is calibrated (AF_FP8_SHIFT_DEFAULT, adaface_hip.h)
@@ -144,20 +167,29 @@ def ff_fp8(x, ln_weight, ln_bias, w1, b1, w2, b2, residual=None, shift1=FP8_ACT_
     return out
 
 
-def linear(x, weight, bias=None, residual=None, geglu=False, dtype="bf16"):
-    """F.linear over the last dim; geglu=True applies GEGLU (attention.py:32-45) to the projection."""
+def linear(x, weight, bias=None, residual=None, geglu=False, dtype="bf16", alpha=1.0, ld_slack=0):
+    """alpha * F.linear(x, weight) + bias [+ residual] over the last dim; geglu=True applies GEGLU (attention.py:32-45) to the
+    projection.  ld_slack > 0: wide rows as conv2d, returns (y, slack) with slack [M, ld_slack]."""
     lib = _lib.load()
     x, weight = _dev_f32(x), _dev_f32(weight)
     K = x.shape[-1]
     M = x.numel() // K
     rows = weight.shape[0]
     N = rows // 2 if geglu else rows
-    y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
     b = None if bias is None else _dev_f32(bias)
     r = None if residual is None else _dev_f32(residual)
-    check(lib.af_op_linear(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), ptr(y), M, K, N, 1 if geglu else 0,
-                           stream_ptr()), "af_op_linear")
-    return y
+    if alpha == 1.0 and ld_slack == 0:
+        y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
+        check(lib.af_op_linear(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), ptr(y), M, K, N, 1 if geglu else 0,
+                               stream_ptr()), "af_op_linear")
+        return y
+    no4 = (N + 3) // 4 * 4
+    y = torch.empty((M, no4 + ld_slack) if ld_slack else (*x.shape[:-1], N), device=x.device, dtype=torch.float32)
+    check(lib.af_op_linear_ex(DTYPES[dtype], ptr(x), ptr(weight), ptr(b), ptr(r), float(alpha), ptr(y), M, K, N, 1 if geglu else 0,
+                              ld_slack, stream_ptr()), "af_op_linear_ex")
+    if not ld_slack:
+        return y
+    return y[:, :N].reshape(*x.shape[:-1], N).contiguous(), y[:, no4:].contiguous()
 
 
 def group_norm(x, weight, bias, eps=1e-5, silu=False, dtype="bf16"):

@@ -302,10 +302,24 @@ int af_knob_reset(void);
 int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
                  float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride, int pad, int upsample,
                  void* stream);
+/* af_op_conv2d in the launch forms only the model states: y = alpha * conv(x, w) + b + rowbias[sample] (+ residual).
+ * rowbias_dev: float [B][Cout] or null (the ResBlocks' time-embedding row), cast to the storage type.  pad: -1 = ks / 2;
+ * 0 with ks 3, stride 2 and even maps = one row / column of zeros below and to the right only (the VAE encoder's Downsample;
+ * output (H + 1 - 3) / 2 + 1).  ld_slack (a multiple of 8): elements added to the row pitches ldc / ldo / ldr / ldrb; the slack
+ * of the source, the residual and the bias row holds NaN and the whole output buffer 3 * 2^14 before the launch.  With
+ * ld_slack > 0 y_dev receives whole rows, float [B * Ho * Wo][rup(Cout, 4) + ld_slack], so that the slack columns can be
+ * inspected; with 0 NCHW as af_op_conv2d, which is this call with rowbias null, alpha 1 and no slack. */
+int af_op_conv2d_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
+                    const float* rowbias_dev, float alpha, float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride,
+                    int pad, int upsample, int ld_slack, void* stream);
 /* F.linear on [M,K] rows: y = x w^T + b (+ residual); geglu != 0: w is [2*Nout,K] and
  * y [M,Nout] = value * gelu(gate)  (attention.py:32-45). */
 int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
                  float* y_dev, int64_t M, int K, int N, int geglu, void* stream);
+/* af_op_linear with alpha on the accumulator (y = alpha * x w^T + b (+ residual)) and ld_slack as af_op_conv2d_ex (ldc / ldo /
+ * ldr; ld_slack > 0: y_dev receives float [M][rup(N, 4) + ld_slack]). */
+int af_op_linear_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev, float alpha,
+                    float* y_dev, int64_t M, int K, int N, int geglu, int ld_slack, void* stream);
 /* F.group_norm(x, 32, gamma, beta, eps) on NCHW, optional SiLU. */
 /* conv3x3 (stride 1, bf16) + GroupNorm(32)(+SiLU) with the GroupNorm statistics summed in the convolution's epilogue, as the
  * ResBlocks run the pair (openaimodel.py:259-279): h_dev = convolution output, y_dev = GroupNorm output, both fp32 NCHW */

@@ -35,10 +35,34 @@ def int_tensor(shape, density, gen, lo=-1, hi=1):
     return v * keep
 
 
-def density_for(K):
+def density_for(K, alpha=1.0):
     """Keep probability that holds the output's standard deviation near 33 for any K with operands in {-1, 0, 1}
-    (variance K * (d * 2/3)^2 = 1100), so that bf16 (integers up to 256) stores every output exactly."""
-    return min(1.0, math.sqrt(1100.0 / (K * 4.0 / 9.0)))
+    (variance K * (d * 2/3)^2 = 1100), so that bf16 (integers up to 256) stores every output exactly.  A launch with
+    |alpha| > 1 multiplies that deviation, so its operands are thinned by 1 / |alpha| (density, never a mask)."""
+    return min(1.0, math.sqrt(1100.0 / (K * 4.0 / 9.0))) / max(1.0, abs(alpha))
+
+
+ALPHAS = (0.5, -2.0)            # powers of two: alpha * (an integer below 2^24) is exact in fp32
+
+
+def rowbias_rows(B, N):
+    """The per-sample bias row of the exact cases, [B, N]: small integers, and any two samples fewer than 17 apart (the
+    samples of one tile are at most four apart) differ in EVERY column, so a row taken from the wrong sample shows at every
+    output of that sample."""
+    b = torch.arange(B).view(B, 1)
+    n = torch.arange(N).view(1, N)
+    return (((7 * b + 3 * n) % 17) - 8).float()
+
+
+def out_hw(H, W, ks, stride, up, pad=None):
+    """Output map of a convolution; pad None = ks // 2 on every side, pad 0 (3x3, stride 2, even maps) = one row / column of
+    zeros below and to the right only: (H + 1 - 3) // 2 + 1."""
+    hi, wi = H << int(up), W << int(up)
+    if pad == 0 and ks == 3:
+        assert stride == 2 and not up and H % 2 == 0 and W % 2 == 0, (H, W, stride, up)
+        return (hi + 1 - ks) // stride + 1, (wi + 1 - ks) // stride + 1
+    assert pad is None or pad == ks // 2, pad
+    return (hi + 2 * (ks // 2) - ks) // stride + 1, (wi + 2 * (ks // 2) - ks) // stride + 1
 
 
 def roundtrip(t, storage):
@@ -47,31 +71,53 @@ def roundtrip(t, storage):
         return t.to(torch.float32).to(torch.bfloat16).double()
     if storage == "f32":
         return t.to(torch.float32).double()
+    if storage == "f16":
+        return t.to(torch.float32).to(torch.float16).double()
     raise ValueError(storage)
 
 
-def fp64_ref_conv(x, w, b=None, r=None, stride=1, up=False):
-    """F.conv2d(nearest-2x(x) if up else x, w, b, stride, padding=ks // 2) [+ r] in float64."""
+def fp64_ref_conv(x, w, b=None, r=None, stride=1, up=False, rowbias=None, alpha=1.0, pad=None):
+    """alpha * F.conv2d(nearest-2x(x) if up else x, w, None, stride, padding) + b [+ rowbias[sample]] [+ r] in float64.
+    pad None: ks // 2 on every side; pad 0: F.pad(x, (0, 1, 0, 1)), zeros below and to the right only."""
     xi = x.double()
     if up:
         xi = F.interpolate(xi, scale_factor=2.0, mode="nearest")
-    y = F.conv2d(xi, w.double(), None if b is None else b.double(), stride=stride, padding=w.shape[-1] // 2)
+    if pad == 0 and w.shape[-1] == 3:
+        xi, padding = F.pad(xi, (0, 1, 0, 1)), 0
+    else:
+        assert pad is None or pad == w.shape[-1] // 2, pad
+        padding = w.shape[-1] // 2
+    y = F.conv2d(xi, w.double(), None, stride=stride, padding=padding)
+    if alpha != 1.0:
+        y = y * float(alpha)
+    if b is not None:
+        y = y + b.double().view(1, -1, 1, 1)
+    if rowbias is not None:
+        y = y + rowbias.double().view(rowbias.shape[0], -1, 1, 1)
     return y if r is None else y + r.double()
 
 
-def fp64_ref_linear(x, w, b=None, r=None):
-    """F.linear(x, w, b) [+ r] in float64."""
-    y = F.linear(x.double(), w.double(), None if b is None else b.double())
+def fp64_ref_linear(x, w, b=None, r=None, alpha=1.0):
+    """alpha * F.linear(x, w) + b [+ r] in float64."""
+    y = F.linear(x.double(), w.double(), None)
+    if alpha != 1.0:
+        y = y * float(alpha)
+    if b is not None:
+        y = y + b.double()
     return y if r is None else y + r.double()
 
 
-def absbound_conv(x, w, b=None, r=None, stride=1, up=False):
-    """conv(|x|, |w|) + |b| + |r|: what any partial sum of any summation order is bounded by."""
-    return fp64_ref_conv(x.abs(), w.abs(), None if b is None else b.abs(), None if r is None else r.abs(), stride, up)
+def _abs(t):
+    return None if t is None else t.abs()
 
 
-def absbound_linear(x, w, b=None, r=None):
-    return fp64_ref_linear(x.abs(), w.abs(), None if b is None else b.abs(), None if r is None else r.abs())
+def absbound_conv(x, w, b=None, r=None, stride=1, up=False, rowbias=None, alpha=1.0, pad=None):
+    """|alpha| conv(|x|, |w|) + |b| + |rowbias| + |r|: what any partial sum of any summation order is bounded by."""
+    return fp64_ref_conv(x.abs(), w.abs(), _abs(b), _abs(r), stride, up, _abs(rowbias), abs(alpha), pad)
+
+
+def absbound_linear(x, w, b=None, r=None, alpha=1.0):
+    return fp64_ref_linear(x.abs(), w.abs(), _abs(b), _abs(r), abs(alpha))
 
 
 def check_exact_case(ref, absbound, storage, operands=(), power_operands=None):
@@ -157,13 +203,16 @@ def add_carrier(x, w):
     return x, w
 
 
-def conv_case(B, Cin, H, W, Cout, ks, stride, up, bias, res, seed, storage="bf16", wide=False, carrier=False):
+def conv_case(B, Cin, H, W, Cout, ks, stride, up, bias, res, seed, storage="bf16", wide=False, carrier=False, rowbias=False,
+              alpha=1.0, pad=None):
     """Integer operands, fp64 reference and |.| bound of one convolution case; the preconditions are asserted before it
     returns.  K = 64 without a bias widens the operand range to [-2, 2] (the shortest K is where the power conditions are
-    tightest)."""
+    tightest).  rowbias: the per-sample row rowbias_rows(B, Cout) ("rb"); alpha in ALPHAS (or 1) scales the convolution before
+    the bias; pad 0: bottom / right padding (out_hw)."""
+    assert alpha == 1.0 or alpha in ALPHAS, alpha
     g = torch.Generator().manual_seed(seed)
     K = Cin * ks * ks
-    d = density_for(K)
+    d = density_for(K, alpha)
     lo, hi = (-2, 2) if (K <= 64 and not bias) else (-1, 1)
     x = int_tensor((B, Cin, H, W), d, g, lo, hi)
     w = int_tensor((Cout, Cin, ks, ks), d, g, lo, hi)
@@ -172,19 +221,32 @@ def conv_case(B, Cin, H, W, Cout, ks, stride, up, bias, res, seed, storage="bf16
         x = add_wide(x, g)
     if carrier:
         x, w = add_carrier(x, w)
-    ho = ((H << int(up)) + 2 * (ks // 2) - ks) // stride + 1
-    wo = ((W << int(up)) + 2 * (ks // 2) - ks) // stride + 1
+    ho, wo = out_hw(H, W, ks, stride, up, pad)
     r = int_tensor((B, Cout, ho, wo), 1.0, g, -16, 16) if res else None
-    ref = fp64_ref_conv(x, w, b, r, stride, up)
-    bound = absbound_conv(x, w, b, r, stride, up)
-    stats = check_exact_case(ref, bound, storage, operands=(x, w, b, r))
-    return {"x": x, "w": w, "b": b, "r": r, "ref": ref, "absbound": bound, "stats": stats}
+    rb = rowbias_rows(B, Cout) if rowbias else None
+    ref = fp64_ref_conv(x, w, b, r, stride, up, rb, alpha, pad)
+    bound = absbound_conv(x, w, b, r, stride, up, rb, alpha, pad)
+    stats = check_exact_case(ref, bound, storage, operands=(x, w, b, r, rb))
+    return {"x": x, "w": w, "b": b, "r": r, "rb": rb, "alpha": alpha, "pad": pad, "ref": ref, "absbound": bound, "stats": stats}
 
 
-def linear_case(M, K, N, bias, res, seed, storage="bf16", wide=False, carrier=False):
+def add_rowbias(c, storage="bf16"):
+    """A convolution case with the per-sample row added to it: same operands, reference + rowbias[sample]; the preconditions
+    are asserted again on the new reference (one fp64 convolution serves the case with and without the row)."""
+    assert c["rb"] is None
+    B, N = c["ref"].shape[:2]
+    rb = rowbias_rows(B, N)
+    ref = c["ref"] + rb.double().view(B, N, 1, 1)
+    bound = c["absbound"] + rb.double().abs().view(B, N, 1, 1)
+    stats = check_exact_case(ref, bound, storage, operands=(c["x"], c["w"], c["b"], c["r"], rb))
+    return dict(c, rb=rb, ref=ref, absbound=bound, stats=stats)
+
+
+def linear_case(M, K, N, bias, res, seed, storage="bf16", wide=False, carrier=False, alpha=1.0):
     """The same for F.linear: x [M, K], w [N, K]; the carrier's "channels" are K columns."""
+    assert alpha == 1.0 or alpha in ALPHAS, alpha
     g = torch.Generator().manual_seed(seed)
-    d = density_for(K)
+    d = density_for(K, alpha)
     lo, hi = (-2, 2) if (K <= 64 and not bias) else (-1, 1)
     x = int_tensor((M, K), d, g, lo, hi)
     w = int_tensor((N, K), d, g, lo, hi)
@@ -194,10 +256,10 @@ def linear_case(M, K, N, bias, res, seed, storage="bf16", wide=False, carrier=Fa
         x = add_wide(x, g)
     if carrier:
         x, w = add_carrier(x, w)
-    ref = fp64_ref_linear(x, w, b, r)
-    bound = absbound_linear(x, w, b, r)
+    ref = fp64_ref_linear(x, w, b, r, alpha)
+    bound = absbound_linear(x, w, b, r, alpha)
     stats = check_exact_case(ref, bound, storage, operands=(x, w, b, r))
-    return {"x": x, "w": w, "b": b, "r": r, "ref": ref, "absbound": bound, "stats": stats}
+    return {"x": x, "w": w, "b": b, "r": r, "alpha": alpha, "ref": ref, "absbound": bound, "stats": stats}
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -211,12 +273,12 @@ GEGLU_GATE_VALUES = (8.0, 16.0, 32.0)
 GEGLU_VALUE_BIASES = (1.0, -1.0, 2.0, -2.0)
 
 
-def geglu_value_probe(M, K, N, seed, storage="bf16", wide=False):
+def geglu_value_probe(M, K, N, seed, storage="bf16", wide=False, alpha=1.0):
     """Gate weight rows zero, gate bias 8 / 16 / 32 cycling with the column; value rows and value bias the signed integer
-    operands above.  Expected: (x @ Wv.T + bv) * g_n.  Isolates the value half of the GEMM, the value | gate interleave and
+    operands above.  Expected: (alpha x @ Wv.T + bv) * g_n.  Isolates the value half of the GEMM, the value | gate interleave and
     the bias permutation.  Returns x [M, K], w [2N, K] (value rows first, as torch's chunk(2) reads them), b [2N], ref [M, N]."""
     g = torch.Generator().manual_seed(seed)
-    d = density_for(K)
+    d = density_for(K, alpha)
     x = int_tensor((M, K), d, g)
     wv = int_tensor((N, K), d, g)
     bv = int_tensor((N,), 1.0, g, -8, 8)
@@ -225,9 +287,9 @@ def geglu_value_probe(M, K, N, seed, storage="bf16", wide=False):
     gate = torch.tensor(GEGLU_GATE_VALUES)[torch.arange(N) % len(GEGLU_GATE_VALUES)]
     w = torch.cat([wv, torch.zeros(N, K)], 0)
     b = torch.cat([bv, gate], 0)
-    val = fp64_ref_linear(x, wv, bv)
+    val = fp64_ref_linear(x, wv, bv, None, alpha)      # (alpha scales both halves; the gate rows are zero)
     ref = val * gate.double()
-    bound = absbound_linear(x, wv, bv) * gate.double()
+    bound = absbound_linear(x, wv, bv, None, alpha) * gate.double()
     stats = check_exact_case(ref, bound, storage, operands=(x, w, b), power_operands=(x, wv, bv))
     return {"x": x, "w": w, "b": b, "ref": ref, "absbound": bound, "stats": stats}
 

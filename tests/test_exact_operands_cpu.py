@@ -325,3 +325,115 @@ def test_geglu_probes_meet_their_preconditions():
         assert p["w"][N:].abs().max() == 0 and set(p["b"][N:].tolist()) == set(X.GEGLU_GATE_VALUES)
         q = X.geglu_gate_probe(M, K, N, seed=M + K)
         assert q["w"][:N].abs().max() == 0 and float(q["gate"].min()) >= 8 and float(q["ref"].abs().max()) <= 512
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The launch forms of tests/test_launch_forms_gpu.py: per-sample bias row, alpha, bottom / right padding.  For every such case
+# the fp64 reference must DIFFER from what each plausible wrong kernel returns -- computed here from the same operands -- in
+# every sample the mistake touches; otherwise the GPU comparison could not fail.
+# ----------------------------------------------------------------------------------------------------------------------
+FORM_CASES = [   # B, Cin, H, W, Cout, stride, rowbias, alpha, pad  (3x3, bias + residual)
+    (4, 64, 16, 8, 16, 1, True, 1.0, None),       # two images per 256-row tile
+    (4, 64, 8, 16, 16, 1, True, 1.0, None),
+    (8, 64, 4, 16, 16, 1, True, 1.0, None),       # four images per tile
+    (5, 64, 12, 12, 16, 1, True, 1.0, None),      # 144-row samples under 256-row tiles: a tile straddles samples in mid-row
+    (4, 64, 8, 8, 16, 1, True, 1.0, None),        # 64-row samples: four per tile
+    (2, 64, 32, 8, 16, 1, True, 1.0, None),       # one image per tile: the tile's first sample IS the sample
+    (4, 128, 16, 8, 16, 1, True, 0.5, None),
+    (4, 128, 16, 8, 16, 1, True, -2.0, None),
+    (2, 64, 12, 12, 24, 1, False, 0.5, None),
+    (2, 64, 12, 12, 24, 1, False, -2.0, None),
+    (2, 128, 16, 16, 16, 2, False, 1.0, 0),       # bottom / right padding
+    (1, 128, 12, 20, 24, 2, True, 1.0, 0),
+    (2, 64, 12, 20, 16, 2, True, -2.0, 0),
+]
+
+
+def _rows(t):
+    """[B, C, H, W] -> [B * H * W, C], the GEMM's row order"""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+def _form_case(case, storage="bf16"):
+    B, Cin, H, W, Cout, stride, rowbias, alpha, pad = case
+    c = X.conv_case(B, Cin, H, W, Cout, 3, stride, False, True, True, seed=sum(int(abs(v or 0) * 2) for v in case), storage=storage,
+                    rowbias=rowbias, alpha=alpha, pad=pad)
+    conv = X.fp64_ref_conv(c["x"], c["w"], None, None, stride, False, None, 1.0, pad)
+    return c, conv
+
+
+def _samples_differing(a, b, B):
+    """the samples in which [B, ...] tensors a and b differ somewhere"""
+    return {i for i in range(B) if not torch.equal(a[i], b[i])}
+
+
+def _with_rowbias_of(c, sample_of_row):
+    """the reference with row m taking its bias row from sample sample_of_row[m] instead of its own"""
+    B, N, Ho, Wo = c["ref"].shape
+    own = torch.arange(B * Ho * Wo) // (Ho * Wo)
+    rows = _rows(c["ref"]) - c["rb"].double()[own] + c["rb"].double()[sample_of_row]
+    return rows.view(B, Ho, Wo, N).permute(0, 3, 1, 2), {int(s) for s in own[sample_of_row != own].unique()}
+
+
+@pytest.mark.parametrize("case", FORM_CASES, ids=["-".join(str(v) for v in c) for c in FORM_CASES])
+def test_launch_form_references_differ_from_every_wrong_kernel(case):
+    B, Cin, H, W, Cout, stride, rowbias, alpha, pad = case
+    c, conv = _form_case(case)
+    ref = c["ref"]
+    Ho, Wo = ref.shape[2:]
+    X.assert_bit_exact("the parts add up", float(alpha) * conv + c["b"].double().view(1, -1, 1, 1)
+                       + (c["rb"].double().view(B, -1, 1, 1) if rowbias else 0) + c["r"].double(), ref, None)
+    m = torch.arange(B * Ho * Wo)
+    if rowbias:
+        # the row of the tile's first sample applied to the whole 256-row tile
+        wrong, touched = _with_rowbias_of(c, (m // 256 * 256) // (Ho * Wo))
+        if Ho * Wo < 256:
+            assert len(touched) >= B // 2                       # (several samples per tile: at least every second one is wrong)
+        elif Ho * Wo % 256 == 0:
+            assert not touched                                  # (a tile inside one sample: this mistake cannot show, others can)
+        assert _samples_differing(wrong, ref, B) == touched, (case, touched)
+        for s in touched:                                       # ... in EVERY column of every row that took the wrong row
+            rows_w, rows_r = _rows(wrong[s:s + 1]), _rows(ref[s:s + 1])
+            bad_rows = (rows_w != rows_r).any(1)
+            assert bool((rows_w != rows_r)[bad_rows].all())
+        # the row indexed by m / Wo instead of m / (Ho * Wo)
+        wrong, touched = _with_rowbias_of(c, (m // Wo) % B)
+        assert len(touched) >= B - 1, touched
+        assert _samples_differing(wrong, ref, B) == touched, (case, touched)
+    if alpha != 1.0:
+        dropped = ref + (1.0 - float(alpha)) * conv
+        assert _samples_differing(dropped, ref, B) == set(range(B)), case
+        after_bias = float(alpha) * (conv + c["b"].double().view(1, -1, 1, 1)) + (c["rb"].double().view(B, -1, 1, 1) if rowbias else 0) + c["r"].double()
+        assert _samples_differing(after_bias, ref, B) == set(range(B)), case
+    if pad == 0:
+        sym = X.fp64_ref_conv(c["x"], c["w"], c["b"], c["r"], stride, False, c["rb"], alpha, None)
+        assert sym.shape == ref.shape
+        assert _samples_differing(sym, ref, B) == set(range(B)), case
+        assert float((sym != ref).double().mean()) > 0.5        # (every window moves by one pixel: most outputs change)
+
+
+def test_rowbias_rows_differ_between_samples_of_a_tile_in_every_column():
+    rb = X.rowbias_rows(32, 1280)
+    assert float(rb.abs().max()) <= 8 and torch.equal(rb, rb.round())
+    for d in range(1, 17):
+        assert bool((rb[d:] != rb[:-d]).all()), d
+
+
+def test_launch_form_cases_are_exact_in_every_storage_type():
+    """alpha in {0.5, -2} and the bias row keep every case exact: the operand density is lowered by 1 / |alpha| (density_for), the
+    preconditions are asserted inside conv_case / linear_case; an fp32 evaluation equals the fp64 reference bit for bit."""
+    for storage, wide in (("bf16", False), ("f16", False), ("f32", True)):
+        for alpha in X.ALPHAS:
+            c = X.conv_case(2, 128, 12, 12, 24, 3, 1, False, True, True, seed=5, storage=storage, wide=wide, rowbias=True, alpha=alpha)
+            y = F.conv2d(c["x"], c["w"], None, padding=1) * alpha + c["b"].view(1, -1, 1, 1) + c["rb"].view(2, -1, 1, 1) + c["r"]
+            assert y.dtype == torch.float32
+            X.assert_bit_exact(f"fp32 evaluation alpha {alpha} [{storage}]", y, c["ref"], None)
+            lc = X.linear_case(130, 320, 64, True, True, seed=6, storage=storage, wide=wide, alpha=alpha)
+            X.assert_bit_exact(f"fp32 linear alpha {alpha} [{storage}]", (lc["x"] @ lc["w"].t()) * alpha + lc["b"] + lc["r"], lc["ref"], None)
+        c = X.conv_case(2, 128, 12, 20, 24, 3, 2, False, True, True, seed=7, storage=storage, wide=wide, rowbias=True, pad=0)
+        assert tuple(c["ref"].shape) == (2, 24, 6, 10)
+        y = F.conv2d(F.pad(c["x"], (0, 1, 0, 1)), c["w"], c["b"], stride=2) + c["rb"].view(2, -1, 1, 1) + c["r"]
+        X.assert_bit_exact(f"fp32 evaluation bottom/right padding [{storage}]", y, c["ref"], None)
+    p = X.geglu_value_probe(300, 320, 128, seed=9, alpha=0.5)
+    q = X.geglu_value_probe(300, 320, 128, seed=9, alpha=-2.0)
+    assert p["stats"]["distinct"] >= 40 and q["stats"]["distinct"] >= 40

@@ -62,6 +62,8 @@ _SIGS = [
     ("af_set_context", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_unet_forward", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_unet_forward_twin", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_unet_forward_cached", C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [_P]),
+    ("af_unet_cache_invalidate", C.c_int, [_P]),
     ("af_ddim_step", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_float, _P, _P, _P]),
     ("af_dpmpp_coeffs", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
@@ -139,6 +141,9 @@ _SIGS = [
     ("af_clock_probe", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGS]
+
+# the `mode` argument of af_unet_forward_cached (include/adaface_hip.h)
+DEEPCACHE_MODES = {"refresh": 1, "reuse": 2}
 
 
 def lib_path() -> Path:

@@ -323,6 +323,17 @@ struct af_handle {
   int tap_index = -1;
   float* tap_out = nullptr;
 
+  // DeepCache (af_unet_forward_cached): while that entry point runs, the concatenation buffer cat[n_out - depth] lives here
+  // and not in the arena (which is re-planned by every forward and shared with the VAE / CLIP calls).  A refresh writes both
+  // halves; a reuse step rewrites the skip half and reads the kept h half D = output of output_blocks[n_out - depth - 1].
+  // The consumer of a concatenation never gets GroupNorm partial sums from its producers, so D is the whole kept state.
+  struct DeepCache {
+    void* buf = nullptr;
+    size_t bytes = 0, need = 0;       // need: what the dry run of a cached forward asks for
+    bool valid = false;
+    int Bf = 0, H = 0, W = 0, twin = 0, depth = 0, fp8_on = 0, fp8_scope = 0;   // the refresh that wrote D (dtype is the handle's)
+  } dc;
+
   // runtime state
   Arena arena;
   float* stage = nullptr;  // fp32 staging for weight upload
@@ -1515,7 +1526,10 @@ static int ensure_arena(af_handle* h, size_t need) {
 // builds it (ddim.py:236-247: torch.cat([x] * 2), cond first).  The time embedding, conv_in, the first ResBlock and the
 // first transformer up to its cross-attention do not see the context: they run on Bf / 2 samples and are copied.
 static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, const int64_t* t_dev, float* eps_dev,
-                             int Bf, int H, int W, bool twin = false) {
+                             int Bf, int H, int W, bool twin = false, int dc_mode = 0, int dc_depth = 0) {
+  // dc_mode (af_unet_forward_cached): AF_DEEPCACHE_REFRESH = this walk with cat[n_out - dc_depth] in the handle's buffer;
+  // AF_DEEPCACHE_REUSE = input_blocks[0 .. dc_depth-1], then output_blocks[n_out - dc_depth ..] from the h half kept there
+  const bool dc_reuse = dc_mode == AF_DEEPCACHE_REUSE;
   Runner R(h, s);
   const af_config& c = h->cfg;
   const int dt = h->dtype;
@@ -1649,8 +1663,17 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
       return AF_ERR_INVALID;
     }
     ch_h[j] = hshape.C;
-    cat[j] = R.alloc_act(Bf, hshape.H, hshape.W, hshape.C + sk.C);
-    AF_TRY(R.check(cat[j]));
+    if (dc_mode && j == n_out - dc_depth) {        // the kept concatenation: handle-owned, sized by the dry run
+      Act& a = cat[j];
+      a.B = Bf; a.H = hshape.H; a.W = hshape.W; a.C = a.ld = hshape.C + sk.C;
+      const size_t bytes = (size_t)a.npix() * a.ld * esize(dt);
+      if (R.dry) { h->dc.need = bytes; a.p = reinterpret_cast<void*>((uintptr_t)0x1000); }
+      else if (bytes > h->dc.bytes) { af_set_error_msg("unet: the DeepCache buffer was not sized for this forward"); return AF_ERR_STATE; }
+      else a.p = h->dc.buf;
+    } else if (!dc_reuse || j > n_out - dc_depth) {   // (a reuse step never touches the deeper concatenations)
+      cat[j] = R.alloc_act(Bf, hshape.H, hshape.W, hshape.C + sk.C);
+      AF_TRY(R.check(cat[j]));
+    }
     hshape = out_shape(h->output_blocks[j], Shp{hshape.C + sk.C, hshape.H, hshape.W});
   }
   auto view = [&](const Act& full, int off, int Cc) -> Act {
@@ -1668,7 +1691,7 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
                     af_launch_nhwc_to_nchw<f16>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
   };
   Act hcur = x;
-  for (int i = 0; i < n_in; ++i) {
+  for (int i = 0; i < (dc_reuse ? dc_depth : n_in); ++i) {
     const int j = n_in - 1 - i;  // the output block that will consume this skip
     Act o;
     // twin: block 0 (conv_in) on the first half, copied (it is a skip connection); block 1 = ResBlock on the first half +
@@ -1688,14 +1711,14 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     hcur = o;
     AF_TRY(tap(i, hcur));
   }
-  {
+  if (!dc_reuse) {
     Act o;
     const Act dst = view(cat[0], 0, ch_h[0]);
     AF_TRY(run_block(h->middle_block, hcur, o, n_out > 0 ? &dst : nullptr, Bf, false));
     hcur = o;
     AF_TRY(tap(n_in, hcur));
   }
-  for (int j = 0; j < n_out; ++j) {
+  for (int j = dc_reuse ? n_out - dc_depth : 0; j < n_out; ++j) {
     Act o;
     if (j + 1 < n_out) {
       const Act dst = view(cat[j + 1], 0, ch_h[j + 1]);
@@ -2000,6 +2023,7 @@ void af_destroy(af_handle* h) {
   for (auto& kv : h->ctx_kv) { if (kv.kv) hipFree(kv.kv); if (kv.vt) hipFree(kv.vt); if (kv.xf_pack) hipFree(kv.xf_pack); }
   if (h->ctx_rowmap) hipFree(h->ctx_rowmap);
   if (h->ctx_cast) hipFree(h->ctx_cast);
+  if (h->dc.buf) hipFree(h->dc.buf);
   if (h->arena.base) hipFree(h->arena.base);
   if (h->stage) hipFree(h->stage);
   delete h;
@@ -2076,6 +2100,7 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
   }
   HIP_CHECK_RET(hipStreamSynchronize(0));
   s.loaded = true;
+  h->dc.valid = false;
   h->ln_fold_dirty = true;
   h->fp8_dirty = true;
   h->up4_dirty = true;
@@ -2232,14 +2257,50 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
   return 0;
 }
 
+// the DeepCache buffer (sized by the dry run of a cached forward); growing it drops the kept feature
+static int ensure_deepcache(af_handle* h, hipStream_t s) {
+  // (kernels address the buffer by pixel stride exactly as they do the arena, where a tensor is never the last thing before
+  // unmapped memory: one page of slack keeps that true here)
+  const size_t need = h->dc.need + 4096;
+  if (need <= h->dc.bytes) return 0;
+  HIP_CHECK_RET(hipStreamSynchronize(s));
+  if (h->dc.buf) hipFree(h->dc.buf);
+  h->dc.buf = nullptr;
+  h->dc.bytes = 0;
+  h->dc.valid = false;
+  if (hipMalloc(&h->dc.buf, need) != hipSuccess) {
+    h->dc.buf = nullptr;
+    af_set_error_msg("hipMalloc of the %zu-byte DeepCache buffer failed", need);
+    return AF_ERR_HIP;
+  }
+  h->dc.bytes = need;
+  return 0;
+}
+
 static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
-                              void* stream, bool twin) {
+                              void* stream, bool twin, int dc_mode = 0, int dc_depth = 0) {
   if (!h || !x_dev || !t_dev || !eps_dev) { af_set_error_msg("af_unet_forward: null argument"); return AF_ERR_INVALID; }
   if (twin && (Bf < 2 || Bf % 2)) { af_set_error_msg("af_unet_forward_twin: the batch [x; x] must be even, got %d", Bf); return AF_ERR_INVALID; }
   if (!h->cfg.build_unet) { af_set_error_msg("af_unet_forward: handle has no UNet"); return AF_ERR_STATE; }
   if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
   const int down = 1 << (h->cfg.n_channel_mult - 1);
   if (H % down || W % down) { af_set_error_msg("af_unet_forward: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
+  af_handle::DeepCache& dc = h->dc;
+  if (dc_mode) {
+    const int n_in = (int)h->input_blocks.size(), n_out = (int)h->output_blocks.size();
+    if (dc_mode != AF_DEEPCACHE_REFRESH && dc_mode != AF_DEEPCACHE_REUSE) { af_set_error_msg("af_unet_forward_cached: mode %d", dc_mode); return AF_ERR_INVALID; }
+    if (n_in != n_out || dc_depth < 1 || dc_depth > n_in - 1) {
+      af_set_error_msg("af_unet_forward_cached: depth %d outside 1 .. %d", dc_depth, n_in - 1);
+      return AF_ERR_INVALID;
+    }
+    if (dc_mode == AF_DEEPCACHE_REUSE &&
+        !(dc.valid && dc.buf && dc.Bf == Bf && dc.H == H && dc.W == W && dc.twin == (int)twin && dc.depth == dc_depth &&
+          dc.fp8_on == (int)h->fp8_on && dc.fp8_scope == h->fp8_scope)) {
+      af_set_error_msg("af_unet_forward_cached: no kept feature for (Bf %d, %dx%d, twin %d, depth %d) -- a refresh with exactly "
+                       "these arguments must come first", Bf, H, W, (int)twin, dc_depth);
+      return AF_ERR_STATE;
+    }
+  }
   HIP_CHECK_RET(hipSetDevice(h->device));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   AF_TRY(fold_layernorms(h, s));
@@ -2247,12 +2308,39 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   AF_TRY(ensure_up4_twins(h, s));
   // size the arena with a dry run
   h->arena.dry = true; h->arena.peak = 0;
-  int rc = unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin);
+  int rc = unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth);
   h->arena.dry = false;
   if (rc) return rc;
   if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
   AF_TRY(ensure_gn_carry(h, s));
-  return unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin);
+  if (dc_mode == AF_DEEPCACHE_REFRESH) {
+    dc.valid = false;                       // (until this refresh has been enqueued completely)
+    AF_TRY(ensure_deepcache(h, s));
+  } else if (dc_mode == AF_DEEPCACHE_REUSE && dc.need + 4096 > dc.bytes) {
+    af_set_error_msg("af_unet_forward_cached: the kept feature does not fit this forward");   // (cannot happen for a valid entry)
+    return AF_ERR_STATE;
+  }
+  rc = unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth);
+  if (rc) { if (dc_mode) dc.valid = false; return rc; }
+  if (dc_mode == AF_DEEPCACHE_REFRESH) {
+    dc.valid = true;
+    dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = (int)twin; dc.depth = dc_depth;
+    dc.fp8_on = (int)h->fp8_on; dc.fp8_scope = h->fp8_scope;
+  }
+  return 0;
+}
+int af_unet_forward_cached(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
+                           int twin, int depth, int mode, void* stream) {
+  if (mode != AF_DEEPCACHE_REFRESH && mode != AF_DEEPCACHE_REUSE) {
+    af_set_error_msg("af_unet_forward_cached: mode %d is neither AF_DEEPCACHE_REFRESH nor AF_DEEPCACHE_REUSE", mode);
+    return AF_ERR_INVALID;
+  }
+  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, twin != 0, mode, depth);
+}
+int af_unet_cache_invalidate(af_handle* h) {
+  if (!h) { af_set_error_msg("af_unet_cache_invalidate: null handle"); return AF_ERR_INVALID; }
+  h->dc.valid = false;
+  return AF_OK;
 }
 int af_unet_forward(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                     void* stream) {
@@ -2531,6 +2619,7 @@ int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }
 int af_set_fp8(af_handle* h, int on) {
   if (!h) { af_set_error_msg("af_set_fp8: null handle"); return AF_ERR_INVALID; }
   if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is %s)", h->dtype == AF_DTYPE_F16 ? "f16" : "f32"); return AF_ERR_STATE; }
+  if (h->fp8_on != (on != 0)) h->dc.valid = false;   // (a kept DeepCache feature belongs to the mode that wrote it)
   h->fp8_on = on != 0;
   return AF_OK;
 }
@@ -2541,6 +2630,7 @@ int af_set_fp8_scope(af_handle* h, int mask) {
     af_set_error_msg("af_set_fp8_scope: mask %d (AF_FP8_SCOPE_BASE is always part of the scope, AF_FP8_SCOPE_FF may be added)", mask);
     return AF_ERR_INVALID;
   }
+  if (mask != h->fp8_scope) h->dc.valid = false;
   if (mask != h->fp8_scope) h->fp8_dirty = true;   // twins of the sites that joined are quantised before the next forward
   h->fp8_scope = mask;
   return AF_OK;
@@ -2589,6 +2679,7 @@ int af_fp8_get_shifts(af_handle* h, int n, int* shifts) {
 }
 int af_fp8_set_shifts(af_handle* h, int n, const int* shifts) {
   if (!h) { af_set_error_msg("af_fp8_set_shifts: null handle"); return AF_ERR_INVALID; }
+  h->dc.valid = false;
   if (!shifts) {
     for (int& v : h->fp8_shift) v = AF_FP8_SHIFT_DEFAULT;
     return AF_OK;

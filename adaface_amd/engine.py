@@ -172,6 +172,29 @@ class Engine:
               "af_unet_forward_twin")
         return out
 
+    def unet_forward_cached(self, x: torch.Tensor, t: torch.Tensor, *, depth: int, mode: str, twin: bool = False,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """af_unet_forward_cached (DeepCache).  mode "refresh": unet_forward / unet_forward_twin bit for bit, which also keeps
+        the output of output_blocks[n_out - depth - 1] in a buffer the handle owns.  mode "reuse": only input_blocks[:depth]
+        and output_blocks[n_out - depth:] run, on that kept feature; AfError when no refresh with the same batch, latent size,
+        twin and depth came before.  twin: x, t hold B samples and eps 2 B, as unet_forward_twin.  set_context / set_conv_attn
+        do not drop the kept feature: call unet_cache_invalidate when the conditioning changes."""
+        if mode not in _lib.DEEPCACHE_MODES:
+            raise ValueError(f"unet_forward_cached: mode {mode!r} (\"refresh\" or \"reuse\")")
+        x = x.contiguous().float()
+        t = t.contiguous().long()
+        B, _, H, W = x.shape
+        Bf = 2 * B if twin else B
+        if out is None:
+            out = torch.empty(Bf, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
+        check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, 1 if twin else 0, int(depth),
+                                               _lib.DEEPCACHE_MODES[mode], stream_ptr()), "af_unet_forward_cached")
+        return out
+
+    def unet_cache_invalidate(self):
+        """Drop the feature kept by unet_forward_cached(mode="refresh"): the next reuse call raises until a refresh ran."""
+        check(self._lib.af_unet_cache_invalidate(self._h), "af_unet_cache_invalidate")
+
     def unet_block_outputs(self, x: torch.Tensor, t: torch.Tensor, blocks=None) -> Dict[int, torch.Tensor]:
         """Outputs of U-Net blocks (forward order: input_blocks, middle_block, output_blocks) as fp32 NCHW tensors, one
         forward per requested block through the diagnostic tap (af_unet_set_tap).  Parity tests only."""

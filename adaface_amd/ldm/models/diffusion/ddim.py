@@ -7,7 +7,8 @@ makes it MI355X-native and device-agnostic:
   * the (cond, uncond) context pair is concatenated once per sample() call, not once per
     step, so the UNet's hoisted cross-attention K/V stay cached across the 50 steps;
   * a scalar guidance_scale means "no annealing" instead of the reference's
-    UnboundLocalError (ddim.py:169-173).
+    UnboundLocalError (ddim.py:169-173, SURVEY.md §8a a4);
+  * deep_cache_interval= / deep_cache_depth= (opt-in, not in the reference): DeepCache, see deep_cache.py.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
+from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
                                                            make_ddim_timesteps, noise_like)
 from adaface_amd.noise import STREAM_QSAMPLE, STREAM_STEP, STREAM_XT
@@ -33,6 +35,7 @@ class DDIMSampler(object):
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule
         self._twin_cache = None
+        self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -72,9 +75,11 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
-               unconditional_conditioning=None, noise_source=None, **kwargs):
+               unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
         """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
-        adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step)."""
+        adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step).
+        deep_cache_interval: None or 1 = off; N >= 2 = the full U-Net on loop indices i % N == 0 only, or an explicit
+        sequence of those indices (with 0); between them the outermost deep_cache_depth blocks run on the kept deep feature."""
         _check_noise_source(noise_source, noise_dropout)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -87,13 +92,15 @@ class DDIMSampler(object):
                                   score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, x_T=x_T,
                                   log_every_t=log_every_t, guidance_scale=guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
-                                  noise_source=noise_source, **kwargs)
+                                  noise_source=noise_source, deep_cache_interval=deep_cache_interval,
+                                  deep_cache_depth=deep_cache_depth, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None, **kwargs):
+                      guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None,
+                      deep_cache_interval=None, deep_cache_depth=2, **kwargs):
         """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
         code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
         step = the loop index."""
@@ -125,6 +132,8 @@ class DDIMSampler(object):
         delta = (max_guide_scale - min_guide_scale) / max_guide_anneal_steps if max_guide_anneal_steps > 0 else 0.
         guide_scale = max_guide_scale
         self._twin_cache = None
+        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
+        self.deep_cache_log = dc_run.log
 
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
@@ -141,7 +150,7 @@ class DDIMSampler(object):
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
                                               corrector_kwargs=corrector_kwargs, guidance_scale=guide_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              noise_source=noise_source, noise_step=i)
+                                              noise_source=noise_source, noise_step=i, deep_cache_run=dc_run)
             if callback:
                 callback(i)
             if img_callback:
@@ -170,16 +179,23 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0):
+                      guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0,
+                      deep_cache_run=None):
         """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
-        torch.randn; repeat_noise then gives every sample the first sample's id."""
+        torch.randn; repeat_noise then gives every sample the first sample's id.  deep_cache_run: the loop's DeepCacheRun
+        (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse)."""
         _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
-        if unconditional_conditioning is None or guidance_scale == 1.:
-            e_c, e_u = self.model.apply_model(x, t, c), None
+        single = unconditional_conditioning is None or guidance_scale == 1.
+        dc = None if deep_cache_run is None else deep_cache_run.step(noise_step, (not single, b, x.shape[2], x.shape[3]))
+        if single:
+            e_c = self.model.apply_model(x, t, c) if dc is None else self.model.apply_model(x, t, c, deep_cache=dc)
+            e_u = None
         else:
             twin = self._twin_condition(c, unconditional_conditioning)
-            if hasattr(self.model, "apply_model_cfg_twin"):
+            if dc is not None:      # (a DeepCacheRun is active only on a model with the twin entry point)
+                e = self.model.apply_model_cfg_twin(x, t, twin, deep_cache=dc)
+            elif hasattr(self.model, "apply_model_cfg_twin"):
                 # [x; x] without the concatenation: the UNet computes its context-independent prefix once (af_unet_forward_twin)
                 e = self.model.apply_model_cfg_twin(x, t, twin)
             else:
@@ -241,8 +257,9 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False):
-        """ddim.py:315-350 (img2img tail): anneals guidance from `guidance_scale` to min(2, guidance_scale)."""
+               use_original_steps=False, deep_cache_interval=None, deep_cache_depth=2):
+        """ddim.py:315-350 (img2img tail): anneals guidance from `guidance_scale` to min(2, guidance_scale).
+        deep_cache_interval / deep_cache_depth: as sample()."""
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         time_range = np.flip(timesteps)
@@ -253,11 +270,14 @@ class DDIMSampler(object):
         g = max_g
         x_dec = x_latent
         self._twin_cache = None
+        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
+        self.deep_cache_log = dc_run.log
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
-                                          guidance_scale=g, unconditional_conditioning=unconditional_conditioning)
+                                          guidance_scale=g, unconditional_conditioning=unconditional_conditioning,
+                                          noise_step=i, deep_cache_run=dc_run)
             g = g - delta
         self._twin_cache = None
         return x_dec

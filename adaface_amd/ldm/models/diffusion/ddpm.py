@@ -31,7 +31,7 @@ class DiffusionWrapper(nn.Module):
         if conditioning_key not in (None, "crossattn"):
             raise NotImplementedError(f"conditioning_key '{conditioning_key}' is not used by SD-v1 txt2img")
 
-    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False):
+    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False, deep_cache=None):
         if self.conditioning_key is None:
             raise NotImplementedError("unconditional UNet is not on the path")
         c0 = c_crossattn[0]
@@ -39,6 +39,9 @@ class DiffusionWrapper(nn.Module):
             c_static_emb, c_in, extra_info = c0
         else:
             c_static_emb, c_in, extra_info = c0, None, None
+        if deep_cache is not None:    # DeepCache refresh / reuse step (UNetModel.forward); None: the calls below, unchanged
+            return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info,
+                                        cfg_twin=bool(cfg_twin), deep_cache=deep_cache)
         if cfg_twin:
             return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info, cfg_twin=True)
         return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info)
@@ -102,6 +105,7 @@ class DDPM(nn.Module):
 
 class LatentDiffusion(DDPM):
     """ddpm.py:712-5396, inference subset."""
+    supports_deep_cache = True    # apply_model / apply_model_cfg_twin take deep_cache= (samplers: deep_cache.py)
 
     def __init__(self, first_stage_config, cond_stage_config=None, personalization_config=None,
                  num_timesteps_cond=None, cond_stage_key="image", cond_stage_trainable=False, concat_mode=True,
@@ -193,19 +197,20 @@ class LatentDiffusion(DDPM):
         return emb.unsqueeze(1).expand(B, n_layers, T, D).reshape(B * n_layers, T, D).contiguous()
 
     # ---- denoiser ----------------------------------------------------------------------------
-    def apply_model(self, x_noisy, t, cond, return_ids=False):
-        """ddpm.py:2192-2297 (the split_input_params patch mode is never active: SURVEY.md §8a a6)."""
+    def apply_model(self, x_noisy, t, cond, return_ids=False, deep_cache=None):
+        """ddpm.py:2192-2297 (the split_input_params patch mode is never active: SURVEY.md §8a a6).
+        deep_cache (not in the reference): None, ("refresh", k) or ("reuse", k), see UNetModel.forward."""
         if not isinstance(cond, dict):
             if not isinstance(cond, list):
                 cond = [cond]
             key = 'c_concat' if self.model.conditioning_key == 'concat' else 'c_crossattn'
             cond = {key: cond}
-        x_recon = self.model(x_noisy, t, **cond)
+        x_recon = self.model(x_noisy, t, **cond) if deep_cache is None else self.model(x_noisy, t, deep_cache=deep_cache, **cond)
         if isinstance(x_recon, tuple) and not return_ids:
             return x_recon[0]
         return x_recon
 
-    def apply_model_cfg_twin(self, x_noisy, t, cond_twin):
+    def apply_model_cfg_twin(self, x_noisy, t, cond_twin, deep_cache=None):
         """apply_model(torch.cat([x] * 2), torch.cat([t] * 2), cond_twin) -- the classifier-free-guidance call of
         p_sample_ddim / p_sample_plms (ddim.py:236-247) -- without the concatenation: `cond_twin` is the condition of the
         2B samples (cond first), x_noisy / t those of one half.  Returns eps of the 2B samples.  Not a reference method: the
@@ -217,6 +222,8 @@ class LatentDiffusion(DDPM):
             cond = {'c_crossattn': cond}
         if 'c_crossattn' not in cond:
             return self.apply_model(torch.cat([x_noisy] * 2), torch.cat([t] * 2), cond_twin)
+        if deep_cache is not None:
+            return self.model(x_noisy, t, cfg_twin=True, deep_cache=deep_cache, **cond)
         return self.model(x_noisy, t, cfg_twin=True, **cond)
 
     # ---- decoder -----------------------------------------------------------------------------

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
+from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
 from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
 
@@ -109,6 +110,7 @@ class DPMSolverSampler(object):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
         self._twin_cache = None
+        self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -119,12 +121,13 @@ class DPMSolverSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, img_callback=None, mask=None, x0=None,
                x_T=None, verbose=True, log_every_t=100, guidance_scale=1., unconditional_guidance_scale=None,
                unconditional_conditioning=None, order=2, lower_order_final=True, skip_type="time_uniform", timesteps=None,
-               algorithm="dpmsolver++", noise_source=None, **kwargs):
+               algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
         """(img, intermediates) as DDIMSampler.sample.  guidance_scale: a scalar or [max, min] (annealed as ddim_sampling
         does); unconditional_guidance_scale: the PLMS / CompVis spelling of the scalar.  timesteps: an explicit strictly
         increasing integer array, overriding S and skip_type.  algorithm: "dpmsolver++" (deterministic) or "sde-dpmsolver++"
         (one N(0, 1) draw per step, scaled by temperature=); noise_source: a PhiloxNoise for the SDE draws, the inpainting
-        blend's q_sample noise and, with x_T None, the start code."""
+        blend's q_sample noise and, with x_T None, the start code.  deep_cache_interval / deep_cache_depth: DeepCache, as
+        DDIMSampler.sample (deep_cache.py)."""
         if algorithm not in ALGORITHMS:
             raise NotImplementedError(f'There is no DPM-Solver algorithm called "{algorithm}" ({", ".join(ALGORITHMS)})')
         sde = algorithm == "sde-dpmsolver++"
@@ -154,7 +157,8 @@ class DPMSolverSampler(object):
         return self.dpm_solver_sampling(conditioning, size, self.schedule, x_T=x_T, callback=callback,
                                         img_callback=img_callback, mask=mask, x0=x0, log_every_t=log_every_t,
                                         unconditional_conditioning=unconditional_conditioning, noise_source=noise_source,
-                                        temperature=temperature)
+                                        temperature=temperature, deep_cache_interval=deep_cache_interval,
+                                        deep_cache_depth=deep_cache_depth)
 
     def _twin_condition(self, c, uc):
         """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
@@ -172,7 +176,8 @@ class DPMSolverSampler(object):
 
     @torch.no_grad()
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
-                            log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.):
+                            log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.,
+                            deep_cache_interval=None, deep_cache_depth=2):
         """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update."""
         device = self.model.betas.device
         b = shape[0]
@@ -191,6 +196,8 @@ class DPMSolverSampler(object):
         hist = [torch.empty(shape, device=device, dtype=torch.float32) for _ in range(2)]
         x0_prev = None
         self._twin_cache = None
+        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
+        self.deep_cache_log = dc_run.log
         for i, row in enumerate(schedule):
             index = total_steps - i - 1
             guide_scale = float(row[COL_G])
@@ -202,11 +209,16 @@ class DPMSolverSampler(object):
                 else:
                     img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
                 img = img_orig * mask + (1. - mask) * img
-            if unconditional_conditioning is None or guide_scale == 1.:
-                e_c, e_u = self.model.apply_model(img, ts, cond), None
+            single = unconditional_conditioning is None or guide_scale == 1.
+            dc = dc_run.step(i, (not single, b, img.shape[2], img.shape[3]))     # None: the full forward, as without DeepCache
+            if single:
+                e_c = self.model.apply_model(img, ts, cond) if dc is None else self.model.apply_model(img, ts, cond, deep_cache=dc)
+                e_u = None
             else:
                 twin = self._twin_condition(cond, unconditional_conditioning)
-                if hasattr(self.model, "apply_model_cfg_twin"):
+                if dc is not None:      # (a DeepCacheRun is active only on a model with the twin entry point)
+                    e = self.model.apply_model_cfg_twin(img, ts, twin, deep_cache=dc)
+                elif hasattr(self.model, "apply_model_cfg_twin"):
                     e = self.model.apply_model_cfg_twin(img, ts, twin)   # [x; x] without the concatenation (af_unet_forward_twin)
                 else:
                     e = self.model.apply_model(torch.cat([img] * 2), torch.cat([ts] * 2), twin)

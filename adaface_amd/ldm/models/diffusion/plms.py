@@ -48,7 +48,11 @@ class PLMSSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, **kwargs):
+               unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
+        from adaface_amd.ldm.models.diffusion.deep_cache import is_off
+        if not is_off(deep_cache_interval):
+            raise NotImplementedError("deep_cache_interval with the PLMS sampler: it calls the model twice in its first step and "
+                                      "extrapolates from an eps history (use DDIMSampler or DPMSolverSampler)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,

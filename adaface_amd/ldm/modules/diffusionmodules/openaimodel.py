@@ -139,12 +139,17 @@ class UNetModel(HipModule):
         return (ks, tuple(batch), tuple(tokens))
 
     @torch.no_grad()
-    def forward(self, x, timesteps=None, context=None, y=None, context_in=None, extra_info=None, cfg_twin=False, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, context_in=None, extra_info=None, cfg_twin=False, deep_cache=None,
+                **kwargs):
         """x [B,C,H,W], timesteps [B], context [B*16,T,D] (layerwise) or [B,T,D]; returns eps [B,C,H,W] fp32.
         Mirrors openaimodel.py:827-1052 for inference: `extra_info` keys read at :849-859.
         cfg_twin (not in the reference; used by this package's samplers): x / timesteps are ONE half of the
         classifier-free-guidance batch, the context is that of [x; x] (cond first, ddim.py:236-247); returns eps for the
-        2B samples exactly as forward(torch.cat([x] * 2), torch.cat([t] * 2), context) would."""
+        2B samples exactly as forward(torch.cat([x] * 2), torch.cat([t] * 2), context) would.
+        deep_cache (not in the reference; DeepCache, set by this package's samplers): None = the plain forward;
+        ("refresh", k) = the same forward, which also keeps the input of output_blocks[-k]; ("reuse", k) = only
+        input_blocks[:k] and output_blocks[-k:] run, on the feature the last refresh kept.  A context or conv-attention spec
+        that differs from the previous call's drops the kept feature (a reuse then raises AfError)."""
         if y is not None:
             raise NotImplementedError("class-conditional UNet (num_classes) is not on the path")
         if timesteps is None or context is None:
@@ -166,11 +171,17 @@ class UNetModel(HipModule):
         # id / storage cannot be recycled for another prompt while the cache is live (data_ptr alone is unsafe).
         key = (id(context), getattr(context, "_version", 0), tuple(context.shape), layerwise, B, conv)
         if key != self._ctx_key or not cache_ok:
+            if key != self._ctx_key:
+                eng.unet_cache_invalidate()     # (the kept DeepCache feature was computed under the previous conditioning)
             eng.set_conv_attn(*conv)
             eng.set_context(context.to(x.device), B, layerwise)
             object.__setattr__(self, "_ctx_key", key if cache_ok else None)
             object.__setattr__(self, "_ctx_ref", context)
-        out = (eng.unet_forward_twin if cfg_twin else eng.unet_forward)(x, timesteps.to(x.device))
+        if deep_cache is None:
+            out = (eng.unet_forward_twin if cfg_twin else eng.unet_forward)(x, timesteps.to(x.device))
+        else:
+            mode, depth = deep_cache
+            out = eng.unet_forward_cached(x, timesteps.to(x.device), depth=int(depth), mode=mode, twin=bool(cfg_twin))
         if extra_info is not None:
             # the reference writes the (here empty) distillation capture into the caller's dict (:1031-1035)
             extra_info["ca_layers_activations"] = {k: {} for k in ("outfeat", "attn", "attnscore", "q")}

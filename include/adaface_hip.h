@@ -116,6 +116,23 @@ int af_unet_forward(af_handle* h, const float* x_dev, const int64_t* t_dev, floa
 int af_unet_forward_twin(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                          void* stream);
 
+/* DeepCache (Ma et al., CVPR 2024), opt-in: reuse the deep part of the U-Net between sampler steps.  With n_in input and
+ * n_out output blocks and 1 <= depth <= n_in - 1 (AF_ERR_INVALID otherwise):
+ *   AF_DEEPCACHE_REFRESH  the forward of af_unet_forward (twin = 0) / af_unet_forward_twin (twin = 1), bit for bit, that also
+ *                         keeps D = the output of output_blocks[n_out - depth - 1] in a buffer the handle owns;
+ *   AF_DEEPCACHE_REUSE    time embedding, input_blocks[0 .. depth-1], h = D, output_blocks[n_out - depth .. n_out-1], out.
+ *                         Nothing else runs; every transformer that runs keeps its own cross-attention layer (context slice,
+ *                         cached K/V, conv-attention rule).  With the x, t of the refresh the result equals it bit for bit.
+ * D is valid for the (Bf, H, W, twin, depth) and the fp8 mode and scope of the refresh that wrote it; a reuse call without a
+ * valid D for exactly its arguments returns AF_ERR_STATE and launches nothing.  af_load_tensor, af_set_fp8,
+ * af_set_fp8_scope, af_fp8_set_shifts and af_unet_cache_invalidate drop D.  af_set_context and af_set_conv_attn do NOT (a
+ * caller may re-set an identical context every step): whoever changes the conditioning between a refresh and a reuse
+ * invalidates.  Other forwards, VAE and CLIP calls leave D alone.  In reuse mode the diagnostic tap writes only blocks that ran. */
+enum { AF_DEEPCACHE_REFRESH = 1, AF_DEEPCACHE_REUSE = 2 };
+int af_unet_forward_cached(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
+                           int twin, int depth, int mode, void* stream);
+int af_unet_cache_invalidate(af_handle* h);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the

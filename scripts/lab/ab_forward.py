@@ -2,6 +2,7 @@
 """Lab: time the full SD-1.5 UNet forward at Bf = 16 (bf16, synthetic weights) with a given build of libadaface_hip.so,
 so that two builds (e.g. the round-1 library and HEAD) can be compared on ONE box:
     python scripts/lab/ab_forward.py [--lib path/to/lib.so] [--reps 20] [--fp8] [--conv-attn KS [--ab-knob NAME]]
+                                     [--twin [--deep-cache refresh:K | reuse:K]]
 --conv-attn KS: subject-token conv attention (kernel size KS) on the first half of the batch (the conditional half of a CFG
 batch).  --ab-knob NAME: time the forward with knob NAME = 1 and = 0 alternately in this one process (five rounds each).
 Older builds lack newer entry points: missing symbols are skipped when --lib is given (lab only)."""
@@ -23,6 +24,8 @@ ap.add_argument("--fp8", action="store_true")
 ap.add_argument("--fp8-scope", dest="fp8_scope", default="base", help="with --fp8: base | base+ff (the FeedForward scope)")
 ap.add_argument("--knob", action="append", default=[])
 ap.add_argument("--twin", action="store_true", help="af_unet_forward_twin on x[:8] (the CFG batch [x; x]) instead of af_unet_forward")
+ap.add_argument("--deep-cache", dest="deep_cache", default="", metavar="MODE:K",
+                help="with --twin: time af_unet_forward_cached in MODE (refresh | reuse, the latter after one refresh) at depth K")
 ap.add_argument("--conv-attn", dest="conv_attn", type=int, default=0, help="conv attention kernel size (2 / 3 / 4) on the first half of the batch")
 ap.add_argument("--ab-knob", dest="ab_knob", default="", help="alternate this knob between 1 and 0 in one process and report both")
 args = ap.parse_args()
@@ -62,6 +65,10 @@ out = torch.empty_like(x)
 if args.twin:
     xh, th = x[:8].contiguous(), t[:8].contiguous()
     fwd = lambda x_, t_, o_: eng.unet_forward_twin(xh, th, o_)
+    if args.deep_cache:
+        dc_mode, dc_k = args.deep_cache.split(":")
+        eng.unet_forward_cached(xh, th, depth=int(dc_k), mode="refresh", twin=True, out=out)
+        fwd = lambda x_, t_, o_: eng.unet_forward_cached(xh, th, depth=int(dc_k), mode=dc_mode, twin=True, out=o_)
 else:
     fwd = eng.unet_forward
 for _ in range(3):
@@ -109,4 +116,4 @@ lib.af_prof_collect(n, ms, la, fl, by)
 names = ["gemm_other", "attention", "groupnorm", "layernorm", "other", "pp160_gather", "pp160_plain", "pp128", "fp8", "halo8"]
 print("   per-class ms per forward: " + ", ".join(f"{names[i]} {ms[i]:.2f} ({la[i]})" for i in range(n) if la[i])
       + f" | gemm total {ms[0] + ms[5] + ms[6] + ms[7] + ms[8] + ms[9]:.2f}")
-print(f"{args.lib or 'HEAD'}{(' fp8 ' + args.fp8_scope) if args.fp8 else ''}{' twin' if args.twin else ''}{(' conv-attn ' + str(args.conv_attn)) if args.conv_attn else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")
+print(f"{args.lib or 'HEAD'}{(' fp8 ' + args.fp8_scope) if args.fp8 else ''}{' twin' if args.twin else ''}{(' deep-cache ' + args.deep_cache) if args.deep_cache else ''}{(' conv-attn ' + str(args.conv_attn)) if args.conv_attn else ''} {' '.join(args.knob)}: UNet forward Bf=16: {best * 1e3:.3f} ms  (-> {8 / (50 * best + 0.026):.2f} images/s at 50 steps + 26 ms VAE)")

@@ -3,7 +3,7 @@
 
 Keeps the reference's flag names for everything that reaches the denoising path
 (stable_txt2img.py:38-310): --config --ckpt --n_samples --n_repeat --ddim_steps --ddim_eta --scale --H --W --C --f
---seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --noise --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
+--seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --noise --deep_cache --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
 
@@ -61,6 +61,11 @@ def parse_args(argv=None):
                          "generator, step noise (--ddim_eta > 0, --dpm_sde) from the device's default generator, which --seed "
                          "does not reach.  philox: all of it keyed by (--seed, global sample index, step): --seed names an image "
                          "whatever the batch split or --gpus")
+    ap.add_argument("--deep_cache", type=int, default=None, metavar="N",
+                    help="DeepCache: the full U-Net on every N-th step only; between them its outermost blocks run on the deep "
+                         "feature kept at the last full step (DDIM and --dpm_solver; 1 = off)")
+    ap.add_argument("--deep_cache_depth", type=int, default=2, metavar="K",
+                    help="--deep_cache: input / output blocks that still run on the steps between (1 .. 11 for SD-1.5)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -79,6 +84,10 @@ def parse_args(argv=None):
     opt = ap.parse_args(argv)
     if opt.dpm_sde and not opt.dpm_solver:
         ap.error("--dpm_sde is a variant of --dpm_solver: give both")
+    if opt.deep_cache is not None and opt.deep_cache < 1:
+        ap.error("--deep_cache N: N >= 1")
+    if opt.deep_cache not in (None, 1) and opt.plms:
+        ap.error("--deep_cache: PLMS calls the model twice in its first step and keeps an eps history (use DDIM or --dpm_solver)")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     return opt
@@ -236,6 +245,8 @@ def main():
                 if opt.init_img_paths:
                     x_T = shard_batch(start_code, rank, world).to(device) + x_T * (1.0 - opt.init_img_weight)
             kw = {} if noise_source is None else dict(noise_source=noise_source)
+            if opt.deep_cache not in (None, 1):
+                kw.update(deep_cache_interval=opt.deep_cache, deep_cache_depth=opt.deep_cache_depth)
             if opt.plms:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,

@@ -16,7 +16,7 @@
 // an activation arena in HBM, and enqueues the kernels on the caller's stream.
 // No CPU fallback exists: every op is a HIP kernel launch.
 #include "../../include/adaface_hip.h"
-#include "af_kernels.h"
+#include "af_host.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -110,21 +110,6 @@ void af_prof_begin_impl(int cls, hipStream_t s, double flops, double bytes) {
   g_prof_recs.push_back(r);
 }
 void af_prof_end_impl(hipStream_t s) { hipEventRecord(g_prof_recs.back().stop, s); }
-
-#define AF_TRY(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != 0) return _rc;   \
-  } while (0)
-
-static inline size_t esize(int dtype) { return dtype == AF_DTYPE_F32 ? 4 : 2; }
-static inline int bk_of(int dtype) { return dtype == AF_DTYPE_F32 ? 32 : 64; }
-// the planner's name for a handle's storage type
-static inline AfStorage storage_of(int dtype) { return dtype == AF_DTYPE_BF16 ? AF_ST_BF16 : dtype == AF_DTYPE_F16 ? AF_ST_F16 : AF_ST_F32; }
-static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
-#define DISPATCH(dtype, CALL_BF16, CALL_F32, CALL_F16) \
-  ((dtype) == AF_DTYPE_BF16 ? (CALL_BF16) : (dtype) == AF_DTYPE_F16 ? (CALL_F16) : (CALL_F32))
 
 // ----------------------------------------------------------------------------
 // activation arena (bump allocator with mark/release); dry mode only measures.
@@ -781,6 +766,60 @@ static int build_vae_encoder(Builder& b) {
 // ----------------------------------------------------------------------------
 // op runner: thin typed dispatch + arena allocation
 // ----------------------------------------------------------------------------
+// LayerNorm folded into a ping-pong GEMM (ConvGemmParams::ln_*): consumer (stats + colsum) or producer (stats_out)
+struct LnArgs {
+  const float* stats = nullptr; const float* colsum = nullptr;   // consumer: finalised (mu, rstd) per row, column sums
+  float* stats_out = nullptr;                                    // producer: partial sums [parts][M][2]
+  // consumer, statistics not finalised yet: the producer's partial sums for exactly this launch's rows.  A row-panel
+  // launch sums them in its prologue; any other gets an ln_finalize launch into `stats_buf` first (conv() decides)
+  const float* parts_in = nullptr;
+  int parts_n = 0, count = 0;
+  float eps = 0.f;
+  float* stats_buf = nullptr;
+  // GroupNorm of the input applied by the (row-panel) GEMM itself: per-sample scale / shift, rows per sample
+  const float* gn_ab = nullptr;
+  int gn_hw = 0;
+};
+
+// Where a convolution also writes the GroupNorm partial sums of its output, if its kernel can (out.gn_part then says so):
+// into the arena (the consumer runs inside the caller's arena scope) or into the handle's carry buffer (the consumer is
+// the next layer)
+enum GnStats { GN_NONE = 0, GN_ARENA = 1, GN_CARRY = 2 };
+
+// What Runner::conv is told beyond (layer, input, output).  The defaults are the plain stride-1 convolution / linear;
+// the setters chain: R.conv(w.c2, t3, out, ConvOpt().res(&sk).gn_carry()).
+struct ConvOpt {
+  int stride = 1;
+  int up = 0;                       // 1: nearest 2x upsampling before the convolution
+  const Act* residual = nullptr;    // added to the output
+  const void* rowbias = nullptr;    // per-sample bias rows (storage dtype), ldrb elements apart
+  int ldrb = 0;
+  int n_valid = -1;                 // output columns; < 0: round_up(cout, 4)
+  // pad < 0: the layer's symmetric ks/2.  pad = 0 with stride 2 on an even map is the VAE Downsample: the reference
+  // pads one zero row / column at the bottom / right only (model.py:73-77), which is exactly what the gather's
+  // bounds check returns for iy == Hi / ix == Wi
+  int pad = -1;
+  bool has_ln = false;              // ln holds LayerNorm / GroupNorm folding arguments
+  LnArgs ln;
+  GnStats want_gn = GN_NONE;
+
+  ConvOpt& strided(int v) { stride = v; return *this; }
+  ConvOpt& upsampled() { up = 1; return *this; }
+  ConvOpt& res(const Act* r) { residual = r; return *this; }
+  ConvOpt& row_bias(const void* rb, int ld) { rowbias = rb; ldrb = ld; return *this; }
+  ConvOpt& cols(int n) { n_valid = n; return *this; }
+  ConvOpt& padded(int v) { pad = v; return *this; }
+  ConvOpt& gn_map(const float* ab, int hw) { ln.gn_ab = ab; ln.gn_hw = hw; has_ln = true; return *this; }
+  ConvOpt& gn_arena() { want_gn = GN_ARENA; return *this; }
+  ConvOpt& gn_carry() { want_gn = GN_CARRY; return *this; }
+};
+
+struct Strided {   // attention operand: first element, row stride and batch stride (elements)
+  const void* p;
+  int ld;
+  long bs;
+};
+
 struct Runner {
   af_handle* h;
   hipStream_t s;
@@ -813,69 +852,54 @@ struct Runner {
     }
     return 0;
   }
+  char* elem_ptr(void* p, long off) { return reinterpret_cast<char*>(p) + off * (long)esize(dt); }
+  // columns [off, ..) of a tensor whose samples have `rows` rows, as an attention operand
+  Strided cols_of(const Act& a, int off, long rows) { return {elem_ptr(a.p, off), a.ld, rows * a.ld}; }
 
-  // conv / linear.  out must be preallocated.  up: nearest 2x before the conv.
-  // pad < 0: the layer's symmetric ks/2.  pad = 0 with stride 2 on an even map is the VAE Downsample: the reference
-  // pads one zero row / column at the bottom / right only (model.py:73-77), which is exactly what the gather's
-  // bounds check returns for iy == Hi / ix == Wi
-  // LayerNorm folded into a ping-pong GEMM (ConvGemmParams::ln_*): consumer (stats + colsum) or producer (stats_out)
-  struct LnArgs {
-    const float* stats = nullptr; const float* colsum = nullptr;   // consumer: finalised (mu, rstd) per row, column sums
-    float* stats_out = nullptr;                                    // producer: partial sums [parts][M][2]
-    // consumer, statistics not finalised yet: the producer's partial sums for exactly this launch's rows.  A row-panel
-    // launch sums them in its prologue; any other gets an ln_finalize launch into `stats_buf` first (conv() decides)
-    const float* parts_in = nullptr;
-    int parts_n = 0, count = 0;
-    float eps = 0.f;
-    float* stats_buf = nullptr;
-    // GroupNorm of the input applied by the (row-panel) GEMM itself: per-sample scale / shift, rows per sample
-    const float* gn_ab = nullptr;
-    int gn_hw = 0;
-  };
   int ln_finalize(const float* part, int parts, long M, int count, float eps, float* out) {
     if (dry) return 0;
     return af_launch_ln_finalize(part, parts, (int)M, count, eps, out, s);
   }
-  void conv_params(ConvGemmParams& p, const Linear& L, const Act& x, const Act& out, int stride, int up,
-                   const Act* residual, const void* rowbias, int ldrb, int n_valid, int pad) const {
+  // the launch parameters of conv(L, x, out, o) without its LayerNorm / GroupNorm arguments
+  ConvGemmParams conv_params(const Linear& L, const Act& x, const Act& out, const ConvOpt& o = {}) const {
+    ConvGemmParams p;
     memset(&p, 0, sizeof(p));
     p.src = x.p;
     p.src_batch_stride = (long)x.H * x.W * x.ld;
     p.ldc = x.ld;
     p.Cin = L.cin_pad;
     p.Hs = x.H; p.Ws = x.W;
-    p.up = up;
-    p.Hi = x.H << up; p.Wi = x.W << up;
+    p.up = o.up;
+    p.Hi = x.H << o.up; p.Wi = x.W << o.up;
     p.Ho = out.H; p.Wo = out.W;
-    p.ks = L.ks; p.stride = stride; p.pad = pad >= 0 ? pad : L.ks / 2;
+    p.ks = L.ks; p.stride = o.stride; p.pad = o.pad >= 0 ? o.pad : L.ks / 2;
     p.W = L.w; p.ldw = L.ldw; p.Wrows = L.rows_pad;
     p.M = (int)out.npix();
-    p.N = n_valid > 0 ? n_valid : round_up(L.cout, 4);
+    p.N = o.n_valid > 0 ? o.n_valid : round_up(L.cout, 4);
     p.K = L.ldw;
     p.k_logical = L.ks * L.ks * L.cin;
     p.bias = L.bias;
-    p.rowbias = rowbias; p.ldrb = ldrb;
-    p.residual = residual ? residual->p : nullptr;
-    p.ldr = residual ? residual->ld : 0;
+    p.rowbias = o.rowbias; p.ldrb = o.ldrb;
+    p.residual = o.residual ? o.residual->p : nullptr;
+    p.ldr = o.residual ? o.residual->ld : 0;
     p.out = out.p; p.ldo = out.ld;
     p.epilogue = L.geglu ? AF_EPI_GEGLU : AF_EPI_NONE;
     p.alpha = 1.0f;
-    p.W_up4 = up ? L.w_up4 : nullptr;
+    p.W_up4 = o.up ? L.w_up4 : nullptr;
     if (x.f8) {   // fp8 operands: the twin's K layout and scales (strides of an e4m3 tensor are bytes = elements)
       p.fp8 = 1;
       p.W = L.w8; p.ldw = L.k8; p.K = L.k8;
       p.w_scale = L.sc8;
       p.x_scale_e8 = 127 - x.f8_shift;
     }
+    return p;
   }
-  // would this convolution run on the fp8 ping-pong kernel?  (asked BEFORE its input is produced as e4m3)
-  bool fp8_capable(const Linear& L, const Act& x, const Act& out, int stride = 1, int up = 0) const {
+  // would this (plain) convolution run on the fp8 ping-pong kernel?  (asked BEFORE its input is produced as e4m3)
+  bool fp8_capable(const Linear& L, const Act& x, const Act& out) const {
     if (!h->fp8_on || dt != AF_DTYPE_BF16 || !L.w8 || L.f8_site < 0 || x.C != L.cin || L.cin != L.cin_pad) return false;
     Act x8 = x;
     x8.f8 = true; x8.ld = x.C;
-    ConvGemmParams p;
-    conv_params(p, L, x8, out, stride, up, nullptr, nullptr, 0, -1, -1);
-    return af_plan_conv_gemm(p, 1, AF_ST_BF16).kernel == AF_GK_PP_FP8;
+    return af_plan_conv_gemm(conv_params(L, x8, out), 1, AF_ST_BF16).kernel == AF_GK_PP_FP8;
   }
   // FeedForward scope: would BOTH GEMMs of a transformer block's FeedForward run on fp8 operands -- ff1 (GEGLU, e4m3 output,
   // ff_geglu_fp8_kernel) on e4m3(norm3 x) and ff2 on its bytes?  From the scope, the shapes and the twins alone.
@@ -888,16 +912,13 @@ struct Runner {
     x8.f8 = true; x8.ld = x.C;
     Act f8 = x8;
     f8.C = f8.ld = ff2.cin;
-    ConvGemmParams p;
-    conv_params(p, ff1, x8, f8, 1, 0, nullptr, nullptr, 0, ff1.cout, -1);
-    return af_ff_geglu_fp8_ok(p) && fp8_capable(ff2, f8, out);
+    return af_ff_geglu_fp8_ok(conv_params(ff1, x8, f8, ConvOpt().cols(ff1.cout))) && fp8_capable(ff2, f8, out);
   }
   // y8 = e4m3(geglu(ff1 x8) * 2^shift of y8's site)
   int ff_geglu8(const Linear& L, const Act& x8, Act& y8) {
     AF_TRY(check(y8));
     if (!x8.f8 || !y8.f8 || !L.w8) { af_set_error_msg("ff_geglu8: e4m3 operands and an fp8 weight twin needed"); return AF_ERR_STATE; }
-    ConvGemmParams p;
-    conv_params(p, L, x8, y8, 1, 0, nullptr, nullptr, 0, L.cout, -1);
+    const ConvGemmParams p = conv_params(L, x8, y8, ConvOpt().cols(L.cout));
     if (dry) return 0;
     return af_launch_ff_geglu_fp8(p, ldexpf(1.f, y8.f8_shift), fp8_rec_of(y8), s);
   }
@@ -905,16 +926,13 @@ struct Runner {
   // into (AfGemmPlan::ln_slabs; 0 = no)
   int ln_capable(const Linear& L, const Act& x, const Act& out, int n_valid = -1) const {
     if (dt != AF_DTYPE_BF16 || L.ks != 1) return 0;
-    ConvGemmParams p;
-    conv_params(p, L, x, out, 1, 0, nullptr, nullptr, 0, n_valid, -1);
-    return af_plan_conv_gemm(p, 1, storage_of(dt)).ln_slabs;
+    return af_plan_conv_gemm(conv_params(L, x, out, ConvOpt().cols(n_valid)), 1, storage_of(dt)).ln_slabs;
   }
-  // would conv(L, x, out, ..., ln) be a row-panel launch (the only kernels that can apply a GroupNorm of their input)?
-  bool rowpanel_capable(const Linear& L, const Act& x, const Act& out, const LnArgs* ln, int gn_hw) const {
+  // would conv(L, x, out, o) be a row-panel launch (the only kernels that can apply a GroupNorm of their input)?
+  bool rowpanel_capable(const Linear& L, const Act& x, const Act& out, const ConvOpt& o, int gn_hw) const {
     if (dt != AF_DTYPE_BF16 || L.ks != 1 || x.f8) return false;
-    ConvGemmParams p;
-    conv_params(p, L, x, out, 1, 0, nullptr, nullptr, 0, -1, -1);
-    if (ln) { p.ln_stats = ln->stats; p.ln_colsum = ln->colsum; p.ln_stats_out = ln->stats_out; }
+    ConvGemmParams p = conv_params(L, x, out);
+    if (o.has_ln) { p.ln_stats = o.ln.stats; p.ln_colsum = o.ln.colsum; p.ln_stats_out = o.ln.stats_out; }
     p.gn_ab = reinterpret_cast<const float*>(1);   // (capability question only)
     p.gn_hw = gn_hw;
     return af_plan_conv_gemm(p, 1, storage_of(dt)).kernel == AF_GK_ROWPANEL;
@@ -927,18 +945,15 @@ struct Runner {
     if (dry) return 0;
     if (x.C != N.C) { af_set_error_msg("groupnorm: C mismatch %d vs %d", x.C, N.C); return AF_ERR_INVALID; }
     const float* pre = g_af_knobs.gn_producer ? x.gn_part : nullptr;
-    return DISPATCH(dt, af_launch_groupnorm_fold<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab),
-                    af_launch_groupnorm_fold<float>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab),
-                    af_launch_groupnorm_fold<f16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s, pre, x.gn_npart, ab));
+    return AF_TYPED(dt, af_launch_groupnorm_fold<Elem>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, ws, s,
+                                                       pre, x.gn_npart, ab));
   }
-  // want_gn: 1 = also write the GroupNorm partial sums of `out` into the arena (consumer inside the caller's arena scope),
-  // 2 = into the handle's carry buffer (consumer = the next layer); out.gn_part is set when the launch can do it
-  int conv(const Linear& L, const Act& x, Act& out, int stride, int up, const Act* residual, const void* rowbias,
-           int ldrb, int n_valid = -1, int pad = -1, const LnArgs* ln = nullptr, int want_gn = 0) {
+  // conv / linear.  out must be preallocated; everything else is in ConvOpt.
+  int conv(const Linear& L, const Act& x, Act& out, const ConvOpt& o = {}) {
     AF_TRY(check(out));
     out.gn_part = nullptr; out.gn_npart = 0;
-    ConvGemmParams p;
-    conv_params(p, L, x, out, stride, up, residual, rowbias, ldrb, n_valid, pad);
+    ConvGemmParams p = conv_params(L, x, out, o);
+    const LnArgs* ln = o.has_ln ? &o.ln : nullptr;
     bool ln_parts_pending = false;
     if (ln) {
       p.ln_stats = ln->stats; p.ln_colsum = ln->colsum;
@@ -967,11 +982,12 @@ struct Runner {
         AF_TRY(ln_finalize(ln->parts_in, ln->parts_n, (long)p.M, ln->count, ln->eps, ln->stats_buf));
       }
     }
-    if (want_gn && dt == AF_DTYPE_BF16 && out.C % 32 == 0 && out.C == p.N && af_conv_gn_stats_ok(p, pl, out.C / 32)) {
+    // (only here does a tensor get gn_part, so only tensors of a bf16 handle ever carry one: groupnorm() relies on it)
+    if (o.want_gn && dt == AF_DTYPE_BF16 && out.C % 32 == 0 && out.C == p.N && af_conv_gn_stats_ok(p, pl, out.C / 32)) {
       const int npart = out.H * out.W / 64;
       const size_t bytes = (size_t)out.B * npart * 32 * 2 * sizeof(float);
       float* st = nullptr;
-      if (want_gn == 1) {
+      if (o.want_gn == GN_ARENA) {
         st = reinterpret_cast<float*>(A.alloc(bytes));
         if (!st) { af_set_error_msg("arena exhausted (GroupNorm partial sums)"); return AF_ERR_STATE; }
       } else if (dry) {
@@ -995,11 +1011,11 @@ struct Runner {
       if (!ws) { af_set_error_msg("arena exhausted (split-K slabs)"); return AF_ERR_STATE; }
     }
     if (dry) return 0;
-    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws));
+    return AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, 1, s, &pl, ws));
   }
   int gemm_raw(const ConvGemmParams& p, int batch) {
     if (dry) return 0;
-    return DISPATCH(dt, af_launch_conv_gemm<bf16>(p, batch, s), af_launch_conv_gemm<float>(p, batch, s), af_launch_conv_gemm<f16>(p, batch, s));
+    return AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, batch, s));
   }
   // the record slot of an e4m3 output while af_fp8_record is on
   unsigned* fp8_rec_of(const Act& y) const { return h->fp8_recording && y.f8_site >= 0 ? h->fp8_rec + 2 * y.f8_site : nullptr; }
@@ -1010,18 +1026,15 @@ struct Runner {
     if (!ws) { af_set_error_msg("arena exhausted (groupnorm workspace)"); return AF_ERR_STATE; }
     if (dry) return 0;
     if (x.C != N.C) { af_set_error_msg("groupnorm: C mismatch %d vs %d", x.C, N.C); return AF_ERR_INVALID; }
-    // (statistics already summed by the convolution that produced x: no pass over the tensor for them)
+    // (statistics already summed by the convolution that produced x: no pass over the tensor for them.  On f32 and fp16
+    // handles no tensor carries them -- conv() sets gn_part under dt == AF_DTYPE_BF16 only, and a handle's tensors all come
+    // from its own Runner -- so there `pre` is null and gn_npart 0: the launcher's defaults)
     const float* pre = g_af_knobs.gn_producer ? x.gn_part : nullptr;
     if (y.f8)
       return af_launch_groupnorm<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu, y.p,
                                        (long)HW * y.ld, y.ld, ws, s, ldexpf(1.f, y.f8_shift), pre, x.gn_npart, fp8_rec_of(y));
-    return DISPATCH(dt,
-                    af_launch_groupnorm<bf16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
-                                              y.p, (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart),
-                    af_launch_groupnorm<float>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
-                                               y.p, (long)HW * y.ld, y.ld, ws, s),
-                    af_launch_groupnorm<f16>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu,
-                                              y.p, (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart));
+    return AF_TYPED(dt, af_launch_groupnorm<Elem>(x.p, (long)HW * x.ld, x.ld, x.B, HW, x.C, N.gamma, N.beta, N.eps, silu, y.p,
+                                                  (long)HW * y.ld, y.ld, ws, s, 0.f, pre, x.gn_npart));
   }
   int layernorm(const Norm& N, const Act& x, Act& y) {
     AF_TRY(check(y));
@@ -1029,36 +1042,36 @@ struct Runner {
     if (y.f8)
       return af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s, ldexpf(1.f, y.f8_shift),
                                        fp8_rec_of(y));
-    return DISPATCH(dt, af_launch_layernorm<bf16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s),
-                    af_launch_layernorm<float>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s),
-                    af_launch_layernorm<f16>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s));
+    return AF_TYPED(dt, af_launch_layernorm<Elem>(x.p, x.ld, x.npix(), x.C, N.gamma, N.beta, N.eps, y.p, y.ld, s));
   }
-  // samples [b0, b0 + nb) of the batch (nb < 0: all of o.B); lse: optional [nb][heads][Nq] log-sum-exp output
-  int attention(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, const void* v, int ldv, long bsv,
-                Act& o, int Nq, int Nk, int heads, int dh, int b0 = 0, int nb = -1, float* lse = nullptr, int causal = 0,
-                const void* vt_pack = nullptr, size_t vt_sample_bytes = 0) {
-    AF_TRY(check(o));
-    if (dry) return 0;
-    if (nb < 0) nb = o.B;
+  // the attention of samples [b0, ..) of the batch: the one place that states AttnParams
+  AttnParams attn_params(Strided q, Strided k, Strided v, const Act& o, int Nq, int Nk, int heads, int dh, int b0, float* lse,
+                         int causal, const void* vt_pack, size_t vt_sample_bytes) {
     AttnParams p;
-    p.bsq = bsq; p.bsk = bsk; p.bsv = bsv; p.bso = (long)Nq * o.ld;
-    p.q = elem_ptr(const_cast<void*>(q), b0 * p.bsq); p.k = elem_ptr(const_cast<void*>(k), b0 * p.bsk);
-    p.v = elem_ptr(const_cast<void*>(v), b0 * p.bsv); p.o = elem_ptr(o.p, b0 * p.bso);
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = o.ld;
+    p.bsq = q.bs; p.bsk = k.bs; p.bsv = v.bs; p.bso = (long)Nq * o.ld;
+    p.q = elem_ptr(const_cast<void*>(q.p), b0 * p.bsq); p.k = elem_ptr(const_cast<void*>(k.p), b0 * p.bsk);
+    p.v = elem_ptr(const_cast<void*>(v.p), b0 * p.bsv); p.o = elem_ptr(o.p, b0 * p.bso);
+    p.ldq = q.ld; p.ldk = k.ld; p.ldv = v.ld; p.ldo = o.ld;
     p.Nq = Nq; p.Nk = Nk; p.H = heads;
     p.scale = 1.0f / sqrtf((float)dh);
     p.lse = lse;
     p.causal = causal;
     p.vt_pack = vt_pack ? reinterpret_cast<const char*>(vt_pack) + (size_t)b0 * vt_sample_bytes : nullptr;
-    return DISPATCH(dt, af_launch_attention<bf16>(p, nb, dh, s), af_launch_attention<float>(p, nb, dh, s), af_launch_attention<f16>(p, nb, dh, s));
+    return p;
+  }
+  // samples [b0, b0 + nb) of the batch (nb < 0: all of o.B); lse: optional [nb][heads][Nq] log-sum-exp output
+  int attention(Strided q, Strided k, Strided v, Act& o, int Nq, int Nk, int heads, int dh, int b0 = 0, int nb = -1,
+                float* lse = nullptr, int causal = 0, const void* vt_pack = nullptr, size_t vt_sample_bytes = 0) {
+    AF_TRY(check(o));
+    if (dry) return 0;
+    const AttnParams p = attn_params(q, k, v, o, Nq, Nk, heads, dh, b0, lse, causal, vt_pack, vt_sample_bytes);
+    if (nb < 0) nb = o.B;
+    return AF_TYPED(dt, af_launch_attention<Elem>(p, nb, dh, s));
   }
   int copy_channels(const Act& src, Act& dst, int off) {
     if (dry) return 0;
-    return DISPATCH(dt, af_launch_copy_channels<bf16>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s),
-                    af_launch_copy_channels<float>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s),
-                    af_launch_copy_channels<f16>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s));
+    return AF_TYPED(dt, af_launch_copy_channels<Elem>(src.p, src.ld, dst.p, dst.ld, off, src.C, src.npix(), s));
   }
-  char* elem_ptr(void* p, long off) { return reinterpret_cast<char*>(p) + off * (long)esize(dt); }
 };
 
 // ResBlock._forward (openaimodel.py:259-279) / ResnetBlock.forward (model.py:122-142)
@@ -1070,312 +1083,333 @@ static int run_resblock(Runner& R, const ResBlockW& w, const Act& x, Act& out, c
   AF_TRY(R.groupnorm(w.n1, x, t1, 1));
   const void* rb = (emb_all && w.emb_off >= 0) ? R.elem_ptr(const_cast<void*>(emb_all), w.emb_off) : nullptr;
   // (conv1 also sums the GroupNorm statistics of its output where its kernel can: n2 then makes no pass for them)
-  AF_TRY(R.conv(w.c1, t1, t2, 1, 0, nullptr, rb, emb_ld, -1, -1, nullptr, 1));
+  AF_TRY(R.conv(w.c1, t1, t2, ConvOpt().row_bias(rb, emb_ld).gn_arena()));
   Act t3 = R.fp8_capable(w.c2, t2, out) ? R.alloc_act8(x.B, x.H, x.W, w.cout, w.c2) : R.alloc_act(x.B, x.H, x.W, w.cout);
   AF_TRY(R.groupnorm(w.n2, t2, t3, 1));
   Act sk = x;
   if (w.has_skip) {
     sk = R.alloc_act(x.B, x.H, x.W, w.cout);
-    AF_TRY(R.conv(w.skip, x, sk, 1, 0, nullptr, nullptr, 0));
+    AF_TRY(R.conv(w.skip, x, sk));
   }
   // (... and conv2 those of the block output, for the GroupNorm that opens the next layer -- a transformer or a ResBlock)
-  AF_TRY(R.conv(w.c2, t3, out, 1, 0, &sk, nullptr, 0, -1, -1, nullptr, 2));
+  AF_TRY(R.conv(w.c2, t3, out, ConvOpt().res(&sk).gn_carry()));
   R.A.release(mk);
   return 0;
 }
 
-// SpatialTransformer.forward (attention.py:321-341) incl. BasicTransformerBlock (:275-285)
+// SpatialTransformer.forward (attention.py:321-341) incl. BasicTransformerBlock (:275-285): run_xfmr below, in steps that
+// share this context.
 // twin (classifier-free-guidance batch [x; x], af_unet_forward_twin): x holds the FIRST half of the batch (x.B = B / 2, its
 // buffer has room for B samples).  Everything up to the first cross-attention is independent of the context and therefore
 // identical for the two halves: GroupNorm, proj_in, norm1 + q/k/v, the self-attention and to_out of the first block run on
 // the first half only, and their result (and x, for proj_out's residual) is copied onto the second half.
-static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin = false) {
-  af_handle* h = R.h;
-  const size_t mk = R.A.mark();
-  const int Bh = x.B, B = twin ? 2 * x.B : x.B, H = x.H, W = x.W, N = H * W, C = w.heads * w.dh;
-  auto half = [&](Act a) { if (twin) a.B = Bh; return a; };   // first-half view: the batch is the outermost dimension
-  auto dup = [&](const Act& a) -> int {                        // samples 0 .. Bh-1 onto Bh .. 2 Bh-1
+struct XfmrCtx {
+  Runner& R;
+  const XfmrW& w;
+  const bool twin;
+  const int B, Bh, H, W, N, C;   // B samples, Bh of them behind x (twin: B / 2); N = H * W positions of C = heads * dh channels
+  // LayerNorm folding (bf16): when every GEMM around the three LayerNorms of a block runs on the ping-pong kernel in
+  // one K slice, the producer of each normalised tensor also writes per-row partial sums and the consumer GEMM applies
+  // mu / rstd in its epilogue on W * gamma — the stand-alone LayerNorm passes (read + write of [M, C] each) disappear.
+  int ln_parts = 0;            // statistics slabs per row (0: this transformer does not fold)
+  float* st_part = nullptr;    // partial sums [ln_parts][B * N][2]: one tensor's statistics are live at a time
+  float* st_row = nullptr;     // finalised (mu, rstd) [B * N][2]
+
+  Act half(Act a) const { if (twin) a.B = Bh; return a; }   // first-half view: the batch is the outermost dimension
+  int dup(const Act& a) const {                             // samples 0 .. Bh-1 onto Bh .. 2 Bh-1
     Act src = a, dst = a;
     src.B = dst.B = Bh;
     dst.p = R.elem_ptr(a.p, (long)Bh * a.H * a.W * a.ld);
     return R.copy_channels(src, dst, 0);
-  };
-  Act g = R.alloc_act(B, H, W, x.C);
-  Act t = R.alloc_act(B, H, W, C);
-  // LayerNorm folding (bf16): when every GEMM around the three LayerNorms of a block runs on the ping-pong kernel in
-  // one K slice, the producer of each normalised tensor also writes per-row partial sums and the consumer GEMM applies
-  // mu / rstd in its epilogue on W * gamma — the stand-alone LayerNorm passes (read + write of [M, C] each) disappear.
-  Act f_probe = t;
-  f_probe.C = 4 * C; f_probe.ld = 4 * C;
-  Act qkv_probe = t;
-  qkv_probe.C = 3 * C; qkv_probe.ld = 3 * C;
-  int ln_parts = 0;
-  if (g_af_knobs.ln_fuse && !w.blocks.empty() && w.blocks[0].qkv1_ln.w) {
-    const XfmrBlockW& b0 = w.blocks[0];
-    const int pp = R.ln_capable(w.proj_in, g, t);
-    const bool ok = pp > 0 && R.ln_capable(b0.out1, t, t) == pp && R.ln_capable(b0.out2, t, t) == pp &&
-                    R.ln_capable(b0.ff2, f_probe, t) == pp && R.ln_capable(b0.qkv1_ln, t, qkv_probe) > 0 &&
-                    R.ln_capable(b0.q2_ln, t, t) > 0 && R.ln_capable(b0.ff1_ln, t, f_probe, 8 * C) > 0;
-    if (ok) ln_parts = pp;
-    if (ok && twin) {   // the half-batch launches of the prefix must fold as well
-      const Act gh = half(g), th = half(t), qh = half(qkv_probe);
-      if (R.ln_capable(w.proj_in, gh, th) != pp || R.ln_capable(b0.out1, th, th) != pp || R.ln_capable(b0.qkv1_ln, th, qh) <= 0)
-        ln_parts = 0;
-    }
   }
-  const size_t st_elems = (size_t)ln_parts * B * N * 2;
-  float* st_part = ln_parts ? reinterpret_cast<float*>(R.A.alloc(st_elems * sizeof(float))) : nullptr;       // partial sums
-  float* st_row = ln_parts ? reinterpret_cast<float*>(R.A.alloc((size_t)B * N * 2 * sizeof(float))) : nullptr;  // (mu, rstd)
-  if (ln_parts && !st_row) { af_set_error_msg("arena exhausted (LayerNorm statistics)"); return AF_ERR_STATE; }
-  float *st_t = st_part, *st_1 = st_part, *st_2 = st_part;   // one tensor's statistics are live at a time
-  auto producer = [&](float* st) { Runner::LnArgs a; a.stats_out = st; return a; };
-  // consumer of statistics that conv() finalises (or lets a row-panel kernel finalise) itself ...
-  auto consumer = [&](const float* st, const float* cs, const Norm& ln) {
-    Runner::LnArgs a; a.colsum = cs;
-    a.parts_in = st; a.parts_n = ln_parts; a.count = C; a.eps = ln.eps;
-    a.stats_buf = st_row;
-    return a;
-  };
-  // ... and of statistics already finalised into st_row (the twin block's cross-attention query: finalised for half the rows,
-  // copied for the other half)
-  auto consumer_final = [&](const float* cs) {
-    Runner::LnArgs a; a.colsum = cs;
-    a.stats = st_row;
-    return a;
-  };
+  // options of the GEMM that writes a tensor a LayerNorm follows ...
+  ConvOpt producer() const {
+    ConvOpt o;
+    if (ln_parts) { o.ln.stats_out = st_part; o.has_ln = true; }
+    return o;
+  }
+  // ... of the folded GEMM that reads it, with statistics that conv() finalises (or lets a row-panel kernel finalise) itself ...
+  ConvOpt consumer(const float* colsum, const Norm& ln) const {
+    ConvOpt o;
+    o.ln.colsum = colsum;
+    o.ln.parts_in = st_part; o.ln.parts_n = ln_parts; o.ln.count = C; o.ln.eps = ln.eps;
+    o.ln.stats_buf = st_row;
+    o.has_ln = true;
+    return o;
+  }
+  // ... and with statistics already finalised into st_row
+  ConvOpt consumer_final(const float* colsum) const {
+    ConvOpt o;
+    o.ln.colsum = colsum;
+    o.ln.stats = st_row;
+    o.has_ln = true;
+    return o;
+  }
   // (rows: the statistics of a half-batch producer are laid out for ITS row count)
-  auto finalize = [&](const float* st, const Norm& ln, long rows) { return R.ln_finalize(st, ln_parts, rows, C, ln.eps, st_row); };
-  {
-    // GroupNorm (eps 1e-6, attention.py:71-72,325) + proj_in.  Where proj_in is a row-panel launch (64x64 / 32x32 levels, bf16)
-    // the normalisation happens in its prologue, on the activation rows it keeps in registers: no pass that reads x and writes
-    // the normalised tensor (31 / 22 us per transformer at Bf = 16), same bf16 values
-    Runner::LnArgs pa = producer(ln_parts ? st_t : nullptr);
-    Act th = half(t);
-    Act xin = x;
-    xin.B = Bh;
-    const bool gn_consumer = g_af_knobs.gn_consumer && x.C == w.proj_in.cin_pad && R.rowpanel_capable(w.proj_in, xin, th, &pa, N);
-    if (gn_consumer) {
-      float* ab = reinterpret_cast<float*>(R.A.alloc((size_t)Bh * 2 * x.C * sizeof(float)));
-      AF_TRY(R.groupnorm_fold(w.gn, xin, ab));
-      pa.gn_ab = ab;
-      pa.gn_hw = N;
-      AF_TRY(R.conv(w.proj_in, xin, th, 1, 0, nullptr, nullptr, 0, -1, -1, &pa));
-    } else {
-      Act gh = half(g);
-      AF_TRY(R.groupnorm(w.gn, x, gh, 0));
-      AF_TRY(R.conv(w.proj_in, gh, th, 1, 0, nullptr, nullptr, 0, -1, -1, ln_parts ? &pa : nullptr));
+  int finalize(const Norm& ln, long rows) const { return R.ln_finalize(st_part, ln_parts, rows, C, ln.eps, st_row); }
+  // twin, the producer ran on the first half: finalise its rows, (mu, rstd) serve the second half as well
+  int finalize_twin(const Norm& ln) const {
+    AF_TRY(finalize(ln, (long)Bh * N));
+    if (!R.dry)
+      HIP_CHECK_RET(hipMemcpyAsync(st_row + (size_t)Bh * N * 2, st_row, (size_t)Bh * N * 2 * sizeof(float), hipMemcpyDeviceToDevice, R.s));
+    return 0;
+  }
+};
+
+// the statistics slabs the GEMMs around the LayerNorms agree on, 0 when one of them cannot fold (g, t: GroupNorm output and
+// residual stream of the whole batch)
+static int xfmr_ln_parts(const XfmrCtx& X, const Act& g, const Act& t) {
+  const Runner& R = X.R;
+  const XfmrW& w = X.w;
+  if (!g_af_knobs.ln_fuse || w.blocks.empty() || !w.blocks[0].qkv1_ln.w) return 0;
+  Act f_probe = t;
+  f_probe.C = 4 * X.C; f_probe.ld = 4 * X.C;
+  Act qkv_probe = t;
+  qkv_probe.C = 3 * X.C; qkv_probe.ld = 3 * X.C;
+  const XfmrBlockW& b0 = w.blocks[0];
+  const int pp = R.ln_capable(w.proj_in, g, t);
+  const bool ok = pp > 0 && R.ln_capable(b0.out1, t, t) == pp && R.ln_capable(b0.out2, t, t) == pp &&
+                  R.ln_capable(b0.ff2, f_probe, t) == pp && R.ln_capable(b0.qkv1_ln, t, qkv_probe) > 0 &&
+                  R.ln_capable(b0.q2_ln, t, t) > 0 && R.ln_capable(b0.ff1_ln, t, f_probe, 8 * X.C) > 0;
+  if (!ok) return 0;
+  if (X.twin) {   // the half-batch launches of the prefix must fold as well
+    const Act gh = X.half(g), th = X.half(t), qh = X.half(qkv_probe);
+    if (R.ln_capable(w.proj_in, gh, th) != pp || R.ln_capable(b0.out1, th, th) != pp || R.ln_capable(b0.qkv1_ln, th, qh) <= 0)
+      return 0;
+  }
+  return pp;
+}
+
+// GroupNorm (eps 1e-6, attention.py:71-72,325) + proj_in on the Bh samples behind x.  Where proj_in is a row-panel launch
+// (64x64 / 32x32 levels, bf16) the normalisation happens in its prologue, on the activation rows it keeps in registers: no pass
+// that reads x and writes the normalised tensor (31 / 22 us per transformer at Bf = 16), same bf16 values
+static int xfmr_proj_in(const XfmrCtx& X, const Act& x, const Act& g, const Act& t) {
+  Runner& R = X.R;
+  const XfmrW& w = X.w;
+  ConvOpt o = X.producer();
+  Act th = X.half(t);
+  Act xin = x;
+  xin.B = X.Bh;
+  if (g_af_knobs.gn_consumer && x.C == w.proj_in.cin_pad && R.rowpanel_capable(w.proj_in, xin, th, o, X.N)) {
+    float* ab = reinterpret_cast<float*>(R.A.alloc((size_t)X.Bh * 2 * x.C * sizeof(float)));
+    AF_TRY(R.groupnorm_fold(w.gn, xin, ab));
+    return R.conv(w.proj_in, xin, th, o.gn_map(ab, X.N));
+  }
+  Act gh = X.half(g);
+  AF_TRY(R.groupnorm(w.gn, x, gh, 0));
+  return R.conv(w.proj_in, gh, th, o);
+}
+
+// x = attn1(norm1(x)) + x on the first Bp samples: t -> t1.  Leaves n (scratch of the stand-alone LayerNorms) and a (attention
+// output) allocated for the steps that follow.
+static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, int Bp, const Act& t, Act& n, Act& a, Act& t1) {
+  Runner& R = X.R;
+  const int B = X.B, H = X.H, W = X.W, N = X.N, C = X.C;
+  auto pv = [&](Act v) { v.B = Bp; return v; };
+  n = R.alloc_act(B, H, W, C);
+  Act qkv = R.alloc_act(B, H, W, 3 * C);
+  const Act tp = pv(t);
+  Act np = pv(n), qkvp = pv(qkv);
+  if (R.fp8_capable(blk.qkv1, tp, qkvp)) {
+    // fp8 mode: LayerNorm writes e4m3 and the q / k / v projection multiplies on the block-scaled fp8 MFMA (the
+    // un-folded weights: its producer's row statistics, if any, simply go unused)
+    Act n8 = R.alloc_act8(Bp, H, W, C, blk.qkv1);
+    AF_TRY(R.layernorm(blk.ln1, tp, n8));
+    AF_TRY(R.conv(blk.qkv1, n8, qkvp));
+  } else if (X.ln_parts) {
+    AF_TRY(R.conv(blk.qkv1_ln, tp, qkvp, X.consumer(blk.qkv1_cs, blk.ln1)));
+  } else {
+    AF_TRY(R.layernorm(blk.ln1, tp, np));
+    AF_TRY(R.conv(blk.qkv1, np, qkvp));
+  }
+  a = R.alloc_act(B, H, W, C);
+  Act ap = pv(a);
+  AF_TRY(R.attention(R.cols_of(qkv, 0, N), R.cols_of(qkv, C, N), R.cols_of(qkv, 2 * C, N), ap, N, N, X.w.heads, X.w.dh));
+  t1 = R.alloc_act(B, H, W, C);
+  Act t1p = pv(t1);
+  return R.conv(blk.out1, ap, t1p, X.producer().res(&tp));
+}
+
+// ONE launch for the whole cross-attention layer (af_xattn_fused.hip): LayerNorm-folded to_q, attention over the packed
+// context K / V, to_out + bias + residual and the LayerNorm partial sums for norm3's consumer.  pre: t1's statistics cover
+// the first half of the batch only
+static int xfmr_cross_attention_fused(const XfmrCtx& X, const XfmrBlockW& blk, bool pre, const CtxKV& kv, int S, const Act& t1,
+                                      const Act& t2) {
+  Runner& R = X.R;
+  AF_TRY(R.check(t2));
+  if (pre) AF_TRY(X.finalize_twin(blk.ln2));
+  if (R.dry) return 0;
+  if (!kv.xf_pack) { af_set_error_msg("fused cross-attention: no K / V pack for this layer (af_set_context)"); return AF_ERR_STATE; }
+  AfXattnFusedParams a;
+  memset(&a, 0, sizeof(a));
+  a.x = t1.p; a.ldx = t1.ld; a.M = X.B * X.N; a.rows_per_sample = X.N;
+  if (pre) { a.ln_stats = X.st_row; a.ln_parts_n = 0; }
+  else { a.ln_stats = X.st_part; a.ln_parts_n = X.ln_parts; a.ln_inv_count = 1.0f / (float)X.C; a.ln_eps = blk.ln2.eps; }
+  a.wq = blk.q2_ln.w; a.ldwq = blk.q2_ln.ldw; a.q_colsum = blk.q2_cs; a.q_bias = blk.q2_ln.bias;
+  a.kvpack = kv.xf_pack;
+  a.wo = blk.out2_perm; a.ldwo = blk.out2.ldw; a.o_bias = blk.out2.bias;
+  a.out = t2.p; a.ldo = t2.ld;
+  a.ln_stats_out = X.st_part;
+  a.Nk = S;
+  return af_launch_xattn_fused(a, R.s);
+}
+
+// Cross-attention with subject-token conv attention: q -> a, in runs of consecutive samples that carry the same NUMBER of
+// subject strings (their keys were moved to the end of the key list by af_set_context).  With a subject: the conv map launch
+// + the short-key kernel over ALL S keys with the subject rows replaced in front of its exact softmax
+// (af_launch_conv_attn_short: bf16, dh 40 / 80, <= 96 keys); where that kernel does not exist (f32 handles, dh 160, longer key
+// lists) or knob conv_attn_short = 0: flash attention over the first S - ng ks^2 keys followed by the exact softmax merge with
+// the ks^2 convolutional score columns of every string (af_launch_conv_attn).  Without a subject: plain attention over all S
+// keys, on the short-key kernel where it exists.
+static int xfmr_cross_attention_conv(const XfmrCtx& X, const CtxKV& kv, int S, const Act& q, Act& a) {
+  Runner& R = X.R;
+  af_handle* h = R.h;
+  const int B = X.B, H = X.H, W = X.W, N = X.N, C = X.C, heads = X.w.heads, dh = X.w.dh;
+  const size_t mk = R.A.mark();
+  const int nt = h->conv_ks * h->conv_ks;
+  auto groups = [&](int b) { return (int)std::count(h->conv_batch.begin(), h->conv_batch.end(), b); };
+  int ng_max = 0;
+  for (int b = 0; b < B; ++b) ng_max = std::max(ng_max, groups(b));
+  // one scratch serves either path (the larger of the two, whichever runs: the sizing pass does not depend on the choice):
+  // lse [B][heads][N] + s9 [B][heads][N][nt], or the conv maps [ng][B][heads][N] + their zero word
+  const size_t per = (size_t)B * heads * N * sizeof(float);
+  float* lse = reinterpret_cast<float*>(R.A.alloc(std::max(per * (size_t)(1 + nt),
+                                                           af_conv_attn_map_floats(ng_max, B, heads, N) * sizeof(float))));
+  if (!lse) { af_set_error_msg("arena exhausted (conv attention scratch)"); return AF_ERR_STATE; }
+  float* s9 = lse + (size_t)B * heads * N;
+  float* amap = lse;
+  const Strided qv = R.cols_of(q, 0, N), kk = {kv.kv, 2 * C, (long)S * 2 * C};
+  const Strided vv = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
+  const size_t vt_sample = B > 0 ? kv.vt_bytes / (size_t)B : 0;
+  const bool one_pass_on = g_af_knobs.conv_attn_short != 0 && g_af_knobs.attn_short != 0;
+  for (int b0 = 0, b1; b0 < B; b0 = b1) {
+    const int ng = groups(b0);
+    b1 = b0 + 1;
+    while (b1 < B && groups(b1) == ng) ++b1;
+    const int nb = b1 - b0;
+    if (ng > 0 && one_pass_on && !R.dry && af_conv_attn_short_ok(R.dt == AF_DTYPE_BF16, dh, S, kv.vt != nullptr, h->conv_ks, ng)) {
+      AF_TRY(R.check(a));
+      const AttnParams p = R.attn_params(qv, kk, vv, a, N, S, heads, dh, b0, nullptr, 0, kv.vt, vt_sample);
+      AF_TRY(af_launch_conv_attn_map<bf16>(p.q, p.ldq, p.bsq, p.k, p.ldk, p.bsk, S - ng * nt, ng, amap, nb, heads, dh, H, W,
+                                           h->conv_ks, R.s));
+      AF_TRY(af_launch_conv_attn_short(p, nb, dh, h->conv_ks, ng, H, W, amap, R.s));
+      continue;
+    }
+    // (knob 0: the samples without a subject take the call they took before the one-pass kernel, without the V^T pack)
+    const bool plain_short = ng == 0 && g_af_knobs.conv_attn_short != 0;
+    AF_TRY(R.attention(qv, kk, vv, a, N, S - ng * nt, heads, dh, b0, nb, ng ? lse : nullptr, 0, plain_short ? kv.vt : nullptr,
+                       plain_short ? vt_sample : 0));
+    for (int gi = 0; gi < ng && !R.dry; ++gi) {
+      const float scale = 1.0f / sqrtf((float)dh);
+      const int tok0 = S - (ng - gi) * nt;
+      AF_TRY(AF_TYPED(R.dt, af_launch_conv_attn<Elem>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
+                                                      R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0,
+                                                      s9, lse, R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb,
+                                                      N, heads, dh, H, W, scale, h->conv_ks, R.s)));
     }
   }
+  R.A.release(mk);
+  return 0;
+}
+
+// x = x + attn2(norm2(x), context): t1 -> t2 (block d of the transformer; pre: t1's statistics cover the first half only)
+static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d, bool pre, const Act& t1, Act& n, Act& a,
+                                Act& t2) {
+  Runner& R = X.R;
+  af_handle* h = R.h;
+  const XfmrW& w = X.w;
+  const int B = X.B, N = X.N, C = X.C;
+  const CtxKV& kv = h->ctx_kv[w.ca_slot + d];
+  const int S = h->ctx_tokens;
+  if (!R.dry && (!kv.kv || h->ctx_Bf != B)) {
+    af_set_error_msg("context not set for batch %d (af_set_context)", B);
+    return AF_ERR_STATE;
+  }
+  const int ca_layer = (w.ca_slot + (int)d) / (int)w.blocks.size();
+  // subject-token conv attention: every conditioned layer except CA layers 6-10 (openaimodel.py:922-932)
+  const bool conv_attn = h->conv_ks >= 2 && !h->conv_batch.empty() && !(ca_layer >= 6 && ca_layer <= 10);
+  t2 = R.alloc_act(B, X.H, X.W, C);
+  Act q = R.alloc_act(B, X.H, X.W, C);   // (allocated either way: the arena's sizing pass must not depend on the choice below)
+  // The fused single launch: bf16, C = 320 / 8 heads x 40, <= 80 keys, LayerNorm folded (the 64x64 level).  Decided from the
+  // shape and the weights alone, so that the sizing pass and the run agree; the pack exists whenever the context was set for
+  // such a layer
+  if (g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && X.ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
+      t1.ld == C && t2.ld == C && af_xattn_fused_ok(B * N, N, C, w.heads, w.dh, S > 0 ? S : 77))
+    return xfmr_cross_attention_fused(X, blk, pre, kv, S, t1, t2);
+  if (!X.ln_parts) {
+    AF_TRY(R.layernorm(blk.ln2, t1, n));
+    AF_TRY(R.conv(blk.q2, n, q));
+  } else if (pre) {
+    AF_TRY(X.finalize_twin(blk.ln2));
+    AF_TRY(R.conv(blk.q2_ln, t1, q, X.consumer_final(blk.q2_cs)));
+  } else {
+    AF_TRY(R.conv(blk.q2_ln, t1, q, X.consumer(blk.q2_cs, blk.ln2)));
+  }
+  if (conv_attn) {
+    AF_TRY(xfmr_cross_attention_conv(X, kv, S, q, a));
+  } else {
+    const Strided k = {kv.kv, 2 * C, (long)S * 2 * C}, v = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
+    AF_TRY(R.attention(R.cols_of(q, 0, N), k, v, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt, B > 0 ? kv.vt_bytes / (size_t)B : 0));
+  }
+  return R.conv(blk.out2, a, t2, X.producer().res(&t1));
+}
+
+// x = ff(norm3(x)) + x: t2 -> t, the block output, written over the block input (its last reader was out1's residual).
+// more: another block of this transformer follows and normalises t again
+static int xfmr_feed_forward(const XfmrCtx& X, const XfmrBlockW& blk, bool more, const Act& t2, Act& n, Act& t) {
+  Runner& R = X.R;
+  const int B = X.B, H = X.H, W = X.W, C = X.C;
+  // FeedForward scope of the fp8 mode: LayerNorm writes e4m3, GEGLU multiplies on the fp8 MFMA and writes e4m3 at the scale
+  // of ff.net.2's site, ff.net.2 (residual, bf16 output) runs on the plain fp8 launch.  Both GEMMs or neither; not where a
+  // following block of this transformer expects ff.net.2's LayerNorm partial sums (an fp8 launch does not write them).
+  if (!(X.ln_parts && more) && R.ff8_capable(blk.ff1, blk.ff2, t2, t)) {
+    Act n8 = R.alloc_act8(B, H, W, C, blk.ff1);
+    AF_TRY(R.layernorm(blk.ln3, t2, n8));
+    Act f8 = R.alloc_act8(B, H, W, 4 * C, blk.ff2);
+    AF_TRY(R.ff_geglu8(blk.ff1, n8, f8));
+    return R.conv(blk.ff2, f8, t, ConvOpt().res(&t2));
+  }
+  Act f = R.alloc_act(B, H, W, 4 * C);
+  if (X.ln_parts) {
+    AF_TRY(R.conv(blk.ff1_ln, t2, f, X.consumer(blk.ff1_cs, blk.ln3).cols(8 * C)));
+  } else {
+    AF_TRY(R.layernorm(blk.ln3, t2, n));
+    AF_TRY(R.conv(blk.ff1, n, f, ConvOpt().cols(8 * C)));
+  }
+  return R.conv(blk.ff2, f, t, (more ? X.producer() : ConvOpt()).res(&t2));
+}
+
+static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin = false) {
+  const size_t mk = R.A.mark();
+  XfmrCtx X = {R, w, twin, twin ? 2 * x.B : x.B, x.B, x.H, x.W, x.H * x.W, w.heads * w.dh};
+  Act g = R.alloc_act(X.B, X.H, X.W, x.C);
+  Act t = R.alloc_act(X.B, X.H, X.W, X.C);
+  X.ln_parts = xfmr_ln_parts(X, g, t);
+  if (X.ln_parts) {
+    const size_t rows2 = (size_t)X.B * X.N * 2;
+    X.st_part = reinterpret_cast<float*>(R.A.alloc(X.ln_parts * rows2 * sizeof(float)));
+    X.st_row = reinterpret_cast<float*>(R.A.alloc(rows2 * sizeof(float)));
+    if (!X.st_row) { af_set_error_msg("arena exhausted (LayerNorm statistics)"); return AF_ERR_STATE; }
+  }
+  AF_TRY(xfmr_proj_in(X, x, g, t));
   for (size_t d = 0; d < w.blocks.size(); ++d) {
     const XfmrBlockW& blk = w.blocks[d];
     const size_t mk2 = R.A.mark();
     const bool pre = twin && d == 0;             // this block's self-attention runs on the first half only
-    const int Bp = pre ? Bh : B;
-    auto pv = [&](Act a) { a.B = Bp; return a; };
-    // --- x = attn1(norm1(x)) + x ---
-    Act n = R.alloc_act(B, H, W, C);
-    Act qkv = R.alloc_act(B, H, W, 3 * C);
-    {
-      const Act tp = pv(t);
-      Act np = pv(n), qkvp = pv(qkv);
-      if (R.fp8_capable(blk.qkv1, tp, qkvp)) {
-        // fp8 mode: LayerNorm writes e4m3 and the q / k / v projection multiplies on the block-scaled fp8 MFMA (the
-        // un-folded weights: its producer's row statistics, if any, simply go unused)
-        Act n8 = R.alloc_act8(Bp, H, W, C, blk.qkv1);
-        AF_TRY(R.layernorm(blk.ln1, tp, n8));
-        AF_TRY(R.conv(blk.qkv1, n8, qkvp, 1, 0, nullptr, nullptr, 0));
-      } else if (ln_parts) {
-        const Runner::LnArgs ca = consumer(st_t, blk.qkv1_cs, blk.ln1);
-        AF_TRY(R.conv(blk.qkv1_ln, tp, qkvp, 1, 0, nullptr, nullptr, 0, -1, -1, &ca));
-      } else {
-        AF_TRY(R.layernorm(blk.ln1, tp, np));
-        AF_TRY(R.conv(blk.qkv1, np, qkvp, 1, 0, nullptr, nullptr, 0));
-      }
-    }
-    Act a = R.alloc_act(B, H, W, C);
-    {
-      Act ap = pv(a);
-      AF_TRY(R.attention(qkv.p, 3 * C, (long)N * 3 * C, R.elem_ptr(qkv.p, C), 3 * C, (long)N * 3 * C,
-                         R.elem_ptr(qkv.p, 2 * C), 3 * C, (long)N * 3 * C, ap, N, N, w.heads, w.dh));
-    }
-    Act t1 = R.alloc_act(B, H, W, C);
-    {
-      const Runner::LnArgs pa = producer(st_1);
-      const Act ap = pv(a), tp = pv(t);
-      Act t1p = pv(t1);
-      AF_TRY(R.conv(blk.out1, ap, t1p, 1, 0, &tp, nullptr, 0, -1, -1, ln_parts ? &pa : nullptr));
-    }
+    Act n, a, t1, t2;
+    AF_TRY(xfmr_self_attention(X, blk, pre ? X.Bh : X.B, t, n, a, t1));
     if (pre) {   // from here on the halves differ (cross-attention): second half := first half
       AF_TRY(R.check(t1));
-      AF_TRY(dup(t1));
-      AF_TRY(dup(x));
+      AF_TRY(X.dup(t1));
+      AF_TRY(X.dup(x));
     }
-    // --- x = x + attn2(norm2(x), context) ---
-    const CtxKV& kv = h->ctx_kv[w.ca_slot + d];
-    const int S = h->ctx_tokens;
-    if (!R.dry && (!kv.kv || h->ctx_Bf != B)) {
-      af_set_error_msg("context not set for batch %d (af_set_context)", B);
-      return AF_ERR_STATE;
-    }
-    const int ca_layer = (w.ca_slot + (int)d) / (int)w.blocks.size();
-    // subject-token conv attention: every conditioned layer except CA layers 6-10 (openaimodel.py:922-932)
-    const bool conv_attn = h->conv_ks >= 2 && !h->conv_batch.empty() && !(ca_layer >= 6 && ca_layer <= 10);
-    Act t2 = R.alloc_act(B, H, W, C);
-    Act q = R.alloc_act(B, H, W, C);              // (allocated either way: the arena's sizing pass must not depend on the choice below)
-    // ONE launch for the whole layer (bf16, C = 320 / 8 heads x 40, <= 80 keys, LayerNorm folded: the 64x64 level):
-    // LayerNorm-folded to_q, attention over the packed context K / V, to_out + bias + residual and the LayerNorm partial sums
-    // for norm3's consumer (af_xattn_fused.hip).  Decided from the shape and the weights alone, so that the sizing pass and
-    // the run agree; the pack exists whenever the context was set for such a layer
-    const bool fused_ca = g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
-                          t1.ld == C && t2.ld == C && af_xattn_fused_ok(B * N, N, C, w.heads, w.dh, S > 0 ? S : 77);
-    if (fused_ca) {
-      AF_TRY(R.check(t2));
-      if (pre) AF_TRY(finalize(st_1, blk.ln2, (long)Bh * N));   // the producer ran on the first half: (mu, rstd) serve both halves
-      if (pre && !R.dry)
-        HIP_CHECK_RET(hipMemcpyAsync(st_row + (size_t)Bh * N * 2, st_row, (size_t)Bh * N * 2 * sizeof(float), hipMemcpyDeviceToDevice, R.s));
-      if (!R.dry) {
-        if (!kv.xf_pack) { af_set_error_msg("fused cross-attention: no K / V pack for this layer (af_set_context)"); return AF_ERR_STATE; }
-        AfXattnFusedParams a;
-        memset(&a, 0, sizeof(a));
-        a.x = t1.p; a.ldx = t1.ld; a.M = B * N; a.rows_per_sample = N;
-        if (pre) { a.ln_stats = st_row; a.ln_parts_n = 0; }
-        else { a.ln_stats = st_1; a.ln_parts_n = ln_parts; a.ln_inv_count = 1.0f / (float)C; a.ln_eps = blk.ln2.eps; }
-        a.wq = blk.q2_ln.w; a.ldwq = blk.q2_ln.ldw; a.q_colsum = blk.q2_cs; a.q_bias = blk.q2_ln.bias;
-        a.kvpack = kv.xf_pack;
-        a.wo = blk.out2_perm; a.ldwo = blk.out2.ldw; a.o_bias = blk.out2.bias;
-        a.out = t2.p; a.ldo = t2.ld;
-        a.ln_stats_out = st_2;
-        a.Nk = S;
-        AF_TRY(af_launch_xattn_fused(a, R.s));
-      }
-    } else {
-    if (ln_parts) {
-      Runner::LnArgs ca = consumer(st_1, blk.q2_cs, blk.ln2);
-      if (pre) {   // the producer ran on the first half: finalise its rows, (mu, rstd) serve the second half as well
-        AF_TRY(finalize(st_1, blk.ln2, (long)Bh * N));
-        if (!R.dry)
-          HIP_CHECK_RET(hipMemcpyAsync(st_row + (size_t)Bh * N * 2, st_row, (size_t)Bh * N * 2 * sizeof(float), hipMemcpyDeviceToDevice, R.s));
-        ca = consumer_final(blk.q2_cs);
-      }
-      AF_TRY(R.conv(blk.q2_ln, t1, q, 1, 0, nullptr, nullptr, 0, -1, -1, &ca));
-    } else {
-      AF_TRY(R.layernorm(blk.ln2, t1, n));
-      AF_TRY(R.conv(blk.q2, n, q, 1, 0, nullptr, nullptr, 0));
-    }
-    if (!conv_attn) {
-      AF_TRY(R.attention(q.p, C, (long)N * C, kv.kv, 2 * C, (long)S * 2 * C, R.dry ? nullptr : R.elem_ptr(kv.kv, C),
-                         2 * C, (long)S * 2 * C, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt, B > 0 ? kv.vt_bytes / (size_t)B : 0));
-    } else {
-      // runs of consecutive samples that carry the same NUMBER of subject strings (their keys were moved to the end of the key
-      // list by af_set_context).  With a subject: the conv map launch + the short-key kernel over ALL S keys with the subject
-      // rows replaced in front of its exact softmax (af_launch_conv_attn_short: bf16, dh 40 / 80, <= 96 keys); where that kernel
-      // does not exist (f32 handles, dh 160, longer key lists) or knob conv_attn_short = 0: flash attention over the first
-      // S - ng ks^2 keys followed by the exact softmax merge with the ks^2 convolutional score columns of every string
-      // (af_launch_conv_attn).  Without a subject: plain attention over all S keys, on the short-key kernel where it exists.
-      const size_t mk3 = R.A.mark();
-      const int nt = h->conv_ks * h->conv_ks;
-      auto groups = [&](int b) { return (int)std::count(h->conv_batch.begin(), h->conv_batch.end(), b); };
-      int ng_max = 0;
-      for (int b = 0; b < B; ++b) ng_max = std::max(ng_max, groups(b));
-      // one scratch serves either path (the larger of the two, whichever runs: the sizing pass does not depend on the choice):
-      // lse [B][heads][N] + s9 [B][heads][N][nt], or the conv maps [ng][B][heads][N] + their zero word
-      const size_t per = (size_t)B * w.heads * N * sizeof(float);
-      float* lse = reinterpret_cast<float*>(R.A.alloc(std::max(per * (size_t)(1 + nt),
-                                                               af_conv_attn_map_floats(ng_max, B, w.heads, N) * sizeof(float))));
-      if (!lse) { af_set_error_msg("arena exhausted (conv attention scratch)"); return AF_ERR_STATE; }
-      float* s9 = lse + (size_t)B * w.heads * N;
-      float* amap = lse;
-      void* vptr = R.dry ? nullptr : R.elem_ptr(kv.kv, C);
-      const size_t vt_sample = B > 0 ? kv.vt_bytes / (size_t)B : 0;
-      const bool one_pass_on = g_af_knobs.conv_attn_short != 0 && g_af_knobs.attn_short != 0;
-      int b0 = 0;
-      while (b0 < B) {
-        const int ng = groups(b0);
-        int b1 = b0 + 1;
-        while (b1 < B && groups(b1) == ng) ++b1;
-        const int nb = b1 - b0;
-        if (ng > 0 && one_pass_on && !R.dry && af_conv_attn_short_ok(R.dt == AF_DTYPE_BF16, w.dh, S, kv.vt != nullptr, h->conv_ks, ng)) {
-          AF_TRY(R.check(a));
-          const bf16* qrun = reinterpret_cast<const bf16*>(q.p) + (long)b0 * N * C;
-          const bf16* krun = reinterpret_cast<const bf16*>(kv.kv) + (long)b0 * S * 2 * C;
-          AF_TRY(af_launch_conv_attn_map<bf16>(qrun, C, (long)N * C, krun, 2 * C, (long)S * 2 * C, S - ng * nt, ng, amap, nb,
-                                               w.heads, w.dh, H, W, h->conv_ks, R.s));
-          AttnParams p;
-          p.q = qrun; p.k = krun; p.v = krun + C; p.o = R.elem_ptr(a.p, (long)b0 * N * a.ld);
-          p.ldq = C; p.ldk = 2 * C; p.ldv = 2 * C; p.ldo = a.ld;
-          p.bsq = (long)N * C; p.bsk = (long)S * 2 * C; p.bsv = (long)S * 2 * C; p.bso = (long)N * a.ld;
-          p.Nq = N; p.Nk = S; p.H = w.heads;
-          p.scale = 1.0f / sqrtf((float)w.dh);
-          p.lse = nullptr; p.causal = 0;
-          p.vt_pack = reinterpret_cast<const char*>(kv.vt) + (size_t)b0 * vt_sample;
-          AF_TRY(af_launch_conv_attn_short(p, nb, w.dh, h->conv_ks, ng, H, W, amap, R.s));
-          b0 = b1;
-          continue;
-        }
-        // (knob 0: the samples without a subject take the call they took before the one-pass kernel, without the V^T pack)
-        const bool plain_short = ng == 0 && g_af_knobs.conv_attn_short != 0;
-        AF_TRY(R.attention(q.p, C, (long)N * C, kv.kv, 2 * C, (long)S * 2 * C, vptr, 2 * C, (long)S * 2 * C, a, N,
-                           S - ng * nt, w.heads, w.dh, b0, nb, ng ? lse : nullptr, 0, plain_short ? kv.vt : nullptr,
-                           plain_short ? vt_sample : 0));
-        for (int gi = 0; gi < ng && !R.dry; ++gi) {
-          const float scale = 1.0f / sqrtf((float)w.dh);
-          const int tok0 = S - (ng - gi) * nt;
-          AF_TRY(DISPATCH(R.dt,
-                          af_launch_conv_attn<bf16>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
-                                                    R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0, s9, lse,
-                                                    R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb, N, w.heads,
-                                                    w.dh, H, W, scale, h->conv_ks, R.s),
-                          af_launch_conv_attn<float>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
-                                                     R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0, s9, lse,
-                                                     R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb, N, w.heads,
-                                                     w.dh, H, W, scale, h->conv_ks, R.s),
-                          af_launch_conv_attn<f16>(R.elem_ptr(q.p, (long)b0 * N * C), C, (long)N * C,
-                                                    R.elem_ptr(kv.kv, (long)b0 * S * 2 * C), 2 * C, (long)S * 2 * C, tok0, s9, lse,
-                                                    R.elem_ptr(a.p, (long)b0 * N * a.ld), a.ld, (long)N * a.ld, nb, N, w.heads,
-                                                    w.dh, H, W, scale, h->conv_ks, R.s)));
-        }
-        b0 = b1;
-      }
-      R.A.release(mk3);
-    }
-    {
-      const Runner::LnArgs pa = producer(st_2);
-      AF_TRY(R.conv(blk.out2, a, t2, 1, 0, &t1, nullptr, 0, -1, -1, ln_parts ? &pa : nullptr));
-    }
-    }
-    // --- x = ff(norm3(x)) + x ---
-    // FeedForward scope of the fp8 mode: LayerNorm writes e4m3, GEGLU multiplies on the fp8 MFMA and writes e4m3 at the scale
-    // of ff.net.2's site, ff.net.2 (residual, bf16 output) runs on the plain fp8 launch.  Both GEMMs or neither; not where a
-    // following block of this transformer expects ff.net.2's LayerNorm partial sums (an fp8 launch does not write them).
-    if (!(ln_parts && d + 1 < w.blocks.size()) && R.ff8_capable(blk.ff1, blk.ff2, t2, t)) {
-      Act n8 = R.alloc_act8(B, H, W, C, blk.ff1);
-      AF_TRY(R.layernorm(blk.ln3, t2, n8));
-      Act f8 = R.alloc_act8(B, H, W, 4 * C, blk.ff2);
-      AF_TRY(R.ff_geglu8(blk.ff1, n8, f8));
-      AF_TRY(R.conv(blk.ff2, f8, t, 1, 0, &t2, nullptr, 0));
-      R.A.release(mk2);
-      continue;
-    }
-    Act f = R.alloc_act(B, H, W, 4 * C);
-    if (ln_parts) {
-      const Runner::LnArgs ca = consumer(st_2, blk.ff1_cs, blk.ln3);
-      AF_TRY(R.conv(blk.ff1_ln, t2, f, 1, 0, nullptr, nullptr, 0, 8 * C, -1, &ca));
-    } else {
-      AF_TRY(R.layernorm(blk.ln3, t2, n));
-      AF_TRY(R.conv(blk.ff1, n, f, 1, 0, nullptr, nullptr, 0, 8 * C));
-    }
-    // write the block output over `t` (its last reader was out1's residual); a following block normalises it again
-    {
-      const Runner::LnArgs pa = producer(st_t);
-      AF_TRY(R.conv(blk.ff2, f, t, 1, 0, &t2, nullptr, 0, -1, -1, (ln_parts && d + 1 < w.blocks.size()) ? &pa : nullptr));
-    }
+    AF_TRY(xfmr_cross_attention(X, blk, d, pre, t1, n, a, t2));
+    AF_TRY(xfmr_feed_forward(X, blk, d + 1 < w.blocks.size(), t2, n, t));
     R.A.release(mk2);
   }
-  {
-    Act xf = x;
-    xf.B = B;
-    AF_TRY(R.conv(w.proj_out, t, out, 1, 0, &xf, nullptr, 0));
-  }
+  Act xf = x;
+  xf.B = X.B;
+  AF_TRY(R.conv(w.proj_out, t, out, ConvOpt().res(&xf)));
   R.A.release(mk);
   return 0;
 }
@@ -1521,6 +1555,17 @@ static int ensure_arena(af_handle* h, size_t need) {
   return 0;
 }
 
+// Size the arena (and the GroupNorm carry buffer) for the forward `run` enqueues: a dry pass of it measures, then the
+// buffers grow if they must.  The caller runs it for real afterwards.
+template <typename F> static int run_sized(af_handle* h, hipStream_t s, F&& run) {
+  h->arena.dry = true; h->arena.peak = 0;
+  const int rc = run();
+  h->arena.dry = false;
+  if (rc) return rc;
+  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
+  return ensure_gn_carry(h, s);
+}
+
 // UNetModel.forward (openaimodel.py:827-1052)
 // twin: x_dev / t_dev hold Bf / 2 samples and the batch is [x; x], [t; t] -- classifier-free guidance as p_sample_ddim
 // builds it (ddim.py:236-247: torch.cat([x] * 2), cond first).  The time embedding, conv_in, the first ResBlock and the
@@ -1558,23 +1603,19 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   Act emb_all = R.alloc_act(Bf, 1, 1, h->emb_total);
   AF_TRY(R.check(emb_all));
   if (!R.dry) {
-    AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<f16>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s)));
-    AF_TRY(DISPATCH(dt, af_launch_timestep_embedding<bf16>((const long long*)t_dev, temb.p, Bin, mc, s),
-                    af_launch_timestep_embedding<float>((const long long*)t_dev, temb.p, Bin, mc, s),
-                    af_launch_timestep_embedding<f16>((const long long*)t_dev, temb.p, Bin, mc, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(x_dev, x.p, Bin, c.in_channels, H * W, x.ld, 1.0f, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_timestep_embedding<Elem>((const long long*)t_dev, temb.p, Bin, mc, s)));
   }
   if (twin && !twin_prefix) AF_TRY(dup_half(x));   // other block structures: the whole network on [x; x]
   {
     // (twin: the embeddings of the Bin distinct timesteps, then copied)
     Act tb = temb, e1b = e1, e2b = e2, eab = emb_all;
     tb.B = e1b.B = e2b.B = eab.B = Bin;
-    AF_TRY(R.conv(h->time_embed0, tb, e1b, 1, 0, nullptr, nullptr, 0));
-    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e1.p, e1.p, (long)Bin * ted, s), af_launch_silu<float>(e1.p, e1.p, (long)Bin * ted, s), af_launch_silu<f16>(e1.p, e1.p, (long)Bin * ted, s)));
-    AF_TRY(R.conv(h->time_embed2, e1b, e2b, 1, 0, nullptr, nullptr, 0));
-    if (!R.dry) AF_TRY(DISPATCH(dt, af_launch_silu<bf16>(e2.p, e2.p, (long)Bin * ted, s), af_launch_silu<float>(e2.p, e2.p, (long)Bin * ted, s), af_launch_silu<f16>(e2.p, e2.p, (long)Bin * ted, s)));
-    AF_TRY(R.conv(h->emb_all, e2b, eab, 1, 0, nullptr, nullptr, 0));
+    AF_TRY(R.conv(h->time_embed0, tb, e1b));
+    if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(e1.p, e1.p, (long)Bin * ted, s)));
+    AF_TRY(R.conv(h->time_embed2, e1b, e2b));
+    if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(e2.p, e2.p, (long)Bin * ted, s)));
+    AF_TRY(R.conv(h->emb_all, e2b, eab));
     if (twin) AF_TRY(dup_half(emb_all));
   }
 
@@ -1603,7 +1644,7 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
           out = new_act(hcur.H, hcur.W, mc);
           Act xin = hcur;
           xin.C = h->conv_in.cin;  // logical channels; ld carries the padding
-          AF_TRY(R.conv(h->conv_in, xin, out, 1, 0, nullptr, nullptr, 0));
+          AF_TRY(R.conv(h->conv_in, xin, out));
         } break;
         case L_RES: {
           const ResBlockW& w = h->res[l.idx];
@@ -1622,11 +1663,11 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
         } break;
         case L_DOWN: {
           out = new_act(hcur.H / 2, hcur.W / 2, hcur.C);
-          AF_TRY(R.conv(h->updown[l.idx], hcur, out, 2, 0, nullptr, nullptr, 0));
+          AF_TRY(R.conv(h->updown[l.idx], hcur, out, ConvOpt().strided(2)));
         } break;
         case L_UP: {
           out = new_act(hcur.H * 2, hcur.W * 2, hcur.C);
-          AF_TRY(R.conv(h->updown[l.idx], hcur, out, 1, 1, nullptr, nullptr, 0));
+          AF_TRY(R.conv(h->updown[l.idx], hcur, out, ConvOpt().upsampled()));
         } break;
       }
       hcur = out;
@@ -1686,9 +1727,7 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   // block outputs in forward order: input_blocks 0..n_in-1, middle_block = n_in, output_blocks = n_in + 1 + j
   auto tap = [&](int idx, const Act& a) -> int {
     if (R.dry || idx != h->tap_index || !h->tap_out) return 0;
-    return DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s),
-                    af_launch_nhwc_to_nchw<float>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s),
-                    af_launch_nhwc_to_nchw<f16>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
+    return AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
   };
   Act hcur = x;
   for (int i = 0; i < (dc_reuse ? dc_depth : n_in); ++i) {
@@ -1734,11 +1773,9 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   AF_TRY(R.groupnorm(h->out_norm, hcur, g, 1));
   const int oc4 = round_up(c.out_channels, 4);
   Act e = R.alloc_act(Bf, hcur.H, hcur.W, c.out_channels, oc4);
-  AF_TRY(R.conv(h->out_conv, g, e, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->out_conv, g, e));
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s),
-                    af_launch_nhwc_to_nchw<float>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s),
-                    af_launch_nhwc_to_nchw<f16>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s)));
   return 0;
 }
 
@@ -1753,7 +1790,7 @@ static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
   Act g = R.alloc_act(B, x.H, x.W, C);
   AF_TRY(R.groupnorm(w.gn, x, g, 0));
   Act qkv = R.alloc_act(B, x.H, x.W, 3 * C);
-  AF_TRY(R.conv(w.qkv, g, qkv, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(w.qkv, g, qkv));
   Act sc = R.alloc_act(B, N, 1, N);       // scores [B][N][N]
   Act vt = R.alloc_act(B, C, 1, N);       // v^T   [B][C][N]
   Act hh = R.alloc_act(B, x.H, x.W, C);
@@ -1769,12 +1806,9 @@ static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
     p.out = sc.p; p.ldo = N; p.alpha = 1.0f / sqrtf((float)C);
     p.bs_src = (long)N * 3 * C; p.bs_w = (long)N * 3 * C; p.bs_out = (long)N * N;
     AF_TRY(R.gemm_raw(p, B));
-    AF_TRY(DISPATCH(dt, af_launch_softmax_rows<bf16>(sc.p, N, N, (long)B * N, R.s),
-                    af_launch_softmax_rows<float>(sc.p, N, N, (long)B * N, R.s),
-                    af_launch_softmax_rows<f16>(sc.p, N, N, (long)B * N, R.s)));
-    AF_TRY(DISPATCH(dt, af_launch_transpose<bf16>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s),
-                    af_launch_transpose<float>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s),
-                    af_launch_transpose<f16>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B, R.s)));
+    AF_TRY(AF_TYPED(dt, af_launch_softmax_rows<Elem>(sc.p, N, N, (long)B * N, R.s)));
+    AF_TRY(AF_TYPED(dt, af_launch_transpose<Elem>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B,
+                                                  R.s)));
     // h[b][i][c] = sum_j P[b][i][j] v[b][j][c]
     memset(&p, 0, sizeof(p));
     p.src = sc.p; p.src_batch_stride = 0; p.ldc = N; p.Cin = N;
@@ -1785,7 +1819,7 @@ static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
     p.bs_src = (long)N * N; p.bs_w = (long)C * N; p.bs_out = (long)N * C;
     AF_TRY(R.gemm_raw(p, B));
   }
-  AF_TRY(R.conv(w.proj_out, hh, out, 1, 0, &x, nullptr, 0));
+  AF_TRY(R.conv(w.proj_out, hh, out, ConvOpt().res(&x)));
   R.A.release(mk);
   return 0;
 }
@@ -1801,14 +1835,12 @@ static int vae_decode_impl(af_handle* h, hipStream_t s, const float* z_dev, floa
   Act z2 = R.alloc_act(B, H, W, c.vae_z_channels, h->vae_conv_in.cin_pad);
   AF_TRY(R.check(z2));
   if (!R.dry) {
-    AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s),
-                    af_launch_nchw_to_nhwc<float>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s),
-                    af_launch_nchw_to_nhwc<f16>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(z_dev, z.p, B, c.vae_embed_dim, H * W, z.ld, 1.0f / scale_factor, s)));
     HIP_CHECK_RET(hipMemsetAsync(z2.p, 0, (size_t)z2.npix() * z2.ld * esize(dt), s));
   }
-  AF_TRY(R.conv(h->post_quant, z, z2, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->post_quant, z, z2));
   Act hcur = R.alloc_act(B, H, W, h->vae_conv_in.cout);
-  AF_TRY(R.conv(h->vae_conv_in, z2, hcur, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->vae_conv_in, z2, hcur));
   auto res = [&](int ri) -> int {
     const ResBlockW& w = h->vres[ri];
     Act out = R.alloc_act(B, hcur.H, hcur.W, w.cout);
@@ -1829,7 +1861,7 @@ static int vae_decode_impl(af_handle* h, hipStream_t s, const float* z_dev, floa
     for (int ri : h->vlevels[lvl].blocks) AF_TRY(res(ri));
     if (h->vlevels[lvl].up >= 0) {
       Act out = R.alloc_act(B, hcur.H * 2, hcur.W * 2, hcur.C);
-      AF_TRY(R.conv(h->vup[h->vlevels[lvl].up], hcur, out, 1, 1, nullptr, nullptr, 0));
+      AF_TRY(R.conv(h->vup[h->vlevels[lvl].up], hcur, out, ConvOpt().upsampled()));
       hcur = out;
     }
   }
@@ -1837,17 +1869,13 @@ static int vae_decode_impl(af_handle* h, hipStream_t s, const float* z_dev, floa
   AF_TRY(R.groupnorm(h->vae_norm_out, hcur, g, 1));
   const int oc4 = round_up(c.vae_out_ch, 4);
   Act img = R.alloc_act(B, hcur.H, hcur.W, c.vae_out_ch, oc4);
-  AF_TRY(R.conv(h->vae_conv_out, g, img, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->vae_conv_out, g, img));
   if (!R.dry) {
     if (img_dev)
-      AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s),
-                      af_launch_nhwc_to_nchw<float>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s),
-                      af_launch_nhwc_to_nchw<f16>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s)));
+      AF_TRY(AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(img.p, img_dev, B, c.vae_out_ch, img.H * img.W, img.ld, s)));
     if (u8_dev) {
       if (c.vae_out_ch != 3) { af_set_error_msg("uint8 output needs out_ch == 3"); return AF_ERR_INVALID; }
-      AF_TRY(DISPATCH(dt, af_launch_to_uint8<bf16>(img.p, img.ld, u8_dev, img.npix(), s),
-                      af_launch_to_uint8<float>(img.p, img.ld, u8_dev, img.npix(), s),
-                      af_launch_to_uint8<f16>(img.p, img.ld, u8_dev, img.npix(), s)));
+      AF_TRY(AF_TYPED(dt, af_launch_to_uint8<Elem>(img.p, img.ld, u8_dev, img.npix(), s)));
     }
   }
   return 0;
@@ -1862,11 +1890,9 @@ static int vae_encode_impl(af_handle* h, hipStream_t s, const float* x_dev, floa
   Act x = R.alloc_act(B, H, W, c.vae_in_channels, h->enc_conv_in.cin_pad);
   AF_TRY(R.check(x));
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_nchw_to_nhwc<bf16>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<float>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s),
-                    af_launch_nchw_to_nhwc<f16>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(x_dev, x.p, B, c.vae_in_channels, H * W, x.ld, 1.0f, s)));
   Act hcur = R.alloc_act(B, H, W, h->enc_conv_in.cout);
-  AF_TRY(R.conv(h->enc_conv_in, x, hcur, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->enc_conv_in, x, hcur));
   auto res = [&](int ri) -> int {
     const ResBlockW& w = h->vres[ri];
     Act out = R.alloc_act(B, hcur.H, hcur.W, w.cout);
@@ -1878,7 +1904,7 @@ static int vae_encode_impl(af_handle* h, hipStream_t s, const float* x_dev, floa
     for (int ri : h->elevels[lvl].blocks) AF_TRY(res(ri));
     if (h->elevels[lvl].up >= 0) {
       Act out = R.alloc_act(B, hcur.H / 2, hcur.W / 2, hcur.C);
-      AF_TRY(R.conv(h->edown[h->elevels[lvl].up], hcur, out, 2, 0, nullptr, nullptr, 0, -1, /*pad=*/0));
+      AF_TRY(R.conv(h->edown[h->elevels[lvl].up], hcur, out, ConvOpt().strided(2).padded(0)));
       hcur = out;
     }
   }
@@ -1894,14 +1920,12 @@ static int vae_encode_impl(af_handle* h, hipStream_t s, const float* x_dev, floa
   Act m1 = R.alloc_act(B, hcur.H, hcur.W, 2 * c.vae_z_channels, h->quant_conv.cin_pad);
   AF_TRY(R.check(m1));
   if (!R.dry) HIP_CHECK_RET(hipMemsetAsync(m1.p, 0, (size_t)m1.npix() * m1.ld * esize(dt), s));
-  AF_TRY(R.conv(h->enc_conv_out, g, m1, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->enc_conv_out, g, m1));
   const int oc = 2 * c.vae_embed_dim;
   Act m2 = R.alloc_act(B, hcur.H, hcur.W, oc, round_up(oc, 4));
-  AF_TRY(R.conv(h->quant_conv, m1, m2, 1, 0, nullptr, nullptr, 0));
+  AF_TRY(R.conv(h->quant_conv, m1, m2));
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_nhwc_to_nchw<bf16>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s),
-                    af_launch_nhwc_to_nchw<float>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s),
-                    af_launch_nhwc_to_nchw<f16>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(m2.p, moments_dev, B, oc, m2.H * m2.W, m2.ld, s)));
   return 0;
 }
 
@@ -1926,9 +1950,7 @@ static int clip_forward_impl(af_handle* h, hipStream_t s, const float* emb_dev, 
   AF_TRY(R.check(f));
   const long rows = (long)Bn * T;
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_add_pos_cast<bf16>(emb_dev, h->clip_pos, T, D, x.p, rows, s),
-                    af_launch_add_pos_cast<float>(emb_dev, h->clip_pos, T, D, x.p, rows, s),
-                    af_launch_add_pos_cast<f16>(emb_dev, h->clip_pos, T, D, x.p, rows, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_add_pos_cast<Elem>(emb_dev, h->clip_pos, T, D, x.p, rows, s)));
   const int L = (int)h->clip_layers.size();
   for (int i = 0; i < L; ++i) {
     const ClipLayerW& w = h->clip_layers[i];
@@ -1937,29 +1959,25 @@ static int clip_forward_impl(af_handle* h, hipStream_t s, const float* emb_dev, 
     if (i == L - 2 && w_prev2 != 0.f && !R.dry)   // encoder_states[-3]
       HIP_CHECK_RET(hipMemcpyAsync(xprev2.p, x.p, (size_t)rows * D * esize(dt), hipMemcpyDeviceToDevice, s));
     AF_TRY(R.layernorm(w.ln1, x, n));
-    AF_TRY(R.conv(w.qkv, n, qkv, 1, 0, nullptr, nullptr, 0));
-    AF_TRY(R.attention(qkv.p, 3 * D, (long)T * 3 * D, R.elem_ptr(qkv.p, D), 3 * D, (long)T * 3 * D, R.elem_ptr(qkv.p, 2 * D),
-                       3 * D, (long)T * 3 * D, a, T, T, H, dh, 0, -1, nullptr, /*causal=*/1));
-    AF_TRY(R.conv(w.out, a, x1, 1, 0, &x, nullptr, 0));
+    AF_TRY(R.conv(w.qkv, n, qkv));
+    AF_TRY(R.attention(R.cols_of(qkv, 0, T), R.cols_of(qkv, D, T), R.cols_of(qkv, 2 * D, T), a, T, T, H, dh, 0, -1, nullptr,
+                       /*causal=*/1));
+    AF_TRY(R.conv(w.out, a, x1, ConvOpt().res(&x)));
     AF_TRY(R.layernorm(w.ln2, x1, n));
-    AF_TRY(R.conv(w.fc1, n, f, 1, 0, nullptr, nullptr, 0));
+    AF_TRY(R.conv(w.fc1, n, f));
     if (!R.dry)
-      AF_TRY(DISPATCH(dt, af_launch_quick_gelu<bf16>(f.p, f.p, rows * F, s), af_launch_quick_gelu<float>(f.p, f.p, rows * F, s), af_launch_quick_gelu<f16>(f.p, f.p, rows * F, s)));
-    AF_TRY(R.conv(w.fc2, f, x, 1, 0, &x1, nullptr, 0));
+      AF_TRY(AF_TYPED(dt, af_launch_quick_gelu<Elem>(f.p, f.p, rows * F, s)));
+    AF_TRY(R.conv(w.fc2, f, x, ConvOpt().res(&x1)));
   }
   if (!R.dry) {
     if (L >= 1)
-      AF_TRY(DISPATCH(dt, af_launch_blend2<bf16>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s),
-                      af_launch_blend2<float>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s),
-                      af_launch_blend2<f16>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s)));
+      AF_TRY(AF_TYPED(dt, af_launch_blend2<Elem>(xprev.p, w_prev, x.p, w_last, n.p, rows * D, s)));
     if (L >= 2 && w_prev2 != 0.f)
-      AF_TRY(DISPATCH(dt, af_launch_blend2<bf16>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s),
-                      af_launch_blend2<float>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s),
-                      af_launch_blend2<f16>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s)));
+      AF_TRY(AF_TYPED(dt, af_launch_blend2<Elem>(xprev2.p, w_prev2, n.p, 1.f, n.p, rows * D, s)));
   }
   AF_TRY(R.layernorm(h->clip_final_ln, L >= 1 ? n : x, a));
   if (!R.dry)
-    AF_TRY(DISPATCH(dt, af_launch_cast_to_f32<bf16>(a.p, out_dev, rows * D, s), af_launch_cast_to_f32<float>(a.p, out_dev, rows * D, s), af_launch_cast_to_f32<f16>(a.p, out_dev, rows * D, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_cast_to_f32<Elem>(a.p, out_dev, rows * D, s)));
   return 0;
 }
 
@@ -2089,12 +2107,10 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
     srcp = h->stage;
   }
   if (s.kind == Slot::TABLE) {
-    AF_TRY(DISPATCH(h->dtype, af_launch_cast_f32<bf16>(srcp, s.dst, (long)n, 0), af_launch_cast_f32<float>(srcp, s.dst, (long)n, 0), af_launch_cast_f32<f16>(srcp, s.dst, (long)n, 0)));
+    AF_TRY(AF_TYPED(h->dtype, af_launch_cast_f32<Elem>(srcp, s.dst, (long)n, 0)));
   } else if (s.kind == Slot::WEIGHT) {
-    AF_TRY(DISPATCH(h->dtype,
-                    af_launch_repack_weight<bf16>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0),
-                    af_launch_repack_weight<float>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0),
-                    af_launch_repack_weight<f16>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm, 0)));
+    AF_TRY(AF_TYPED(h->dtype, af_launch_repack_weight<Elem>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off,
+                                                            s.perm, 0)));
   } else {
     AF_TRY(af_launch_permute_bias(srcp, s.dst_f, s.rows, s.perm, 0));
   }
@@ -2220,11 +2236,9 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
     }
     HIP_CHECK_RET(hipMemcpyAsync(h->ctx_rowmap, map.data(), rows * sizeof(int), hipMemcpyHostToDevice, s));
     HIP_CHECK_RET(hipStreamSynchronize(s));   // `map` is a pageable host temporary
-    AF_TRY(DISPATCH(dt, af_launch_gather_rows_cast<bf16>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s),
-                    af_launch_gather_rows_cast<float>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s),
-                    af_launch_gather_rows_cast<f16>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_gather_rows_cast<Elem>(ctx_dev, h->ctx_rowmap, h->ctx_cast, (long)rows, D, s)));
   } else {
-    AF_TRY(DISPATCH(dt, af_launch_cast_f32<bf16>(ctx_dev, h->ctx_cast, (long)n, s), af_launch_cast_f32<float>(ctx_dev, h->ctx_cast, (long)n, s), af_launch_cast_f32<f16>(ctx_dev, h->ctx_cast, (long)n, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_cast_f32<Elem>(ctx_dev, h->ctx_cast, (long)n, s)));
   }
   for (size_t i = 0; i < h->ca_list.size(); ++i) {
     const XfmrW& x = h->xf[h->ca_list[i].first];
@@ -2243,7 +2257,7 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
     p.W = blk.kv2.w; p.ldw = blk.kv2.ldw; p.Wrows = blk.kv2.rows_pad;
     p.M = Bf * n_tokens; p.N = 2 * C; p.K = D;
     p.out = h->ctx_kv[i].kv; p.ldo = 2 * C; p.alpha = 1.0f;
-    AF_TRY(DISPATCH(dt, af_launch_conv_gemm<bf16>(p, 1, s), af_launch_conv_gemm<float>(p, 1, s), af_launch_conv_gemm<f16>(p, 1, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, 1, s)));
     if (h->ctx_kv[i].xf_pack)   // K and V of this layer as the operand fragments of xattn_fused_kernel
       AF_TRY(af_launch_xattn_fused_pack(h->ctx_kv[i].kv, 2 * C, (long)n_tokens * 2 * C, n_tokens, Bf,
                                         h->ctx_kv[i].xf_pack, s));
@@ -2306,13 +2320,8 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   AF_TRY(fold_layernorms(h, s));
   AF_TRY(ensure_fp8_twins(h, s));
   AF_TRY(ensure_up4_twins(h, s));
-  // size the arena with a dry run
-  h->arena.dry = true; h->arena.peak = 0;
-  int rc = unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth);
-  h->arena.dry = false;
-  if (rc) return rc;
-  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
-  AF_TRY(ensure_gn_carry(h, s));
+  auto run = [&] { return unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth); };
+  AF_TRY(run_sized(h, s, run));
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = false;                       // (until this refresh has been enqueued completely)
     AF_TRY(ensure_deepcache(h, s));
@@ -2320,8 +2329,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     af_set_error_msg("af_unet_forward_cached: the kept feature does not fit this forward");   // (cannot happen for a valid entry)
     return AF_ERR_STATE;
   }
-  rc = unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth);
-  if (rc) { if (dc_mode) dc.valid = false; return rc; }
+  if (const int rc = run()) { if (dc_mode) dc.valid = false; return rc; }
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = true;
     dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = (int)twin; dc.depth = dc_depth;
@@ -2393,10 +2401,8 @@ int af_clip_embed_tokens(af_handle* h, const int64_t* ids_dev, int64_t n, float*
   HIP_CHECK_RET(hipSetDevice(h->device));
   AF_TRY(check_loaded(h, "cond_stage_model.transformer.text_model.embeddings.token_embedding."));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  return DISPATCH(h->dtype,
-                  af_launch_embed_rows<bf16>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s),
-                  af_launch_embed_rows<float>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s),
-                  af_launch_embed_rows<f16>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab, h->cfg.clip_hidden, emb_dev, (long)n, s));
+  return AF_TYPED(h->dtype, af_launch_embed_rows<Elem>((const long long*)ids_dev, h->clip_tok, h->cfg.clip_vocab,
+                                                       h->cfg.clip_hidden, emb_dev, (long)n, s));
 }
 
 int af_clip_text_forward(af_handle* h, const float* inputs_embeds_dev, int Bn, int T, float w_prev, float w_last,
@@ -2407,13 +2413,9 @@ int af_clip_text_forward(af_handle* h, const float* inputs_embeds_dev, int Bn, i
   HIP_CHECK_RET(hipSetDevice(h->device));
   AF_TRY(check_loaded(h, "cond_stage_model.transformer.text_model."));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  h->arena.dry = true; h->arena.peak = 0;
-  int rc = clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev);
-  h->arena.dry = false;
-  if (rc) return rc;
-  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
-  AF_TRY(ensure_gn_carry(h, s));
-  return clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev);
+  auto run = [&] { return clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev); };
+  AF_TRY(run_sized(h, s, run));
+  return run();
 }
 
 int af_clip_text_forward3(af_handle* h, const float* inputs_embeds_dev, int Bn, int T, float w_prev2, float w_prev, float w_last,
@@ -2425,13 +2427,9 @@ int af_clip_text_forward3(af_handle* h, const float* inputs_embeds_dev, int Bn, 
   HIP_CHECK_RET(hipSetDevice(h->device));
   AF_TRY(check_loaded(h, "cond_stage_model.transformer.text_model."));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  h->arena.dry = true; h->arena.peak = 0;
-  int rc = clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev, w_prev2);
-  h->arena.dry = false;
-  if (rc) return rc;
-  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
-  AF_TRY(ensure_gn_carry(h, s));
-  return clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev, w_prev2);
+  auto run = [&] { return clip_forward_impl(h, s, inputs_embeds_dev, Bn, T, w_prev, w_last, out_dev, w_prev2); };
+  AF_TRY(run_sized(h, s, run));
+  return run();
 }
 
 int af_ddim_step(const float* x_dev, const float* eps_cond_dev, const float* eps_uncond_dev, const float* noise_dev,
@@ -2509,13 +2507,9 @@ int af_vae_decode(af_handle* h, const float* z_dev, float scale_factor, float* i
   AF_TRY(check_loaded(h, "first_stage_model.post_quant_conv."));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   AF_TRY(ensure_up4_twins(h, s));
-  h->arena.dry = true; h->arena.peak = 0;
-  int rc = vae_decode_impl(h, s, z_dev, scale_factor, img_dev, u8_dev, B, H, W);
-  h->arena.dry = false;
-  if (rc) return rc;
-  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
-  AF_TRY(ensure_gn_carry(h, s));
-  return vae_decode_impl(h, s, z_dev, scale_factor, img_dev, u8_dev, B, H, W);
+  auto run = [&] { return vae_decode_impl(h, s, z_dev, scale_factor, img_dev, u8_dev, B, H, W); };
+  AF_TRY(run_sized(h, s, run));
+  return run();
 }
 
 int af_vae_encode(af_handle* h, const float* x_dev, float* moments_dev, int B, int H, int W, void* stream) {
@@ -2527,13 +2521,9 @@ int af_vae_encode(af_handle* h, const float* x_dev, float* moments_dev, int B, i
   AF_TRY(check_loaded(h, "first_stage_model.encoder."));
   AF_TRY(check_loaded(h, "first_stage_model.quant_conv."));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  h->arena.dry = true; h->arena.peak = 0;
-  int rc = vae_encode_impl(h, s, x_dev, moments_dev, B, H, W);
-  h->arena.dry = false;
-  if (rc) return rc;
-  if (h->arena.peak > h->arena.cap) { HIP_CHECK_RET(hipStreamSynchronize(s)); AF_TRY(ensure_arena(h, h->arena.peak)); }
-  AF_TRY(ensure_gn_carry(h, s));
-  return vae_encode_impl(h, s, x_dev, moments_dev, B, H, W);
+  auto run = [&] { return vae_encode_impl(h, s, x_dev, moments_dev, B, H, W); };
+  AF_TRY(run_sized(h, s, run));
+  return run();
 }
 
 int af_posterior_sample(const float* moments_dev, const float* noise_dev, float scale, float* z_dev, int B, int C,

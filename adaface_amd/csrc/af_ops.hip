@@ -4,7 +4,7 @@
 // kernels the UNet / VAE executors use, and convert back.  Temporary buffers are
 // hipMalloc'd per call (test path only, never on the hot path).
 #include "../../include/adaface_hip.h"
-#include "af_kernels.h"
+#include "af_host.h"
 
 #include <algorithm>
 #include <cstring>
@@ -25,10 +25,6 @@ struct Tmp {
     for (void* p : bufs) hipFree(p);
   }
 };
-inline size_t esz(int dtype) { return dtype == AF_DTYPE_F32 ? 4 : 2; }
-inline int bk(int dtype) { return dtype == AF_DTYPE_F32 ? 32 : 64; }
-inline AfStorage storage_of(int dtype) { return dtype == AF_DTYPE_BF16 ? AF_ST_BF16 : dtype == AF_DTYPE_F16 ? AF_ST_F16 : AF_ST_F32; }
-inline int rup(int a, int b) { return (a + b - 1) / b * b; }
 }  // namespace
 
 // columns [c0, ld) of every row of a [rows][ld] buffer of T become v (slack columns of a wide-row test buffer; c0 = 0: the whole buffer)
@@ -49,20 +45,13 @@ template <typename T> static int fill_cols(void* y, long rows, int ld, int c0, f
   return 0;
 }
 static int fill_cols_dt(int dtype, void* y, long rows, int ld, int c0, float v, hipStream_t s) {
-  return dtype == AF_DTYPE_BF16 ? fill_cols<bf16>(y, rows, ld, c0, v, s) : dtype == AF_DTYPE_F16 ? fill_cols<f16>(y, rows, ld, c0, v, s)
-                                                                                                 : fill_cols<float>(y, rows, ld, c0, v, s);
+  return AF_TYPED(dtype, fill_cols<Elem>(y, rows, ld, c0, v, s));
 }
 // what af_op_conv2d_ex / af_op_linear_ex put into the output buffer before the launch (exact in bf16 / fp16, above any result of
 // the tests) and into the slack columns of the operands
 static const float OP_SENTINEL = 49152.f;   // 3 * 2^14
 static const float OP_NAN = __builtin_nanf("");
 
-#define OP_TRY(expr)          \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-#define DISP(dtype, A, B, C) ((dtype) == AF_DTYPE_BF16 ? (A) : (dtype) == AF_DTYPE_F16 ? (C) : (B))
 #define OP_ALLOC(var, bytes, zero)                               \
   void* var = tmp.get((bytes), (zero));                          \
   if (!var) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
@@ -151,7 +140,7 @@ int af_clock_probe(void* stream, int iters, double* mfma_mhz, double* mfma_tflop
 // padding (pad 0: 3x3, stride 2, even maps; pad -1: ks / 2) and row pitches wider than the channel count (ld_slack elements,
 // a multiple of 8, added to ldc / ldo / ldr / ldrb).  The slack of the source, the residual and the bias row holds NaN, the
 // whole output buffer the sentinel before the launch.  ld_slack > 0: y_dev receives the whole rows, float [B * Ho * Wo][ldo]
-// with ldo = rup(Cout, 4) + ld_slack; otherwise NCHW as af_op_conv2d.
+// with ldo = round_up(Cout, 4) + ld_slack; otherwise NCHW as af_op_conv2d.
 int af_op_conv2d_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
                     const float* rowbias_dev, float alpha, float* y_dev, int B, int Cin, int H, int W, int Cout, int ks, int stride,
                     int pad, int upsample, int ld_slack, void* stream) {
@@ -164,48 +153,40 @@ int af_op_conv2d_ex(int dtype, const float* x_dev, const float* w_dev, const flo
   if (ld_slack < 0 || ld_slack % 8 != 0) { af_set_error_msg("af_op_conv2d_ex: ld_slack must be a non-negative multiple of 8"); return AF_ERR_INVALID; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  const int cin_pad = rup(Cin, bk(dtype));
+  const int cin_pad = round_up(Cin, bk_of(dtype));
   const int Hi = H << upsample, Wi = W << upsample;
   // (pad 0: one row / column of zeros below and to the right, as the model's (H + 1 - 3) / 2 + 1)
   const int Ho = br_pad ? (Hi + 1 - ks) / stride + 1 : (Hi + 2 * pad - ks) / stride + 1;
   const int Wo = br_pad ? (Wi + 1 - ks) / stride + 1 : (Wi + 2 * pad - ks) / stride + 1;
-  const int co4 = rup(Cout, 4), rows_pad = rup(Cout, 128), ldw = ks * ks * cin_pad;
+  const int co4 = round_up(Cout, 4), rows_pad = round_up(Cout, 128), ldw = ks * ks * cin_pad;
   const int ldc = cin_pad + ld_slack, ldo = co4 + ld_slack;
   const long M = (long)B * Ho * Wo;
-  OP_ALLOC(xn, (size_t)B * H * W * ldc * esz(dtype), false);
-  OP_ALLOC(wn, (size_t)rows_pad * ldw * esz(dtype), true);
-  OP_ALLOC(yn, (size_t)M * ldo * esz(dtype), false);
+  OP_ALLOC(xn, (size_t)B * H * W * ldc * esize(dtype), false);
+  OP_ALLOC(wn, (size_t)rows_pad * ldw * esize(dtype), true);
+  OP_ALLOC(yn, (size_t)M * ldo * esize(dtype), false);
   void* rn = nullptr;
   void* rbn = nullptr;
   float* bn = nullptr;
-  OP_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
-  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s),
-              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s)));
-  OP_TRY(fill_cols_dt(dtype, xn, (long)B * H * W, ldc, cin_pad, OP_NAN, s));
-  OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
-              af_launch_repack_weight<float>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s),
-              af_launch_repack_weight<f16>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s)));
+  AF_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
+  AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(x_dev, xn, B, Cin, H * W, ldc, 1.f, s)));
+  AF_TRY(fill_cols_dt(dtype, xn, (long)B * H * W, ldc, cin_pad, OP_NAN, s));
+  AF_TRY(AF_TYPED(dtype, af_launch_repack_weight<Elem>(w_dev, wn, Cout, Cin, cin_pad, ks, ldw, 0, 0, s)));
   if (bias_dev) {
-    bn = reinterpret_cast<float*>(tmp.get((size_t)rup(Cout, 128) * 4, true));
+    bn = reinterpret_cast<float*>(tmp.get((size_t)round_up(Cout, 128) * 4, true));
     if (!bn) return AF_ERR_HIP;
     if (hipMemcpyAsync(bn, bias_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   }
   if (residual_dev) {
-    rn = tmp.get((size_t)M * ldo * esz(dtype), false);
+    rn = tmp.get((size_t)M * ldo * esize(dtype), false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s)));
-    OP_TRY(fill_cols_dt(dtype, rn, M, ldo, co4, OP_NAN, s));
+    AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(residual_dev, rn, B, Cout, Ho * Wo, ldo, 1.f, s)));
+    AF_TRY(fill_cols_dt(dtype, rn, M, ldo, co4, OP_NAN, s));
   }
   if (rowbias_dev) {   // [B][Cout] rows = NCHW with one pixel per sample
-    rbn = tmp.get((size_t)B * ldo * esz(dtype), false);
+    rbn = tmp.get((size_t)B * ldo * esize(dtype), false);
     if (!rbn) return AF_ERR_HIP;
-    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<f16>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s)));
-    OP_TRY(fill_cols_dt(dtype, rbn, B, ldo, co4, OP_NAN, s));
+    AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(rowbias_dev, rbn, B, Cout, 1, ldo, 1.f, s)));
+    AF_TRY(fill_cols_dt(dtype, rbn, B, ldo, co4, OP_NAN, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -220,21 +201,18 @@ int af_op_conv2d_ex(int dtype, const float* x_dev, const float* w_dev, const flo
   if (upsample && ks == 3 && dtype == AF_DTYPE_BF16 && cin_pad % 64 == 0) {
     // as the model does for its Upsample layers: phase weights next to the 3x3 ones, the launcher decides (AF_CONV_UP_PHASE4)
     OP_ALLOC(w4, (size_t)4 * rows_pad * 4 * cin_pad * 2, false);
-    OP_TRY(af_launch_up_phase4_weights(wn, rows_pad, cin_pad, ldw, w4, s));
+    AF_TRY(af_launch_up_phase4_weights(wn, rows_pad, cin_pad, ldw, w4, s));
     p.W_up4 = w4;
   }
   const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype));
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
+  AF_TRY(AF_TYPED(dtype, af_launch_conv_gemm<Elem>(p, 1, s, &pl, ws)));
   if (ld_slack > 0) {
-    OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, M * ldo, s), af_launch_cast_to_f32<float>(yn, y_dev, M * ldo, s),
-                af_launch_cast_to_f32<f16>(yn, y_dev, M * ldo, s)));
+    AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, M * ldo, s)));
     return 0;
   }
-  OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, Cout, Ho * Wo, co4, s),
-              af_launch_nhwc_to_nchw<f16>(yn, y_dev, B, Cout, Ho * Wo, co4, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nhwc_to_nchw<Elem>(yn, y_dev, B, Cout, Ho * Wo, co4, s)));
   return 0;
 }
 int af_op_conv2d(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
@@ -260,7 +238,7 @@ int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, 
   p.src = d; p.src_batch_stride = (long)Hs * Ws * ldc; p.ldc = ldc; p.Cin = cin_pad;
   p.Hs = Hs; p.Ws = Ws; p.up = up; p.Hi = Hs << up; p.Wi = Ws << up; p.Ho = Ho; p.Wo = Wo;
   p.ks = ks; p.stride = stride; p.pad = pad;
-  p.W = d; p.ldw = K; p.Wrows = rup(N, 128);
+  p.W = d; p.ldw = K; p.Wrows = round_up(N, 128);
   p.M = (int)M; p.N = N; p.K = K; p.k_logical = K;
   p.out = d; p.ldo = ldo; p.alpha = 1.f;
   if (flags & AF_PQ_GEGLU) p.epilogue = AF_EPI_GEGLU;
@@ -298,7 +276,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   Tmp tmp;
   const int Hi = H << upsample, Wi = W << upsample;
   const int Ho = (Hi + 2 * pad - ks) / stride + 1, Wo = (Wi + 2 * pad - ks) / stride + 1;
-  const int co4 = rup(Cout, 4), rows_pad = rup(Cout, 128), ldw = ks * ks * Cin, k8 = rup(ldw, 128);
+  const int co4 = round_up(Cout, 4), rows_pad = round_up(Cout, 128), ldw = ks * ks * Cin, k8 = round_up(ldw, 128);
   const size_t nx = (size_t)B * H * W * Cin;
   OP_ALLOC(xn, nx * 2, false);
   OP_ALLOC(x8, nx, false);
@@ -308,10 +286,10 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   unsigned char* sc = reinterpret_cast<unsigned char*>(w8) + (size_t)rows_pad * k8;
   void* rn = nullptr;
   float* bn = nullptr;
-  OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, Cin, 1.f, s));
-  OP_TRY(af_launch_cast_fp8(xn, x8, (long)nx, ldexpf(1.f, act_shift), s));
-  OP_TRY(af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, Cin, ks, ldw, 0, 0, s));
-  OP_TRY(af_launch_quant_weight_fp8(wn, rows_pad, ldw, Cin, ks, w8, k8, sc, s));
+  AF_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, H * W, Cin, 1.f, s));
+  AF_TRY(af_launch_cast_fp8(xn, x8, (long)nx, ldexpf(1.f, act_shift), s));
+  AF_TRY(af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, Cin, ks, ldw, 0, 0, s));
+  AF_TRY(af_launch_quant_weight_fp8(wn, rows_pad, ldw, Cin, ks, w8, k8, sc, s));
   if (bias_dev) {
     bn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad * 4, true));
     if (!bn) return AF_ERR_HIP;
@@ -320,7 +298,7 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   if (residual_dev) {
     rn = tmp.get((size_t)B * Ho * Wo * co4 * 2, false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s));
+    AF_TRY(af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, Ho * Wo, co4, 1.f, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -336,8 +314,8 @@ int af_op_conv2d_fp8(const float* x_dev, const float* w_dev, const float* bias_d
   if (pl.kernel != AF_GK_PP_FP8) { af_set_error_msg("af_op_conv2d_fp8: no fp8 plan for M=%d N=%d K=%d", p.M, p.N, p.K); return AF_ERR_INVALID; }
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws));
-  OP_TRY(af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, Ho * Wo, co4, s));
+  AF_TRY(af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws));
+  AF_TRY(af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, Ho * Wo, co4, s));
   return 0;
 }
 
@@ -352,8 +330,8 @@ static int op_groupnorm_fp8(const float* x_dev, const float* gamma_dev, const fl
   OP_ALLOC(xn, (size_t)B * HW * C * 2, false);
   OP_ALLOC(ws, af_gn_workspace_bytes(B, HW), false);
   if (rec_out_dev && hipMemsetAsync(rec_out_dev, 0, 2 * sizeof(unsigned), s) != hipSuccess) return AF_ERR_HIP;
-  OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s));
-  OP_TRY(af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, y8_dev, (long)HW * C, C, ws, s,
+  AF_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s));
+  AF_TRY(af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, y8_dev, (long)HW * C, C, ws, s,
                                    ldexpf(1.f, act_shift), nullptr, 0, rec_out_dev));
   return 0;
 }
@@ -375,8 +353,8 @@ static int op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const fl
   Tmp tmp;
   OP_ALLOC(xn, (size_t)rows * C * 2, false);
   if (rec_out_dev && hipMemsetAsync(rec_out_dev, 0, 2 * sizeof(unsigned), s) != hipSuccess) return AF_ERR_HIP;
-  OP_TRY(af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s));
-  OP_TRY(af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, y8_dev, C, s, ldexpf(1.f, act_shift), rec_out_dev));
+  AF_TRY(af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s));
+  AF_TRY(af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, y8_dev, C, s, ldexpf(1.f, act_shift), rec_out_dev));
   return 0;
 }
 int af_op_layernorm_fp8(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, unsigned char* y8_dev,
@@ -404,7 +382,7 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int Mi = (int)M;
-  const int rows1 = rup(2 * F, 128), k1 = rup(C, 128), rows2 = rup(Cout, 160), k2 = rup(F, 128);
+  const int rows1 = round_up(2 * F, 128), k1 = round_up(C, 128), rows2 = round_up(Cout, 160), k2 = round_up(F, 128);
   OP_ALLOC(n8, (size_t)M * C, false);
   OP_ALLOC(f8, (size_t)M * F, true);
   OP_ALLOC(w1n, (size_t)rows1 * C * 2, true);
@@ -422,20 +400,20 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
     if (hipMemcpyAsync(n8, x8_dev, (size_t)M * C, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   } else {
     OP_ALLOC(xn, (size_t)M * C * 2, false);
-    OP_TRY(af_launch_cast_f32<bf16>(x_dev, xn, M * C, s));
-    OP_TRY(af_launch_layernorm<bf16>(xn, C, M, C, gamma_dev, beta_dev, eps, n8, C, s, ldexpf(1.f, shift1), nullptr));
+    AF_TRY(af_launch_cast_f32<bf16>(x_dev, xn, M * C, s));
+    AF_TRY(af_launch_layernorm<bf16>(xn, C, M, C, gamma_dev, beta_dev, eps, n8, C, s, ldexpf(1.f, shift1), nullptr));
   }
-  OP_TRY(af_launch_repack_weight<bf16>(w1_dev, w1n, 2 * F, C, C, 1, C, 0, 1, s));
-  OP_TRY(af_launch_quant_weight_fp8(w1n, rows1, C, C, 1, w18, k1, sc1, s));
-  OP_TRY(af_launch_repack_weight<bf16>(w2_dev, w2n, Cout, F, F, 1, F, 0, 0, s));
-  OP_TRY(af_launch_quant_weight_fp8(w2n, rows2, F, F, 1, w28, k2, sc2, s));
-  if (b1_dev) OP_TRY(af_launch_permute_bias(b1_dev, reinterpret_cast<float*>(b1n), 2 * F, 1, s));
+  AF_TRY(af_launch_repack_weight<bf16>(w1_dev, w1n, 2 * F, C, C, 1, C, 0, 1, s));
+  AF_TRY(af_launch_quant_weight_fp8(w1n, rows1, C, C, 1, w18, k1, sc1, s));
+  AF_TRY(af_launch_repack_weight<bf16>(w2_dev, w2n, Cout, F, F, 1, F, 0, 0, s));
+  AF_TRY(af_launch_quant_weight_fp8(w2n, rows2, F, F, 1, w28, k2, sc2, s));
+  if (b1_dev) AF_TRY(af_launch_permute_bias(b1_dev, reinterpret_cast<float*>(b1n), 2 * F, 1, s));
   if (b2_dev && hipMemcpyAsync(b2n, b2_dev, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   void* rn = nullptr;
   if (residual_dev) {
     rn = tmp.get((size_t)M * Cout * 2, false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(af_launch_cast_f32<bf16>(residual_dev, rn, M * Cout, s));
+    AF_TRY(af_launch_cast_f32<bf16>(residual_dev, rn, M * Cout, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -449,7 +427,7 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   p.epilogue = AF_EPI_GEGLU;
   p.fp8 = 1; p.w_scale = sc1; p.x_scale_e8 = 127 - shift1;
   if (!af_ff_geglu_fp8_ok(p)) { af_set_error_msg("af_op_ff_fp8: no e4m3 GEGLU launch for M=%d C=%d F=%d", Mi, C, F); return AF_ERR_INVALID; }
-  OP_TRY(af_launch_ff_geglu_fp8(p, ldexpf(1.f, shift2), rec, s));
+  AF_TRY(af_launch_ff_geglu_fp8(p, ldexpf(1.f, shift2), rec, s));
   if (mid8_dev && hipMemcpyAsync(mid8_dev, f8, (size_t)M * F, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   ConvGemmParams q;
   memset(&q, 0, sizeof(q));
@@ -466,50 +444,44 @@ int af_op_ff_fp8(const float* x_dev, const unsigned char* x8_dev, const float* g
   if (plan_out) { plan_out[0] = pl.tile; plan_out[1] = pl.splitk; }
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, ws));
-  OP_TRY(af_launch_cast_to_f32<bf16>(yn, y_dev, M * Cout, s));
+  AF_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, ws));
+  AF_TRY(af_launch_cast_to_f32<bf16>(yn, y_dev, M * Cout, s));
   return 0;
 }
 
 // af_op_linear with alpha on the accumulator and row pitches wider than K / N (ld_slack elements, a multiple of 8, added to
 // ldc / ldo / ldr; NaN in the slack of the source and the residual, the sentinel in the whole output buffer before the launch).
-// ld_slack > 0: y_dev receives the whole rows, float [M][rup(N, 4) + ld_slack].
+// ld_slack > 0: y_dev receives the whole rows, float [M][round_up(N, 4) + ld_slack].
 int af_op_linear_ex(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev, float alpha,
                     float* y_dev, int64_t M, int K, int N, int geglu, int ld_slack, void* stream) {
   if (ld_slack < 0 || ld_slack % 8 != 0) { af_set_error_msg("af_op_linear_ex: ld_slack must be a non-negative multiple of 8"); return AF_ERR_INVALID; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  const int kp = rup(K, bk(dtype));
+  const int kp = round_up(K, bk_of(dtype));
   const int rows = geglu ? 2 * N : N;  // weight rows
-  const int rows_pad = rup(rows, 128);
-  const int no4 = rup(N, 4);
+  const int rows_pad = round_up(rows, 128);
+  const int no4 = round_up(N, 4);
   const int ldc = kp + ld_slack, ldo = no4 + ld_slack;
-  OP_ALLOC(xn, (size_t)M * ldc * esz(dtype), false);
-  OP_ALLOC(wn, (size_t)rows_pad * kp * esz(dtype), true);
-  OP_ALLOC(yn, (size_t)M * ldo * esz(dtype), false);
+  OP_ALLOC(xn, (size_t)M * ldc * esize(dtype), false);
+  OP_ALLOC(wn, (size_t)rows_pad * kp * esize(dtype), true);
+  OP_ALLOC(yn, (size_t)M * ldo * esize(dtype), false);
   float* bn = nullptr;
   void* rn = nullptr;
-  OP_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(dtype, yn, M, ldo, 0, OP_SENTINEL, s));
   // [M,K] rows == NCHW with C=K, HW=1 per "sample": reuse the NCHW converter with B=M, HW=1
-  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s),
-              af_launch_nchw_to_nhwc<f16>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s)));
-  OP_TRY(fill_cols_dt(dtype, xn, M, ldc, kp, OP_NAN, s));
-  OP_TRY(DISP(dtype, af_launch_repack_weight<bf16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
-              af_launch_repack_weight<float>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s),
-              af_launch_repack_weight<f16>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(x_dev, xn, (int)M, K, 1, ldc, 1.f, s)));
+  AF_TRY(fill_cols_dt(dtype, xn, M, ldc, kp, OP_NAN, s));
+  AF_TRY(AF_TYPED(dtype, af_launch_repack_weight<Elem>(w_dev, wn, rows, K, kp, 1, kp, 0, geglu ? 1 : 0, s)));
   if (bias_dev) {
     bn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad * 4, true));
     if (!bn) return AF_ERR_HIP;
-    OP_TRY(af_launch_permute_bias(bias_dev, bn, rows, geglu ? 1 : 0, s));
+    AF_TRY(af_launch_permute_bias(bias_dev, bn, rows, geglu ? 1 : 0, s));
   }
   if (residual_dev) {
-    rn = tmp.get((size_t)M * ldo * esz(dtype), false);
+    rn = tmp.get((size_t)M * ldo * esize(dtype), false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<float>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s),
-                af_launch_nchw_to_nhwc<f16>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s)));
-    OP_TRY(fill_cols_dt(dtype, rn, M, ldo, no4, OP_NAN, s));
+    AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(residual_dev, rn, (int)M, N, 1, ldo, 1.f, s)));
+    AF_TRY(fill_cols_dt(dtype, rn, M, ldo, no4, OP_NAN, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -525,15 +497,12 @@ int af_op_linear_ex(int dtype, const float* x_dev, const float* w_dev, const flo
   const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dtype));
   void* ws = nullptr;
   if (pl.splitk > 1) { ws = tmp.get(pl.ws_bytes, false); if (!ws) return AF_ERR_HIP; }
-  OP_TRY(DISP(dtype, af_launch_conv_gemm<bf16>(p, 1, s, &pl, ws), af_launch_conv_gemm<float>(p, 1, s, &pl, ws), af_launch_conv_gemm<f16>(p, 1, s, &pl, ws)));
+  AF_TRY(AF_TYPED(dtype, af_launch_conv_gemm<Elem>(p, 1, s, &pl, ws)));
   if (ld_slack > 0) {
-    OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, M * ldo, s), af_launch_cast_to_f32<float>(yn, y_dev, M * ldo, s),
-                af_launch_cast_to_f32<f16>(yn, y_dev, M * ldo, s)));
+    AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, M * ldo, s)));
     return 0;
   }
-  OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, (int)M, N, 1, no4, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, (int)M, N, 1, no4, s),
-              af_launch_nhwc_to_nchw<f16>(yn, y_dev, (int)M, N, 1, no4, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nhwc_to_nchw<Elem>(yn, y_dev, (int)M, N, 1, no4, s)));
   return 0;
 }
 int af_op_linear(int dtype, const float* x_dev, const float* w_dev, const float* bias_dev, const float* residual_dev,
@@ -549,7 +518,7 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
                      void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  const int HW = H * W, rows_pad = rup(N, 128);
+  const int HW = H * W, rows_pad = round_up(N, 128);
   if (C % 64 || N % 4) { af_set_error_msg("af_op_gn_conv1x1: C %% 64 and N %% 4"); return AF_ERR_INVALID; }
   OP_ALLOC(xn, (size_t)B * HW * C * 2, false);
   OP_ALLOC(gn, (size_t)B * HW * C * 2, false);
@@ -564,8 +533,8 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
     if (!bn) return AF_ERR_HIP;
     if (hipMemcpyAsync(bn, bias_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return AF_ERR_HIP;
   }
-  OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s));
-  OP_TRY(af_launch_repack_weight<bf16>(w_dev, wn, N, C, C, 1, C, 0, 0, s));
+  AF_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s));
+  AF_TRY(af_launch_repack_weight<bf16>(w_dev, wn, N, C, C, 1, C, 0, 0, s));
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
   p.src_batch_stride = (long)HW * C; p.ldc = C; p.Cin = C;
@@ -575,27 +544,27 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
   p.M = B * HW; p.N = N; p.K = C; p.k_logical = C;
   p.bias = bn; p.ldo = N; p.alpha = 1.f;
   // plain: GroupNorm apply pass, then the GEMM as the planner places it
-  OP_TRY(af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, 0, gn, (long)HW * C, C, ws, s));
+  AF_TRY(af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, 0, gn, (long)HW * C, C, ws, s));
   {
     ConvGemmParams q = p;
     q.src = gn; q.out = y0;
     const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
     void* wsk = nullptr;
     if (pl.splitk > 1) { wsk = tmp.get(pl.ws_bytes, false); if (!wsk) return AF_ERR_HIP; }
-    OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, wsk));
+    AF_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, wsk));
   }
   // fused: statistics + fold, the GEMM reads the un-normalised rows
-  OP_TRY(af_launch_groupnorm_fold<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, ws, s, nullptr, 0, (float*)ab));
+  AF_TRY(af_launch_groupnorm_fold<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, ws, s, nullptr, 0, (float*)ab));
   {
     ConvGemmParams q = p;
     q.src = xn; q.out = y1;
     q.gn_ab = (const float*)ab; q.gn_hw = HW;
     const AfGemmPlan pl = af_plan_conv_gemm(q, 1, AF_ST_BF16);
     if (pl.kernel != AF_GK_ROWPANEL) { af_set_error_msg("af_op_gn_conv1x1: M=%d K=%d N=%d has no row-panel launch", q.M, q.K, q.N); return AF_ERR_INVALID; }
-    OP_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, nullptr));
+    AF_TRY(af_launch_conv_gemm<bf16>(q, 1, s, &pl, nullptr));
   }
-  OP_TRY(af_launch_nhwc_to_nchw<bf16>(y0, y_plain_dev, B, N, HW, N, s));
-  OP_TRY(af_launch_nhwc_to_nchw<bf16>(y1, y_fused_dev, B, N, HW, N, s));
+  AF_TRY(af_launch_nhwc_to_nchw<bf16>(y0, y_plain_dev, B, N, HW, N, s));
+  AF_TRY(af_launch_nhwc_to_nchw<bf16>(y1, y_fused_dev, B, N, HW, N, s));
   return 0;
 }
 
@@ -604,19 +573,13 @@ int af_op_groupnorm(int dtype, const float* x_dev, const float* gamma_dev, const
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int HW = H * W;
-  OP_ALLOC(xn, (size_t)B * HW * C * esz(dtype), false);
-  OP_ALLOC(yn, (size_t)B * HW * C * esz(dtype), false);
+  OP_ALLOC(xn, (size_t)B * HW * C * esize(dtype), false);
+  OP_ALLOC(yn, (size_t)B * HW * C * esize(dtype), false);
   OP_ALLOC(ws, af_gn_workspace_bytes(B, HW), false);
-  OP_TRY(DISP(dtype, af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, C, HW, C, 1.f, s),
-              af_launch_nchw_to_nhwc<float>(x_dev, xn, B, C, HW, C, 1.f, s),
-              af_launch_nchw_to_nhwc<f16>(x_dev, xn, B, C, HW, C, 1.f, s)));
-  OP_TRY(DISP(dtype,
-              af_launch_groupnorm<bf16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s),
-              af_launch_groupnorm<float>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s),
-              af_launch_groupnorm<f16>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn, (long)HW * C, C, ws, s)));
-  OP_TRY(DISP(dtype, af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, C, HW, C, s),
-              af_launch_nhwc_to_nchw<float>(yn, y_dev, B, C, HW, C, s),
-              af_launch_nhwc_to_nchw<f16>(yn, y_dev, B, C, HW, C, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(x_dev, xn, B, C, HW, C, 1.f, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_groupnorm<Elem>(xn, (long)HW * C, C, B, HW, C, gamma_dev, beta_dev, eps, silu, yn,
+                                                   (long)HW * C, C, ws, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nhwc_to_nchw<Elem>(yn, y_dev, B, C, HW, C, s)));
   return 0;
 }
 
@@ -629,7 +592,7 @@ int af_op_conv_gn(const float* x_dev, const float* w_dev, const float* bias_dev,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   if (Cin % 64 != 0 || Cout % 32 != 0) { af_set_error_msg("af_op_conv_gn: Cin%%64==0 and Cout%%32==0"); return AF_ERR_INVALID; }
-  const int HW = H * W, rows_pad = rup(Cout, 128), ldw = 9 * Cin;
+  const int HW = H * W, rows_pad = round_up(Cout, 128), ldw = 9 * Cin;
   OP_ALLOC(xn, (size_t)B * HW * Cin * 2, false);
   OP_ALLOC(wn, (size_t)rows_pad * ldw * 2, true);
   OP_ALLOC(hn, (size_t)B * HW * Cout * 2, true);
@@ -638,8 +601,8 @@ int af_op_conv_gn(const float* x_dev, const float* w_dev, const float* bias_dev,
   OP_ALLOC(st, (size_t)B * (HW / 64 + 1) * 32 * 2 * sizeof(float), true);
   void* rn = nullptr;
   float* bn = nullptr;
-  OP_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, HW, Cin, 1.f, s));
-  OP_TRY(af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, Cin, 3, ldw, 0, 0, s));
+  AF_TRY(af_launch_nchw_to_nhwc<bf16>(x_dev, xn, B, Cin, HW, Cin, 1.f, s));
+  AF_TRY(af_launch_repack_weight<bf16>(w_dev, wn, Cout, Cin, Cin, 3, ldw, 0, 0, s));
   if (bias_dev) {
     bn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad * 4, true));
     if (!bn) return AF_ERR_HIP;
@@ -648,7 +611,7 @@ int af_op_conv_gn(const float* x_dev, const float* w_dev, const float* bias_dev,
   if (residual_dev) {
     rn = tmp.get((size_t)B * HW * Cout * 2, false);
     if (!rn) return AF_ERR_HIP;
-    OP_TRY(af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, HW, Cout, 1.f, s));
+    AF_TRY(af_launch_nchw_to_nhwc<bf16>(residual_dev, rn, B, Cout, HW, Cout, 1.f, s));
   }
   ConvGemmParams p;
   memset(&p, 0, sizeof(p));
@@ -666,11 +629,11 @@ int af_op_conv_gn(const float* x_dev, const float* w_dev, const float* bias_dev,
   }
   p.gn_stats_out = reinterpret_cast<float*>(st);
   p.gn_cpg = Cout / 32;
-  OP_TRY(af_launch_conv_gemm<bf16>(p, 1, s, &pl, nullptr));
-  OP_TRY(af_launch_groupnorm<bf16>(hn, (long)HW * Cout, Cout, B, HW, Cout, gamma_dev, beta_dev, eps, silu, yn, (long)HW * Cout,
+  AF_TRY(af_launch_conv_gemm<bf16>(p, 1, s, &pl, nullptr));
+  AF_TRY(af_launch_groupnorm<bf16>(hn, (long)HW * Cout, Cout, B, HW, Cout, gamma_dev, beta_dev, eps, silu, yn, (long)HW * Cout,
                                    Cout, ws, s, 0.f, reinterpret_cast<const float*>(st), HW / 64));
-  OP_TRY(af_launch_nhwc_to_nchw<bf16>(hn, h_dev, B, Cout, HW, Cout, s));
-  OP_TRY(af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, HW, Cout, s));
+  AF_TRY(af_launch_nhwc_to_nchw<bf16>(hn, h_dev, B, Cout, HW, Cout, s));
+  AF_TRY(af_launch_nhwc_to_nchw<bf16>(yn, y_dev, B, Cout, HW, Cout, s));
   return 0;
 }
 
@@ -678,13 +641,11 @@ int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const
                     float* y_dev, int64_t rows, int C, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  OP_ALLOC(xn, (size_t)rows * C * esz(dtype), false);
-  OP_ALLOC(yn, (size_t)rows * C * esz(dtype), false);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(x_dev, xn, rows * C, s), af_launch_cast_f32<float>(x_dev, xn, rows * C, s), af_launch_cast_f32<f16>(x_dev, xn, rows * C, s)));
-  OP_TRY(DISP(dtype, af_launch_layernorm<bf16>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s),
-              af_launch_layernorm<float>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s),
-              af_launch_layernorm<f16>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, rows * C, s), af_launch_cast_to_f32<float>(yn, y_dev, rows * C, s), af_launch_cast_to_f32<f16>(yn, y_dev, rows * C, s)));
+  OP_ALLOC(xn, (size_t)rows * C * esize(dtype), false);
+  OP_ALLOC(yn, (size_t)rows * C * esize(dtype), false);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(x_dev, xn, rows * C, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_layernorm<Elem>(xn, C, rows, C, gamma_dev, beta_dev, eps, yn, C, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, rows * C, s)));
   return 0;
 }
 
@@ -694,22 +655,22 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
   Tmp tmp;
   const int C = heads * dh;
   const long nq = (long)B * Nq * C, nk = (long)B * Nk * C;
-  OP_ALLOC(qn, (size_t)nq * esz(dtype), false);
+  OP_ALLOC(qn, (size_t)nq * esize(dtype), false);
   // flags bit 1 (test hook): K and V are the heads of larger allocations whose 128 tail rows hold NaNs, so a kernel that
   // reads rows >= Nk of the last sample's last key tile (instead of having them zero-filled) shows up as NaN in O
   const bool guard = (causal & 2) != 0;
   causal &= 1;
-  const size_t tail = guard ? (size_t)128 * C * esz(dtype) : 0;
-  OP_ALLOC(kn, (size_t)nk * esz(dtype) + tail, false);
-  OP_ALLOC(vn, (size_t)nk * esz(dtype) + tail, false);
+  const size_t tail = guard ? (size_t)128 * C * esize(dtype) : 0;
+  OP_ALLOC(kn, (size_t)nk * esize(dtype) + tail, false);
+  OP_ALLOC(vn, (size_t)nk * esize(dtype) + tail, false);
   if (guard) {
-    if (hipMemsetAsync((char*)kn + (size_t)nk * esz(dtype), 0xFF, tail, s) != hipSuccess ||   // 0xFFFF / 0xFFFFFFFF: NaN
-        hipMemsetAsync((char*)vn + (size_t)nk * esz(dtype), 0xFF, tail, s) != hipSuccess) return AF_ERR_HIP;
+    if (hipMemsetAsync((char*)kn + (size_t)nk * esize(dtype), 0xFF, tail, s) != hipSuccess ||   // 0xFFFF / 0xFFFFFFFF: NaN
+        hipMemsetAsync((char*)vn + (size_t)nk * esize(dtype), 0xFF, tail, s) != hipSuccess) return AF_ERR_HIP;
   }
-  OP_ALLOC(on, (size_t)nq * esz(dtype), true);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s), af_launch_cast_f32<f16>(q_dev, qn, nq, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s), af_launch_cast_f32<f16>(k_dev, kn, nk, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s), af_launch_cast_f32<f16>(v_dev, vn, nk, s)));
+  OP_ALLOC(on, (size_t)nq * esize(dtype), true);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(q_dev, qn, nq, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(k_dev, kn, nk, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(v_dev, vn, nk, s)));
   AttnParams p;
   p.q = qn; p.k = kn; p.v = vn; p.o = on; p.lse = nullptr; p.causal = causal;
   p.ldq = p.ldk = p.ldv = p.ldo = C;
@@ -720,16 +681,16 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
     const long pe = af_attn_short_pack_elems<bf16>(B, heads, dh, Nk);
     if (pe > 0) {
       OP_ALLOC(vt, (size_t)pe * 2, false);
-      OP_TRY(af_launch_attn_short_pack<bf16>(vn, C, (long)Nk * C, Nk, heads, dh, B, vt, s));
+      AF_TRY(af_launch_attn_short_pack<bf16>(vn, C, (long)Nk * C, Nk, heads, dh, B, vt, s));
       p.vt_pack = vt;
     }
   }
-  OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s), af_launch_attention<f16>(p, B, dh, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s), af_launch_cast_to_f32<f16>(on, o_dev, nq, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_attention<Elem>(p, B, dh, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, nq, s)));
   return 0;
 }
 
-// Cross-attention with subject-token conv attention, on the launches transformer_forward (af_model.hip) makes for a run of
+// Cross-attention with subject-token conv attention, on the launches xfmr_cross_attention_conv (af_model.hip) makes for a run of
 // samples that all carry n_groups subject strings at the end of their key list.
 int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Hh,
                          int Ww, int Nk, int heads, int dh, float scale, int ks, int n_groups, int path, void* stream) {
@@ -752,22 +713,18 @@ int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, cons
     return AF_ERR_INVALID;
   }
   const bool one_pass = path == 2 || (path == 0 && can && g_af_knobs.conv_attn_short && g_af_knobs.attn_short);
-  OP_ALLOC(qn, (size_t)nq * esz(dtype), false);
-  OP_ALLOC(kn, (size_t)nk * esz(dtype), false);
-  OP_ALLOC(vn, (size_t)nk * esz(dtype), false);
-  OP_ALLOC(kvn, (size_t)2 * nk * esz(dtype), false);   // K | V rows, as the cached context
-  OP_ALLOC(on, (size_t)nq * esz(dtype), true);
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(q_dev, qn, nq, s), af_launch_cast_f32<float>(q_dev, qn, nq, s), af_launch_cast_f32<f16>(q_dev, qn, nq, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(k_dev, kn, nk, s), af_launch_cast_f32<float>(k_dev, kn, nk, s), af_launch_cast_f32<f16>(k_dev, kn, nk, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_f32<bf16>(v_dev, vn, nk, s), af_launch_cast_f32<float>(v_dev, vn, nk, s), af_launch_cast_f32<f16>(v_dev, vn, nk, s)));
-  OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s),
-              af_launch_copy_channels<float>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s),
-              af_launch_copy_channels<f16>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s)));
-  OP_TRY(DISP(dtype, af_launch_copy_channels<bf16>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s),
-              af_launch_copy_channels<float>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s),
-              af_launch_copy_channels<f16>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s)));
+  OP_ALLOC(qn, (size_t)nq * esize(dtype), false);
+  OP_ALLOC(kn, (size_t)nk * esize(dtype), false);
+  OP_ALLOC(vn, (size_t)nk * esize(dtype), false);
+  OP_ALLOC(kvn, (size_t)2 * nk * esize(dtype), false);   // K | V rows, as the cached context
+  OP_ALLOC(on, (size_t)nq * esize(dtype), true);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(q_dev, qn, nq, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(k_dev, kn, nk, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(v_dev, vn, nk, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(kn, C, kvn, 2 * C, 0, C, (long)B * Nk, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(vn, C, kvn, 2 * C, C, C, (long)B * Nk, s)));
   AttnParams p;
-  p.q = qn; p.k = kvn; p.v = (char*)kvn + (size_t)C * esz(dtype); p.o = on; p.lse = nullptr; p.causal = 0;
+  p.q = qn; p.k = kvn; p.v = (char*)kvn + (size_t)C * esize(dtype); p.o = on; p.lse = nullptr; p.causal = 0;
   p.ldq = C; p.ldo = C; p.ldk = p.ldv = 2 * C;
   p.bsq = p.bso = (long)N * C; p.bsk = p.bsv = (long)Nk * 2 * C;
   p.Nq = N; p.Nk = Nk; p.H = heads; p.scale = scale;
@@ -775,29 +732,24 @@ int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, cons
   if (one_pass) {
     OP_ALLOC(vt, (size_t)pe * 2, false);
     OP_ALLOC(amap, af_conv_attn_map_floats(n_groups, B, heads, N) * sizeof(float), false);
-    OP_TRY(af_launch_attn_short_pack<bf16>(p.v, 2 * C, (long)Nk * 2 * C, Nk, heads, dh, B, vt, s));
+    AF_TRY(af_launch_attn_short_pack<bf16>(p.v, 2 * C, (long)Nk * 2 * C, Nk, heads, dh, B, vt, s));
     p.vt_pack = vt;
-    OP_TRY(af_launch_conv_attn_map<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, Nk - n_groups * nt, n_groups,
+    AF_TRY(af_launch_conv_attn_map<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, Nk - n_groups * nt, n_groups,
                                          (float*)amap, B, heads, dh, Hh, Ww, ks, s));
-    OP_TRY(af_launch_conv_attn_short(p, B, dh, ks, n_groups, Hh, Ww, (const float*)amap, s));
+    AF_TRY(af_launch_conv_attn_short(p, B, dh, ks, n_groups, Hh, Ww, (const float*)amap, s));
   } else {
     OP_ALLOC(lse, (size_t)B * heads * N * sizeof(float), false);
     OP_ALLOC(s9, (size_t)B * heads * N * nt * sizeof(float), false);
     p.lse = (float*)lse;
     p.Nk = Nk - n_groups * nt;
-    OP_TRY(DISP(dtype, af_launch_attention<bf16>(p, B, dh, s), af_launch_attention<float>(p, B, dh, s), af_launch_attention<f16>(p, B, dh, s)));
+    AF_TRY(AF_TYPED(dtype, af_launch_attention<Elem>(p, B, dh, s)));
     for (int g = 0; g < n_groups; ++g) {
       const int tok0 = Nk - (n_groups - g) * nt;
-      OP_TRY(DISP(dtype,
-                  af_launch_conv_attn<bf16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
-                                            (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s),
-                  af_launch_conv_attn<float>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
-                                             (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s),
-                  af_launch_conv_attn<f16>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9, (float*)lse, on, C,
-                                            (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s)));
+      AF_TRY(AF_TYPED(dtype, af_launch_conv_attn<Elem>(qn, C, (long)N * C, kvn, 2 * C, (long)Nk * 2 * C, tok0, (float*)s9,
+                                                       (float*)lse, on, C, (long)N * C, B, N, heads, dh, Hh, Ww, scale, ks, s)));
     }
   }
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(on, o_dev, nq, s), af_launch_cast_to_f32<float>(on, o_dev, nq, s), af_launch_cast_to_f32<f16>(on, o_dev, nq, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, nq, s)));
   return 0;
 }
 
@@ -810,7 +762,7 @@ int af_op_xattn_fused(const float* x_dev, const float* ln_stats_dev, const float
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   constexpr int C = 320, Hh = 8, dh = 40;
-  const int M = B * N, rows_pad = rup(C, 128);
+  const int M = B * N, rows_pad = round_up(C, 128);
   if (!af_xattn_fused_ok(M, N, C, Hh, dh, S)) { af_set_error_msg("af_op_xattn_fused: B=%d N=%d S=%d has no fused kernel", B, N, S); return AF_ERR_INVALID; }
   OP_ALLOC(xn, (size_t)M * C * 2, false);
   OP_ALLOC(yn, (size_t)M * C * 2, true);
@@ -824,13 +776,13 @@ int af_op_xattn_fused(const float* x_dev, const float* ln_stats_dev, const float
   const long pe = af_xattn_fused_pack_elems(B, Hh, dh, S);
   OP_ALLOC(pack, (size_t)pe * 2, false);
   OP_ALLOC(parts, (size_t)4 * M * 2 * sizeof(float), true);
-  OP_TRY(af_launch_cast_f32<bf16>(x_dev, xn, (long)M * C, s));
-  OP_TRY(af_launch_cast_f32<bf16>(kv_dev, kvn, (long)B * S * 2 * C, s));
-  OP_TRY(af_launch_repack_weight<bf16>(wq_dev, wq, C, C, C, 1, C, 0, 0, s));
-  OP_TRY(af_launch_repack_weight<bf16>(wo_dev, wo, C, C, C, 1, C, 0, 0, s));
-  OP_TRY(af_launch_ln_fold<bf16>(wq, wqf, gamma_dev, beta_dev, nullptr, (float*)cs, (float*)bf, rows_pad, C, C, s));
-  OP_TRY(af_launch_xattn_fused_permute_wo(wo, C, C, wop, C, s));
-  OP_TRY(af_launch_xattn_fused_pack(kvn, 2 * C, (long)S * 2 * C, S, B, pack, s));
+  AF_TRY(af_launch_cast_f32<bf16>(x_dev, xn, (long)M * C, s));
+  AF_TRY(af_launch_cast_f32<bf16>(kv_dev, kvn, (long)B * S * 2 * C, s));
+  AF_TRY(af_launch_repack_weight<bf16>(wq_dev, wq, C, C, C, 1, C, 0, 0, s));
+  AF_TRY(af_launch_repack_weight<bf16>(wo_dev, wo, C, C, C, 1, C, 0, 0, s));
+  AF_TRY(af_launch_ln_fold<bf16>(wq, wqf, gamma_dev, beta_dev, nullptr, (float*)cs, (float*)bf, rows_pad, C, C, s));
+  AF_TRY(af_launch_xattn_fused_permute_wo(wo, C, C, wop, C, s));
+  AF_TRY(af_launch_xattn_fused_pack(kvn, 2 * C, (long)S * 2 * C, S, B, pack, s));
   AfXattnFusedParams a;
   memset(&a, 0, sizeof(a));
   a.x = xn; a.ldx = C; a.M = M; a.rows_per_sample = N;
@@ -841,8 +793,8 @@ int af_op_xattn_fused(const float* x_dev, const float* ln_stats_dev, const float
   a.out = yn; a.ldo = C;
   a.ln_stats_out = (float*)parts;
   a.Nk = S;
-  OP_TRY(af_launch_xattn_fused(a, s));
-  OP_TRY(af_launch_cast_to_f32<bf16>(yn, y_dev, (long)M * C, s));
+  AF_TRY(af_launch_xattn_fused(a, s));
+  AF_TRY(af_launch_cast_to_f32<bf16>(yn, y_dev, (long)M * C, s));
   if (ln_parts_out_dev && hipMemcpyAsync(ln_parts_out_dev, parts, (size_t)4 * M * 2 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
     return AF_ERR_HIP;
   return 0;
@@ -851,13 +803,9 @@ int af_op_xattn_fused(const float* x_dev, const float* ln_stats_dev, const float
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  OP_ALLOC(yn, (size_t)B * dim * esz(dtype), false);
-  OP_TRY(DISP(dtype, af_launch_timestep_embedding<bf16>((const long long*)t_dev, yn, B, dim, s),
-              af_launch_timestep_embedding<float>((const long long*)t_dev, yn, B, dim, s),
-              af_launch_timestep_embedding<f16>((const long long*)t_dev, yn, B, dim, s)));
-  OP_TRY(DISP(dtype, af_launch_cast_to_f32<bf16>(yn, y_dev, (long)B * dim, s),
-              af_launch_cast_to_f32<float>(yn, y_dev, (long)B * dim, s),
-              af_launch_cast_to_f32<f16>(yn, y_dev, (long)B * dim, s)));
+  OP_ALLOC(yn, (size_t)B * dim * esize(dtype), false);
+  AF_TRY(AF_TYPED(dtype, af_launch_timestep_embedding<Elem>((const long long*)t_dev, yn, B, dim, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, (long)B * dim, s)));
   return 0;
 }
 

@@ -25,12 +25,10 @@
 //     the V^T fragment is read in that same key order), no LDS round trip for P.
 //   * dh is padded in LDS only: QK^T K-dim to a multiple of 32 bytes, O to
 //     32-row blocks; HBM traffic is exactly the unpadded Q, K, V, O.
-#include "af_common.h"
+#include "af_device.h"
 #include <math.h>
-#include <type_traits>
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 template <typename T, int DH> struct AttnCfg {
   static constexpr bool BF = sizeof(T) == 2;      // 16-bit storage (bf16 or fp16): the LDS layout, double buffering, ds_read_b64_tr_b16
@@ -441,26 +439,6 @@ template <int DH_, int W_ = 8> struct Cfg {
   static constexpr int KPADS = KCH - NCH, VPADS = VCH - NCH, PADS = 64 * (KPADS + VPADS);
   static_assert(DH % 8 == 0 && KCH > NCH && VCH > NCH && 2 * (FS - 1) < KCH, "row layout");
 };
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // (HIP's uint4 / uint2 are structs: asm operands must be vectors)
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_base, unsigned voffset, unsigned soffset) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
-#endif
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read128(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF> __device__ __forceinline__ u32x2 lds_read_tr64(unsigned addr) {
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-// the wait names the registers it covers ("+v"): no consumer of them can be scheduled above it (cdna guide 5.7, form ii)
-template <int N> __device__ __forceinline__ void wait_lgkm(u32x4& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkm2(u32x2& a, u32x2& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory"); }
 __device__ __forceinline__ void mma(const u32x4& a, const uint4& b, f32x16& c) {
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -478,13 +456,6 @@ __device__ __forceinline__ void ring_coords(int& qb, int& head, int& b) {
   b = yz / H;
   head = yz - b * H;
 }
-template <int I, int N, typename F> __device__ __forceinline__ void sfor(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    sfor<I + 1, N>(f);
-  }
-}
-
 // one pass over the keys for this workgroup's 256 queries.  RUNMAX = false: reference from the first tile only;
 // returns whether this lane saw a non-finite result (outputs are written either way; a repeat overwrites them).
 // MODE 0: softmax reference from the first tile only (RUNMAX = false above); 1: the running bf16 reference (the repeat);
@@ -508,8 +479,8 @@ template <int DH, int MODE, int W = 8> __device__ __forceinline__ bool pass(cons
   const T* K = reinterpret_cast<const T*>(p.k) + (long)b * p.bsk + head * DH;
   const T* V = reinterpret_cast<const T*>(p.v) + (long)b * p.bsv + head * DH;
   T* O = reinterpret_cast<T*>(p.o) + (long)b * p.bso + head * DH;
-  const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(K), 0, (p.Nk - 1) * p.ldk * 2 + DH * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(V), 0, (p.Nk - 1) * p.ldv * 2 + DH * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_k = buffer_rsrc(K, (p.Nk - 1) * p.ldk * 2 + DH * 2);
+  const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(V, (p.Nk - 1) * p.ldv * 2 + DH * 2);
 
   const float sl2 = p.scale * 1.44269504088896340736f;
   uint4 qf[FS];
@@ -607,11 +578,11 @@ template <int DH, int MODE, int W = 8> __device__ __forceinline__ bool pass(cons
     {
       const unsigned ka = kaddr0 + bo, kl = kaddr_last + bo;
       u32x4 a[2][FS];
-      sfor<0, 2 * FS>([&](auto mc) {
+      static_for<0, 2 * FS>([&](auto mc) {
         constexpr int m = decltype(mc)::value, kb = m / FS, st = m % FS;
         a[kb][st] = (C::KLASTFIX && st == C::FS - 1) ? lds_read128<kb * 32 * KROW + 32 * st>(kl) : lds_read128<kb * 32 * KROW + 32 * st>(ka);
       });
-      sfor<0, 2 * FS>([&](auto mc) {
+      static_for<0, 2 * FS>([&](auto mc) {
         constexpr int m = decltype(mc)::value, kb = m / FS, st = m % FS;
         wait_lgkm<2 * FS - 1 - m>(a[kb][st]);
         mma(a[kb][st], qf[st], s[kb]);
@@ -688,11 +659,11 @@ template <int DH, int MODE, int W = 8> __device__ __forceinline__ bool pass(cons
         for (int r = 0; r < 16; ++r) s[kb][r] = __builtin_amdgcn_exp2f(s[kb][r]);
     }
     // ---- O^T += V^T P^T : four k steps of 16 keys, DB blocks of 32 rows each ----
-    sfor<0, 4>([&](auto kc) {
+    static_for<0, 4>([&](auto kc) {
       constexpr int ks = decltype(kc)::value, KB = ks >> 1, S2 = ks & 1;
       constexpr int RO = (KB * 32 + S2 * 16) * VROW;
       u32x2 lo[DB], hi[DB];
-      sfor<0, DB>([&](auto dc) {
+      static_for<0, DB>([&](auto dc) {
         constexpr int d = decltype(dc)::value;
         const unsigned va = vaddr0 + bo + (unsigned)(64 * (d ^ sw));   // (sw = 0 unless the rows are 128 bytes: then DB = 2)
         lo[d] = lds_read_tr64<RO>(va);
@@ -701,13 +672,13 @@ template <int DH, int MODE, int W = 8> __device__ __forceinline__ bool pass(cons
       Vec16<T> pb;
 #pragma unroll
       for (int j = 0; j < 8; ++j) pb.e[j] = from_f32<T>(s[KB][8 * S2 + j]);
-      sfor<0, DB>([&](auto dc) {
+      static_for<0, DB>([&](auto dc) {
         constexpr int d = decltype(dc)::value;
-        wait_lgkm2<2 * (DB - 1 - d)>(lo[d], hi[d]);
+        wait_lgkm<2 * (DB - 1 - d)>(lo[d], hi[d]);
         mma(u32x4{lo[d].x, lo[d].y, hi[d].x, hi[d].y}, pb.u, o[d]);
       });
     });
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own pieces of tile t+1 landed
+    wait_vm<0>();   // own pieces of tile t+1 landed
     __builtin_amdgcn_s_barrier();                      // everyone's pieces landed; everyone is done reading tile t
   }
   // row DH of O^T (the ones column): block DH/32, in-block row rr -> register (rr&3)+4*(rr>>3) of lane-half (rr>>2)&1
@@ -847,37 +818,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
 template <typename T, int DH> static int launch_attn(const AttnParams& p, int B, hipStream_t stream) {
   using C = AttnCfg<T, DH>;
-  static unsigned long long attr_done = 0, attr_done_w4 = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&attn_kernel<T, DH>), C::LDS_BYTES)) return rc;
-  if constexpr (!std::is_same_v<T, f16>) {   // (the 128-VGPR cap was sized for the bf16 dh-40 body: fp16 has no such instantiation)
-    if (int rc = af_ensure_dynamic_lds(attr_done_w4, reinterpret_cast<const void*>(&attn_kernel_w4<T, DH>), C::LDS_BYTES)) return rc;
-  }
   if constexpr (C::IS_BF16 && DH == 40) {
     if ((g_af_knobs.attn_ring & 1) && !p.causal) {   // eight-wave LDS-DMA ring kernel (the 64x64 level)
-      static unsigned long long attr_done_ring = 0;
-      if (int rc = af_ensure_dynamic_lds(attr_done_ring, reinterpret_cast<const void*>(&ring::attn_ring40_kernel), ring::Cfg<40>::LDS_BYTES)) return rc;
-      hipLaunchKernelGGL(ring::attn_ring40_kernel, dim3((p.Nq + 255) / 256, p.H, B), dim3(512), ring::Cfg<40>::LDS_BYTES, stream, p);
-      HIP_CHECK_RET(hipGetLastError());
-      return 0;
+      constexpr int lds40 = ring::Cfg<40>::LDS_BYTES;
+      return af_launch_lds<ring::attn_ring40_kernel>(dim3((p.Nq + 255) / 256, p.H, B), dim3(512), lds40, lds40, stream, p);
     }
   }
   if constexpr (C::IS_BF16 && DH == 80) {
     if ((g_af_knobs.attn_ring & 2) && !p.causal && (p.Nk >= 256 || (g_af_knobs.attn_ring & 4))) {   // 80-wide heads (the 32x32 level; bit 2: tests force it for short key lists)
-      static unsigned long long attr_done_ring = 0;
       constexpr int lds80 = ring::Cfg<80, 4>::LDS_BYTES;
-      if (int rc = af_ensure_dynamic_lds(attr_done_ring, reinterpret_cast<const void*>(&ring::attn_ring80_kernel), lds80)) return rc;
-      hipLaunchKernelGGL(ring::attn_ring80_kernel, dim3((p.Nq + 127) / 128, p.H, B), dim3(256), lds80, stream, p);
-      HIP_CHECK_RET(hipGetLastError());
-      return 0;
+      return af_launch_lds<ring::attn_ring80_kernel>(dim3((p.Nq + 127) / 128, p.H, B), dim3(256), lds80, lds80, stream, p);
     }
   }
   dim3 grid((p.Nq + 127) / 128, p.H, B);
-  if constexpr (C::IS_BF16 && DH == 40)
-    hipLaunchKernelGGL((attn_kernel_w4<T, DH>), grid, dim3(256), C::LDS_BYTES, stream, p);
-  else
-    hipLaunchKernelGGL((attn_kernel<T, DH>), grid, dim3(256), C::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  if constexpr (!std::is_same_v<T, f16>) {   // (the 128-VGPR cap was sized for the bf16 dh-40 body: fp16 has no such instantiation)
+    // (a plain `if`: both kernels stay instantiated for every other T / DH, as they have always been)
+    if (C::IS_BF16 && DH == 40) return af_launch_lds<attn_kernel_w4<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
+  }
+  return af_launch_lds<attn_kernel<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
 }
 
 // packed V^T fragments for xs::xattn_short_kernel (elements; 0 = this (dtype, dh, Nk) has no short-key kernel)

@@ -49,6 +49,16 @@ static inline int af_ensure_dynamic_lds(unsigned long long& done_mask, const voi
   if (dev >= 0 && dev < 64) __atomic_fetch_or(&done_mask, 1ull << dev, __ATOMIC_RELEASE);
   return 0;
 }
+// Launch of a kernel that needs dynamic LDS beyond the default limit: raise the kernel's limit to max_lds (once per device;
+// the mask is a function-local static, so one per kernel instantiation), launch with lds bytes, report a launch error
+template <auto Kernel, typename... Args>
+static inline int af_launch_lds(dim3 grid, dim3 block, int max_lds, int lds, hipStream_t stream, const Args&... args) {
+  static unsigned long long attr_done = 0;
+  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(Kernel), max_lds)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
 
 // per-kernel-class HIP-event profiling (enabled only by bench.py; see af_prof_* in adaface_hip.h)
 // classes 5-7 split the eight-wave ping-pong kernel out of the conv/linear class by instantiation, so that the bench can

@@ -33,12 +33,12 @@
 //     a second kernel reduces them and applies the epilogue.
 //   * fused epilogues: alpha, bias, per-sample time-embedding bias, residual add,
 //     GEGLU (value*gelu(gate) with value/gate rows interleaved in 16-row groups).
+#include "af_device.h"
 #include "af_kernels.h"
 
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <type_traits>
 
 template <int BM, int BN> struct TileCfg {
   static constexpr int XR = BM / 32, WR = BN / 32;
@@ -49,16 +49,6 @@ template <int BM, int BN> struct TileCfg {
   static constexpr int EPI_BYTES = BM * EPI_LD * 4;
   static constexpr int LDS_BYTES = (2 * TILE_BYTES > EPI_BYTES) ? 2 * TILE_BYTES : EPI_BYTES;
 };
-
-// LDS-DMA: 16 bytes per lane from a buffer resource straight into LDS at (wave-uniform base) + lane*16.
-// (The builtin only exists in the device pass; the host pass of this translation unit must not see it, or clang
-// silently drops the kernel's host stub.)
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_base, unsigned voffset, unsigned soffset) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset,
-                                           0, 0);
-#endif
-}
 
 // Workgroup id -> (M tile, N tile).  First the bijective XCD remap (blocks b, b+8, ... share an XCD and its L2:
 // give each XCD one contiguous range of ids), then grouped ordering: ids sweep `gm` M tiles before moving to the next
@@ -150,11 +140,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvGemmParams p) 
   // Buffer resources (wave-uniform base, 32-bit per-lane byte offsets).  Lanes that must read zero (image
   // padding, rows beyond M / Wrows) get voffset 0xFFFFFFFF: the hardware range check returns 0 for them, so the
   // gather needs neither branches nor 64-bit address arithmetic.
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.src) + zb * p.bs_src), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.W) + zb * p.bs_w), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(reinterpret_cast<const T*>(p.src) + zb * p.bs_src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(reinterpret_cast<const T*>(p.W) + zb * p.bs_w);
 
   const int chunk = tid & 7, r0 = tid >> 3;
   // DMA variant: LDS-DMA writes lane-linearly (slot = lane&7 of row r0+32i), so the XOR swizzle moves to the
@@ -319,13 +306,13 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvGemmParams p) 
       }
     };
     if (KT > 0) gdma(0, kt_begin * BK);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
     for (int kt = 0; kt < KT; ++kt) {
       const int cur = kt & 1;
       if (kt + 1 < KT) gdma(cur ^ 1, (kt_begin + kt + 1) * BK);
       compute(cur);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __syncthreads();
     }
   }
@@ -469,25 +456,6 @@ template <int BN> struct PpCfg {
   static_assert(XP0 % 4 == 0 && (XP - XP0) % 4 == 0 && WP % 4 == 0 && HN % 16 == 0, "piece split");
   static_assert(EPI_BYTES <= LDS_BYTES && NP0 >= NX1, "epilogue tile / gather state");
 };
-
-typedef __attribute__((ext_vector_type(4))) unsigned pp_u32x4;
-template <int I, int N, typename F> __device__ __forceinline__ void pp_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    pp_static_for<I + 1, N>(f);
-  }
-}
-template <int OFF> __device__ __forceinline__ pp_u32x4 pp_lds_read128(unsigned addr) {
-  pp_u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int N> __device__ __forceinline__ void pp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void pp_wait_lgkm0() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);   // hipcc hoists register-only MFMAs over an asm wait without this
-}
 
 // One output quad of a sliced-K launch: out[m][n .. n+3] = T(sum_z slab[z][m][n..] + bias + rowbias + residual), slabs summed
 // in slice order (splitk_reduce_kernel).
@@ -866,11 +834,6 @@ __device__ __forceinline__ void ff8_epilogue(const ConvGemmParams& p, f32x4 (&ac
   if constexpr (REC) fp8_rec_commit<8>(r_amax, r_nsat, rec);
 }
 
-template <int N> __device__ __forceinline__ void pp_wait_lgkm() {   // counted: LDS reads return in order
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 typedef __attribute__((ext_vector_type(8))) int pp_i32x8;
 typedef __attribute__((ext_vector_type(4))) int pp_i32x4;
 
@@ -973,10 +936,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
   tile_coords(blockIdx.x, gridDim.x, ntm, ntn, p.group_m, tm, tn);
   const int m0 = tm * 256, n0 = tn * BN;
   const int zk = blockIdx.z;
-  T* const xsrc = const_cast<T*>(reinterpret_cast<const T*>(p.src));
-  T* const wsrc = const_cast<T*>(reinterpret_cast<const T*>(p.W));
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(xsrc, 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(wsrc, 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
 
   // K range: steps s = (chunk, tap), nine per chunk; a slice is a whole number of chunks (the launcher checks)
   const int KT_all = p.K / 64;
@@ -1063,25 +1024,25 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
     for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // w8: the weight fragments of the current step (block NI - 1 is held over into the next one); xp: the activation
   // fragments of the previous step
-  pp_u32x4 w8[NI][2], xp[MI][2];
+  u32x4 w8[NI][2], xp[MI][2];
 #pragma unroll
-  for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
+  for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-  for (int j = 0; j < MI; ++j) xp[j][0] = xp[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
-  auto mfma2 = [&](f32x4& c, const pp_u32x4 (&wv)[2], const pp_u32x4 (&xv)[2]) {
+  for (int j = 0; j < MI; ++j) xp[j][0] = xp[j][1] = u32x4{0u, 0u, 0u, 0u};
+  auto mfma2 = [&](f32x4& c, const u32x4 (&wv)[2], const u32x4 (&xv)[2]) {
     if constexpr ((LABL & 4) == 0) {
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[0]), __builtin_bit_cast(bf16x8, xv[0]), c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[1]), __builtin_bit_cast(bf16x8, xv[1]), c, 0, 0, 0);
       asm volatile("" : "+v"(c));
     }
   };
-  auto wait_block = [&](auto nc, pp_u32x4 (&blk)[2]) {
+  auto wait_block = [&](auto nc, u32x4 (&blk)[2]) {
     constexpr int n = decltype(nc)::value;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
+    wait_lgkm<n>(blk[0], blk[1]);
   };
-  auto wait_block2 = [&](auto nc, pp_u32x4 (&b0)[2], pp_u32x4 (&b1)[2]) {   // (one s_waitcnt for two blocks)
+  auto wait_block2 = [&](auto nc, u32x4 (&b0)[2], u32x4 (&b1)[2]) {   // (one s_waitcnt for two blocks)
     constexpr int n = decltype(nc)::value;
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(b0[0]), "+v"(b0[1]), "+v"(b1[0]), "+v"(b1[1]) : "n"(n) : "memory");
+    wait_lgkm<n>(b0[0], b0[1], b1[0], b1[1]);
   };
   auto dma = [&](__amdgpu_buffer_rsrc_t rs, char* dst, unsigned voff, unsigned soff) {
     if constexpr ((LABL & 1) == 0) lds_dma16(rs, dst, voff, soff);
@@ -1118,16 +1079,16 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
     for (int c = 0; c < nch; ++c) {
       const unsigned kc = (unsigned)(chunk0 + c) * 128u;
       const int nrec = c + 1 < nch ? (int)0xFFFFFFF0u : 0;          // the pieces of the next chunk: none after the last
-      const __amdgpu_buffer_rsrc_t rs_xn = __builtin_amdgcn_make_buffer_rsrc(xsrc, 0, nrec, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rs_wn = __builtin_amdgcn_make_buffer_rsrc(wsrc, 0, nrec, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs_xn = buffer_rsrc(p.src, nrec);
+      const __amdgpu_buffer_rsrc_t rs_wn = buffer_rsrc(p.W, nrec);
       const unsigned hrd8 = (lds0 + (unsigned)((c & 1) * H::HBUF)) >> 3;   // halo buffer read ...
       char* const hdst = smem + ((c & 1) ^ 1) * H::HBUF + wid * 1024;       // ... and staged
-      pp_static_for<0, 9>([&](auto tc) {
+      static_for<0, 9>([&](auto tc) {
         constexpr int TAP = decltype(tc)::value;
         constexpr int KY = TAP / 3, KX = TAP % 3, WS = TAP % 3, WS2 = (TAP + 2) % 3, T2 = TAP + 2;
         constexpr int NB = NI + MI;
         // vmcnt at the head of a step: everything but what the PREVIOUS step issued (its weight pieces + its halo piece)
-        pp_wait_vm<NWQ + (TAP >= 1 && TAP <= NHT ? 1 : 0)>();
+        wait_vm<NWQ + (TAP >= 1 && TAP <= NHT ? 1 : 0)>();
         __builtin_amdgcn_s_barrier();
         const unsigned ut = hrd8 + KY * hw16 + KX * 16u;
         unsigned xa0[MI];
@@ -1136,23 +1097,23 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
           const unsigned u = xh16[j] + ut;
           xa0[j] = (u << 3) | ((u ^ qsel16) & 0x70u);
         }
-        pp_u32x4 xc[MI][2];
+        u32x4 xc[MI][2];
         if constexpr ((LABL & 2) != 0) {
 #pragma unroll
-          for (int j = 0; j < MI; ++j) xc[j][0] = xc[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+          for (int j = 0; j < MI; ++j) xc[j][0] = xc[j][1] = u32x4{0u, 0u, 0u, 0u};
         }
         auto rd_block = [&](auto bc) {
           constexpr int bi = decltype(bc)::value;
           if constexpr ((LABL & 2) != 0) {
           } else if constexpr (bi == 0) {
-            w8[0][0] = pp_lds_read128<WS * H::WBYTES>(wrd0);
-            w8[0][1] = pp_lds_read128<WS * H::WBYTES>(wrd1);
+            w8[0][0] = lds_read128<WS * H::WBYTES>(wrd0);
+            w8[0][1] = lds_read128<WS * H::WBYTES>(wrd1);
           } else if constexpr (bi <= MI) {
-            xc[bi - 1][0] = pp_lds_read128<0>(xa0[bi - 1]);
-            xc[bi - 1][1] = pp_lds_read128<0>(xa0[bi - 1] ^ 64u);
+            xc[bi - 1][0] = lds_read128<0>(xa0[bi - 1]);
+            xc[bi - 1][1] = lds_read128<0>(xa0[bi - 1] ^ 64u);
           } else {
-            w8[bi - MI][0] = pp_lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd0);
-            w8[bi - MI][1] = pp_lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd1);
+            w8[bi - MI][0] = lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd0);
+            w8[bi - MI][1] = lds_read128<WS * H::WBYTES + (bi - MI) * 2048>(wrd1);
           }
         };
         // weight piece q of step + 2 (the first two taps of the next chunk from tap 7 on)
@@ -1171,7 +1132,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
         rd_block(std::integral_constant<int, 0>{});
         rd_block(std::integral_constant<int, 1>{});
         __builtin_amdgcn_sched_barrier(0);
-        pp_static_for<0, MI * NI>([&](auto mc) {
+        static_for<0, MI * NI>([&](auto mc) {
           constexpr int m = decltype(mc)::value;
           if constexpr (m < MI) {
             mfma2(acc[NI - 1][m], w8[NI - 1], xp[m]);          // held back from the previous step
@@ -1194,7 +1155,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
           if constexpr (m == MI + 6 + G) stage_h();
           __builtin_amdgcn_sched_barrier(0);
         });
-        pp_wait_lgkm0();
+        wait_lgkm_fenced<0>();
 #pragma unroll
         for (int j = 0; j < MI; ++j) xp[j][0] = xc[j][0], xp[j][1] = xc[j][1];
       });
@@ -1202,7 +1163,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
   };
   if (g == 0) chunk_loop(std::integral_constant<int, 0>{});
   else chunk_loop(std::integral_constant<int, 1>{});
-  pp_wait_vm<0>();
+  wait_vm<0>();
 #pragma unroll
   for (int j = 0; j < MI; ++j) mfma2(acc[NI - 1][j], w8[NI - 1], xp[j]);
   __builtin_amdgcn_s_barrier();
@@ -1230,7 +1191,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo8_kernel(const ConvGemmParams
   pp_epilogue<160, 0>(p, acc, bias_r, ln_cs, ln_mu, ln_rs, smem, tid, lane, g, wq, m0, n0, tn, zk);
 #ifdef AF_LAB_ABLATE
   if (lab & 64) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
     const unsigned long long st3 = lab_now();
     unsigned xcc, hwid;
@@ -1301,11 +1262,9 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
   const int ntn_all = p.N / C::BN;                 // column tiles (GEGLU: value | gate interleaved in 16-row groups)
   const int nt_begin = (int)((long)blockIdx.y * ntn_all / gridDim.y), nt_end = (int)((long)(blockIdx.y + 1) * ntn_all / gridDim.y);
   const int ntn = nt_end - nt_begin;               // ... of this workgroup
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.src)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.W)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(p.out), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
+  const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(p.out);
 
   // ---- the bias (and, LayerNorm consumer, the column sums) of this workgroup's columns -> LDS, once.  Fetched from memory in
   // every tile's epilogue they were the YOUNGEST vector-memory operations of the wave: waiting for them waits for every LDS-DMA
@@ -1326,7 +1285,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
   }
 
   // ---- the wave's 32 activation rows as MFMA B fragments: block j, K chunk kc, half u -> k = 64 kc + 32 u + 8 (lane >> 4) ----
-  pp_u32x4 xr[MJ][KC][2];
+  u32x4 xr[MJ][KC][2];
   // store mapping: chunk c = lane + 64 i of the wave's 32 x CPR chunks -> row c / CPR, 16-byte chunk c % CPR of its segment
   unsigned orow[NST];
 #pragma unroll
@@ -1346,7 +1305,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
     for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
       for (int u = 0; u < 2; ++u)
-        xr[j][kc][u] = __builtin_bit_cast(pp_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, xo, (kc * 64 + u * 32) * 2, 0));
+        xr[j][kc][u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, xo, (kc * 64 + u * 32) * 2, 0));
     if constexpr (LNMODE == 1) {
       float2 st = float2{0.f, 0.f};
       if (ok && p.ln_parts_n > 0) {
@@ -1358,9 +1317,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
           s1 += pq2.x;
           s2 += pq2.y;
         }
-        const float mu = s1 * p.ln_inv_count;
-        const float var = fmaxf(s2 * p.ln_inv_count - mu * mu, 0.f);
-        st = float2{mu, __builtin_amdgcn_rsqf(var + p.ln_eps)};
+        st = ln_mu_rstd(s1, s2, p.ln_inv_count, p.ln_eps);
       } else if (ok) {
         st = *reinterpret_cast<const float2*>(p.ln_stats + (long)m * 2);
       }
@@ -1377,7 +1334,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
       if constexpr (LNMODE == 1) *reinterpret_cast<float4*>(vecs + nvcol + 4 * c4) = vc[r];
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (visible to the other waves behind the first step's barrier)
+  wait_lgkm<0>();   // (visible to the other waves behind the first step's barrier)
 
   if (p.gn_ab) {
     // GroupNorm of the consumer's input (see ConvGemmParams::gn_ab), after every row load of the wave has been issued: the
@@ -1399,7 +1356,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
           v.u = __builtin_bit_cast(uint4, xr[j][kc][u]);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v.e[e] = from_f32<T>(fmaf(to_f32<T>(v.e[e]), sc[e], sh[e]));
-          xr[j][kc][u] = __builtin_bit_cast(pp_u32x4, v.u);
+          xr[j][kc][u] = __builtin_bit_cast(u32x4, v.u);
         }
       }
   }
@@ -1437,7 +1394,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
 #endif
   char* otile = smem + NS * C::WBYTES + wid * C::OBYTES;
   f32x4 acc[NIW][MJ];
-  pp_u32x4 wf[NIW][2];
+  u32x4 wf[NIW][2];
   auto zero_acc = [&]() {
 #pragma unroll
     for (int i = 0; i < NIW; ++i)
@@ -1445,9 +1402,9 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
       for (int j = 0; j < MJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
   zero_acc();
-  auto wait_block = [&](auto nc, pp_u32x4 (&blk)[2]) {
+  auto wait_block = [&](auto nc, u32x4 (&blk)[2]) {
     constexpr int n = decltype(nc)::value;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
+    wait_lgkm<n>(blk[0], blk[1]);
   };
   // one K step of one column tile: weight blocks read two ahead of their MFMAs, counted waits; DMA for step t + D
   auto step = [&](auto kcc, int slot, int t, int stage_slot) {
@@ -1457,14 +1414,14 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
     auto rd = [&](auto ic) {
       constexpr int i = decltype(ic)::value;
       if (lab & 2) return;
-      wf[i][0] = pp_lds_read128<i * 2048>(b0);
-      wf[i][1] = pp_lds_read128<i * 2048>(b1);
+      wf[i][0] = lds_read128<i * 2048>(b0);
+      wf[i][1] = lds_read128<i * 2048>(b1);
     };
     rd(std::integral_constant<int, 0>{});
     rd(std::integral_constant<int, 1>{});
     rd(std::integral_constant<int, 2>{});
     __builtin_amdgcn_sched_barrier(0);
-    pp_static_for<0, NIW>([&](auto ic) {
+    static_for<0, NIW>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       constexpr int issued = (i + 3) < NIW ? (i + 3) : NIW;          // blocks issued before block i's MFMAs
       wait_block(std::integral_constant<int, 2 * (issued - i - 1)>{}, wf[i]);
@@ -1479,7 +1436,7 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
       if constexpr (i == 1) { if (!(lab & 1)) stage(t + D, stage_slot); }
       __builtin_amdgcn_sched_barrier(0);
     });
-    pp_wait_lgkm0();
+    wait_lgkm_fenced<0>();
   };
 
   // ---- main loop: steps t = (column tile, K chunk); steps 0 .. D-1 of the ring in flight; step t sits in slot t % NS and
@@ -1490,15 +1447,15 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
   int after_epi = 0;                               // heads that still see the previous tile's stores in the counter
   for (int ntl = 0; ntl < ntn; ++ntl) {
     const int nt = nt_begin + ntl;
-    pp_static_for<0, KC>([&](auto kcc) {
+    static_for<0, KC>([&](auto kcc) {
       constexpr int kc = decltype(kcc)::value;
       // own pieces of this step landed: everything but the pieces of the next D - 1 steps (and, for D heads after an epilogue,
       // its NST stores, which are YOUNGER than the pieces waited for).  (BN = 160: waves 0-3 stage three pieces a step.)
       if (after_epi > 0) {
-        if (nwq == 3) pp_wait_vm<3 * (D - 1) + NST>(); else pp_wait_vm<2 * (D - 1) + NST>();
+        if (nwq == 3) wait_vm<3 * (D - 1) + NST>(); else wait_vm<2 * (D - 1) + NST>();
         --after_epi;
       } else {
-        if (nwq == 3) pp_wait_vm<3 * (D - 1)>(); else pp_wait_vm<2 * (D - 1)>();
+        if (nwq == 3) wait_vm<3 * (D - 1)>(); else wait_vm<2 * (D - 1)>();
       }
       __builtin_amdgcn_s_barrier();
       const int prev = cur == 0 ? NS - 1 : cur - 1;
@@ -1512,13 +1469,13 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
       float4 bvec[NIW], cvec[LNMODE == 1 ? NIW : 1];
       {
         const unsigned va = lds0 + (unsigned)C::LDS_BYTES + (unsigned)((ntl * C::BN + cl) * 4);
-        pp_u32x4 tb[NIW], tc[LNMODE == 1 ? NIW : 1];
-        pp_static_for<0, NIW>([&](auto ic) {
+        u32x4 tb[NIW], tc[LNMODE == 1 ? NIW : 1];
+        static_for<0, NIW>([&](auto ic) {
           constexpr int i = decltype(ic)::value;
-          tb[i] = pp_lds_read128<i * 64>(va);
-          if constexpr (LNMODE == 1) tc[i] = pp_lds_read128<i * 64>(va + (unsigned)nvcol * 4u);
+          tb[i] = lds_read128<i * 64>(va);
+          if constexpr (LNMODE == 1) tc[i] = lds_read128<i * 64>(va + (unsigned)nvcol * 4u);
         });
-        pp_wait_lgkm0();
+        wait_lgkm_fenced<0>();
 #pragma unroll
         for (int i = 0; i < NIW; ++i) {
           asm volatile("" : "+v"(tb[i]));
@@ -1568,13 +1525,13 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
         float4 bvec[NH], cvec[LNMODE == 1 ? NH : 1];
         {
           const unsigned va = lds0 + (unsigned)C::LDS_BYTES + (unsigned)((ntl * C::BN + hh * NH * 16 + cl) * 4);
-          pp_u32x4 tb[NH], tc[LNMODE == 1 ? NH : 1];
-          pp_static_for<0, NH>([&](auto ic) {
+          u32x4 tb[NH], tc[LNMODE == 1 ? NH : 1];
+          static_for<0, NH>([&](auto ic) {
             constexpr int ii = decltype(ic)::value;
-            tb[ii] = pp_lds_read128<ii * 64>(va);
-            if constexpr (LNMODE == 1) tc[ii] = pp_lds_read128<ii * 64>(va + (unsigned)nvcol * 4u);
+            tb[ii] = lds_read128<ii * 64>(va);
+            if constexpr (LNMODE == 1) tc[ii] = lds_read128<ii * 64>(va + (unsigned)nvcol * 4u);
           });
-          pp_wait_lgkm0();
+          wait_lgkm_fenced<0>();
 #pragma unroll
           for (int ii = 0; ii < NH; ++ii) {
             asm volatile("" : "+v"(tb[ii]));
@@ -1637,20 +1594,18 @@ __global__ __launch_bounds__(512) void rowpanel_kernel(const ConvGemmParams p) {
     for (int i = 0; i < NST; ++i) {
       const int c = lane + 64 * i;
       const int row = c / CPR, ch = c - row * CPR;
-      const pp_u32x4 v = *reinterpret_cast<const pp_u32x4*>(otile + row * C::OPITCH + ch * 16);
+      const u32x4 v = *reinterpret_cast<const u32x4*>(otile + row * C::OPITCH + ch * 16);
       __builtin_amdgcn_raw_buffer_store_b128(v, rs_o, orow[i], ncol * 2, 0);
     }
     zero_acc();
     after_epi = D;
   }
-  pp_wait_vm<0>();
+  wait_vm<0>();
 }
 
 template <bool GEGLU, int LNMODE, bool RES, int KC, int MJ, int D>
 static int launch_rowpanel_depth(const ConvGemmParams& p, hipStream_t stream) {
   using C = RowPanelCfgT<GEGLU, KC, MJ, D>;
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&rowpanel_kernel<GEGLU, LNMODE, RES, KC, MJ, D>), 160 * 1024)) return rc;
   const int panels = (p.M + C::BM - 1) / C::BM, ntn = p.N / C::BN;
   int ny = 1;                                       // column tiles of a panel over ny workgroups until ~256 exist
   while (panels * ny < 192 && ny * 2 <= ntn && ntn % (ny * 2) == 0) ny *= 2;
@@ -1658,9 +1613,7 @@ static int launch_rowpanel_depth(const ConvGemmParams& p, hipStream_t stream) {
   const int lds_bytes = C::LDS_BYTES + (LNMODE == 1 ? 2 : 1) * ((ntn + ny - 1) / ny) * C::BN * 4;
   if (lds_bytes > 160 * 1024 || ((ntn + ny - 1) / ny) * C::BN > 6144) { af_set_error_msg("row-panel GEMM: N = %d does not leave room for its bias vectors in LDS", p.N); return -1; }
   dim3 grid(panels, ny, 1);
-  hipLaunchKernelGGL((rowpanel_kernel<GEGLU, LNMODE, RES, KC, MJ, D>), grid, dim3(512), lds_bytes, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<rowpanel_kernel<GEGLU, LNMODE, RES, KC, MJ, D>>(grid, dim3(512), 160 * 1024, lds_bytes, stream, p);
 }
 // ring depth: the deepest the form's LDS allows (see RowPanelCfgT).  (Measured against the round-2 depth of 2: nothing, 15.596 vs
 // 15.631 ms per forward -- the knob that selected between them left in round 4.)
@@ -1738,11 +1691,9 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
   int tm, tn;
   tile_coords(blockIdx.x, gridDim.x, ntm, ntn, p.group_m, tm, tn);
   const int m0 = tm * C::BM, n0 = tn * C::BN;
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.src)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.W)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(p.out), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
+  const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(p.out);
 
   // ---- staging: piece = 8 rows x 128 B; lane -> row lane >> 3, LDS slot lane & 7 <- data chunk (lane & 7) ^ row (the swizzle
   // lives in the SOURCE address).  Activations: pieces wid, wid + 8 (all waves two); weights: wid, wid + 8, and wid + 16 for
@@ -1787,10 +1738,10 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < MJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  pp_u32x4 xf[MJ][2], wf[NI][2];
-  auto wait_block = [&](auto nc, pp_u32x4 (&blk)[2]) {
+  u32x4 xf[MJ][2], wf[NI][2];
+  auto wait_block = [&](auto nc, u32x4 (&blk)[2]) {
     constexpr int n = decltype(nc)::value;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
+    wait_lgkm<n>(blk[0], blk[1]);
   };
   // one K step: the two activation blocks and the first weight block are read first; weight block i + 2 is read behind the
   // MFMAs of block i; the LDS-DMA of step t + D is issued behind the second weight block's MFMAs
@@ -1798,20 +1749,20 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
     const unsigned sb = lds0 + (unsigned)(slot * C::SLOT);
     auto rd_x = [&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      xf[j][0] = pp_lds_read128<j * 2048>(sb + x_base + fch0);
-      xf[j][1] = pp_lds_read128<j * 2048>(sb + x_base + fch1);
+      xf[j][0] = lds_read128<j * 2048>(sb + x_base + fch0);
+      xf[j][1] = lds_read128<j * 2048>(sb + x_base + fch1);
     };
     auto rd_w = [&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      wf[i][0] = pp_lds_read128<i * 2048>(sb + w_base + fch0);
-      wf[i][1] = pp_lds_read128<i * 2048>(sb + w_base + fch1);
+      wf[i][0] = lds_read128<i * 2048>(sb + w_base + fch0);
+      wf[i][1] = lds_read128<i * 2048>(sb + w_base + fch1);
     };
     rd_x(std::integral_constant<int, 0>{});
     rd_x(std::integral_constant<int, 1>{});
     rd_w(std::integral_constant<int, 0>{});
     rd_w(std::integral_constant<int, 1>{});
     __builtin_amdgcn_sched_barrier(0);
-    pp_static_for<0, NI>([&](auto ic) {
+    static_for<0, NI>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       // reads outstanding behind block i's: the blocks issued after it (two ahead, until the last ones)
       constexpr int issued = (i + 2) < NI ? (i + 2) : NI;          // weight blocks issued before block i's MFMAs
@@ -1827,7 +1778,7 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
       if constexpr (i == 1) stage(t + D, stage_slot);
       __builtin_amdgcn_sched_barrier(0);
     });
-    pp_wait_lgkm0();
+    wait_lgkm_fenced<0>();
   };
 
   // LayerNorm consumer: (mu, rstd) of this lane's two rows, fetched BEFORE the first LDS-DMA is issued (the loop's vmcnt
@@ -1838,7 +1789,7 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
   if constexpr (LNMODE == 1) {
     // every slab of both rows in flight at once (out-of-range offsets = zeros, no branches): summed one after the other in a
     // loop these 8-byte loads cost 16 memory latencies per launch
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.ln_stats), 0, (int)0xFFFFFFF8u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_s = buffer_rsrc(p.ln_stats, (int)0xFFFFFFF8u);
 #pragma unroll
     for (int j = 0; j < MJ; ++j) {
       const int m = m0 + wq * 32 + j * 16 + (lane & 15);
@@ -1846,8 +1797,7 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
       for (int q = 0; q < LNP; ++q) {
         const bool live = m < p.M && (p.ln_parts_n > 0 ? q < p.ln_parts_n : q == 0);
         const unsigned off = live ? (unsigned)(((long)q * p.M + m) * 8) : 0xFFFFFFFFu;
-        typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs_s, off, 0, 0);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_s, off, 0, 0);
         ln_part[j][q] = float2{__uint_as_float(v.x), __uint_as_float(v.y)};
       }
     }
@@ -1867,10 +1817,9 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
             s1 += pq2.x;
             s2 += pq2.y;
           }
-          const float mu = s1 * p.ln_inv_count;
-          const float var = fmaxf(s2 * p.ln_inv_count - mu * mu, 0.f);
-          ln_mu[j] = mu;
-          ln_rs[j] = __builtin_amdgcn_rsqf(var + p.ln_eps);
+          const float2 st = ln_mu_rstd(s1, s2, p.ln_inv_count, p.ln_eps);
+          ln_mu[j] = st.x;
+          ln_rs[j] = st.y;
         } else {
           ln_mu[j] = ln_part[j][0].x;
           ln_rs[j] = ln_part[j][0].y;
@@ -1889,14 +1838,14 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
   for (int t = 0; t < KT; ++t) {
     // own pieces of step t landed: everything but the pieces of the next D - 1 steps (2 + nwq per step); in the last D - 1
     // steps fewer are in flight: wait for all of them
-    if (t + D > KT) pp_wait_vm<0>();
-    else if (nwq == 3) pp_wait_vm<5 * (D - 1)>(); else pp_wait_vm<4 * (D - 1)>();
+    if (t + D > KT) wait_vm<0>();
+    else if (nwq == 3) wait_vm<5 * (D - 1)>(); else wait_vm<4 * (D - 1)>();
     __builtin_amdgcn_s_barrier();
     const int prev = cur == 0 ? NS - 1 : cur - 1;
     step(cur, t, prev);
     cur = cur + 1 == NS ? 0 : cur + 1;
   }
-  pp_wait_vm<0>();
+  wait_vm<0>();
   __builtin_amdgcn_s_barrier();   // every wave has read its last step: the ring is free for the output tiles
   asm volatile("" ::: "memory");  // (s_barrier is no memory operation for hipcc: keeps the tile stores below it)
 
@@ -1950,14 +1899,14 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
   // All chunks and offsets first, then the stores back to back with nothing between them: a 16-byte buffer store whose data
   // register a VALU instruction rewrites in the next slot was seen to store the NEW value on gfx950 (hipcc pads that hazard only
   // for stores without an SGPR offset, and this one has ncol * 2 there).
-  pp_u32x4 ov[NST];
+  u32x4 ov[NST];
   unsigned ooff[NST];
 #pragma unroll
   for (int i = 0; i < NST; ++i) {
     const int c = lane + 64 * i;
     const int row = c / CPR, ch = c - row * CPR;
     const int m = r0 + row;
-    ov[i] = *reinterpret_cast<const pp_u32x4*>(otile + row * C::OPITCH + ch * 16);
+    ov[i] = *reinterpret_cast<const u32x4*>(otile + row * C::OPITCH + ch * 16);
     ooff[i] = m < p.M ? (unsigned)((long)m * p.ldo * 2) + (unsigned)ch * 16u : 0xFFFFFFFFu;
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1967,12 +1916,8 @@ __global__ __launch_bounds__(512) void gemm_m128_kernel(const ConvGemmParams p) 
 
 template <bool RES, int DEPTH, int LNMODE> static int launch_gemm_m128_one(const ConvGemmParams& p, hipStream_t stream) {
   using C = M128CfgT<DEPTH>;
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&gemm_m128_kernel<RES, DEPTH, LNMODE>), C::LDS_BYTES)) return rc;
   dim3 grid((p.M / C::BM) * (p.N / C::BN), 1, 1);
-  hipLaunchKernelGGL((gemm_m128_kernel<RES, DEPTH, LNMODE>), grid, dim3(512), C::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<gemm_m128_kernel<RES, DEPTH, LNMODE>>(grid, dim3(512), C::LDS_BYTES, C::LDS_BYTES, stream, p);
 }
 template <int DEPTH> static int launch_gemm_m128_depth(const ConvGemmParams& p, hipStream_t stream) {
   if (p.ln_stats) return p.residual ? launch_gemm_m128_one<true, DEPTH, 1>(p, stream) : launch_gemm_m128_one<false, DEPTH, 1>(p, stream);
@@ -2034,10 +1979,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvGemmParams 
   const int ty0 = (tt / tiles_x) * C::TH, tx0 = (tt - (tt / tiles_x) * tiles_x) * TW;
   const int n0 = tn * BN;
 
-  const __amdgpu_buffer_rsrc_t rs_x =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.src), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
   const unsigned ldcb = (unsigned)p.ldc * (unsigned)sizeof(T);
   const unsigned img_off = (unsigned)((long)b * p.src_batch_stride * (long)sizeof(T));
 
@@ -2232,9 +2175,7 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float* __restric
     s1 += st.x;
     s2 += st.y;
   }
-  const float mu = s1 * inv_count;
-  const float var = fmaxf(s2 * inv_count - mu * mu, 0.f);
-  *reinterpret_cast<float2*>(out + (long)m * 2) = float2{mu, __builtin_amdgcn_rsqf(var + eps)};
+  *reinterpret_cast<float2*>(out + (long)m * 2) = ln_mu_rstd(s1, s2, inv_count, eps);
 }
 int af_launch_ln_finalize(const float* part, int parts, int M, int count, float eps, float* out, hipStream_t s) {
   if (M <= 0) return 0;
@@ -2513,13 +2454,9 @@ static void plan_group_m(AfGemmPlan& pl, const ConvGemmParams& p) {
 template <typename T, int BM, int BN, bool DMA>
 static int launch_cfg2(const ConvGemmParams& p, int batch, hipStream_t stream) {
   using C = TileCfg<BM, BN>;
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, DMA>), C::LDS_BYTES)) return rc;
   const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   dim3 grid(ntm * ntn, 1, p.splitk > 1 ? p.splitk : batch);
-  hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, DMA>), grid, dim3(256), C::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<conv_gemm_kernel<T, BM, BN, DMA>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
 }
 template <typename T, int BM, int BN>
 static int launch_cfg(const ConvGemmParams& p, int batch, hipStream_t stream) {
@@ -2557,11 +2494,7 @@ template <typename T> static int launch_splitk_reduce(const ConvGemmParams& p, h
 template <int BN, int LNMODE, bool GATHER, bool FP8, int SCHED>
 static int launch_pp_one(const ConvGemmParams& p, dim3 grid, hipStream_t stream) {
   using C = PpCfg<BN>;
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv_gemm_pp_kernel<BN, GATHER, LNMODE, FP8, SCHED>), C::LDS_BYTES)) return rc;
-  hipLaunchKernelGGL((conv_gemm_pp_kernel<BN, GATHER, LNMODE, FP8, SCHED>), grid, dim3(512), C::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<conv_gemm_pp_kernel<BN, GATHER, LNMODE, FP8, SCHED>>(grid, dim3(512), C::LDS_BYTES, C::LDS_BYTES, stream, p);
 }
 // The schedule, by rule: the phased one (SCHED 0) for GEGLU launches (K = 320 .. 1280, an epilogue of ~1/3 of the workgroup's
 // time that wants its bias and LayerNorm operands fetched before the loop: 3-5 % ahead of the merged one there) and for the
@@ -2633,26 +2566,13 @@ int af_launch_ff_geglu_fp8(ConvGemmParams p, float out_mul, unsigned* rec, hipSt
   AfProfScope prof(AF_K_PP_FP8, stream, 2.0 * p.M * (double)p.N * (p.k_logical ? p.k_logical : p.K),
                    (double)p.M * p.Cin + (double)p.N * p.K + (double)p.M * p.N * 0.5);
   const dim3 grid(((p.M + 255) / 256) * (p.N / 128), 1, 1);
-  static unsigned long long attr_done[2] = {0, 0};
-  if (rec) {
-    if (int rc = af_ensure_dynamic_lds(attr_done[1], reinterpret_cast<const void*>(&ff_geglu_fp8_kernel<true>), C::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(ff_geglu_fp8_kernel<true>, grid, dim3(512), C::LDS_BYTES, stream, p, out_mul, rec);
-  } else {
-    if (int rc = af_ensure_dynamic_lds(attr_done[0], reinterpret_cast<const void*>(&ff_geglu_fp8_kernel<false>), C::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(ff_geglu_fp8_kernel<false>, grid, dim3(512), C::LDS_BYTES, stream, p, out_mul, nullptr);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  if (rec) return af_launch_lds<ff_geglu_fp8_kernel<true>>(grid, dim3(512), C::LDS_BYTES, C::LDS_BYTES, stream, p, out_mul, rec);
+  return af_launch_lds<ff_geglu_fp8_kernel<false>>(grid, dim3(512), C::LDS_BYTES, C::LDS_BYTES, stream, p, out_mul, nullptr);
 }
 
 template <int LABL> static int launch_halo8_lab(const ConvGemmParams& p, hipStream_t stream) {
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv3x3_halo8_kernel<LABL>), Halo8Cfg::LDS_BYTES))
-    return rc;
   dim3 grid((p.M / 256) * (p.N / 160), 1, p.splitk > 1 ? p.splitk : 1);
-  hipLaunchKernelGGL(conv3x3_halo8_kernel<LABL>, grid, dim3(512), Halo8Cfg::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<conv3x3_halo8_kernel<LABL>>(grid, dim3(512), Halo8Cfg::LDS_BYTES, Halo8Cfg::LDS_BYTES, stream, p);
 }
 static int launch_halo8(const ConvGemmParams& p, hipStream_t stream) {
   if (p.Cin % 64 != 0 || (p.Cin / 64) % (p.splitk > 1 ? p.splitk : 1) != 0) {   // the K loop walks whole chunks
@@ -2676,12 +2596,8 @@ static int launch_halo8(const ConvGemmParams& p, hipStream_t stream) {
 
 template <typename T, int TW, int BN> static int launch_halo(const ConvGemmParams& p, hipStream_t stream) {
   using C = HaloCfg<TW, BN>;
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&conv3x3_halo_kernel<T, TW, BN>), C::LDS_BYTES)) return rc;
   dim3 grid((p.M / 128) * ((p.N + BN - 1) / BN), 1, 1);
-  hipLaunchKernelGGL((conv3x3_halo_kernel<T, TW, BN>), grid, dim3(256), C::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  return af_launch_lds<conv3x3_halo_kernel<T, TW, BN>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
 }
 
 // ---------------------------------------------------------------------------

@@ -36,10 +36,8 @@
   const int ph4 = (GATHER && p.phase4) ? (int)blockIdx.y : 0;
   const int pad_y = (GATHER && p.phase4) ? 1 - (ph4 >> 1) : p.pad, pad_x = (GATHER && p.phase4) ? 1 - (ph4 & 1) : p.pad;
 
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.src)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.W)), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
 
   // K range of this block (split-K slices)
   const int KT_all = p.K / (FP8 ? 128 : 64);
@@ -57,7 +55,7 @@
   const unsigned ldcb = (unsigned)p.ldc * XE;
   unsigned x_off[NXM];
   int x_yx[GATHER ? NXM : 1];   // tap masks: validity mask; else (iy0 << 16) | (ix0 & 0xffff): input coordinate of tap (0,0)
-  pp_static_for<0, NXM>([&](auto qc) {
+  static_for<0, NXM>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
     const int piece = g == 0 ? wq + 4 * q : XP0 + wq + 4 * q;
     const int m = m0 + piece * 8 + srow;
@@ -218,7 +216,7 @@
   auto stage = [&](int slot_off) {
     const StageCtx sc = stage_begin(kw);
     char* base = smem + slot_off;
-    pp_static_for<0, NPMAX>([&](auto qc) { stage_piece(qc, base, sc); });
+    static_for<0, NPMAX>([&](auto qc) { stage_piece(qc, base, sc); });
     kw = kw_next(kw);
   };
 
@@ -234,22 +232,22 @@
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < MI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  pp_u32x4 xf[MI][2], wf[NI][2];
+  u32x4 xf[MI][2], wf[NI][2];
 #pragma unroll
-  for (int i = 0; i < NI; ++i) wf[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
+  for (int i = 0; i < NI; ++i) wf[i][1] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-  for (int j = 0; j < MI; ++j) xf[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+  for (int j = 0; j < MI; ++j) xf[j][1] = u32x4{0u, 0u, 0u, 0u};
 
   // one half of a compute segment: MFMAs of unit UM, the NI + MI fragment reads of unit UR one behind each of the
   // first MFMAs (in-order issue: reads placed after the MFMAs would not overlap them)
   auto half = [&](int slot_off, auto rc, auto mc) {
     constexpr int ur = decltype(rc)::value, um = decltype(mc)::value;
     const unsigned b = lds0 + (unsigned)slot_off + (ur ? fch1 : fch0);
-    pp_static_for<0, NI * MI>([&](auto nc) {
+    static_for<0, NI * MI>([&](auto nc) {
       constexpr int n = decltype(nc)::value;
       constexpr int i = n / MI, j = n % MI;
-      if constexpr (n < NI) wf[n][ur] = pp_lds_read128<n * 2048>(b + w_base);
-      else if constexpr (n < NI + MI) xf[n - NI][ur] = pp_lds_read128<(n - NI) * 2048>(b + x_base);
+      if constexpr (n < NI) wf[n][ur] = lds_read128<n * 2048>(b + w_base);
+      else if constexpr (n < NI + MI) xf[n - NI][ur] = lds_read128<(n - NI) * 2048>(b + x_base);
       acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[i][um]),
                                                           __builtin_bit_cast(bf16x8, xf[j][um]), acc[i][j], 0, 0, 0);
       if constexpr (n < NI + MI) __builtin_amdgcn_sched_barrier(0);
@@ -293,14 +291,14 @@
   // those are double-buffered (xa8 / xb8 alternate per tile).  Reads are issued in the order W0 X0 X1 X2 X3 W1 .. W(NI-1):
   // two blocks up front, then one block (two ds_read_b128) behind each MFMA; every MFMA waits with a counted lgkmcnt for
   // exactly the blocks it needs (LDS reads return in order).
-  pp_u32x4 w8[MG ? NI : 1][2], xa8[MG ? MI : 1][2], xb8[MG ? MI : 1][2];
+  u32x4 w8[MG ? NI : 1][2], xa8[MG ? MI : 1][2], xb8[MG ? MI : 1][2];
   int wsc8[FP8 ? NI : 1];
   int xsc8 = p.x_scale_e8;
   if constexpr (MG && !FP8) {
 #pragma unroll
-    for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
+    for (int i = 0; i < NI; ++i) w8[i][0] = w8[i][1] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int j = 0; j < MI; ++j) xa8[j][0] = xa8[j][1] = xb8[j][0] = xb8[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+    for (int j = 0; j < MI; ++j) xa8[j][0] = xa8[j][1] = xb8[j][0] = xb8[j][1] = u32x4{0u, 0u, 0u, 0u};
   }
   if constexpr (FP8) {
     // the activation scale as a VGPR made HERE: first used inside the loop, the kernel-argument load behind it would get
@@ -308,13 +306,13 @@
     asm volatile("" : "+v"(xsc8));
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      w8[i][0] = w8[i][1] = pp_u32x4{0u, 0u, 0u, 0u};
+      w8[i][0] = w8[i][1] = u32x4{0u, 0u, 0u, 0u};
       wsc8[i] = (int)p.w_scale[n0 + g * C::HN + i * 16 + (lane & 15)];
     }
 #pragma unroll
-    for (int j = 0; j < MI; ++j) xa8[j][0] = xa8[j][1] = xb8[j][0] = xb8[j][1] = pp_u32x4{0u, 0u, 0u, 0u};
+    for (int j = 0; j < MI; ++j) xa8[j][0] = xa8[j][1] = xb8[j][0] = xb8[j][1] = u32x4{0u, 0u, 0u, 0u};
   }
-  auto mfma8 = [&](f32x4& c, const pp_u32x4 (&wv)[2], const pp_u32x4 (&xv)[2], int wscale) {
+  auto mfma8 = [&](f32x4& c, const u32x4 (&wv)[2], const u32x4 (&xv)[2], int wscale) {
     if constexpr (!FP8) {   // bf16: the two K halves of the 64-value tile (chunks q and q + 4)
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[0]), __builtin_bit_cast(bf16x8, xv[0]), c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[1]), __builtin_bit_cast(bf16x8, xv[1]), c, 0, 0, 0);
@@ -327,9 +325,9 @@
     asm volatile("" : "+v"(c));   // a use at this point: hipcc otherwise SINKS the whole tile's MFMAs below the last wait
   };
   // counted wait that hands the guarded fragment block through (a data dependency: the MFMA cannot be hoisted over it)
-  auto wait_block = [&](auto nc, pp_u32x4 (&blk)[2]) {
+  auto wait_block = [&](auto nc, u32x4 (&blk)[2]) {
     constexpr int n = decltype(nc)::value;
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blk[0]), "+v"(blk[1]) : "n"(n) : "memory");
+    wait_lgkm<n>(blk[0], blk[1]);
   };
   // (stage_off: the LDS-DMA pieces of tile t + 2 go out one behind every other MFMA)
   // Timing ablations (a separate lab build with -DAF_LAB_ABLATE, scripts/lab/ablate_conv.sh; results are WRONG): bits
@@ -339,7 +337,7 @@
 #else
   constexpr int lab = 0;
 #endif
-  auto cphase8 = [&](int slot_off, pp_u32x4 (&xc)[MG ? MI : 1][2], pp_u32x4 (&xp)[MG ? MI : 1][2], int stage_off,
+  auto cphase8 = [&](int slot_off, u32x4 (&xc)[MG ? MI : 1][2], u32x4 (&xp)[MG ? MI : 1][2], int stage_off,
                      const StageCtx& sc) {
     if constexpr (MG) {
       constexpr int NB = NI + MI;
@@ -349,20 +347,20 @@
         constexpr int bi = decltype(bc)::value;
         if (lab & 2) return;
         if constexpr (bi == 0) {
-          w8[0][0] = pp_lds_read128<0>(b0 + w_base);
-          w8[0][1] = pp_lds_read128<0>(b1 + w_base);
+          w8[0][0] = lds_read128<0>(b0 + w_base);
+          w8[0][1] = lds_read128<0>(b1 + w_base);
         } else if constexpr (bi <= MI) {
-          xc[bi - 1][0] = pp_lds_read128<(bi - 1) * 2048>(b0 + x_base);
-          xc[bi - 1][1] = pp_lds_read128<(bi - 1) * 2048>(b1 + x_base);
+          xc[bi - 1][0] = lds_read128<(bi - 1) * 2048>(b0 + x_base);
+          xc[bi - 1][1] = lds_read128<(bi - 1) * 2048>(b1 + x_base);
         } else {
-          w8[bi - MI][0] = pp_lds_read128<(bi - MI) * 2048>(b0 + w_base);
-          w8[bi - MI][1] = pp_lds_read128<(bi - MI) * 2048>(b1 + w_base);
+          w8[bi - MI][0] = lds_read128<(bi - MI) * 2048>(b0 + w_base);
+          w8[bi - MI][1] = lds_read128<(bi - MI) * 2048>(b1 + w_base);
         }
       };
       rd_block(std::integral_constant<int, 0>{});
       rd_block(std::integral_constant<int, 1>{});
       __builtin_amdgcn_sched_barrier(0);
-      pp_static_for<0, MI * NI>([&](auto mc) {
+      static_for<0, MI * NI>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         if constexpr (m < MI) {
           if (!(lab & 4)) mfma8(acc[NI - 1][m], w8[NI - 1], xp[m], wsc8[FP8 ? NI - 1 : 0]);   // held back from the previous tile
@@ -385,7 +383,7 @@
         __builtin_amdgcn_sched_barrier(0);
       });
       static_assert(MI + 2 * (NPMAX - 1) + 1 < MI * NI, "merged schedule: a staging slot behind an MFMA for every piece");
-      pp_wait_lgkm0();       // every read of the tile is back (the last weight block included)
+      wait_lgkm_fenced<0>();       // every read of the tile is back (the last weight block included)
     }
   };
 
@@ -397,7 +395,7 @@
     stage(0);
     stage(SLOT);
     auto tile = [&](auto& xc, auto& xp) {
-      if (g == 0) pp_wait_vm<NP0>(); else pp_wait_vm<NP1>();
+      if (g == 0) wait_vm<NP0>(); else wait_vm<NP1>();
       __builtin_amdgcn_s_barrier();
       // (gathers: tap masks only -- the launcher sends upsampled convolutions to the phased schedule)
       const StageCtx sc = stage_begin(kw);
@@ -410,7 +408,7 @@
       tile(xb8, xa8);
     }
     if (KT & 1) tile(xa8, xb8);
-    pp_wait_vm<0>();          // the out-of-range pieces of tiles KT, KT + 1 (zero fill) before the epilogue reuses the LDS
+    wait_vm<0>();          // the out-of-range pieces of tiles KT, KT + 1 (zero fill) before the epilogue reuses the LDS
     if (KT & 1) {
 #pragma unroll
       for (int j = 0; j < MI; ++j) mfma8(acc[NI - 1][j], w8[NI - 1], xa8[j], wsc8[FP8 ? NI - 1 : 0]);
@@ -421,23 +419,23 @@
     __builtin_amdgcn_s_barrier();
   } else {
     // ---- phased schedule, prologue: tile 0 (group 1 also tile 1) in flight; group 1's part of tile 0 landed ----
-    auto wait_keep1 = [&]() { if (g == 0) pp_wait_vm<NP0>(); else pp_wait_vm<NP1>(); };
+    auto wait_keep1 = [&]() { if (g == 0) wait_vm<NP0>(); else wait_vm<NP1>(); };
     stage(0);
     if (g == 1) {
-      if (KT > 1) { stage(SLOT); wait_keep1(); } else pp_wait_vm<0>();
+      if (KT > 1) { stage(SLOT); wait_keep1(); } else wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();
     if (g == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one interval behind
     auto dphase = [&](int t) {
       if (g == 0) {
-        if (t + 1 < KT) { stage(w0); wait_keep1(); } else pp_wait_vm<0>();   // own part of tile t landed
+        if (t + 1 < KT) { stage(w0); wait_keep1(); } else wait_vm<0>();   // own part of tile t landed
       } else {
         if (t + 2 < KT) stage(w1);
       }
       __builtin_amdgcn_s_barrier();
     };
     auto cend = [&](int t) {
-      if (g == 1) { if (t + 2 < KT) wait_keep1(); else pp_wait_vm<0>(); }    // own part of tile t+1 landed
+      if (g == 1) { if (t + 2 < KT) wait_keep1(); else wait_vm<0>(); }    // own part of tile t+1 landed
       __builtin_amdgcn_s_barrier();
       const int tmp = rd; rd = w0; w0 = w1; w1 = tmp;
     };
@@ -447,9 +445,9 @@
       // ---------------- C(t) ----------------
       __builtin_amdgcn_s_setprio(1);
       half(rd, U0, U1);      // (t == 0: MFMAs on the zeroed fragments of "unit -1")
-      pp_wait_lgkm0();
+      wait_lgkm_fenced<0>();
       half(rd, U1, U0);
-      pp_wait_lgkm0();       // every read of tile t is back: the barrier below releases its slot
+      wait_lgkm_fenced<0>();       // every read of tile t is back: the barrier below releases its slot
       __builtin_amdgcn_s_setprio(0);
       cend(t);
     }

@@ -18,50 +18,16 @@
 // a tile is one whole image x 80 columns -- 16 x 16 = 256 tiles, so no K slices, no slabs, no reduce launch (round 3: 256 x 160
 // tiles over two slices + reduce) -- its 18 x 18 halo (324 pixels) resident per chunk; bias, time-embedding row and residual are
 // applied on the accumulators and the bf16 rows leave through a wave-private transposition tile as 16-byte stores.
+#include "af_device.h"
 #include "af_kernels.h"
-
-#include <type_traits>
 
 namespace cs8 {
 typedef bf16 T;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 constexpr int BM = 256, BN = 80, NI = 5, MI = 2, SPLITK = 4;
 constexpr int HSLOTS = 448, HBUF = HSLOTS * 128, NHQ = HSLOTS / 8 / 8;     // 56 pieces of 8 pixels: 7 per wave and chunk
 constexpr int WBYTES = BN * 128, WPIECES = BN / 8, D = 3, NS = 4;
 constexpr int W_BASE = 2 * HBUF, LDS_BYTES = W_BASE + NS * WBYTES;         // 114688 + 40960 = 155648
 static_assert(LDS_BYTES <= 160 * 1024 && NHQ == 7, "LDS plan");
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_base, unsigned voffset, unsigned soffset) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
-#endif
-}
-__device__ __forceinline__ u32x4 lds_read128(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read128o(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkm2(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_lgkm4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 template <int SPLITK_T>
 __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p) {
@@ -72,8 +38,8 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
   const int tm = blockIdx.x / ntn, tn = blockIdx.x - tm * ntn;   // (consecutive ids share the row tile = its halo: same XCD or not, L2 or MALL)
   const int m0 = tm * BM, n0 = tn * BN, zk = blockIdx.z;
   const int nch = (p.Cin >> 6) / SPLITK_T, chunk0 = zk * nch;    // this slice's channel chunks
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(p.src)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(p.W)), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.src);
+  const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(p.W);
 
   // ---- halo pieces of this wave: piece wid + 8 q covers halo slots 8 piece .. + 7 (lane >> 3 = slot, lane & 7 = 16-byte chunk);
   // slot hp = HP1 img + HW hy + hx holds input pixel (hy - 1, hx - 1) of image (img0 + img); slots past the last image: nothing ----
@@ -174,56 +140,53 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
         xs[cs][j][0] = lds_read128(xa[j]);
         xs[cs][j][1] = lds_read128(xa[j] ^ 64u);
       }
-      wf[0][0] = lds_read128o<0 * 2048>(wa0); wf[0][1] = lds_read128o<0 * 2048>(wa1);
-      wf[1][0] = lds_read128o<1 * 2048>(wa0); wf[1][1] = lds_read128o<1 * 2048>(wa1);
-      wf[2][0] = lds_read128o<2 * 2048>(wa0); wf[2][1] = lds_read128o<2 * 2048>(wa1);
+      wf[0][0] = lds_read128<0 * 2048>(wa0); wf[0][1] = lds_read128<0 * 2048>(wa1);
+      wf[1][0] = lds_read128<1 * 2048>(wa0); wf[1][1] = lds_read128<1 * 2048>(wa1);
+      wf[2][0] = lds_read128<2 * 2048>(wa0); wf[2][1] = lds_read128<2 * 2048>(wa1);
       __builtin_amdgcn_sched_barrier(0);
       // ---- the previous step's blocks 3, 4 (registers only) ----
 #pragma unroll
       for (int b2 = 0; b2 < 2; ++b2)
 #pragma unroll
         for (int j = 0; j < MI; ++j) {
-          acc[3 + b2][j] = mma(wh[ps][b2][0], xs[ps][j][0], acc[3 + b2][j]);
-          acc[3 + b2][j] = mma(wh[ps][b2][1], xs[ps][j][1], acc[3 + b2][j]);
+          acc[3 + b2][j] = mma16(wh[ps][b2][0], xs[ps][j][0], acc[3 + b2][j]);
+          acc[3 + b2][j] = mma16(wh[ps][b2][1], xs[ps][j][1], acc[3 + b2][j]);
           asm volatile("" : "+v"(acc[3 + b2][j]));
         }
       __builtin_amdgcn_sched_barrier(0);
       // ---- blocks 0, 1, 2 of this step; blocks 3, 4 are read for the next one ----
-      wait_lgkm4<4>(xs[cs][0][0], xs[cs][0][1], xs[cs][1][0], xs[cs][1][1]);
-      wait_lgkm2<4>(wf[0][0], wf[0][1]);
+      wait_lgkm<4>(xs[cs][0][0], xs[cs][0][1], xs[cs][1][0], xs[cs][1][1]);
+      wait_lgkm<4>(wf[0][0], wf[0][1]);
 #pragma unroll
       for (int j = 0; j < MI; ++j) {
-        acc[0][j] = mma(wf[0][0], xs[cs][j][0], acc[0][j]);
-        acc[0][j] = mma(wf[0][1], xs[cs][j][1], acc[0][j]);
+        acc[0][j] = mma16(wf[0][0], xs[cs][j][0], acc[0][j]);
+        acc[0][j] = mma16(wf[0][1], xs[cs][j][1], acc[0][j]);
         asm volatile("" : "+v"(acc[0][j]));
       }
-      wh[cs][0][0] = lds_read128o<3 * 2048>(wa0); wh[cs][0][1] = lds_read128o<3 * 2048>(wa1);
+      wh[cs][0][0] = lds_read128<3 * 2048>(wa0); wh[cs][0][1] = lds_read128<3 * 2048>(wa1);
       __builtin_amdgcn_sched_barrier(0);
-      wait_lgkm2<4>(wf[1][0], wf[1][1]);
+      wait_lgkm<4>(wf[1][0], wf[1][1]);
 #pragma unroll
       for (int j = 0; j < MI; ++j) {
-        acc[1][j] = mma(wf[1][0], xs[cs][j][0], acc[1][j]);
-        acc[1][j] = mma(wf[1][1], xs[cs][j][1], acc[1][j]);
+        acc[1][j] = mma16(wf[1][0], xs[cs][j][0], acc[1][j]);
+        acc[1][j] = mma16(wf[1][1], xs[cs][j][1], acc[1][j]);
         asm volatile("" : "+v"(acc[1][j]));
       }
       // the slot the previous step left: weights of step + D; then (taps 0-6) one halo piece of the next chunk
       stage_w(c * 9 + tap + D, (slot + D) & (NS - 1));
       if constexpr (tap < NHQ) stage_h(std::integral_constant<int, tap>{}, hb ^ 1, c + 1);
-      wh[cs][1][0] = lds_read128o<4 * 2048>(wa0); wh[cs][1][1] = lds_read128o<4 * 2048>(wa1);
+      wh[cs][1][0] = lds_read128<4 * 2048>(wa0); wh[cs][1][1] = lds_read128<4 * 2048>(wa1);
       __builtin_amdgcn_sched_barrier(0);
-      wait_lgkm2<4>(wf[2][0], wf[2][1]);
+      wait_lgkm<4>(wf[2][0], wf[2][1]);
 #pragma unroll
       for (int j = 0; j < MI; ++j) {
-        acc[2][j] = mma(wf[2][0], xs[cs][j][0], acc[2][j]);
-        acc[2][j] = mma(wf[2][1], xs[cs][j][1], acc[2][j]);
+        acc[2][j] = mma16(wf[2][0], xs[cs][j][0], acc[2][j]);
+        acc[2][j] = mma16(wf[2][1], xs[cs][j][1], acc[2][j]);
         asm volatile("" : "+v"(acc[2][j]));
       }
       __builtin_amdgcn_sched_barrier(0);
       // every read of this step's slot is back before the wave reaches the next barrier (the slot is restaged behind it)
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(wh[cs][0][0]), "+v"(wh[cs][0][1]), "+v"(wh[cs][1][0]), "+v"(wh[cs][1][1])
-                   :
-                   : "memory");
+      wait_lgkm<0>(wh[cs][0][0], wh[cs][0][1], wh[cs][1][0], wh[cs][1][1]);
       slot = (slot + 1) & (NS - 1);
     });
     // tap 8 left its fragments in set 0; tap 0 of the next chunk looks for them in set 1
@@ -238,8 +201,8 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
   for (int b2 = 0; b2 < 2; ++b2)
 #pragma unroll
     for (int j = 0; j < MI; ++j) {
-      acc[3 + b2][j] = mma(wh[1][b2][0], xs[1][j][0], acc[3 + b2][j]);
-      acc[3 + b2][j] = mma(wh[1][b2][1], xs[1][j][1], acc[3 + b2][j]);
+      acc[3 + b2][j] = mma16(wh[1][b2][0], xs[1][j][0], acc[3 + b2][j]);
+      acc[3 + b2][j] = mma16(wh[1][b2][1], xs[1][j][1], acc[3 + b2][j]);
     }
   wait_vm<0>();   // (dead pieces of the steps past the end: none may land after the workgroup has gone)
 
@@ -291,7 +254,7 @@ __global__ __launch_bounds__(512) void conv3x3_s8_kernel(const ConvGemmParams p)
         o.store(reinterpret_cast<T*>(otile + (j * 16 + l15) * OPITCH) + i * 16 + cl);
       }
     }
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(p.out), 0, (int)0xFFFFFFF0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(p.out);
     u32x4 chunk[NST];
     unsigned orow[NST];
 #pragma unroll
@@ -325,20 +288,12 @@ int af_conv_s8_slices(const ConvGemmParams& p, int batch) {
           (long)(p.M / cs8::BM) * (p.N / cs8::BN) >= 128) ? 1 : 0;
 }
 int af_launch_conv_s8(const ConvGemmParams& p, hipStream_t stream) {
-  static unsigned long long attr_done4 = 0, attr_done1 = 0;
   const int sl = af_conv_s8_slices(p, 1);
   if (sl == 0 || p.splitk != sl || (sl > 1 && !p.ws) || p.wo_shift < 3 || p.howo_shift < p.wo_shift) {
     af_set_error_msg("conv_s8: shape / slice count %d not taken by the small-map kernel", p.splitk);
     return -1;
   }
   const dim3 grid((p.M / cs8::BM) * (p.N / cs8::BN), 1, sl);
-  if (sl > 1) {
-    if (int rc = af_ensure_dynamic_lds(attr_done4, reinterpret_cast<const void*>(&cs8::conv3x3_s8_kernel<cs8::SPLITK>), cs8::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(cs8::conv3x3_s8_kernel<cs8::SPLITK>, grid, dim3(512), cs8::LDS_BYTES, stream, p);
-  } else {
-    if (int rc = af_ensure_dynamic_lds(attr_done1, reinterpret_cast<const void*>(&cs8::conv3x3_s8_kernel<1>), cs8::LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(cs8::conv3x3_s8_kernel<1>, grid, dim3(512), cs8::LDS_BYTES, stream, p);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
+  if (sl > 1) return af_launch_lds<cs8::conv3x3_s8_kernel<cs8::SPLITK>>(grid, dim3(512), cs8::LDS_BYTES, cs8::LDS_BYTES, stream, p);
+  return af_launch_lds<cs8::conv3x3_s8_kernel<1>>(grid, dim3(512), cs8::LDS_BYTES, cs8::LDS_BYTES, stream, p);
 }

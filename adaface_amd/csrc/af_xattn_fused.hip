@@ -30,14 +30,11 @@
 //
 // Per workgroup 1184 MFMAs per wave against ~40 KB of x + out traffic; the three launches it replaces moved 5 x that.
 // f32 (parity) mode, other widths / head sizes, conv attention (needs the log-sum-exp) and > 80 keys keep the unfused path.
+#include "af_device.h"
 #include "af_kernels.h"
-
-#include <type_traits>
 
 namespace xf {
 typedef bf16 T;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int C = 320, H = 8, DH = 40, KC = 5, NPAIR = 4;
 constexpr int BNT = 80, NIW = 5, NTILE = 4;          // 80-column tiles = one head pair; 16-column blocks per tile
@@ -137,36 +134,6 @@ __global__ __launch_bounds__(256) void permute_wo_kernel(const bf16* __restrict_
   }
 }
 
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_base, unsigned voffset, unsigned soffset) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
-#endif
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read128(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// the wait names the registers it covers ("+v"): no consumer of them can be scheduled above it
-template <int N> __device__ __forceinline__ void wait_lgkm(u32x4& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkm2(u32x4& a, u32x4& b) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-__device__ __forceinline__ f32x4 mma(const u32x4& a, const u32x4& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ unsigned pack2(float a, float b) {   // one v_cvt_pk_bf16_f32 (element 0 = low half)
   typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
@@ -223,13 +190,12 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
   const int l15 = lane & 15, g = lane >> 4;
   const int m0 = blockIdx.x * BM, r0 = m0 + wid * WROWS;
   const int bsample = m0 / p.rows_per_sample;
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(p.x)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wq = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(p.wq)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wo = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(p.wo)), 0, (int)0xFFFFFFF0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_kv = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(reinterpret_cast<const T*>(p.kvpack) + (long)bsample * NPAIR * PACK_ELEMS_PER_PAIR), 0,
-      (int)(NPAIR * PACK_ELEMS_PER_PAIR * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(p.out), 0, (int)0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(p.x);
+  const __amdgpu_buffer_rsrc_t rs_wq = buffer_rsrc(p.wq);
+  const __amdgpu_buffer_rsrc_t rs_wo = buffer_rsrc(p.wo);
+  const __amdgpu_buffer_rsrc_t rs_kv = buffer_rsrc(reinterpret_cast<const T*>(p.kvpack) + (long)bsample * NPAIR * PACK_ELEMS_PER_PAIR,
+                                                       (int)(NPAIR * PACK_ELEMS_PER_PAIR * 2));
+  const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(p.out);
 
   // ---- K / V packs of a head pair -> buffer (pair & 1): KV_PPW pieces per wave, lane-linear ----
   auto stage_kv = [&](int pair) {
@@ -250,7 +216,7 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
     const float4 val = src ? *reinterpret_cast<const float4*>(src + 4 * c4) : float4{0.f, 0.f, 0.f, 0.f};
     *reinterpret_cast<float4*>(smem + VEC0 + (v * C + 4 * c4) * 4) = val;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (visible to the other waves after the first step's barrier)
+  wait_lgkm<0>();   // (visible to the other waves after the first step's barrier)
 
   // ---- the wave's 32 rows as MFMA B fragments: block j, K chunk kc, half u -> k = 64 kc + 32 u + 8 g ----
   u32x4 xr[MJ][KC][2];
@@ -273,9 +239,7 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
         s1 += pq2.x;
         s2 += pq2.y;
       }
-      const float mu = s1 * p.ln_inv_count;
-      const float var = fmaxf(s2 * p.ln_inv_count - mu * mu, 0.f);
-      st = float2{mu, __builtin_amdgcn_rsqf(var + p.ln_eps)};
+      st = ln_mu_rstd(s1, s2, p.ln_inv_count, p.ln_eps);
     } else if (ok) {
       st = *reinterpret_cast<const float2*>(p.ln_stats + (long)m * 2);
     }
@@ -339,18 +303,18 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
     static_for<0, NIW>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       constexpr int issued = (i + 3) < NIW ? (i + 3) : NIW;
-      wait_lgkm2<2 * (issued - i - 1)>(wf[i][0], wf[i][1]);
+      wait_lgkm<2 * (issued - i - 1)>(wf[i][0], wf[i][1]);
 #pragma unroll
       for (int j = 0; j < MJ; ++j) {
-        acc[i][j] = mma(wf[i][0], b0[j], first ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[i][j]);
-        acc[i][j] = mma(wf[i][1], b1[j], acc[i][j]);
+        acc[i][j] = mma16(wf[i][0], b0[j], first ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[i][j]);
+        acc[i][j] = mma16(wf[i][1], b1[j], acc[i][j]);
         asm volatile("" : "+v"(acc[i][j]));
       }
       if constexpr (i + 3 < NIW) rd(std::integral_constant<int, i + 3>{});
       if constexpr (i == 1) stage(t + D, stage_slot);
       __builtin_amdgcn_sched_barrier(0);
     });
-    wait_lgkm0();
+    wait_lgkm_fenced<0>();
   };
 
 #pragma unroll
@@ -387,7 +351,7 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
       u32x2 qb[NIW][MJ];
       static_for<0, NIW>([&](auto ic) {
         constexpr int k = decltype(ic)::value;
-        wait_lgkm2<2 * (NIW - 1 - k)>(csv[k], bvv[k]);
+        wait_lgkm<2 * (NIW - 1 - k)>(csv[k], bvv[k]);
         const f32x4 cs = __builtin_bit_cast(f32x4, csv[k]), bv = __builtin_bit_cast(f32x4, bvv[k]);
 #pragma unroll
         for (int j = 0; j < MJ; ++j) {
@@ -444,11 +408,11 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
         });
         static_for<0, NKB>([&](auto kbc) {
           constexpr int kb = decltype(kbc)::value;
-          wait_lgkm2<2 * (NKB - 1 - kb)>(kf[kb][0], kf[kb][1]);
+          wait_lgkm<2 * (NKB - 1 - kb)>(kf[kb][0], kf[kb][1]);
 #pragma unroll
           for (int j = 0; j < MJ; ++j) {
-            sc[j][kb] = mma(kf[kb][0], hh == 0 ? qA[pr][j] : qB[pr][j], f32x4{0.f, 0.f, 0.f, 0.f});
-            sc[j][kb] = mma(kf[kb][1], qC[pr / 2][j], sc[j][kb]);
+            sc[j][kb] = mma16(kf[kb][0], hh == 0 ? qA[pr][j] : qB[pr][j], f32x4{0.f, 0.f, 0.f, 0.f});
+            sc[j][kb] = mma16(kf[kb][1], qC[pr / 2][j], sc[j][kb]);
           }
         });
         // every S^T MFMA is ISSUED here: hipcc otherwise sinks some of them into the v_max3 chains below, which read their
@@ -519,10 +483,10 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
         }
         static_for<0, NSP>([&](auto spc) {
           constexpr int sp = decltype(spc)::value;
-          ls[j] = mma(ones, pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : ls[j]);
-          o0[j] = mma(vf[0][sp], pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : o0[j]);
-          o1[j] = mma(vf[1][sp], pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : o1[j]);
-          oc[j] = mma(vf[2][sp], pb[sp], (hh == 0 && sp == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : oc[j]);
+          ls[j] = mma16(ones, pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : ls[j]);
+          o0[j] = mma16(vf[0][sp], pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : o0[j]);
+          o1[j] = mma16(vf[1][sp], pb[sp], sp == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : o1[j]);
+          oc[j] = mma16(vf[2][sp], pb[sp], (hh == 0 && sp == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : oc[j]);
         });
       });
       // normalise; O tuples take the place of the q tuples they came from
@@ -573,7 +537,7 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
 #pragma unroll
       for (int j = 0; j < MJ; ++j) acc3[i][j] = __builtin_bit_cast(f32x4, lds_read128<i * 64>(va));
     });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
 #pragma unroll
     for (int i = 0; i < NIW3; ++i)
 #pragma unroll
@@ -596,18 +560,18 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
     static_for<0, NIW3>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       constexpr int issued = (i + 3) < NIW3 ? (i + 3) : NIW3;
-      wait_lgkm2<2 * (issued - i - 1)>(wf3[i][0], wf3[i][1]);
+      wait_lgkm<2 * (issued - i - 1)>(wf3[i][0], wf3[i][1]);
 #pragma unroll
       for (int j = 0; j < MJ; ++j) {
-        acc3[i][j] = mma(wf3[i][0], b0[j], acc3[i][j]);
-        acc3[i][j] = mma(wf3[i][1], b1[j], acc3[i][j]);
+        acc3[i][j] = mma16(wf3[i][0], b0[j], acc3[i][j]);
+        acc3[i][j] = mma16(wf3[i][1], b1[j], acc3[i][j]);
         asm volatile("" : "+v"(acc3[i][j]));
       }
       if constexpr (i + 3 < NIW3) rd(std::integral_constant<int, i + 3>{});
       if constexpr (i == 1) stage3(t + D3, stage_slot);
       __builtin_amdgcn_sched_barrier(0);
     });
-    wait_lgkm0();
+    wait_lgkm_fenced<0>();
   };
   // vmcnt at the head of a phase-3 step: everything but the pieces of the next step -- and, while they are younger than the
   // pieces waited for, the previous epilogue's NST stores + the NRES residual pieces issued behind them (tile 0: the residual
@@ -702,7 +666,7 @@ __global__ __launch_bounds__(512) void xattn_fused_kernel(const Params p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (nt + 1 < NTILE3) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the tile's chunks are in registers before the next residual lands on it)
+      wait_lgkm<0>();   // (the tile's chunks are in registers before the next residual lands on it)
       stage_res(nt + 1);
       init_acc3((nt + 1) * BN3);
     }
@@ -743,8 +707,6 @@ int af_launch_xattn_fused(const AfXattnFusedParams& a, hipStream_t stream) {
     af_set_error_msg("xattn_fused: unsupported shape M=%d rows/sample=%d Nk=%d", a.M, a.rows_per_sample, a.Nk);
     return -1;
   }
-  static unsigned long long attr_done = 0;
-  if (int rc = af_ensure_dynamic_lds(attr_done, reinterpret_cast<const void*>(&xf::xattn_fused_kernel), xf::LDS_BYTES)) return rc;
   xf::Params p;
   p.x = a.x; p.ldx = a.ldx; p.M = a.M;
   p.ln_stats = a.ln_stats; p.ln_parts_n = a.ln_parts_n; p.ln_inv_count = a.ln_inv_count; p.ln_eps = a.ln_eps;
@@ -757,8 +719,7 @@ int af_launch_xattn_fused(const AfXattnFusedParams& a, hipStream_t stream) {
   // algorithmic work of the three launches it replaces: two [M, 320] x [320, 320] projections + the attention
   const double flops = 2.0 * 2.0 * a.M * (double)xf::C * xf::C + 4.0 * a.M * (double)a.Nk * xf::C;
   AfProfScope prof(AF_K_ATTENTION, stream, flops, 2.0 * a.M * (double)xf::C * 2);
-  hipLaunchKernelGGL(xf::xattn_fused_kernel, dim3(a.M / xf::BM), dim3(512), xf::LDS_BYTES, stream, p);
-  HIP_CHECK_RET(hipGetLastError());
+  if (int rc = af_launch_lds<xf::xattn_fused_kernel>(dim3(a.M / xf::BM), dim3(512), xf::LDS_BYTES, xf::LDS_BYTES, stream, p)) return rc;
   g_af_xattn_fused_launches += 1;
   return 0;
 }

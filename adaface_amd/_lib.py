@@ -124,6 +124,7 @@ _SIGS = [
     ("af_xattn_fused_launches", C.c_int64, []),
     ("af_conv_attn_short_launches", C.c_int64, []),
     ("af_op_conv_attention", C.c_int, [C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3 + [_P]),
+    ("af_op_vae_attention", C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int), _P]),
     ("af_op_xattn_fused", C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p]),
     ("af_op_conv2d_fp8", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 10 + [_P]),
     ("af_op_groupnorm_fp8", C.c_int, [_P, _P, _P, C.c_float, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

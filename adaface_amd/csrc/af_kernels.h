@@ -119,6 +119,21 @@ int af_launch_lincomb(float* out, long n, const float* x0, float w0, const float
 template <typename T> int af_launch_softmax_rows(void* x, int ld, int ncols, long rows, hipStream_t s);
 template <typename T>
 int af_launch_transpose(const void* x, long x_bs, int ldx, void* y, long y_bs, int R, int Cn, int B, hipStream_t s);
+// The VAE AttnBlock between its qkv convolution and proj_out (model.py:179-242; defined in af_model.hip, which calls it with
+// taps = null; af_op_vae_attention is the other caller): qkv [B][N][3C] of storage type `dtype` (q | k | v per position) ->
+//   sc [B][N][N]  = C^-1/2 q k^T, stored, then softmax_rows_kernel in place,
+//   vt [B][C][N]  = v^T,
+//   out [B][N][C] = P v (contraction over the N positions: N must be a multiple of the K tile, af_vae_attn_shape_ok).
+// Both GEMMs are batched (blockIdx.z) launches of af_launch_conv_gemm without a caller's plan.
+struct AfVaeAttnTaps {
+  void* scores;      // device [B][N][N] of `dtype` or null: the stored scores before the softmax (copied between the launches)
+  void* probs;       // ... P after it
+  int plans[2][3];   // (kernel, tile, splitk) of the scores GEMM and of the P v GEMM, from af_get_last_plan()
+};
+// false + the error message when N positions cannot be contracted over (nothing is launched for such a shape)
+bool af_vae_attn_shape_ok(int dtype, int N);
+int af_vae_attn_core(int dtype, void* qkv, void* sc, void* vt, void* out, int B, int N, int C, hipStream_t s,
+                     AfVaeAttnTaps* taps = nullptr);
 template <typename T> int af_launch_to_uint8(const void* x, int ld, uint8_t* y, long npix, hipStream_t s);
 int af_launch_nchw_to_uint8(const float* x, uint8_t* y, int B, int HW, hipStream_t s);
 

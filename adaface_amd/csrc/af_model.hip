@@ -1013,10 +1013,6 @@ struct Runner {
     if (dry) return 0;
     return AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, 1, s, &pl, ws));
   }
-  int gemm_raw(const ConvGemmParams& p, int batch) {
-    if (dry) return 0;
-    return AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, batch, s));
-  }
   // the record slot of an e4m3 output while af_fp8_record is on
   unsigned* fp8_rec_of(const Act& y) const { return h->fp8_recording && y.f8_site >= 0 ? h->fp8_rec + 2 * y.f8_site : nullptr; }
   int groupnorm(const Norm& N, const Act& x, Act& y, int silu) {
@@ -1779,14 +1775,54 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   return 0;
 }
 
+bool af_vae_attn_shape_ok(int dtype, int N) {
+  if (N % bk_of(dtype) == 0) return true;   // the P·V GEMM contracts over the N positions
+  af_set_error_msg("VAE mid-block attention: H*W = %d positions must be a multiple of %d", N, bk_of(dtype));
+  return false;
+}
+
+// scores GEMM, softmax, transpose, P·V GEMM of the AttnBlock (af_kernels.h)
+int af_vae_attn_core(int dt, void* qkv, void* sc, void* vt, void* out, int B, int N, int C, hipStream_t s, AfVaeAttnTaps* taps) {
+  if (!af_vae_attn_shape_ok(dt, N)) return AF_ERR_INVALID;
+  const auto elem_ptr = [dt](void* p, long off) { return reinterpret_cast<char*>(p) + off * (long)esize(dt); };
+  const auto tap = [&](void* dst, int which) -> int {
+    const AfGemmPlan pl = af_get_last_plan();
+    taps->plans[which][0] = pl.kernel; taps->plans[which][1] = pl.tile; taps->plans[which][2] = pl.splitk;
+    if (dst) HIP_CHECK_RET(hipMemcpyAsync(dst, sc, (size_t)B * N * N * esize(dt), hipMemcpyDeviceToDevice, s));
+    return 0;
+  };
+  ConvGemmParams p;
+  memset(&p, 0, sizeof(p));
+  // scores[b][i][j] = C^-0.5 * sum_c q[b][i][c] k[b][j][c]
+  p.src = qkv; p.src_batch_stride = 0; p.ldc = 3 * C; p.Cin = C;
+  p.Hs = 1; p.Ws = N; p.Hi = 1; p.Wi = N; p.Ho = 1; p.Wo = N; p.ks = 1; p.stride = 1; p.pad = 0;
+  p.W = elem_ptr(qkv, C); p.ldw = 3 * C; p.Wrows = N;
+  p.M = N; p.N = N; p.K = C;
+  p.out = sc; p.ldo = N; p.alpha = 1.0f / sqrtf((float)C);
+  p.bs_src = (long)N * 3 * C; p.bs_w = (long)N * 3 * C; p.bs_out = (long)N * N;
+  AF_TRY(AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, B, s)));
+  if (taps) AF_TRY(tap(taps->scores, 0));
+  AF_TRY(AF_TYPED(dt, af_launch_softmax_rows<Elem>(sc, N, N, (long)B * N, s)));
+  if (taps && taps->probs) HIP_CHECK_RET(hipMemcpyAsync(taps->probs, sc, (size_t)B * N * N * esize(dt), hipMemcpyDeviceToDevice, s));
+  AF_TRY(AF_TYPED(dt, af_launch_transpose<Elem>(elem_ptr(qkv, 2 * C), (long)N * 3 * C, 3 * C, vt, (long)C * N, N, C, B, s)));
+  // h[b][i][c] = sum_j P[b][i][j] v[b][j][c]
+  memset(&p, 0, sizeof(p));
+  p.src = sc; p.src_batch_stride = 0; p.ldc = N; p.Cin = N;
+  p.Hs = 1; p.Ws = N; p.Hi = 1; p.Wi = N; p.Ho = 1; p.Wo = N; p.ks = 1; p.stride = 1; p.pad = 0;
+  p.W = vt; p.ldw = N; p.Wrows = C;
+  p.M = N; p.N = C; p.K = N;
+  p.out = out; p.ldo = C; p.alpha = 1.0f;
+  p.bs_src = (long)N * N; p.bs_w = (long)C * N; p.bs_out = (long)N * C;
+  AF_TRY(AF_TYPED(dt, af_launch_conv_gemm<Elem>(p, B, s)));
+  if (taps) AF_TRY(tap(nullptr, 1));
+  return 0;
+}
+
 // AttnBlock.forward (model.py:179-242): single head over C channels, N = H*W tokens
 static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
   const size_t mk = R.A.mark();
   const int B = x.B, N = x.H * x.W, C = w.C, dt = R.dt;
-  if (N % bk_of(dt) != 0) {   // the P·V GEMM contracts over the N positions
-    af_set_error_msg("VAE mid-block attention: H*W = %d positions must be a multiple of %d", N, bk_of(dt));
-    return AF_ERR_INVALID;
-  }
+  if (!af_vae_attn_shape_ok(dt, N)) return AF_ERR_INVALID;   // (before anything is allocated or launched; the sizing pass too)
   Act g = R.alloc_act(B, x.H, x.W, C);
   AF_TRY(R.groupnorm(w.gn, x, g, 0));
   Act qkv = R.alloc_act(B, x.H, x.W, 3 * C);
@@ -1795,30 +1831,7 @@ static int run_vae_attn(Runner& R, const VaeAttnW& w, const Act& x, Act& out) {
   Act vt = R.alloc_act(B, C, 1, N);       // v^T   [B][C][N]
   Act hh = R.alloc_act(B, x.H, x.W, C);
   AF_TRY(R.check(hh));
-  if (!R.dry) {
-    ConvGemmParams p;
-    memset(&p, 0, sizeof(p));
-    // scores[b][i][j] = C^-0.5 * sum_c q[b][i][c] k[b][j][c]
-    p.src = qkv.p; p.src_batch_stride = 0; p.ldc = 3 * C; p.Cin = C;
-    p.Hs = 1; p.Ws = N; p.Hi = 1; p.Wi = N; p.Ho = 1; p.Wo = N; p.ks = 1; p.stride = 1; p.pad = 0;
-    p.W = R.elem_ptr(qkv.p, C); p.ldw = 3 * C; p.Wrows = N;
-    p.M = N; p.N = N; p.K = C;
-    p.out = sc.p; p.ldo = N; p.alpha = 1.0f / sqrtf((float)C);
-    p.bs_src = (long)N * 3 * C; p.bs_w = (long)N * 3 * C; p.bs_out = (long)N * N;
-    AF_TRY(R.gemm_raw(p, B));
-    AF_TRY(AF_TYPED(dt, af_launch_softmax_rows<Elem>(sc.p, N, N, (long)B * N, R.s)));
-    AF_TRY(AF_TYPED(dt, af_launch_transpose<Elem>(R.elem_ptr(qkv.p, 2 * C), (long)N * 3 * C, 3 * C, vt.p, (long)C * N, N, C, B,
-                                                  R.s)));
-    // h[b][i][c] = sum_j P[b][i][j] v[b][j][c]
-    memset(&p, 0, sizeof(p));
-    p.src = sc.p; p.src_batch_stride = 0; p.ldc = N; p.Cin = N;
-    p.Hs = 1; p.Ws = N; p.Hi = 1; p.Wi = N; p.Ho = 1; p.Wo = N; p.ks = 1; p.stride = 1; p.pad = 0;
-    p.W = vt.p; p.ldw = N; p.Wrows = C;
-    p.M = N; p.N = C; p.K = N;
-    p.out = hh.p; p.ldo = C; p.alpha = 1.0f;
-    p.bs_src = (long)N * N; p.bs_w = (long)C * N; p.bs_out = (long)N * C;
-    AF_TRY(R.gemm_raw(p, B));
-  }
+  if (!R.dry) AF_TRY(af_vae_attn_core(dt, qkv.p, sc.p, vt.p, hh.p, B, N, C, R.s));
   AF_TRY(R.conv(w.proj_out, hh, out, ConvOpt().res(&x)));
   R.A.release(mk);
   return 0;

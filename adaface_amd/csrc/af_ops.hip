@@ -753,6 +753,66 @@ int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, cons
   return 0;
 }
 
+// The VAE AttnBlock between its qkv convolution and proj_out, on the launches run_vae_attn (af_model.hip) makes: q | k | v
+// interleaved into one [B][N][3C] buffer, then af_vae_attn_core.  Test hooks around the core: 128 rows of NaN behind the qkv
+// buffer (a ragged tile of the last sample's K rows must be zero-filled, not read), the sentinel in the whole scores, V^T and
+// output buffers before the run and in 4 KiB behind each of them, which must still hold it afterwards.
+int af_op_vae_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int N, int C,
+                        float* scores_dev, float* probs_dev, int* plans6, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if ((dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) || !q_dev || !k_dev || !v_dev || !o_dev ||
+      B <= 0 || N <= 0 || C <= 0 || C % bk_of(dtype) != 0 || (double)B * N * std::max(N, C) >= 1073741824.0) {
+    af_set_error_msg("af_op_vae_attention: dtype=%d B=%d N=%d C=%d (C: a multiple of the K tile; B * N * max(N, C) below 2^30)", dtype, B,
+                     N, C);
+    return AF_ERR_INVALID;
+  }
+  if (!af_vae_attn_shape_ok(dtype, N)) return AF_ERR_INVALID;   // (before anything is allocated or launched)
+  const size_t es = esize(dtype), guard = 4096;
+  const long nx = (long)B * N * C, nn = (long)B * N * N, ng = (long)(guard / es);
+  const size_t tail = (size_t)128 * 3 * C * es;
+  OP_ALLOC(qn, (size_t)nx * es, false);
+  OP_ALLOC(kn, (size_t)nx * es, false);
+  OP_ALLOC(vn, (size_t)nx * es, false);
+  OP_ALLOC(qkv, (size_t)3 * nx * es + tail, false);
+  OP_ALLOC(sc, (size_t)nn * es + guard, false);
+  OP_ALLOC(vt, (size_t)nx * es + guard, false);
+  OP_ALLOC(on, (size_t)nx * es + guard, false);
+  HIP_CHECK_RET(hipMemsetAsync((char*)qkv + (size_t)3 * nx * es, 0xFF, tail, s));   // 0xFFFF / 0xFFFFFFFF: NaN
+  AF_TRY(fill_cols_dt(dtype, sc, 1, (int)(nn + ng), 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(dtype, vt, 1, (int)(nx + ng), 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(dtype, on, 1, (int)(nx + ng), 0, OP_SENTINEL, s));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(q_dev, qn, nx, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(k_dev, kn, nx, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(v_dev, vn, nx, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(qn, C, qkv, 3 * C, 0, C, (long)B * N, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(kn, C, qkv, 3 * C, C, C, (long)B * N, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(vn, C, qkv, 3 * C, 2 * C, C, (long)B * N, s)));
+  AfVaeAttnTaps taps;
+  memset(&taps, 0, sizeof(taps));
+  if (scores_dev) { taps.scores = tmp.get((size_t)nn * es); if (!taps.scores) return AF_ERR_HIP; }
+  if (probs_dev) { taps.probs = tmp.get((size_t)nn * es); if (!taps.probs) return AF_ERR_HIP; }
+  void* const guards[3] = {(char*)sc + (size_t)nn * es, (char*)vt + (size_t)nx * es, (char*)on + (size_t)nx * es};
+  static const char* const guard_names[3] = {"scores", "V^T", "output"};
+  std::vector<unsigned char> before(3 * guard), after(3 * guard);
+  for (int i = 0; i < 3; ++i) HIP_CHECK_RET(hipMemcpyAsync(before.data() + i * guard, guards[i], guard, hipMemcpyDeviceToHost, s));
+  AF_TRY(af_vae_attn_core(dtype, qkv, sc, vt, on, B, N, C, s, &taps));
+  for (int i = 0; i < 3; ++i) HIP_CHECK_RET(hipMemcpyAsync(after.data() + i * guard, guards[i], guard, hipMemcpyDeviceToHost, s));
+  HIP_CHECK_RET(hipStreamSynchronize(s));
+  for (int i = 0; i < 3; ++i)
+    for (size_t j = 0; j < guard; ++j)
+      if (before[i * guard + j] != after[i * guard + j]) {
+        af_set_error_msg("af_op_vae_attention: byte %zu behind the %s buffer was written (B=%d N=%d C=%d dtype=%d)", j, guard_names[i],
+                         B, N, C, dtype);
+        return AF_ERR_STATE;
+      }
+  if (plans6) memcpy(plans6, taps.plans, sizeof(taps.plans));
+  if (scores_dev) AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(taps.scores, scores_dev, nn, s)));
+  if (probs_dev) AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(taps.probs, probs_dev, nn, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, nx, s)));
+  return 0;
+}
+
 // One cross-attention layer through xattn_fused_kernel (bf16), prepared as the model prepares it: LayerNorm folded into to_q
 // (af_launch_ln_fold), K / V packed per head pair, to_out's K dimension permuted.  ln_parts_out_dev (optional): [4][B * N][2]
 // partial sums of the stored rows, as the next LayerNorm's consumer reads them.

@@ -307,6 +307,34 @@ def conv_attention(q, k, v, heads, hw, ks, token_idx, scale=None, dtype="bf16", 
     return o
 
 
+GEMM_KERNELS = {1: "wave4", 2: "halo4", 3: "pp", 4: "pp_fp8", 5: "halo8", 6: "s8", 7: "up_phase4", 8: "rowpanel", 9: "m128"}
+
+
+def vae_attention(q, k, v, dtype="bf16", taps=False):
+    """The VAE mid-block attention between its qkv convolution and proj_out (model.py:179-242; af_op_vae_attention): one head
+    over C channels, softmax(C^-1/2 q k^T) v with q, k, v [B, N, C]; the scores are stored in `dtype` before the softmax, as the
+    VAE executors keep them.  Returns out [B, N, C].  taps=True: a dict of out, scores and probs ([B, N, N]: the stored scores
+    before the softmax and P after it, storage values as fp32) and plans = ((kernel, tile, splitk) of the scores GEMM, the
+    same of the P v GEMM), kernel by its GEMM_KERNELS name.  AfError where N is not a multiple of the K tile."""
+    import ctypes as C
+    lib = _lib.load()
+    q, k, v = _dev_f32(q), _dev_f32(k), _dev_f32(v)
+    if q.dim() != 3 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"vae_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must all be [B, N, C]")
+    B, N, Cn = q.shape
+    o = torch.empty_like(q)
+    sc = torch.empty(B, N, N, device=q.device, dtype=torch.float32) if taps else None
+    pr = torch.empty(B, N, N, device=q.device, dtype=torch.float32) if taps else None
+    plans = (C.c_int * 6)()
+    check(lib.af_op_vae_attention(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(o), B, N, Cn, ptr(sc), ptr(pr), plans, stream_ptr()),
+          "af_op_vae_attention")
+    if not taps:
+        return o
+    return {"out": o, "scores": sc, "probs": pr,
+            "plans": tuple((GEMM_KERNELS.get(int(plans[3 * i]), int(plans[3 * i])), int(plans[3 * i + 1]), int(plans[3 * i + 2]))
+                           for i in range(2))}
+
+
 def xattn_fused(x, gamma, beta, wq, kv, wo, bo, eps=1e-5):
     """One cross-attention layer of a 64x64-level BasicTransformerBlock in ONE kernel (bf16; attention.py:172-257, 279):
     y = x + to_out(softmax(to_q(LayerNorm(x)) K^T / sqrt(40)) V) with x [B, N, 320], kv [B, S, 640] = the context's K | V

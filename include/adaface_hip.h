@@ -423,6 +423,15 @@ int64_t af_conv_attn_short_launches(void);
  * one-pass short-key kernel (bf16, dh 40 / 80, Nk <= 96, n_groups * ks^2 < Nk; AF_ERR_INVALID with a message otherwise). */
 int af_op_conv_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Hh,
                          int Ww, int Nk, int heads, int dh, float scale, int ks, int n_groups, int path, void* stream);
+/* The VAE mid-block attention (single head over C channels) between its qkv convolution and proj_out, on the four launches the
+ * VAE executors make: q, k, v, o [B, N, C] fp32 (cast to the storage type and interleaved into the [B][N][3C] qkv tensor);
+ * scores = C^-1/2 q k^T stored in the storage type (batched GEMM), row softmax in place, v^T, o = P v (batched GEMM over the
+ * N positions).  N must be a multiple of the K tile (64; f32: 32) and C too: AF_ERR_INVALID with a message, nothing is launched.
+ * Optional outputs: scores_dev / probs_dev [B, N, N] fp32 = the stored scores before the softmax / P after it; plans6 (host) =
+ * {kernel, tile, splitk} of the scores GEMM, then of the P v GEMM (kernel as af_gemm_plan_query reports it).  Test guards: NaN
+ * rows behind the qkv tensor; AF_ERR_STATE with a message if anything was written behind the scores, v^T or output buffer. */
+int af_op_vae_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int N, int C,
+                        float* scores_dev, float* probs_dev, int* plans6, void* stream);
 /* the same layer as an operator (parity tests; /root/reference/ldm/modules/attention.py:172-257, 279): x [B, N, 320] fp32,
  * ln_stats [B * N][2] = (mean, rstd) of the bf16-rounded rows, gamma / beta [320], wq [320, 320] (to_q, no bias), kv [B, S, 640]
  * = the context's K | V projections, wo [320, 320] + bo [320] (to_out); y = x + to_out(softmax(to_q(LN(x)) K^T / sqrt(40)) V) */

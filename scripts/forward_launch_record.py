@@ -2,6 +2,7 @@
 """What the library launches and computes on every path of its model executor, for comparing two builds of it:
 
     python scripts/forward_launch_record.py --out DIR          # in each tree (the tree the script lies in is the one it runs)
+    python scripts/forward_launch_record.py --out DIR --only bf16_vae bf16_vae_encode    # these records alone
     python scripts/forward_launch_record.py --compare A B [C]  # every later record against the first
 
 SD-1.5 with synthetic weights and inputs as bench.py builds them.  One record per line of this table; each holds the
@@ -41,7 +42,7 @@ MODES = (("bf16", "bf16", "base"), ("f32", "f32", "base"), ("fp16", "fp16", "bas
 N_CLASSES = 10    # AF_K_COUNT (af_common.h)
 
 
-def record(out: Path):
+def record(out: Path, only=None):
     sys.path.insert(0, str(ROOT))
     import torch
     from adaface_amd import _lib
@@ -55,6 +56,8 @@ def record(out: Path):
 
     def capture(tag, eng, run):
         """run() -> {name: tensor}: once to size the arena and fold weights, once logged (its tensors are kept), once counted"""
+        if only and tag not in only:
+            return
         run()
         torch.cuda.synchronize()
         _lib.plan_counts(reset=True)
@@ -115,6 +118,8 @@ def record(out: Path):
         return mod.engine(dev)
 
     def unet_record(tag, ctx, run, conv_attn=False, conv_attn_short=1):
+        if only and tag not in only:
+            return
         eng = fresh(unet)
         object.__setattr__(unet, "_ctx_key", None)            # (the module's context cache no longer describes the engine)
         if conv_attn:
@@ -154,7 +159,9 @@ def record(out: Path):
             ceng = fresh(clip)
             capture("bf16_clip3", ceng, lambda: {"states": ceng.clip_text_forward3(tok_emb, 0.25, 0.25, 0.5)})
         else:
-            meta["bf16_clip"] = meta["bf16_clip3"] = {"absent": "the bench model builds no CLIP text tower"}
+            for tag in ("bf16_clip", "bf16_clip3"):
+                if not only or tag in only:
+                    meta[tag] = {"absent": "the bench model builds no CLIP text tower"}
     (out / "meta.json").write_text(json.dumps(meta, indent=1, sort_keys=True))
 
 
@@ -194,8 +201,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=Path)
     ap.add_argument("--compare", type=Path, nargs="+")
+    ap.add_argument("--only", nargs="+", metavar="RECORD", help="with --out: record only these")
     a = ap.parse_args()
     if a.out:
-        record(a.out)
+        record(a.out, set(a.only) if a.only else None)
     if a.compare:
         sys.exit(1 if compare(a.compare) else 0)

@@ -15,7 +15,7 @@ Pairs the planner can never produce, hence not here: conv_gemm_pp_kernel and the
 storage (plan_tiled: bf16 only); the bias row on a row-panel, 128 x 160 or four-phase launch (rowpanel_kind / up_phase4_ok
 refuse it) and on any linear; bottom / right padding on the LDS-halo and small-map kernels (stride 1, pad 1 only); a tile that
 straddles samples on the LDS-halo kernels (their tiles are whole image rows); alpha != 1 on row-panel kinds 2, 3 and 5 (section c
-asserts the refusal).  The batched (blockIdx.z) form of the VAE attention is out of scope.
+asserts the refusal).  The batched (blockIdx.z) form of the VAE attention: tests/test_vae_attn_gpu.py.
 """
 import functools
 import math

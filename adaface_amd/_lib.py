@@ -93,6 +93,7 @@ _SIGS = [
     ("af_gemm_plan_counts", C.c_int, [C.POINTER(C.c_int64)]),
     ("af_gemm_plan_counts_reset", C.c_int, []),
     ("af_gemm_plan_query", C.c_int, [C.c_int, C.c_int64] + [C.c_int] * 16 + [C.POINTER(C.c_int64)]),
+    ("af_norm_plan_query", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     ("af_knob_set", C.c_int, [C.c_char_p, C.c_int]),
     ("af_knob_get", C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     ("af_knob_reset", C.c_int, []),
@@ -215,6 +216,26 @@ def gemm_plan_query(dtype, M, N, K, cin_pad, ks=1, stride=1, pad=0, up=0, Hs=1, 
                                     cin_pad if ldc is None else ldc, N if ldo is None else ldo, gn_hw, gn_cpg, flags, out),
           "af_gemm_plan_query")
     return tuple(int(v) for v in out)
+
+
+GN_KERNELS = ("refused", "small", "fold", "finalize")     # AfGnKernel (csrc/af_kernels.h)
+LN_KERNELS = ("refused", "wave_row", "rowgroup")          # AfLnKernel
+_Out5 = C.c_int64 * 5
+
+
+def norm_plan_query(kind, dtype, B=1, HW=None, C=None, pre_npart=0, rows=None) -> dict:
+    """af_norm_plan_query: the plan of a norm launch, by name.  Host only: no GPU is needed.
+    kind "groupnorm" (B, HW, C[, pre_npart]): {"kernel": one of GN_KERNELS, "P", "nchunk", "npart", "wide"};
+    kind "layernorm" (rows, C): {"kernel": one of LN_KERNELS, "nv", "rows_per_block"}.  dtype: a name or an AF_DTYPE_* value."""
+    dt = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    out = _Out5()   # (the parameter C hides the ctypes module here)
+    if kind == "groupnorm":
+        check(load().af_norm_plan_query(0, dt, int(B), int(HW), int(C), int(pre_npart), out), "af_norm_plan_query")
+        return {"kernel": GN_KERNELS[out[0]], "P": int(out[1]), "nchunk": int(out[2]), "npart": int(out[3]), "wide": bool(out[4])}
+    if kind == "layernorm":
+        check(load().af_norm_plan_query(1, dt, 1, int(rows), int(C), 0, out), "af_norm_plan_query")
+        return {"kernel": LN_KERNELS[out[0]], "nv": int(out[1]), "rows_per_block": int(out[2])}
+    raise ValueError(f"norm_plan_query: kind {kind!r}")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -48,6 +48,36 @@ bool af_ff_geglu_fp8_ok(const ConvGemmParams& p);
 int af_launch_ff_geglu_fp8(ConvGemmParams p, float out_mul, unsigned* rec, hipStream_t stream);
 extern std::atomic<long> g_af_ff8_launches;
 
+// The plan of a GroupNorm(32) launch (af_norm.hip): which kernels run and how the map is cut.  The launchers follow it and
+// af_norm_plan_query reports it, so a test knows on the CPU which kernel a shape reaches.  The values are part of that result.
+enum AfGnKernel {
+  AF_GNK_REFUSED = 0,    // C the kernels do not take (C % 32, whole 16-byte vectors, C <= 2560): the launcher fails, nothing runs
+  AF_GNK_SMALL = 1,      // gn_small_kernel: one launch, a (sample, group) per workgroup held in registers
+  AF_GNK_FOLD = 2,       // gn_stats_kernel + gn_apply_kernel, whose blocks combine the <= 64 partial sums themselves
+  AF_GNK_FINALIZE = 3    // gn_stats_kernel + gn_finalize_kernel + gn_apply_kernel
+};
+struct AfGnPlan {
+  int kernel;       // AfGnKernel
+  int P;            // pixels per chunk (one workgroup of the statistics and the apply pass); 0 on SMALL / REFUSED, as all below
+  int nchunk;       // chunks per sample, ceil(HW / P): the last one holds HW - (nchunk - 1) * P pixels
+  int npart;        // partial sums per sample the statistics are combined from: nchunk, or the producer convolution's pre_npart
+  int wide_stats;   // 1: gn_stats_kernel runs and walks more than 256 vectors per pixel with its one-thread-per-column loop
+};
+// pre_npart > 0: a producer convolution left that many partial sums per sample and no statistics pass runs.  to_affine: the
+// plan of af_launch_groupnorm_fold, which writes no tensor (no small kernel; `kernel` only tells refused from not).
+AfGnPlan af_plan_groupnorm(AfStorage st, int B, int HW, int Cn, int pre_npart, bool to_affine = false);
+enum AfLnKernel {
+  AF_LNK_REFUSED = 0,    // C that is no whole number of 16-byte vectors, or more of them than a wave holds (64 * 5)
+  AF_LNK_WAVE_ROW = 1,   // layernorm_kernel: one wave per row, four rows per workgroup
+  AF_LNK_ROWGROUP = 2    // layernorm_rowgroup_kernel: 8 (16-bit storage) or 16 (f32) lanes per row
+};
+struct AfLnPlan {
+  int kernel;           // AfLnKernel
+  int nv;               // 16-byte vectors a lane holds at most (WAVE_ROW: ceil(vectors / 64), ROWGROUP: vectors / lanes per row)
+  int rows_per_block;   // rows of one 256-thread workgroup: 4, or 256 / lanes per row
+};
+AfLnPlan af_plan_layernorm(AfStorage st, long rows, int Cn);
+
 size_t af_gn_workspace_bytes(int B, int HW);
 template <typename T>
 int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn, const float* gamma,

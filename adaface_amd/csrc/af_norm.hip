@@ -13,6 +13,7 @@
 //   gn_apply    grid (chunks, B): y = (x-mean)*rstd*gamma+beta, optional SiLU
 //   layernorm   one wave per row, row held in registers, two-pass variance
 #include "af_common.h"
+#include "af_kernels.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -517,6 +518,32 @@ size_t af_gn_workspace_bytes(int B, int HW) {
   return ((size_t)B * nchunk * GN_GROUPS * 2 + (size_t)B * GN_GROUPS * 2) * sizeof(float);
 }
 
+// elements of a 16-byte vector (the kernels' EPC) and the storage type of a launcher's T
+static inline int epc_of(AfStorage st) { return st == AF_ST_F32 ? 4 : 8; }
+template <typename T> constexpr AfStorage storage_tag() {
+  return std::is_same_v<T, bf16> ? AF_ST_BF16 : std::is_same_v<T, f16> ? AF_ST_F16 : AF_ST_F32;
+}
+
+// Every decision of af_launch_groupnorm / af_launch_groupnorm_fold (af_kernels.h: AfGnPlan); the launchers re-derive none.
+AfGnPlan af_plan_groupnorm(AfStorage st, int B, int HW, int Cn, int pre_npart, bool to_affine) {
+  const int EPC = epc_of(st);
+  AfGnPlan pl = {AF_GNK_REFUSED, 0, 0, 0, 0};
+  if (B <= 0 || HW <= 0 || Cn <= 0 || Cn % GN_GROUPS != 0 || Cn % EPC != 0 || Cn > GN_MAX_C) return pl;
+  // small maps: single-launch register-resident kernel (group channels must be whole 16-byte vectors)
+  const int cpg = Cn / GN_GROUPS;
+  if (!to_affine && g_af_knobs.gn_small != 0 && cpg % EPC == 0 && (long)HW * (cpg / EPC) <= 256 * GNS_MAXV && Cn % 4 == 0) {
+    pl.kernel = AF_GNK_SMALL;
+    return pl;
+  }
+  pl.nchunk = af_gn_chunking(HW, B, &pl.P);
+  // pre_npart: the producer convolution wrote [B][pre_npart][32][2] partial sums of the values it stored
+  // (ConvGemmParams::gn_stats_out): no statistics pass over x at all
+  pl.npart = pre_npart > 0 ? pre_npart : pl.nchunk;
+  pl.wide_stats = pre_npart <= 0 && Cn / EPC > 256;
+  pl.kernel = pl.npart <= 64 ? AF_GNK_FOLD : AF_GNK_FINALIZE;   // few chunks: the apply blocks finalize the statistics themselves
+  return pl;
+}
+
 template <typename T>
 int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn, const float* gamma,
                         const float* beta, float eps, int silu, void* y, long y_bs, int ldy, void* workspace,
@@ -524,43 +551,34 @@ int af_launch_groupnorm(const void* x, long x_bs, int ldx, int B, int HW, int Cn
   constexpr int EPC = 16 / sizeof(T);
   if (fp8_mul != 0.f && !std::is_same_v<T, bf16>) { af_set_error_msg("groupnorm: fp8 output needs the bf16 storage mode"); return -1; }
   if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("groupnorm: an fp8 record needs the fp8 output"); return -1; }
-  if (Cn % GN_GROUPS != 0 || Cn % EPC != 0 || Cn > GN_MAX_C || ldx % EPC != 0 || ldy % EPC != 0) {
+  if (pre_partial && pre_npart <= 0) { af_set_error_msg("groupnorm: producer statistics without their count"); return -1; }
+  const AfGnPlan pl = af_plan_groupnorm(storage_tag<T>(), B, HW, Cn, pre_partial ? pre_npart : 0);
+  if (pl.kernel == AF_GNK_REFUSED || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("groupnorm: unsupported C=%d (need C%%32==0, C%%%d==0, C<=%d)", Cn, EPC, GN_MAX_C);
     return -1;
   }
   AfProfScope prof(AF_K_GROUPNORM, stream, 0.0, 2.0 * B * HW * (double)Cn * sizeof(T));
-  {
-    // small maps: single-launch register-resident kernel (group channels must be whole 16-byte vectors)
-    const int cpg = Cn / GN_GROUPS;
-    const bool small_ok = g_af_knobs.gn_small != 0;
-    if (small_ok && cpg % EPC == 0 && (long)HW * (cpg / EPC) <= 256 * GNS_MAXV && Cn % 4 == 0) {
-      if (fp8_rec) {   // (e4m3 output exists for bf16 only: no recording variant of the f32 kernels)
-        if constexpr (std::is_same_v<T, bf16>)
-          hipLaunchKernelGGL((gn_small_kernel<T, true>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
-                             x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
-      } else
-        hipLaunchKernelGGL((gn_small_kernel<T>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
+  if (pl.kernel == AF_GNK_SMALL) {
+    if (fp8_rec) {   // (e4m3 output exists for bf16 only: no recording variant of the f32 kernels)
+      if constexpr (std::is_same_v<T, bf16>)
+        hipLaunchKernelGGL((gn_small_kernel<T, true>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
                            x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
-      HIP_CHECK_RET(hipGetLastError());
-      return 0;
-    }
+    } else
+      hipLaunchKernelGGL((gn_small_kernel<T>), dim3(GN_GROUPS, B), dim3(256), 0, stream, reinterpret_cast<const T*>(x),
+                         x_bs, ldx, HW, Cn, gamma, beta, eps, silu, reinterpret_cast<T*>(y), y_bs, ldy, fp8_mul, fp8_rec);
+    HIP_CHECK_RET(hipGetLastError());
+    return 0;
   }
-  int P;
-  const int nchunk = af_gn_chunking(HW, B, &P);
-  const float* partial = reinterpret_cast<float*>(workspace);
+  const int P = pl.P, nchunk = pl.nchunk, npart = pl.npart;
   float* stats = reinterpret_cast<float*>(workspace) + (size_t)B * nchunk * GN_GROUPS * 2;
-  int npart = nchunk;
-  if (pre_partial) {
-    // the producer convolution wrote [B][pre_npart][32][2] partial sums of the values it stored (ConvGemmParams::gn_stats_out):
-    // no statistics pass over x at all
-    partial = pre_partial;
-    npart = pre_npart;
-  } else {
+  const float* partial = pre_partial;
+  if (!pre_partial) {
+    partial = reinterpret_cast<float*>(workspace);
     hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(nchunk, B), dim3(256), 0, stream,
                        reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, reinterpret_cast<float*>(workspace), nchunk);
   }
   const double count = (double)HW * (double)(Cn / GN_GROUPS);
-  const bool fold = npart <= 64;  // few chunks: the apply blocks finalize the statistics themselves
+  const bool fold = pl.kernel == AF_GNK_FOLD;
   if (!fold) hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, stream, partial, npart, count, eps, stats);
   if (fp8_rec) {
     if constexpr (std::is_same_v<T, bf16>)
@@ -618,26 +636,46 @@ int af_launch_groupnorm_fold(const void* x, long x_bs, int ldx, int B, int HW, i
                              float eps, void* workspace, hipStream_t stream, const float* pre_partial, int pre_npart,
                              float* ab_out) {
   constexpr int EPC = 16 / sizeof(T);
-  if (Cn % GN_GROUPS != 0 || Cn % EPC != 0 || Cn > GN_MAX_C || ldx % EPC != 0) {
+  if (pre_partial && pre_npart <= 0) { af_set_error_msg("groupnorm fold: producer statistics without their count"); return -1; }
+  const AfGnPlan pl = af_plan_groupnorm(storage_tag<T>(), B, HW, Cn, pre_partial ? pre_npart : 0, true);
+  if (pl.kernel == AF_GNK_REFUSED || ldx % EPC != 0) {
     af_set_error_msg("groupnorm fold: unsupported C=%d", Cn);
     return -1;
   }
-  int P;
-  const int nchunk = af_gn_chunking(HW, B, &P);
-  const float* partial = reinterpret_cast<float*>(workspace);
-  int npart = nchunk;
-  if (pre_partial) {
-    partial = pre_partial;
-    npart = pre_npart;
-  } else {
+  const float* partial = pre_partial;
+  if (!pre_partial) {
+    partial = reinterpret_cast<float*>(workspace);
     AfProfScope prof(AF_K_GROUPNORM, stream, 0.0, 1.0 * B * HW * (double)Cn * sizeof(T));
-    hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(nchunk, B), dim3(256), 0, stream,
-                       reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, P, reinterpret_cast<float*>(workspace), nchunk);
+    hipLaunchKernelGGL((gn_stats_kernel<T>), dim3(pl.nchunk, B), dim3(256), 0, stream,
+                       reinterpret_cast<const T*>(x), x_bs, ldx, HW, Cn, pl.P, reinterpret_cast<float*>(workspace), pl.nchunk);
   }
-  hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(256), 0, stream, partial, npart, (double)HW * (double)(Cn / GN_GROUPS), eps,
+  hipLaunchKernelGGL(gn_fold_kernel, dim3(B), dim3(256), 0, stream, partial, pl.npart, (double)HW * (double)(Cn / GN_GROUPS), eps,
                      gamma, beta, Cn, ab_out);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
+}
+
+// lanes that share a row in layernorm_rowgroup_kernel (its RL), by the elements of a 16-byte vector
+constexpr int ln_row_lanes(int epc) { return epc == 8 ? 8 : 16; }
+
+// Every decision of af_launch_layernorm (af_kernels.h: AfLnPlan).
+AfLnPlan af_plan_layernorm(AfStorage st, long rows, int Cn) {
+  const int EPC = epc_of(st);
+  AfLnPlan pl = {AF_LNK_REFUSED, 0, 0};
+  if (Cn <= 0 || Cn % EPC != 0 || Cn / EPC > 64 * LN_MAXV) return pl;
+  const int RL = ln_row_lanes(EPC), RPB = 256 / RL;
+  const int NV = Cn / EPC;
+  // (few rows of many vectors -- [4096, 1280] -- fill the chip better with one wave per row: measured 10 vs 19 us)
+  if (NV % RL == 0 && NV / RL <= LNG_MAXV && Cn <= 1280 && Cn % 4 == 0 && rows / RPB >= 256) {
+    pl.kernel = AF_LNK_ROWGROUP;
+    pl.nv = NV / RL;
+    pl.rows_per_block = RPB;
+    return pl;
+  }
+  pl.kernel = AF_LNK_WAVE_ROW;
+  pl.nv = (NV + 63) / 64;
+  pl.rows_per_block = 4;
+  return pl;
 }
 
 template <typename T>
@@ -646,34 +684,33 @@ int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* 
   constexpr int EPC = 16 / sizeof(T);
   if (fp8_mul != 0.f && !std::is_same_v<T, bf16>) { af_set_error_msg("layernorm: fp8 output needs the bf16 storage mode"); return -1; }
   if (fp8_rec && fp8_mul == 0.f) { af_set_error_msg("layernorm: an fp8 record needs the fp8 output"); return -1; }
-  if (Cn % EPC != 0 || Cn / EPC > 64 * LN_MAXV || ldx % EPC != 0 || ldy % EPC != 0) {
+  const AfLnPlan pl = af_plan_layernorm(storage_tag<T>(), rows, Cn);
+  if (pl.kernel == AF_LNK_REFUSED || ldx % EPC != 0 || ldy % EPC != 0) {
     af_set_error_msg("layernorm: unsupported C=%d", Cn);
     return -1;
   }
   if (rows <= 0) return 0;
   AfProfScope prof(AF_K_LAYERNORM, stream, 0.0, 2.0 * rows * (double)Cn * sizeof(T));
-  constexpr int RL = sizeof(T) == 2 ? 8 : 16;
-  const int NV = Cn / EPC;
-  constexpr int RPB = 256 / RL;
-  // (few rows of many vectors -- [4096, 1280] -- fill the chip better with one wave per row: measured 10 vs 19 us)
-  if (NV % RL == 0 && NV / RL <= 10 && Cn <= 1280 && Cn % 4 == 0 && rows / RPB >= 256) {
+  constexpr int RL = ln_row_lanes(EPC);
+  const unsigned nblock = (unsigned)((rows + pl.rows_per_block - 1) / pl.rows_per_block);
+  if (pl.kernel == AF_LNK_ROWGROUP) {
     if (fp8_rec) {
       if constexpr (std::is_same_v<T, bf16>)
-        hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL, true>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
+        hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL, true>), dim3(nblock), dim3(256), 0, stream,
                            reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
     } else
-      hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, stream,
+      hipLaunchKernelGGL((layernorm_rowgroup_kernel<T, RL>), dim3(nblock), dim3(256), 0, stream,
                          reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps, reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
     HIP_CHECK_RET(hipGetLastError());
     return 0;
   }
   if (fp8_rec) {
     if constexpr (std::is_same_v<T, bf16>)
-      hipLaunchKernelGGL((layernorm_kernel<T, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
+      hipLaunchKernelGGL((layernorm_kernel<T, true>), dim3(nblock), dim3(256), 0, stream,
                          reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
                          reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
   } else
-    hipLaunchKernelGGL((layernorm_kernel<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
+    hipLaunchKernelGGL((layernorm_kernel<T>), dim3(nblock), dim3(256), 0, stream,
                        reinterpret_cast<const T*>(x), ldx, rows, Cn, gamma, beta, eps,
                        reinterpret_cast<T*>(y), ldy, fp8_mul, fp8_rec);
   HIP_CHECK_RET(hipGetLastError());

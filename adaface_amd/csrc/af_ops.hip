@@ -256,6 +256,27 @@ int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, 
   return AF_OK;
 }
 
+// Host-only diagnostic: the plan af_launch_groupnorm (kind 0) or af_launch_layernorm (kind 1) would follow; no device is
+// touched.  kind 0: n = pixels per sample, out5 = {kernel (AfGnKernel), P, nchunk, npart, wide_stats}; kind 1: n = rows (B and
+// pre_npart unused), out5 = {kernel (AfLnKernel), vectors per lane, rows per block, 0, 0}
+int af_norm_plan_query(int kind, int dtype, int B, int64_t n, int C, int pre_npart, int64_t* out5) {
+  if (!out5 || (kind != 0 && kind != 1) || n < 0 || (kind == 0 && n > 0x7fffffff) ||
+      (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16)) {
+    af_set_error_msg("af_norm_plan_query: bad argument");
+    return AF_ERR_INVALID;
+  }
+  if (kind == 0) {
+    const AfGnPlan pl = af_plan_groupnorm(storage_of(dtype), B, (int)n, C, pre_npart);
+    const int64_t o[5] = {pl.kernel, pl.P, pl.nchunk, pl.npart, pl.wide_stats};
+    memcpy(out5, o, sizeof(o));
+  } else {
+    const AfLnPlan pl = af_plan_layernorm(storage_of(dtype), (long)n, C);
+    const int64_t o[5] = {pl.kernel, pl.nv, pl.rows_per_block, 0, 0};
+    memcpy(out5, o, sizeof(o));
+  }
+  return AF_OK;
+}
+
 // activation shifts of the fp8 mode: e4m3 of value * 2^s, s in [AF_FP8_SHIFT_MIN, AF_FP8_SHIFT_MAX] (adaface_hip.h)
 static bool act_shift_ok(int act_shift, const char* who) {
   if (act_shift >= AF_FP8_SHIFT_MIN && act_shift <= AF_FP8_SHIFT_MAX) return true;
@@ -573,6 +594,11 @@ int af_op_groupnorm(int dtype, const float* x_dev, const float* gamma_dev, const
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
   const int HW = H * W;
+  // (a shape the launcher would refuse is refused here, before the layout conversion: nothing is allocated or launched)
+  if (af_plan_groupnorm(storage_of(dtype), B, HW, C, 0).kernel == AF_GNK_REFUSED) {
+    af_set_error_msg("af_op_groupnorm: unsupported B=%d C=%d %dx%d", B, C, H, W);
+    return AF_ERR_INVALID;
+  }
   OP_ALLOC(xn, (size_t)B * HW * C * esize(dtype), false);
   OP_ALLOC(yn, (size_t)B * HW * C * esize(dtype), false);
   OP_ALLOC(ws, af_gn_workspace_bytes(B, HW), false);
@@ -641,6 +667,10 @@ int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const
                     float* y_dev, int64_t rows, int C, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
+  if (af_plan_layernorm(storage_of(dtype), rows, C).kernel == AF_LNK_REFUSED) {   // (before the cast: nothing is launched)
+    af_set_error_msg("af_op_layernorm: unsupported C=%d", C);
+    return AF_ERR_INVALID;
+  }
   OP_ALLOC(xn, (size_t)rows * C * esize(dtype), false);
   OP_ALLOC(yn, (size_t)rows * C * esize(dtype), false);
   AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(x_dev, xn, rows * C, s)));

@@ -294,6 +294,16 @@ enum {
 };
 int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, int stride, int pad, int up, int Hs, int Ws, int Ho,
                        int Wo, int ldc, int ldo, int gn_hw, int gn_cpg, int flags, int64_t* out7);
+/* Host-only diagnostic: the plan a GroupNorm(32) (kind 0) or LayerNorm (kind 1) launch would follow (no device is touched;
+ * honours af_knob_set "gn_small").  The launchers follow the same plan, so this names the kernels a shape reaches.
+ * kind 0: B samples of n pixels and C channels; pre_npart > 0 = a producer convolution left that many partial sums per sample.
+ *   out5 = {kernel, P, nchunk, npart, wide_stats}.  kernel: 0 refused (the launch fails), 1 the single-launch small-map kernel,
+ *   2 statistics + apply with the combine folded into the apply pass (npart <= 64), 3 statistics + finalize + apply.  P = pixels
+ *   per chunk, nchunk = ceil(n / P) chunks per sample, npart = partial sums combined per sample, wide_stats = the statistics
+ *   pass walks more than 256 16-byte vectors per pixel; all four are 0 with kernel 0 / 1.
+ * kind 1: n rows of C elements (B, pre_npart ignored).  out5 = {kernel, vectors per lane, rows per workgroup, 0, 0}.  kernel:
+ *   0 refused, 1 one wave per row, 2 the row-group kernel (8 lanes per row on 16-bit storage, 16 on f32). */
+int af_norm_plan_query(int kind, int dtype, int B, int64_t n, int C, int pre_npart, int64_t* out5);
 
 /* ---- tuning / diagnostic knobs ----
  * The planner thresholds and "force this kernel variant" switches live in one struct that is filled once from the

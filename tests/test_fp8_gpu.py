@@ -99,7 +99,9 @@ def test_conv2d_fp8_refuses_unplannable_shape(gpu):
 
 
 @pytest.mark.parametrize("B,C,H,W,silu", [(2, 320, 64, 64, True), (2, 1280, 8, 8, True), (1, 640, 32, 32, False),
-                                          (1, 2560, 16, 16, True)])
+                                          (1, 2560, 16, 16, True),
+                                          # (ragged last chunk + finalize remainder loop; small kernel with partly filled waves)
+                                          (2, 320, 9, 29, True), (2, 256, 5, 7, True)])
 def test_groupnorm_fp8_output(gpu, report, B, C, H, W, silu):
     """Both GroupNorm kernels (chunked apply / small-map single launch) with the e4m3 output: every byte decodes to within
     half an e4m3 step (2^-4 relative, 2^-10 / 8 absolute in the subnormal range) of the f32 result, saturating at 448 / 8."""
@@ -121,9 +123,10 @@ def test_groupnorm_fp8_output(gpu, report, B, C, H, W, silu):
     assert excess <= 0.0, excess
 
 
-@pytest.mark.parametrize("rows,C", [(4096, 320), (1024, 640), (256, 1280), (130, 1280)])
+@pytest.mark.parametrize("rows,C", [(4096, 320), (1024, 640), (256, 1280), (130, 1280), (8197, 320)])
 def test_layernorm_fp8_output(gpu, report, rows, C):
-    """Both LayerNorm kernels (row-group / wave-per-row) with the e4m3 output, same bound as the GroupNorm test."""
+    """Both LayerNorm kernels (row-group: 8197 rows, a last workgroup of 5 live rows / wave-per-row: the others) with the e4m3
+    output, same bound as the GroupNorm test."""
     from adaface_amd import ops
     g = torch.Generator().manual_seed(rows + C)
     x = (torch.randn(rows, C, generator=g) * 2.0 + 0.3).to(torch.bfloat16).float()

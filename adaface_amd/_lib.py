@@ -139,6 +139,13 @@ _SIGS = [
     ("af_clip_text_forward3", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P]),
     ("af_op_timestep_embedding", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     ("af_op_gn_conv1x1", C.c_int, [_P, _P, _P, C.c_float, _P, _P, _P, _P] + [C.c_int] * 5 + [_P]),
+    ("af_set_tome", C.c_int, [_P, C.c_double, C.c_int]),
+    ("af_tome_plan_query", C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64)]),
+    ("af_tome_num_sites", C.c_int, [_P]),
+    ("af_tome_set_tap", C.c_int, [_P, C.c_int, _P]),
+    ("af_op_tome_match", C.c_int, [C.c_int, _P] + [C.c_int] * 4 + [C.c_double, C.c_int, _P, _P, _P, _P]),
+    ("af_op_tome_merge", C.c_int, [C.c_int, _P, _P, _P, C.c_float, _P] + [C.c_int] * 4 + [_P, _P]),
+    ("af_op_tome_unmerge_add", C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 4 + [_P, _P]),
     ("af_flops_issued", C.c_double, [C.c_int]),
     ("af_clock_probe", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
@@ -215,6 +222,13 @@ def gemm_plan_query(dtype, M, N, K, cin_pad, ks=1, stride=1, pad=0, up=0, Hs=1, 
     check(load().af_gemm_plan_query(int(dtype), int(M), N, K, cin_pad, ks, stride, pad, up, Hs, Ws, Ho, Wo,
                                     cin_pad if ldc is None else ldc, N if ldo is None else ldo, gn_hw, gn_cpg, flags, out),
           "af_gemm_plan_query")
+    return tuple(int(v) for v in out)
+
+
+def tome_plan_query(H, W, ratio) -> tuple:
+    """af_tome_plan_query: (Nd, Ns, r, N') of token merging on an H x W map at `ratio`.  Host only: no GPU is needed."""
+    out = (C.c_int64 * 4)()
+    check(load().af_tome_plan_query(int(H), int(W), float(ratio), out), "af_tome_plan_query")
     return tuple(int(v) for v in out)
 
 

@@ -64,7 +64,10 @@ static inline int af_launch_lds(dim3 grid, dim3 block, int max_lds, int lds, hip
 // classes 5-7 split the eight-wave ping-pong kernel out of the conv/linear class by instantiation, so that the bench can
 // quote ONE kernel (conv_gemm_pp_kernel<160, true>, the 3x3 convolutions) with its own launch count and duration
 enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNORM = 3, AF_K_OTHER = 4,
-       AF_K_PP160_GATHER = 5, AF_K_PP160_PLAIN = 6, AF_K_PP128 = 7, AF_K_PP_FP8 = 8, AF_K_HALO8 = 9, AF_K_COUNT = 10 };
+       AF_K_PP160_GATHER = 5, AF_K_PP160_PLAIN = 6, AF_K_PP128 = 7, AF_K_PP_FP8 = 8, AF_K_HALO8 = 9,
+       // the token-merging kernels, one class each (af_tome.hip; scripts/tome_mode.py quotes them one by one)
+       AF_K_TOME_RNORM = 10, AF_K_TOME_MATCH = 11, AF_K_TOME_RANK = 12, AF_K_TOME_MAP = 13, AF_K_TOME_MERGE = 14,
+       AF_K_TOME_UNMERGE = 15, AF_K_COUNT = 16 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)

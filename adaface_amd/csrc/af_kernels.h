@@ -101,6 +101,26 @@ template <typename T>
 int af_launch_layernorm(const void* x, int ldx, long rows, int Cn, const float* gamma, const float* beta,
                         float eps, void* y, int ldy, hipStream_t stream, float fp8_mul = 0.f, unsigned* fp8_rec = nullptr);
 
+// Token merging in front of the U-Net's self-attention (af_tome.hip; tomesd with sx = sy = 2, use_rand = False).  Storage types
+// bf16 and float.  The plan of an H x W map (both even) at `ratio` in [0, 0.75]: Nd = N / 4 dst tokens, Ns = N - Nd src tokens,
+// r = min(Ns, int(N * ratio)) of them merged, Np = N - r rows left; -1 with a message for a map or ratio it refuses.
+struct AfTomePlan { long Nd, Ns, r, Np; };
+int af_tome_plan(int H, int W, double ratio, AfTomePlan* pl);
+size_t af_tome_match_ws_bytes(int B, int H, int W);
+// x [B][H * W][ldx] -> node_idx / node_max [B][Ns] and map [B][H * W] (values in [0, Np)); normalize: cosine scores.  Launches:
+// reciprocal norms (normalize only), match, rank, map.  ws: af_tome_match_ws_bytes bytes
+template <typename T>
+int af_launch_tome_match(const void* x, int ldx, int B, int H, int W, int C, double ratio, int normalize, int* node_idx,
+                         float* node_max, int* map, void* ws, hipStream_t s);
+// y [B][Np][ldy]: row j = mean over {i : map[i] = j} of LayerNorm(x_i) (gamma null: of x_i), N <= 16384 tokens per sample
+template <typename T>
+int af_launch_tome_merge(const void* x, int ldx, const float* gamma, const float* beta, float eps, const int* map, int B, int N,
+                         int Np, int C, void* y, int ldy, hipStream_t s);
+// y [B][N][ldy] = res + o[map]; ln_stats_out (optional): LayerNorm partial sums [ln_parts][B * N][2] of y's rows
+template <typename T>
+int af_launch_tome_unmerge_add(const void* o, int ldo, const void* res, int ldr, const int* map, int B, int N, int Np, int C,
+                               void* y, int ldy, float* ln_stats_out, int ln_parts, hipStream_t s);
+
 template <typename T>
 int af_launch_nchw_to_nhwc(const float* x, void* y, int B, int Cn, int HW, int Cpad, float scale, hipStream_t s);
 template <typename T> int af_launch_nhwc_to_nchw(const void* x, float* y, int B, int Cn, int HW, int ld, hipStream_t s);

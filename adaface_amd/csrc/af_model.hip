@@ -192,6 +192,7 @@ struct XfmrW {
   Linear proj_in, proj_out;
   std::vector<XfmrBlockW> blocks;
   int ca_slot = -1;  // index into the cached context K/V list (first block of this transformer)
+  int ds = 1;        // the latent's side divided by this transformer's map side (1 at the outermost level)
 };
 struct VaeAttnW {
   Norm gn;
@@ -307,6 +308,28 @@ struct af_handle {
   // diagnostic tap (af_unet_set_tap): block whose output the next forwards also write, fp32 NCHW
   int tap_index = -1;
   float* tap_out = nullptr;
+
+  // token merging in front of attn1 (af_set_tome): ratio 0 = off; transformers with ds <= tome_max_down merge.  A site is one
+  // transformer block that merges, numbered in forward order (the order of ca_list); tome_tap_*: af_tome_set_tap
+  double tome_ratio = 0.0;
+  int tome_max_down = 1;
+  int tome_tap_site = -1;
+  int* tome_tap_out = nullptr;
+  bool tome_merges(const XfmrW& x) const { return tome_ratio > 0.0 && x.ds <= tome_max_down; }
+  int tome_site(int xi, int d) const {   // -1: that block does not merge
+    if (!tome_merges(xf[xi])) return -1;
+    int site = 0;
+    for (const auto& e : ca_list) {
+      if (e.first == xi && e.second == d) return site;
+      if (tome_merges(xf[e.first])) ++site;
+    }
+    return -1;
+  }
+  int tome_num_sites() const {
+    int n = 0;
+    for (const auto& e : ca_list) n += tome_merges(xf[e.first]) ? 1 : 0;
+    return n;
+  }
 
   // DeepCache (af_unet_forward_cached): while that entry point runs, the concatenation buffer cat[n_out - depth] lives here
   // and not in the arena (which is re-planned by every forward and shared with the VAE / CLIP calls).  A refresh writes both
@@ -502,9 +525,10 @@ static int build_unet(Builder& b) {
   b.make_conv(h->time_embed0, P + "time_embed.0", mc, ted, 1, true, false);
   b.make_conv(h->time_embed2, P + "time_embed.2", ted, ted, 1, true, false);
 
-  auto add_xfmr = [&](UBlock& ub, const std::string& prefix, int ch) {
+  auto add_xfmr = [&](UBlock& ub, const std::string& prefix, int ch, int ds) {
     const int dh = ch / c.num_heads;
     int xi = make_xfmr(b, prefix, ch, c.num_heads, dh, c.transformer_depth, c.context_dim);
+    h->xf[xi].ds = ds;
     ub.layers.push_back({L_XFMR, xi});
   };
 
@@ -524,7 +548,7 @@ static int build_unet(Builder& b) {
       int ri = make_unet_resblock(b, pre + ".0", ch, mult * mc);
       ub.layers.push_back({L_RES, ri});
       ch = mult * mc;
-      if (in_list(c.attention_resolutions, c.n_attention_resolutions, ds)) add_xfmr(ub, pre + ".1", ch);
+      if (in_list(c.attention_resolutions, c.n_attention_resolutions, ds)) add_xfmr(ub, pre + ".1", ch, ds);
       h->input_blocks.push_back(ub);
       chans.push_back(ch);
     }
@@ -544,7 +568,7 @@ static int build_unet(Builder& b) {
     UBlock& ub = h->middle_block;
     int r0 = make_unet_resblock(b, P + "middle_block.0", ch, ch);
     ub.layers.push_back({L_RES, r0});
-    add_xfmr(ub, P + "middle_block.1", ch);
+    add_xfmr(ub, P + "middle_block.1", ch, ds);
     int r2 = make_unet_resblock(b, P + "middle_block.2", ch, ch);
     ub.layers.push_back({L_RES, r2});
   }
@@ -560,7 +584,7 @@ static int build_unet(Builder& b) {
       ch = mc * mult;
       int li = 1;
       if (in_list(c.attention_resolutions, c.n_attention_resolutions, ds)) {
-        add_xfmr(ub, pre + "." + std::to_string(li), ch);
+        add_xfmr(ub, pre + "." + std::to_string(li), ch, ds);
         ++li;
       }
       if (level && i == c.num_res_blocks) {
@@ -1196,10 +1220,60 @@ static int xfmr_proj_in(const XfmrCtx& X, const Act& x, const Act& g, const Act&
   return R.conv(w.proj_in, gh, th, o);
 }
 
-// x = attn1(norm1(x)) + x on the first Bp samples: t -> t1.  Leaves n (scratch of the stand-alone LayerNorms) and a (attention
-// output) allocated for the steps that follow.
-static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, int Bp, const Act& t, Act& n, Act& a, Act& t1) {
+// The same with token merging (af_set_tome): match on t, merged rows = means of norm1(t), q / k / v (the un-folded
+// weights), attention and to_out + bias on the N' rows of every sample, then t1 = t + o[map].  Where the transformer folds
+// its LayerNorms the unmerge launch leaves t1's row sums for norm2's consumer, as out1's producer epilogue does without merging.
+static int xfmr_self_attention_tome(const XfmrCtx& X, const XfmrBlockW& blk, int site, int Bp, const Act& t, Act& n, Act& a,
+                                    Act& t1) {
   Runner& R = X.R;
+  af_handle* h = R.h;
+  const int B = X.B, H = X.H, W = X.W, N = X.N, C = X.C;
+  AfTomePlan pl;
+  if (af_tome_plan(H, W, h->tome_ratio, &pl)) return AF_ERR_INVALID;
+  const int Np = (int)pl.Np, Ns = (int)pl.Ns;
+  n = R.alloc_act(B, H, W, C);
+  a = R.alloc_act(B, H, W, C);
+  t1 = R.alloc_act(B, H, W, C);
+  Act m = R.alloc_act(Bp, 1, Np, C), qkv = R.alloc_act(Bp, 1, Np, 3 * C), am = R.alloc_act(Bp, 1, Np, C), om = R.alloc_act(Bp, 1, Np, C);
+  int* node_idx = reinterpret_cast<int*>(R.A.alloc((size_t)Bp * Ns * sizeof(int)));
+  float* node_max = reinterpret_cast<float*>(R.A.alloc((size_t)Bp * Ns * sizeof(float)));
+  int* map = reinterpret_cast<int*>(R.A.alloc((size_t)Bp * N * sizeof(int)));
+  void* ws = R.A.alloc(af_tome_match_ws_bytes(Bp, H, W));
+  if (!n.p || !a.p || !t1.p || !m.p || !qkv.p || !am.p || !om.p || !node_idx || !node_max || !map || !ws) {
+    af_set_error_msg("activation arena exhausted (token merging, cap %zu)", R.A.cap);
+    return AF_ERR_STATE;
+  }
+  const bool is_bf16 = R.dt == AF_DTYPE_BF16;   // (af_set_tome takes bf16 and f32 handles only)
+  Act tp = t, t1p = t1;
+  tp.B = t1p.B = Bp;
+  if (!R.dry) {
+    AF_TRY(is_bf16 ? af_launch_tome_match<bf16>(tp.p, tp.ld, Bp, H, W, C, h->tome_ratio, 1, node_idx, node_max, map, ws, R.s)
+                   : af_launch_tome_match<float>(tp.p, tp.ld, Bp, H, W, C, h->tome_ratio, 1, node_idx, node_max, map, ws, R.s));
+    AF_TRY(is_bf16 ? af_launch_tome_merge<bf16>(tp.p, tp.ld, blk.ln1.gamma, blk.ln1.beta, blk.ln1.eps, map, Bp, N, Np, C, m.p, m.ld, R.s)
+                   : af_launch_tome_merge<float>(tp.p, tp.ld, blk.ln1.gamma, blk.ln1.beta, blk.ln1.eps, map, Bp, N, Np, C, m.p, m.ld, R.s));
+  }
+  AF_TRY(R.conv(blk.qkv1, m, qkv));
+  AF_TRY(R.attention(R.cols_of(qkv, 0, Np), R.cols_of(qkv, C, Np), R.cols_of(qkv, 2 * C, Np), am, Np, Np, X.w.heads, X.w.dh));
+  AF_TRY(R.conv(blk.out1, am, om));
+  if (R.dry) return 0;
+  float* st = X.ln_parts ? X.st_part : nullptr;
+  AF_TRY(is_bf16 ? af_launch_tome_unmerge_add<bf16>(om.p, om.ld, tp.p, tp.ld, map, Bp, N, Np, C, t1p.p, t1p.ld, st, X.ln_parts, R.s)
+                 : af_launch_tome_unmerge_add<float>(om.p, om.ld, tp.p, tp.ld, map, Bp, N, Np, C, t1p.p, t1p.ld, st, X.ln_parts, R.s));
+  if (site == h->tome_tap_site && h->tome_tap_out) {   // [B][N]: a half-batch prefix serves both halves
+    for (int rep = 0; rep * Bp < B; ++rep)
+      HIP_CHECK_RET(hipMemcpyAsync(h->tome_tap_out + (size_t)rep * Bp * N, map, (size_t)Bp * N * sizeof(int), hipMemcpyDeviceToDevice, R.s));
+  }
+  return 0;
+}
+
+// x = attn1(norm1(x)) + x on the first Bp samples: t -> t1.  Leaves n (scratch of the stand-alone LayerNorms) and a (attention
+// output) allocated for the steps that follow.  d: the block's index in its transformer.
+static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d, int Bp, const Act& t, Act& n, Act& a, Act& t1) {
+  Runner& R = X.R;
+  if (R.h->tome_ratio > 0.0) {
+    const int site = R.h->tome_site((int)(&X.w - R.h->xf.data()), (int)d);
+    if (site >= 0) return xfmr_self_attention_tome(X, blk, site, Bp, t, n, a, t1);
+  }
   const int B = X.B, H = X.H, W = X.W, N = X.N, C = X.C;
   auto pv = [&](Act v) { v.B = Bp; return v; };
   n = R.alloc_act(B, H, W, C);
@@ -1393,7 +1467,7 @@ static int run_xfmr(Runner& R, const XfmrW& w, const Act& x, Act& out, bool twin
     const size_t mk2 = R.A.mark();
     const bool pre = twin && d == 0;             // this block's self-attention runs on the first half only
     Act n, a, t1, t2;
-    AF_TRY(xfmr_self_attention(X, blk, pre ? X.Bh : X.B, t, n, a, t1));
+    AF_TRY(xfmr_self_attention(X, blk, d, pre ? X.Bh : X.B, t, n, a, t1));
     if (pre) {   // from here on the halves differ (cross-attention): second half := first half
       AF_TRY(R.check(t1));
       AF_TRY(X.dup(t1));
@@ -2408,6 +2482,40 @@ int af_unet_set_tap(af_handle* h, int block, float* out_dev) {
   return AF_OK;
 }
 
+int af_set_tome(af_handle* h, double ratio, int max_downsample) {
+  if (!h) { af_set_error_msg("af_set_tome: null handle"); return AF_ERR_INVALID; }
+  if (!(ratio >= 0.0 && ratio <= 0.75)) { af_set_error_msg("af_set_tome: ratio %g outside [0, 0.75]", ratio); return AF_ERR_INVALID; }
+  if (max_downsample != 1 && max_downsample != 2) { af_set_error_msg("af_set_tome: max_downsample %d is neither 1 nor 2", max_downsample); return AF_ERR_INVALID; }
+  if (ratio > 0.0) {
+    if (!h->cfg.build_unet) { af_set_error_msg("af_set_tome: handle has no UNet"); return AF_ERR_STATE; }
+    if (h->dtype == AF_DTYPE_F16) { af_set_error_msg("af_set_tome: token merging takes bf16 and f32 handles (handle is f16)"); return AF_ERR_STATE; }
+    if (h->fp8_on) { af_set_error_msg("af_set_tome: token merging does not combine with the fp8 mode (af_set_fp8)"); return AF_ERR_STATE; }
+  }
+  if (ratio != h->tome_ratio || max_downsample != h->tome_max_down) {
+    h->dc.valid = false;   // (a kept DeepCache feature belongs to the setting that wrote it)
+    h->tome_tap_site = -1;
+    h->tome_tap_out = nullptr;
+  }
+  h->tome_ratio = ratio;
+  h->tome_max_down = max_downsample;
+  return AF_OK;
+}
+int af_tome_plan_query(int H, int W, double ratio, int64_t out[4]) {
+  if (!out) { af_set_error_msg("af_tome_plan_query: null output"); return AF_ERR_INVALID; }
+  AfTomePlan pl;
+  if (af_tome_plan(H, W, ratio, &pl)) return AF_ERR_INVALID;
+  out[0] = pl.Nd; out[1] = pl.Ns; out[2] = pl.r; out[3] = pl.Np;
+  return AF_OK;
+}
+int af_tome_num_sites(af_handle* h) { return (h && h->cfg.build_unet) ? h->tome_num_sites() : 0; }
+int af_tome_set_tap(af_handle* h, int site, int32_t* map_dev) {
+  if (!h) { af_set_error_msg("af_tome_set_tap: null handle"); return AF_ERR_INVALID; }
+  if (site >= af_tome_num_sites(h)) { af_set_error_msg("af_tome_set_tap: site %d out of range (%d sites)", site, af_tome_num_sites(h)); return AF_ERR_INVALID; }
+  h->tome_tap_site = (site >= 0 && map_dev) ? site : -1;
+  h->tome_tap_out = h->tome_tap_site >= 0 ? map_dev : nullptr;
+  return AF_OK;
+}
+
 int af_clip_embed_tokens(af_handle* h, const int64_t* ids_dev, int64_t n, float* emb_dev, void* stream) {
   if (!h || !ids_dev || !emb_dev || n <= 0) { af_set_error_msg("af_clip_embed_tokens: bad argument"); return AF_ERR_INVALID; }
   if (!h->cfg.build_clip) { af_set_error_msg("af_clip_embed_tokens: handle has no CLIP text tower"); return AF_ERR_STATE; }
@@ -2621,6 +2729,7 @@ int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches
 int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }
 int af_set_fp8(af_handle* h, int on) {
   if (!h) { af_set_error_msg("af_set_fp8: null handle"); return AF_ERR_INVALID; }
+  if (on && h->tome_ratio > 0.0) { af_set_error_msg("af_set_fp8: the fp8 mode does not combine with token merging (af_set_tome)"); return AF_ERR_STATE; }
   if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is %s)", h->dtype == AF_DTYPE_F16 ? "f16" : "f32"); return AF_ERR_STATE; }
   if (h->fp8_on != (on != 0)) h->dc.valid = false;   // (a kept DeepCache feature belongs to the mode that wrote it)
   h->fp8_on = on != 0;

@@ -254,6 +254,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 
 // ---------------------------------------------------------------------------
 // LayerNorm: one wave per row; C*sizeof(T)/16 <= 64*LN_MAXV vectors.
+// tome::ln_row_wave (af_tome.hip) mirrors this kernel's row arithmetic -- the summation order, the separate multiply and add of
+// the sum of squares and the one fma of the affine map, as hipcc compiles them here -- because a merged row with one member must
+// hold these bits.  A change to the arithmetic below (or a toolchain that contracts it differently) must be made there too;
+// tests/test_tome_gpu.py::test_merge_rows fails when the two part.
 // ---------------------------------------------------------------------------
 #define LN_MAXV 5
 template <typename T, bool REC = false>

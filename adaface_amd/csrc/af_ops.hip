@@ -890,6 +890,65 @@ int af_op_xattn_fused(const float* x_dev, const float* ln_stats_dev, const float
   return 0;
 }
 
+// Token merging (af_tome.hip), the launches xfmr_self_attention_tome makes
+static bool tome_dtype_ok(int dtype, const char* who) {
+  if (dtype == AF_DTYPE_BF16 || dtype == AF_DTYPE_F32) return true;
+  af_set_error_msg("%s: storage type %d (token merging takes bf16 and f32)", who, dtype);
+  return false;
+}
+int af_op_tome_match(int dtype, const float* x_dev, int B, int H, int W, int C, double ratio, int normalize, int32_t* node_idx_dev,
+                     float* node_max_dev, int32_t* map_dev, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  AfTomePlan pl;
+  if (!tome_dtype_ok(dtype, "af_op_tome_match") || af_tome_plan(H, W, ratio, &pl)) return AF_ERR_INVALID;
+  if (B <= 0 || C <= 0 || !x_dev || !node_idx_dev || !node_max_dev || !map_dev) { af_set_error_msg("af_op_tome_match: bad argument"); return AF_ERR_INVALID; }
+  const long n = (long)B * H * W * C;
+  OP_ALLOC(xn, (size_t)n * esize(dtype), false);
+  OP_ALLOC(ws, af_tome_match_ws_bytes(B, H, W), false);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(x_dev, xn, n, s)));
+  const int rc = dtype == AF_DTYPE_BF16
+                     ? af_launch_tome_match<bf16>(xn, C, B, H, W, C, ratio, normalize, node_idx_dev, node_max_dev, map_dev, ws, s)
+                     : af_launch_tome_match<float>(xn, C, B, H, W, C, ratio, normalize, node_idx_dev, node_max_dev, map_dev, ws, s);
+  return rc ? AF_ERR_INVALID : AF_OK;
+}
+int af_op_tome_merge(int dtype, const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps,
+                     const int32_t* map_dev, int B, int N, int Nprime, int C, float* y_dev, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if (!tome_dtype_ok(dtype, "af_op_tome_merge")) return AF_ERR_INVALID;
+  if (B <= 0 || N <= 0 || Nprime <= 0 || Nprime > N || C <= 0 || !x_dev || !map_dev || !y_dev) { af_set_error_msg("af_op_tome_merge: bad argument"); return AF_ERR_INVALID; }
+  const long nx = (long)B * N * C, ny = (long)B * Nprime * C;
+  OP_ALLOC(xn, (size_t)nx * esize(dtype), false);
+  OP_ALLOC(yn, (size_t)ny * esize(dtype), true);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(x_dev, xn, nx, s)));
+  const int rc = dtype == AF_DTYPE_BF16
+                     ? af_launch_tome_merge<bf16>(xn, C, gamma_dev, beta_dev, eps, map_dev, B, N, Nprime, C, yn, C, s)
+                     : af_launch_tome_merge<float>(xn, C, gamma_dev, beta_dev, eps, map_dev, B, N, Nprime, C, yn, C, s);
+  if (rc) return AF_ERR_INVALID;
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, ny, s)));
+  return AF_OK;
+}
+int af_op_tome_unmerge_add(int dtype, const float* o_dev, const float* res_dev, const int32_t* map_dev, int B, int N, int Nprime,
+                           int C, float* y_dev, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if (!tome_dtype_ok(dtype, "af_op_tome_unmerge_add")) return AF_ERR_INVALID;
+  if (B <= 0 || N <= 0 || Nprime <= 0 || Nprime > N || C <= 0 || !o_dev || !res_dev || !map_dev || !y_dev) { af_set_error_msg("af_op_tome_unmerge_add: bad argument"); return AF_ERR_INVALID; }
+  const long no = (long)B * Nprime * C, ny = (long)B * N * C;
+  OP_ALLOC(on, (size_t)no * esize(dtype), false);
+  OP_ALLOC(rn, (size_t)ny * esize(dtype), false);
+  OP_ALLOC(yn, (size_t)ny * esize(dtype), true);
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(o_dev, on, no, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(res_dev, rn, ny, s)));
+  const int rc = dtype == AF_DTYPE_BF16
+                     ? af_launch_tome_unmerge_add<bf16>(on, C, rn, C, map_dev, B, N, Nprime, C, yn, C, nullptr, 0, s)
+                     : af_launch_tome_unmerge_add<float>(on, C, rn, C, map_dev, B, N, Nprime, C, yn, C, nullptr, 0, s);
+  if (rc) return AF_ERR_INVALID;
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(yn, y_dev, ny, s)));
+  return AF_OK;
+}
+
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;

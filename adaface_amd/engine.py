@@ -19,6 +19,16 @@ UNET_PREFIX = "model.diffusion_model."
 VAE_PREFIX = "first_stage_model."
 
 
+def check_tome_args(ratio, max_downsample=1):
+    """(ratio, max_downsample) of token merging as the C library takes them; ValueError for anything it would refuse.  No GPU
+    is needed."""
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 <= float(ratio) <= 0.75:
+        raise ValueError(f"token merging: ratio {ratio!r} (a number in [0, 0.75]; 0 = off)")
+    if isinstance(max_downsample, bool) or max_downsample not in (1, 2):
+        raise ValueError(f"token merging: max_downsample {max_downsample!r} (1: the outermost level only, 2: the next one too)")
+    return float(ratio), int(max_downsample)
+
+
 def _fill(arr, values: Sequence[int]):
     if len(values) > 8:
         raise ValueError("at most 8 entries supported")
@@ -190,6 +200,19 @@ class Engine:
         check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, 1 if twin else 0, int(depth),
                                                _lib.DEEPCACHE_MODES[mode], stream_ptr()), "af_unet_forward_cached")
         return out
+
+    def set_tome(self, ratio: float, max_downsample: int = 1):
+        """af_set_tome: token merging (ToMe for Stable Diffusion, tomesd's defaults without the random dst choice) in front of
+        the self-attention of every transformer block whose map is the latent's divided by at most max_downsample.  ratio in
+        [0, 0.75]: the share of a map's tokens that is merged away; 0 = off.  bf16 and f32 engines without the fp8 mode
+        (AfError otherwise).  Drops a kept DeepCache feature when the setting changes."""
+        ratio, max_downsample = check_tome_args(ratio, max_downsample)
+        check(self._lib.af_set_tome(self._h, ratio, max_downsample), "af_set_tome")
+        self.tome = (ratio, max_downsample)
+
+    def tome_num_sites(self) -> int:
+        """Transformer blocks that merge under the current setting (forward order)."""
+        return int(self._lib.af_tome_num_sites(self._h))
 
     def unet_cache_invalidate(self):
         """Drop the feature kept by unet_forward_cached(mode="refresh"): the next reuse call raises until a refresh ran."""

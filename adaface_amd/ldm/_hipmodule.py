@@ -57,6 +57,7 @@ class HipModule(nn.Module):
         # engine is rebuilt when the compute dtype or the device changes, and every fp8 engine gets them again
         object.__setattr__(self, "_fp8_shifts", None)
         object.__setattr__(self, "_fp8_scope", ("base",))     # kept here like the shifts: every fp8 engine gets it again
+        object.__setattr__(self, "_tome", (0.0, 1))           # token merging (UNetModel.set_token_merging), kept the same way
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
@@ -80,6 +81,8 @@ class HipModule(nn.Module):
             dtype = "f16"
         if dtype not in ("bf16", "f32", "f16", "fp8"):
             raise ValueError(dtype)
+        if dtype in ("f16", "fp8") and self._tome[0] > 0.0:
+            raise ValueError(f"compute dtype {dtype!r} does not combine with token merging (set_token_merging(0) first)")
         if dtype != self.compute_dtype:
             self.compute_dtype = dtype
             if self._engine is not None:
@@ -122,14 +125,22 @@ class HipModule(nn.Module):
             fp8 = self.compute_dtype == "fp8"
             object.__setattr__(self, "_engine", Engine(dtype="bf16" if fp8 else self.compute_dtype, device=idx,
                                                        **self._engine_kwargs()))
-            if fp8:
-                self._engine.set_fp8(True, scope=self._fp8_scope)
-                if self._fp8_shifts is not None:
-                    try:
-                        self._engine.set_fp8_shifts(self._fp8_shifts)
-                    except KeyError as e:
-                        raise KeyError(f"{type(self).__name__}: the shifts given to set_fp8_shifts / load_fp8_scales do not "
-                                       f"name this model's fp8 sites ({e.args[0]})") from None
+            try:
+                if fp8:
+                    self._engine.set_fp8(True, scope=self._fp8_scope)
+                    if self._fp8_shifts is not None:
+                        try:
+                            self._engine.set_fp8_shifts(self._fp8_shifts)
+                        except KeyError as e:
+                            raise KeyError(f"{type(self).__name__}: the shifts given to set_fp8_shifts / load_fp8_scales do not "
+                                           f"name this model's fp8 sites ({e.args[0]})") from None
+                if self._tome[0] > 0.0:
+                    self._engine.set_tome(*self._tome)
+            except Exception:
+                # (an engine whose configuration failed is not kept: the next call builds and configures again)
+                self._engine.close()
+                object.__setattr__(self, "_engine", None)
+                raise
             self._mark_dirty()
         if self._weights_dirty:
             self.sync_weights()

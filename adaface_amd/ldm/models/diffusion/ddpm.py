@@ -285,6 +285,11 @@ class LatentDiffusion(DDPM):
         self.model.diffusion_model.load_fp8_scales(path, self.device)
         return self
 
+    def set_token_merging(self, ratio, max_downsample=1):
+        """UNetModel.set_token_merging: opt-in token merging in front of the U-Net's self-attention (0 = off)."""
+        self.model.diffusion_model.set_token_merging(ratio, max_downsample)
+        return self
+
     def set_compute_dtype(self, dtype: str, fp8_scope: str = "base"):
         """'bf16' | 'f32' | 'f16' (alias 'fp16') | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).
         fp8_scope: 'base' (ResBlock convolutions and self-attention q / k / v) or 'base+ff' (also the transformer blocks'

@@ -110,6 +110,24 @@ class UNetModel(HipModule):
             object.__setattr__(self, "_compel_refs", (context, empty))
         return ctx, deterministic
 
+    def set_token_merging(self, ratio, max_downsample=1):
+        """Token merging in front of every self-attention whose map is the latent's divided by at most max_downsample (1 or 2):
+        `ratio` in [0, 0.75] of a map's tokens are merged into their most similar neighbour of a 2 x 2 cell before attn1 and
+        copied back after it (ToMe for Stable Diffusion; not in the reference, off by default, 0 = off).  Kept for every later
+        engine; a live one is switched now.  bf16 and f32 compute dtypes."""
+        from adaface_amd.engine import check_tome_args
+        setting = check_tome_args(ratio, max_downsample)
+        if setting[0] > 0.0 and self.compute_dtype in ("f16", "fp8"):
+            raise ValueError(f"token merging runs with the compute dtypes 'bf16' and 'f32' (compute dtype is {self.compute_dtype!r})")
+        if self._engine is not None:
+            self._engine.set_tome(*setting)
+        object.__setattr__(self, "_tome", setting)
+        return self
+
+    @property
+    def token_merging(self) -> tuple:
+        return self._tome
+
     @staticmethod
     def _conv_attn_spec(ks, placeholder2indices):
         """(ks, batch indices, token positions) for Engine.set_conv_attn from the reference's

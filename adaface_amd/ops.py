@@ -243,6 +243,51 @@ def layer_norm(x, weight, bias, eps=1e-5, dtype="bf16"):
     return y
 
 
+def tome_match(x, hw, ratio, normalize=True, dtype="bf16"):
+    """Token-merging match on x [B, H*W, C] (hw = (H, W), both even): (node_idx int32 [B, Ns], node_max fp32 [B, Ns],
+    map int32 [B, H*W]) -- per src token the lowest best dst ordinal and its score (cosine, or the plain dot product with
+    normalize=False), and the merged row of every token when r = min(Ns, int(N * ratio)) src tokens are merged."""
+    lib = _lib.load()
+    x = _dev_f32(x)
+    B, N, Cn = x.shape
+    H, W = hw
+    if H * W != N:
+        raise ValueError(f"tome_match: {H} x {W} map, {N} tokens")
+    Nd, Ns, _, _ = _lib.tome_plan_query(H, W, ratio)
+    node_idx = torch.empty(B, Ns, device=x.device, dtype=torch.int32)
+    node_max = torch.empty(B, Ns, device=x.device, dtype=torch.float32)
+    tmap = torch.empty(B, N, device=x.device, dtype=torch.int32)
+    check(lib.af_op_tome_match(DTYPES[dtype], ptr(x), B, H, W, Cn, float(ratio), 1 if normalize else 0, ptr(node_idx),
+                               ptr(node_max), ptr(tmap), stream_ptr()), "af_op_tome_match")
+    return node_idx, node_max, tmap
+
+
+def tome_merge(x, tmap, n_rows, weight=None, bias=None, eps=1e-5, dtype="bf16"):
+    """Rows of the merged sequence [B, n_rows, C]: row j = the mean over the tokens i with tmap[b, i] = j of LayerNorm(x[b, i])
+    (weight = None: of x[b, i]), summed in fp32 in ascending i and rounded once."""
+    lib = _lib.load()
+    x = _dev_f32(x)
+    B, N, Cn = x.shape
+    tmap = tmap.to(device=x.device, dtype=torch.int32).contiguous()
+    y = torch.empty(B, int(n_rows), Cn, device=x.device, dtype=torch.float32)
+    check(lib.af_op_tome_merge(DTYPES[dtype], ptr(x), ptr(_dev_f32(weight)) if weight is not None else None,
+                               ptr(_dev_f32(bias)) if bias is not None else None, eps, ptr(tmap), B, N, int(n_rows), Cn, ptr(y),
+                               stream_ptr()), "af_op_tome_merge")
+    return y
+
+
+def tome_unmerge_add(o, res, tmap, dtype="bf16"):
+    """res [B, N, C] + o [B, N', C] gathered by tmap [B, N], in fp32, rounded once."""
+    lib = _lib.load()
+    o, res = _dev_f32(o), _dev_f32(res)
+    B, N, Cn = res.shape
+    tmap = tmap.to(device=res.device, dtype=torch.int32).contiguous()
+    y = torch.empty_like(res)
+    check(lib.af_op_tome_unmerge_add(DTYPES[dtype], ptr(o), ptr(res), ptr(tmap), B, N, o.shape[1], Cn, ptr(y), stream_ptr()),
+          "af_op_tome_unmerge_add")
+    return y
+
+
 def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=False):
     """softmax(q k^T * scale) v per head; q [B,N,heads*dh], k/v [B,S,heads*dh] (attention.py:197-243).  causal: query i
     attends to keys <= i (the CLIP text tower's mask).  nan_guard (tests): K / V sit in front of 128 rows of NaNs."""

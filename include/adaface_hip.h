@@ -133,6 +133,39 @@ int af_unet_forward_cached(af_handle* h, const float* x_dev, const int64_t* t_de
                            int twin, int depth, int mode, void* stream);
 int af_unet_cache_invalidate(af_handle* h);
 
+/* Token merging (Bolya & Hoffman, "Token Merging for Fast Stable Diffusion", CVPR-W 2023; tomesd with sx = sy = 2,
+ * use_rand = False, merge_attn only), opt-in: in front of attn1 of every transformer block whose map is the latent's divided by
+ * at most max_downsample (1 or 2), r = min(Ns, int(N * ratio)) of the N = H W tokens of a sample are merged into their most
+ * similar (cosine) destination token -- the Nd = N / 4 tokens with even y and x; Ns = N - Nd -- and q / k / v, the attention
+ * and to_out run on the N' = N - r rows left; the result is copied back to the merged tokens.  attn2 and the
+ * FeedForward see all N tokens.  ratio in [0, 0.75], 0 = off: the forwards are then what they are without this call, launch
+ * for launch.  bf16 and f32 handles; an fp16 handle and the fp8 mode are refused (AF_ERR_STATE).  A change of the setting
+ * drops a kept DeepCache feature and the tap below.  The map sides at a merging level must be even (AF_ERR_INVALID from the
+ * forward otherwise).
+ * af_tome_plan_query: out = {Nd, Ns, r, N'} for an H x W map; host only, no GPU needed; odd or non-positive sides and a ratio
+ * outside [0, 0.75] are refused (AF_ERR_INVALID).
+ * A site is one transformer block that merges, numbered in forward order (input, middle, output blocks), whether or not a
+ * DeepCache reuse step runs it.  af_tome_set_tap makes every following forward that runs site `site` also copy its map --
+ * int32 [Bf][N], map[i] in [0, N') the merged row of token i: dst tokens in ordinal order, then the unmerged src tokens in
+ * raster order -- to map_dev (site < 0 or map_dev NULL: off). */
+int af_set_tome(af_handle* h, double ratio, int max_downsample);
+int af_tome_plan_query(int H, int W, double ratio, int64_t out[4]);
+int af_tome_num_sites(af_handle* h);
+int af_tome_set_tap(af_handle* h, int site, int32_t* map_dev);
+/* The three steps as operators on fp32 device tensors (cast to `dtype` = bf16 or f32 storage first, as every af_op_*):
+ *   match:   x [B][H W][C] -> node_idx int32 [B][Ns] (the lowest dst ordinal attaining the maximum), node_max fp32 [B][Ns],
+ *            map int32 [B][H W]; normalize = 1: cosine scores, 0: plain dot products.  Of equal node_max the lower src
+ *            ordinal is merged first.
+ *   merge:   y [B][Nprime][C] = per row the mean over its tokens of LayerNorm(x) (gamma_dev = NULL: of x), fp32 sums in
+ *            ascending token order, rounded once; N <= 16384.
+ *   unmerge: y [B][N][C] = res + o[map], fp32, rounded once. */
+int af_op_tome_match(int dtype, const float* x_dev, int B, int H, int W, int C, double ratio, int normalize, int32_t* node_idx_dev,
+                     float* node_max_dev, int32_t* map_dev, void* stream);
+int af_op_tome_merge(int dtype, const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps,
+                     const int32_t* map_dev, int B, int N, int Nprime, int C, float* y_dev, void* stream);
+int af_op_tome_unmerge_add(int dtype, const float* o_dev, const float* res_dev, const int32_t* map_dev, int B, int N, int Nprime,
+                           int C, float* y_dev, void* stream);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the
@@ -250,7 +283,9 @@ int64_t af_arena_bytes(af_handle* h);
  * 3 layernorm, 4 other, 5 conv_gemm_pp_kernel<160,gather> (3x3 / strided convs on the eight-wave ping-pong kernel),
  * 6 conv_gemm_pp_kernel<160,plain> (1x1 convs / linears), 7 conv_gemm_pp_kernel<128,*> (GEGLU, VAE widths),
  * 8 conv_gemm_pp_kernel<*,*,0,true> (fp8 operands, af_set_fp8), 9 conv3x3_halo8_kernel (3x3 / stride-1 convolutions with an
- * LDS-resident input halo: the largest single kernel of a bf16 step).
+ * LDS-resident input halo: the largest single kernel of a bf16 step); 10-15 the token-merging kernels (af_set_tome), one class per
+ * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual.  A caller that asks af_prof_collect for the
+ * first 10 classes gets what it got before those existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */
 int af_prof_enable(int class_mask); /* bit c set = time class c; 0 = off */

@@ -39,7 +39,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 MODES = (("bf16", "bf16", "base"), ("f32", "f32", "base"), ("fp16", "fp16", "base"), ("fp8_ff", "fp8", "base+ff"))
-N_CLASSES = 10    # AF_K_COUNT (af_common.h)
+N_CLASSES = 10    # the classes of af_common.h in front of the token-merging ones (off here)
 
 
 def record(out: Path, only=None):

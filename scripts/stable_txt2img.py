@@ -66,6 +66,11 @@ def parse_args(argv=None):
                          "feature kept at the last full step (DDIM and --dpm_solver; 1 = off)")
     ap.add_argument("--deep_cache_depth", type=int, default=2, metavar="K",
                     help="--deep_cache: input / output blocks that still run on the steps between (1 .. 11 for SD-1.5)")
+    ap.add_argument("--tome", type=float, default=0.0, metavar="RATIO",
+                    help="token merging in front of the U-Net's self-attention: the share of a map's tokens merged away, "
+                         "0 .. 0.75 (0 = off); composes with every sampler, --deep_cache and --gpus; --dtype bf16 / f32")
+    ap.add_argument("--tome_max_downsample", type=int, default=1, choices=[1, 2],
+                    help="--tome: 1 = the 64x64-level transformers only, 2 = the 32x32 level too")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -88,6 +93,10 @@ def parse_args(argv=None):
         ap.error("--deep_cache N: N >= 1")
     if opt.deep_cache not in (None, 1) and opt.plms:
         ap.error("--deep_cache: PLMS calls the model twice in its first step and keeps an eps history (use DDIM or --dpm_solver)")
+    if not 0.0 <= opt.tome <= 0.75:
+        ap.error("--tome RATIO: 0 <= RATIO <= 0.75")
+    if opt.tome > 0.0 and opt.dtype in ("fp16", "fp8"):
+        ap.error("--tome: token merging runs with --dtype bf16 or f32")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     return opt
@@ -137,6 +146,8 @@ def main():
         model = instantiate_from_config(config["model"]).eval()
     model = model.to(device)
     model = model.set_compute_dtype(opt.dtype, fp8_scope=opt.fp8_scope) if opt.dtype == "fp8" else model.set_compute_dtype(opt.dtype)
+    if opt.tome > 0.0:
+        model.set_token_merging(opt.tome, opt.tome_max_downsample)
     if not opt.ckpt:  # seeded synthetic weights (identical on every rank)
         g = torch.Generator(device=device).manual_seed(1234)
         with torch.no_grad():

@@ -146,6 +146,11 @@ _SIGS = [
     ("af_op_tome_match", C.c_int, [C.c_int, _P] + [C.c_int] * 4 + [C.c_double, C.c_int, _P, _P, _P, _P]),
     ("af_op_tome_merge", C.c_int, [C.c_int, _P, _P, _P, C.c_float, _P] + [C.c_int] * 4 + [_P, _P]),
     ("af_op_tome_unmerge_add", C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 4 + [_P, _P]),
+    ("af_set_freeu", C.c_int, [_P, C.c_int] + [C.c_double] * 4),
+    ("af_freeu_num_sites", C.c_int, [_P]),
+    ("af_freeu_site", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("af_freeu_plan_query", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int64)]),
+    ("af_op_freeu", C.c_int, [C.c_int, _P, _P] + [C.c_int] * 6 + [C.c_double, C.c_double, _P, _P, _P]),
     ("af_flops_issued", C.c_double, [C.c_int]),
     ("af_clock_probe", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
@@ -230,6 +235,18 @@ def tome_plan_query(H, W, ratio) -> tuple:
     out = (C.c_int64 * 4)()
     check(load().af_tome_plan_query(int(H), int(W), float(ratio), out), "af_tome_plan_query")
     return tuple(int(v) for v in out)
+
+
+FREEU_KERNELS = ("refused", "single", "chunked")           # AfFreeuKernel (csrc/af_kernels.h)
+
+
+def freeu_plan_query(dtype, H, W, Ch, Cs, version=1) -> dict:
+    """af_freeu_plan_query: how FreeU runs on one site's H x W map with Ch backbone and Cs skip channels -- kernel form by name,
+    launches (backbone and skip both live), 256-pixel chunks and partial-sum bytes per sample.  Host only: no GPU is needed."""
+    out = (C.c_int64 * 4)()
+    dt = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    check(load().af_freeu_plan_query(dt, int(H), int(W), int(Ch), int(Cs), int(version), out), "af_freeu_plan_query")
+    return {"kernel": FREEU_KERNELS[int(out[0])], "launches": int(out[1]), "chunks": int(out[2]), "partial_bytes": int(out[3])}
 
 
 GN_KERNELS = ("refused", "small", "fold", "finalize")     # AfGnKernel (csrc/af_kernels.h)

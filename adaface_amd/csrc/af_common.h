@@ -67,7 +67,9 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        AF_K_PP160_GATHER = 5, AF_K_PP160_PLAIN = 6, AF_K_PP128 = 7, AF_K_PP_FP8 = 8, AF_K_HALO8 = 9,
        // the token-merging kernels, one class each (af_tome.hip; scripts/tome_mode.py quotes them one by one)
        AF_K_TOME_RNORM = 10, AF_K_TOME_MATCH = 11, AF_K_TOME_RANK = 12, AF_K_TOME_MAP = 13, AF_K_TOME_MERGE = 14,
-       AF_K_TOME_UNMERGE = 15, AF_K_COUNT = 16 };
+       AF_K_TOME_UNMERGE = 15,
+       // the FreeU kernels, one class each (af_freeu.hip; scripts/freeu_mode.py)
+       AF_K_FREEU_MEAN = 16, AF_K_FREEU_SUMS = 17, AF_K_FREEU_APPLY = 18, AF_K_FREEU_SMALL = 19, AF_K_COUNT = 20 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)

@@ -121,6 +121,26 @@ template <typename T>
 int af_launch_tome_unmerge_add(const void* o, int ldo, const void* res, int ldr, const int* map, int B, int N, int Np, int C,
                                void* y, int ldy, float* ln_stats_out, int ln_parts, hipStream_t s);
 
+// FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
+// types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
+enum AfFreeuKernel {
+  AF_FREEUK_REFUSED = 0,   // a map side < 2, Ch % 16, Cs % 8, a version that is neither 1 nor 2: -1 with a message, nothing runs
+  AF_FREEUK_SINGLE = 1,    // freeu_small_kernel: H W <= 256, low-band sums and apply in one launch
+  AF_FREEUK_CHUNKED = 2    // freeu_sums_kernel (one partial per 256-pixel chunk) + freeu_apply_kernel
+};
+struct AfFreeuPlan {
+  int kernel;         // AfFreeuKernel
+  int launches;       // with backbone and skip both live: 1 / 2, one more (freeu_mean_kernel) for version 2
+  int nchunk;         // 256-pixel chunks of a sample's map
+  long part_bytes;    // partial sums per sample, [nchunk][7][Cs] fp32 (0 on SINGLE)
+};
+int af_plan_freeu(int H, int W, int Ch, int Cs, int version, AfFreeuPlan* pl);
+size_t af_freeu_ws_bytes(int B, int H, int W, int Ch, int Cs, int version);   // 0 for a refused plan
+// backbone / skip false: that half is left alone (b == 1 / s == 1 do the same).  b in [1, 2], s in [0, 1].  ws: af_freeu_ws_bytes
+template <typename T>
+int af_launch_freeu(void* cat, int ld, int B, int H, int W, int Ch, int Cs, int version, float b, float s, bool backbone,
+                    bool skip, void* ws, hipStream_t stream);
+
 template <typename T>
 int af_launch_nchw_to_nhwc(const float* x, void* y, int B, int Cn, int HW, int Cpad, float scale, hipStream_t s);
 template <typename T> int af_launch_nhwc_to_nchw(const void* x, float* y, int B, int Cn, int HW, int ld, hipStream_t s);

@@ -331,6 +331,37 @@ struct af_handle {
     return n;
   }
 
+  // FreeU (af_set_freeu): version 0 = off.  A site is an output block whose incoming backbone has 4 mc (pair 0:
+  // b1, s1) or 2 mc (pair 1: b2, s2) channels, numbered in forward order; ds = the latent's side over the site's map side.
+  int freeu_version = 0;
+  double freeu_b[2] = {1.0, 1.0}, freeu_s[2] = {1.0, 1.0};
+  struct FreeuSite { int j, Ch, Cs, pair, ds; };
+  int freeu_pair(int Ch) const { return Ch == 4 * cfg.model_channels ? 0 : Ch == 2 * cfg.model_channels ? 1 : -1; }
+  std::vector<FreeuSite> freeu_sites() const {   // from the block structure alone (the walk of unet_forward_impl, channels only)
+    struct Shp { int C, ds; };
+    auto out_shape = [&](const UBlock& ub, Shp in) {
+      for (const auto& l : ub.layers) {
+        if (l.kind == L_CONV_IN) in.C = cfg.model_channels;
+        else if (l.kind == L_RES) in.C = res[l.idx].cout;
+        else if (l.kind == L_DOWN) in.ds *= 2;
+        else if (l.kind == L_UP) in.ds /= 2;
+      }
+      return in;
+    };
+    std::vector<FreeuSite> sites;
+    std::vector<Shp> shp_in;
+    Shp cur = {cfg.in_channels, 1};
+    for (const auto& ub : input_blocks) shp_in.push_back(cur = out_shape(ub, cur));
+    cur = out_shape(middle_block, cur);
+    for (size_t j = 0; j < output_blocks.size() && j < shp_in.size(); ++j) {
+      const Shp sk = shp_in[shp_in.size() - 1 - j];
+      const int pair = freeu_pair(cur.C);
+      if (pair >= 0) sites.push_back({(int)j, cur.C, sk.C, pair, cur.ds > 0 ? cur.ds : 1});
+      cur = out_shape(output_blocks[j], Shp{cur.C + sk.C, cur.ds});
+    }
+    return sites;
+  }
+
   // DeepCache (af_unet_forward_cached): while that entry point runs, the concatenation buffer cat[n_out - depth] lives here
   // and not in the arena (which is re-planned by every forward and shared with the VAE / CLIP calls).  A refresh writes both
   // halves; a reuse step rewrites the skip half and reads the kept h half D = output of output_blocks[n_out - depth - 1].
@@ -1827,8 +1858,29 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     hcur = o;
     AF_TRY(tap(n_in, hcur));
   }
+  // FreeU (af_set_freeu), in place on cat[j] just before its only reader.  The DeepCache feature D is the h half of
+  // cat[n_out - dc_depth]: a refresh scales it where it is kept, so a reuse step filters that concatenation's fresh skip only.
+  auto freeu = [&](int j) -> int {
+    const int pair = h->freeu_version ? h->freeu_pair(ch_h[j]) : -1;
+    if (pair < 0) return 0;
+    const Act& a = cat[j];
+    const int Ch = ch_h[j], Cs = a.C - Ch;
+    const bool kept = dc_reuse && j == n_out - dc_depth;
+    const size_t bytes = af_freeu_ws_bytes(Bf, a.H, a.W, Ch, Cs, h->freeu_version);
+    if (!bytes) return AF_ERR_INVALID;   // (a side-1 map or a width the kernels refuse; the plan left the message)
+    const size_t mk = R.A.mark();
+    void* ws = R.A.alloc(bytes);
+    if (!ws) { af_set_error_msg("activation arena exhausted (FreeU, cap %zu)", R.A.cap); return AF_ERR_STATE; }
+    int rc = 0;
+    if (!R.dry)
+      rc = AF_TYPED(dt, af_launch_freeu<Elem>(a.p, a.ld, Bf, a.H, a.W, Ch, Cs, h->freeu_version, (float)h->freeu_b[pair],
+                                              (float)h->freeu_s[pair], !kept, true, ws, s));
+    R.A.release(mk);
+    return rc ? AF_ERR_INVALID : 0;
+  };
   for (int j = dc_reuse ? n_out - dc_depth : 0; j < n_out; ++j) {
     Act o;
+    AF_TRY(freeu(j));
     if (j + 1 < n_out) {
       const Act dst = view(cat[j + 1], 0, ch_h[j + 1]);
       AF_TRY(run_block(h->output_blocks[j], cat[j], o, &dst, Bf, false));
@@ -2386,6 +2438,12 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
   const int down = 1 << (h->cfg.n_channel_mult - 1);
   if (H % down || W % down) { af_set_error_msg("af_unet_forward: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
+  if (h->freeu_version)   // (before anything is enqueued: the closed form of the Fourier filter needs two rows and two columns)
+    for (const auto& st : h->freeu_sites())
+      if (H / st.ds < 2 || W / st.ds < 2) {
+        af_set_error_msg("af_unet_forward: FreeU needs map sides >= 2, output block %d sees %d x %d", st.j, H / st.ds, W / st.ds);
+        return AF_ERR_INVALID;
+      }
   af_handle::DeepCache& dc = h->dc;
   if (dc_mode) {
     const int n_in = (int)h->input_blocks.size(), n_out = (int)h->output_blocks.size();
@@ -2513,6 +2571,40 @@ int af_tome_set_tap(af_handle* h, int site, int32_t* map_dev) {
   if (site >= af_tome_num_sites(h)) { af_set_error_msg("af_tome_set_tap: site %d out of range (%d sites)", site, af_tome_num_sites(h)); return AF_ERR_INVALID; }
   h->tome_tap_site = (site >= 0 && map_dev) ? site : -1;
   h->tome_tap_out = h->tome_tap_site >= 0 ? map_dev : nullptr;
+  return AF_OK;
+}
+
+int af_set_freeu(af_handle* h, int version, double b1, double b2, double s1, double s2) {
+  if (!h) { af_set_error_msg("af_set_freeu: null handle"); return AF_ERR_INVALID; }
+  if (version < 0 || version > 2) { af_set_error_msg("af_set_freeu: version %d (0 = off, 1, 2)", version); return AF_ERR_INVALID; }
+  if (version == 0) {
+    b1 = b2 = s1 = s2 = 1.0;   // (off is always accepted)
+  } else {
+    if (!(b1 >= 1.0 && b1 <= 2.0) || !(b2 >= 1.0 && b2 <= 2.0)) { af_set_error_msg("af_set_freeu: b1 %g, b2 %g outside [1, 2]", b1, b2); return AF_ERR_INVALID; }
+    if (!(s1 >= 0.0 && s1 <= 1.0) || !(s2 >= 0.0 && s2 <= 1.0)) { af_set_error_msg("af_set_freeu: s1 %g, s2 %g outside [0, 1]", s1, s2); return AF_ERR_INVALID; }
+    if (!h->cfg.build_unet) { af_set_error_msg("af_set_freeu: handle has no UNet"); return AF_ERR_STATE; }
+  }
+  if (version != h->freeu_version || b1 != h->freeu_b[0] || b2 != h->freeu_b[1] || s1 != h->freeu_s[0] || s2 != h->freeu_s[1])
+    h->dc.valid = false;   // (a kept DeepCache feature belongs to the setting that wrote it)
+  h->freeu_version = version;
+  h->freeu_b[0] = b1; h->freeu_b[1] = b2;
+  h->freeu_s[0] = s1; h->freeu_s[1] = s2;
+  return AF_OK;
+}
+int af_freeu_num_sites(af_handle* h) { return (h && h->cfg.build_unet) ? (int)h->freeu_sites().size() : 0; }
+int af_freeu_site(af_handle* h, int site, int out[4]) {
+  if (!h || !out) { af_set_error_msg("af_freeu_site: null argument"); return AF_ERR_INVALID; }
+  const auto sites = h->cfg.build_unet ? h->freeu_sites() : std::vector<af_handle::FreeuSite>();
+  if (site < 0 || site >= (int)sites.size()) { af_set_error_msg("af_freeu_site: site %d out of range (%d sites)", site, (int)sites.size()); return AF_ERR_INVALID; }
+  out[0] = sites[site].j; out[1] = sites[site].Ch; out[2] = sites[site].Cs; out[3] = sites[site].pair;
+  return AF_OK;
+}
+int af_freeu_plan_query(int dtype, int H, int W, int Ch, int Cs, int version, int64_t out[4]) {
+  if (!out) { af_set_error_msg("af_freeu_plan_query: null output"); return AF_ERR_INVALID; }
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_freeu_plan_query: storage type %d", dtype); return AF_ERR_INVALID; }
+  AfFreeuPlan pl;
+  if (af_plan_freeu(H, W, Ch, Cs, version, &pl)) return AF_ERR_INVALID;
+  out[0] = pl.kernel; out[1] = pl.launches; out[2] = pl.nchunk; out[3] = pl.part_bytes;
   return AF_OK;
 }
 

@@ -949,6 +949,32 @@ int af_op_tome_unmerge_add(int dtype, const float* o_dev, const float* res_dev, 
   return AF_OK;
 }
 
+// FreeU on one concatenation (af_freeu.hip): the buffer [B][H W][Ch + Cs] as the model holds it, the model's launcher, and back
+int af_op_freeu(int dtype, const float* h_dev, const float* skip_dev, int B, int Ch, int Cs, int H, int W, int version, double b,
+                double s, float* h_out_dev, float* skip_out_dev, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_op_freeu: storage type %d", dtype); return AF_ERR_INVALID; }
+  if (B <= 0 || !h_dev || !skip_dev || !h_out_dev || !skip_out_dev) { af_set_error_msg("af_op_freeu: bad argument"); return AF_ERR_INVALID; }
+  if (!(b >= 1.0 && b <= 2.0) || !(s >= 0.0 && s <= 1.0)) { af_set_error_msg("af_op_freeu: b %g outside [1, 2] or s %g outside [0, 1]", b, s); return AF_ERR_INVALID; }
+  AfFreeuPlan pl;
+  if (af_plan_freeu(H, W, Ch, Cs, version, &pl)) return AF_ERR_INVALID;
+  const int HW = H * W, ld = Ch + Cs;
+  const long npix = (long)B * HW;
+  OP_ALLOC(hn, (size_t)npix * Ch * esize(dtype), false);
+  OP_ALLOC(sn, (size_t)npix * Cs * esize(dtype), false);
+  OP_ALLOC(cat, (size_t)npix * ld * esize(dtype) + 4096, false);
+  OP_ALLOC(ws, af_freeu_ws_bytes(B, H, W, Ch, Cs, version), false);
+  AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(h_dev, hn, B, Ch, HW, Ch, 1.0f, st)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nchw_to_nhwc<Elem>(skip_dev, sn, B, Cs, HW, Cs, 1.0f, st)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(hn, Ch, cat, ld, 0, Ch, npix, st)));
+  AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(sn, Cs, cat, ld, Ch, Cs, npix, st)));
+  if (AF_TYPED(dtype, af_launch_freeu<Elem>(cat, ld, B, H, W, Ch, Cs, version, (float)b, (float)s, true, true, ws, st))) return AF_ERR_INVALID;
+  AF_TRY(AF_TYPED(dtype, af_launch_nhwc_to_nchw<Elem>(cat, h_out_dev, B, Ch, HW, ld, st)));
+  AF_TRY(AF_TYPED(dtype, af_launch_nhwc_to_nchw<Elem>(reinterpret_cast<char*>(cat) + (size_t)Ch * esize(dtype), skip_out_dev, B, Cs, HW, ld, st)));
+  return AF_OK;
+}
+
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;

@@ -29,6 +29,21 @@ def check_tome_args(ratio, max_downsample=1):
     return float(ratio), int(max_downsample)
 
 
+def check_freeu_args(version, b1=1.0, b2=1.0, s1=1.0, s2=1.0):
+    """(version, b1, b2, s1, s2) of FreeU as the C library takes them; ValueError for anything it would refuse.  Version 0 (off)
+    takes any numbers and returns ones.  No GPU is needed."""
+    if isinstance(version, bool) or version not in (0, 1, 2):
+        raise ValueError(f"FreeU: version {version!r} (0 = off, 1, 2)")
+    if version == 0:
+        return 0, 1.0, 1.0, 1.0, 1.0
+    vals = []
+    for name, v, lo, hi in (("b1", b1, 1.0, 2.0), ("b2", b2, 1.0, 2.0), ("s1", s1, 0.0, 1.0), ("s2", s2, 0.0, 1.0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) <= hi:
+            raise ValueError(f"FreeU: {name} {v!r} (a number in [{lo:g}, {hi:g}])")
+        vals.append(float(v))
+    return (int(version), *vals)
+
+
 def _fill(arr, values: Sequence[int]):
     if len(values) > 8:
         raise ValueError("at most 8 entries supported")
@@ -213,6 +228,28 @@ class Engine:
     def tome_num_sites(self) -> int:
         """Transformer blocks that merge under the current setting (forward order)."""
         return int(self._lib.af_tome_num_sites(self._h))
+
+    def set_freeu(self, version: int, b1: float = 1.0, b2: float = 1.0, s1: float = 1.0, s2: float = 1.0):
+        """af_set_freeu: FreeU in front of every output block whose incoming backbone has 4 (b1, s1) or 2 (b2, s2) times
+        model_channels channels: the first half of the backbone's channels scaled by b (version 1) or by (b - 1) * mhat + 1
+        (version 2: mhat the min-max normalised channel mean), the skip's lowest frequencies scaled by s.  version 0 = off;
+        b in [1, 2], s in [0, 1].  Every dtype and mode.  Drops a kept DeepCache feature when the setting changes."""
+        setting = check_freeu_args(version, b1, b2, s1, s2)
+        check(self._lib.af_set_freeu(self._h, *setting), "af_set_freeu")
+        self.freeu = setting
+
+    def freeu_num_sites(self) -> int:
+        """Output blocks FreeU acts on (whether or not it is switched on)."""
+        return int(self._lib.af_freeu_num_sites(self._h))
+
+    def freeu_sites(self) -> list:
+        """[(output block j, Ch, Cs, pair)] of the FreeU sites in forward order; pair 0: (b1, s1), 1: (b2, s2)."""
+        out = (C.c_int * 4)()
+        sites = []
+        for i in range(self.freeu_num_sites()):
+            check(self._lib.af_freeu_site(self._h, i, out), "af_freeu_site")
+            sites.append(tuple(int(v) for v in out))
+        return sites
 
     def unet_cache_invalidate(self):
         """Drop the feature kept by unet_forward_cached(mode="refresh"): the next reuse call raises until a refresh ran."""

@@ -290,6 +290,11 @@ class LatentDiffusion(DDPM):
         self.model.diffusion_model.set_token_merging(ratio, max_downsample)
         return self
 
+    def set_freeu(self, version, b1=1.0, b2=1.0, s1=1.0, s2=1.0):
+        """UNetModel.set_freeu: opt-in FreeU backbone scaling and Fourier-filtered skips in the U-Net (version 0 = off)."""
+        self.model.diffusion_model.set_freeu(version, b1, b2, s1, s2)
+        return self
+
     def set_compute_dtype(self, dtype: str, fp8_scope: str = "base"):
         """'bf16' | 'f32' | 'f16' (alias 'fp16') | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).
         fp8_scope: 'base' (ResBlock convolutions and self-attention q / k / v) or 'base+ff' (also the transformer blocks'

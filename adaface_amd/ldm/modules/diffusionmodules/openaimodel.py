@@ -128,6 +128,23 @@ class UNetModel(HipModule):
     def token_merging(self) -> tuple:
         return self._tome
 
+    def set_freeu(self, version, b1=1.0, b2=1.0, s1=1.0, s2=1.0):
+        """FreeU (Si et al., CVPR 2024; not in the reference, off by default): in front of every output block whose incoming
+        backbone has 4 * model_channels (b1, s1) or 2 * model_channels (b2, s2) channels, the first half of the backbone's
+        channels is scaled by b (version 1) or by (b - 1) * mhat + 1 (version 2) and the skip's lowest frequencies by s.
+        version 0 = off; b in [1, 2], s in [0, 1].  Kept for every later engine; a live one is switched now.  Every compute
+        dtype."""
+        from adaface_amd.engine import check_freeu_args
+        setting = check_freeu_args(version, b1, b2, s1, s2)
+        if self._engine is not None:
+            self._engine.set_freeu(*setting)
+        object.__setattr__(self, "_freeu", setting)
+        return self
+
+    @property
+    def freeu(self) -> tuple:
+        return self._freeu
+
     @staticmethod
     def _conv_attn_spec(ks, placeholder2indices):
         """(ks, batch indices, token positions) for Engine.set_conv_attn from the reference's

@@ -288,6 +288,21 @@ def tome_unmerge_add(o, res, tmap, dtype="bf16"):
     return y
 
 
+def freeu(h, skip, version, b, s, dtype="bf16"):
+    """FreeU on one concatenation, h [B, Ch, H, W] and skip [B, Cs, H, W] (Ch % 16 == 0, Cs % 8 == 0, H, W >= 2): the first
+    Ch / 2 channels of h times b (version 1) or times (b - 1) * mhat + 1 (version 2), skip + (s - 1) * its part at the
+    frequencies {-1, 0}^2; fp32 arithmetic on the values stored as `dtype`, rounded once.  Returns (h', skip') in fp32."""
+    lib = _lib.load()
+    h, skip = _dev_f32(h), _dev_f32(skip)
+    B, Ch, H, W = h.shape
+    if skip.shape[0] != B or tuple(skip.shape[2:]) != (H, W):
+        raise ValueError(f"freeu: h {tuple(h.shape)} and skip {tuple(skip.shape)} do not concatenate")
+    h_out, skip_out = torch.empty_like(h), torch.empty_like(skip)
+    check(lib.af_op_freeu(DTYPES[dtype], ptr(h), ptr(skip), B, Ch, skip.shape[1], H, W, int(version), float(b), float(s),
+                          ptr(h_out), ptr(skip_out), stream_ptr()), "af_op_freeu")
+    return h_out, skip_out
+
+
 def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=False):
     """softmax(q k^T * scale) v per head; q [B,N,heads*dh], k/v [B,S,heads*dh] (attention.py:197-243).  causal: query i
     attends to keys <= i (the CLIP text tower's mask).  nan_guard (tests): K / V sit in front of 128 rows of NaNs."""

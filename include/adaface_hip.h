@@ -166,6 +166,31 @@ int af_op_tome_merge(int dtype, const float* x_dev, const float* gamma_dev, cons
 int af_op_tome_unmerge_add(int dtype, const float* o_dev, const float* res_dev, const int32_t* map_dev, int B, int N, int Nprime,
                            int C, float* y_dev, void* stream);
 
+/* FreeU (Si, Huang, Jiang, Liu, "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024; the authors' LDM patch with threshold = 1),
+ * opt-in: just before h = cat([h, hs.pop()]) of every output block whose incoming backbone h has Ch = 4 model_channels (b1, s1)
+ * or 2 model_channels (b2, s2) channels -- the FreeU sites, numbered in forward order; j = 0..6 and 7..9 for SD-1.5 --
+ *   backbone, first Ch / 2 channels: version 1: h *= b; version 2: h *= (b - 1) mhat + 1, mhat = the per-sample min-max
+ *                                    normalised mean of h over all Ch channels, one value per pixel;
+ *   skip, all Cs channels:           hs += (s - 1) low(hs), low = the part of the map at the frequencies (ky, kx) in {-1, 0}^2:
+ *                                    what fftn / fftshift / the 2 x 2 box / ifftshift / ifftn / .real of the reference keep.
+ * fp32 arithmetic on the stored values, one rounding, no atomics: bit-identical run to run and whatever else is in the batch.
+ * version 0 = off (always accepted; the forwards are then what they are without this call, launch for launch), 1, 2; b1, b2 in
+ * [1, 2], s1, s2 in [0, 1], else AF_ERR_INVALID.  b = 1 / s = 1 leave their half's bits alone.  Every handle dtype, the fp8
+ * mode, token merging, the twin and the cached forwards; a change of the setting drops a kept DeepCache feature (which is kept
+ * scaled: a reuse step filters the kept concatenation's skip only).  Maps at a site need sides >= 2 (AF_ERR_INVALID from the
+ * forward, nothing launched).  The published SD-1.5 values: version 1: 1.2, 1.4, 0.9, 0.2; version 2: 1.3, 1.4, 0.9, 0.2.
+ * af_freeu_site: out = {output block j, Ch, Cs, pair (0: b1 / s1, 1: b2 / s2)}.
+ * af_freeu_plan_query (host only): out = {kernel form (1: one launch for sums and apply, H W <= 256; 2: per-chunk sums + apply),
+ * launches, 256-pixel chunks, partial-sum bytes per sample}; sides < 2, Ch % 16 and Cs % 8 are refused.
+ * af_op_freeu: one site as an operator, fp32 NCHW h [B][Ch][H][W] and skip [B][Cs][H][W] in and out (stored as `dtype` in the
+ * model's [h | skip] rows, the model's launcher, and back). */
+int af_set_freeu(af_handle* h, int version, double b1, double b2, double s1, double s2);
+int af_freeu_num_sites(af_handle* h);
+int af_freeu_site(af_handle* h, int site, int out[4]);
+int af_freeu_plan_query(int dtype, int H, int W, int Ch, int Cs, int version, int64_t out[4]);
+int af_op_freeu(int dtype, const float* h_dev, const float* skip_dev, int B, int Ch, int Cs, int H, int W, int version, double b,
+                double s, float* h_out_dev, float* skip_out_dev, void* stream);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the
@@ -284,8 +309,9 @@ int64_t af_arena_bytes(af_handle* h);
  * 6 conv_gemm_pp_kernel<160,plain> (1x1 convs / linears), 7 conv_gemm_pp_kernel<128,*> (GEGLU, VAE widths),
  * 8 conv_gemm_pp_kernel<*,*,0,true> (fp8 operands, af_set_fp8), 9 conv3x3_halo8_kernel (3x3 / stride-1 convolutions with an
  * LDS-resident input halo: the largest single kernel of a bf16 step); 10-15 the token-merging kernels (af_set_tome), one class per
- * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual.  A caller that asks af_prof_collect for the
- * first 10 classes gets what it got before those existed.
+ * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual; 16-19 the FreeU kernels (af_set_freeu): hidden
+ * mean + min / max, low-band sums, apply, the single-launch small-map form.  A caller that asks af_prof_collect for the first 10
+ * or 16 classes gets what it got before the later ones existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */
 int af_prof_enable(int class_mask); /* bit c set = time class c; 0 = off */

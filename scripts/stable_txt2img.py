@@ -71,6 +71,11 @@ def parse_args(argv=None):
                          "0 .. 0.75 (0 = off); composes with every sampler, --deep_cache and --gpus; --dtype bf16 / f32")
     ap.add_argument("--tome_max_downsample", type=int, default=1, choices=[1, 2],
                     help="--tome: 1 = the 64x64-level transformers only, 2 = the 32x32 level too")
+    ap.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
+                    help="FreeU: backbone factors B1, B2 in [1, 2] and skip factors S1, S2 in [0, 1] (SD-1.5: 1.2 1.4 0.9 0.2, "
+                         "version 2: 1.3 1.4 0.9 0.2); composes with every sampler, --dtype, --deep_cache, --tome and --gpus")
+    ap.add_argument("--freeu_version", type=int, default=1, choices=[1, 2],
+                    help="--freeu: 1 = a constant backbone factor, 2 = the factor follows the backbone's channel mean")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -97,6 +102,12 @@ def parse_args(argv=None):
         ap.error("--tome RATIO: 0 <= RATIO <= 0.75")
     if opt.tome > 0.0 and opt.dtype in ("fp16", "fp8"):
         ap.error("--tome: token merging runs with --dtype bf16 or f32")
+    if opt.freeu is not None:
+        b1, b2, s1, s2 = opt.freeu
+        if not (1.0 <= b1 <= 2.0 and 1.0 <= b2 <= 2.0):
+            ap.error("--freeu B1 B2 S1 S2: 1 <= B1, B2 <= 2")
+        if not (0.0 <= s1 <= 1.0 and 0.0 <= s2 <= 1.0):
+            ap.error("--freeu B1 B2 S1 S2: 0 <= S1, S2 <= 1")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     return opt
@@ -148,6 +159,8 @@ def main():
     model = model.set_compute_dtype(opt.dtype, fp8_scope=opt.fp8_scope) if opt.dtype == "fp8" else model.set_compute_dtype(opt.dtype)
     if opt.tome > 0.0:
         model.set_token_merging(opt.tome, opt.tome_max_downsample)
+    if opt.freeu is not None:
+        model.set_freeu(opt.freeu_version, *opt.freeu)
     if not opt.ckpt:  # seeded synthetic weights (identical on every rank)
         g = torch.Generator(device=device).manual_seed(1234)
         with torch.no_grad():

@@ -166,7 +166,7 @@ say()
 
 
 # ---------------------------------------------------------------- (b) the kernels ------------------------------------
-N_CLS = 16                                   # AF_K_COUNT (af_common.h)
+N_CLS = 16                                   # the classes of af_common.h in front of the FreeU ones (off here)
 GEMM_CLS, ATTN_CLS, LN_CLS = (0, 5, 6, 7, 8, 9), 1, 3
 TOME_CLS = (("rnorm", 10), ("match", 11), ("rank", 12), ("map", 13), ("merge", 14), ("unmerge", 15))
 

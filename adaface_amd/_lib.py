@@ -151,6 +151,13 @@ _SIGS = [
     ("af_freeu_site", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("af_freeu_plan_query", C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int64)]),
     ("af_op_freeu", C.c_int, [C.c_int, _P, _P] + [C.c_int] * 6 + [C.c_double, C.c_double, _P, _P, _P]),
+    ("af_set_pag", C.c_int, [_P, C.POINTER(C.c_int), C.c_int]),
+    ("af_pag_num_sites", C.c_int, [_P]),
+    ("af_pag_site", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("af_pag_plan_query", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("af_unet_forward_pag", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_guidance", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    ("af_guidance_plan_query", C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("af_flops_issued", C.c_double, [C.c_int]),
     ("af_clock_probe", C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
@@ -158,6 +165,9 @@ EXPORTED_SYMBOLS = [s[0] for s in _SIGS]
 
 # the `mode` argument of af_unet_forward_cached (include/adaface_hip.h)
 DEEPCACHE_MODES = {"refresh": 1, "reuse": 2}
+# ... and its `twin` argument, the form of the forward (AF_UNET_FORM_*); False / True keep their meaning
+UNET_FORMS = {False: 0, True: 1, "plain": 0, "twin": 1, "pag": 2}
+UNET_FORM_LEGS = {0: 1, 1: 2, 2: 3}
 
 
 def lib_path() -> Path:
@@ -247,6 +257,17 @@ def freeu_plan_query(dtype, H, W, Ch, Cs, version=1) -> dict:
     dt = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
     check(load().af_freeu_plan_query(dt, int(H), int(W), int(Ch), int(Cs), int(version), out), "af_freeu_plan_query")
     return {"kernel": FREEU_KERNELS[int(out[0])], "launches": int(out[1]), "chunks": int(out[2]), "partial_bytes": int(out[3])}
+
+
+GUIDANCE_KERNELS = ("refused", "combine", "single", "chunked")   # AfGuidanceKernel (csrc/af_kernels.h)
+
+
+def guidance_plan_query(n_samples, per_sample, rescale_on) -> dict:
+    """af_guidance_plan_query: how af_guidance runs -- kernel form by name, launches, 256-element chunks per sample and
+    partial bytes per sample.  Host only: no GPU is needed."""
+    out = (C.c_int64 * 4)()
+    check(load().af_guidance_plan_query(int(n_samples), int(per_sample), int(bool(rescale_on)), out), "af_guidance_plan_query")
+    return {"kernel": GUIDANCE_KERNELS[int(out[0])], "launches": int(out[1]), "chunks": int(out[2]), "partial_bytes": int(out[3])}
 
 
 GN_KERNELS = ("refused", "small", "fold", "finalize")     # AfGnKernel (csrc/af_kernels.h)

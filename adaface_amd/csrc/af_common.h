@@ -69,7 +69,9 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        AF_K_TOME_RNORM = 10, AF_K_TOME_MATCH = 11, AF_K_TOME_RANK = 12, AF_K_TOME_MAP = 13, AF_K_TOME_MERGE = 14,
        AF_K_TOME_UNMERGE = 15,
        // the FreeU kernels, one class each (af_freeu.hip; scripts/freeu_mode.py)
-       AF_K_FREEU_MEAN = 16, AF_K_FREEU_SUMS = 17, AF_K_FREEU_APPLY = 18, AF_K_FREEU_SMALL = 19, AF_K_COUNT = 20 };
+       AF_K_FREEU_MEAN = 16, AF_K_FREEU_SUMS = 17, AF_K_FREEU_APPLY = 18, AF_K_FREEU_SMALL = 19,
+       // the guidance kernels (af_guidance.hip; scripts/pag_mode.py): the chunk statistics, and every form that writes the output
+       AF_K_GUIDANCE_STATS = 20, AF_K_GUIDANCE_APPLY = 21, AF_K_COUNT = 22 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)
@@ -139,6 +141,9 @@ struct AfKnobs {
   int conv_attn_short;      // AF_CONV_ATTN_SHORT      0 = subject-token conv attention stays on the flash kernels + subj_scores / merge
                             //                         (and its samples without a subject on the flash kernels too), as before the
                             //                         one-pass xattn_short_conv_kernel: the A/B handle of that kernel
+  int pag_share_prefix;     // AF_PAG_SHARE_PREFIX     0 = af_unet_forward_pag computes all three legs from conv_in on; 1 = every block in
+                            //                         front of the first one with a set site runs on legs 0-1 and leg 0 is copied onto
+                            //                         leg 2: the A/B handle of that sharing
 };
 extern AfKnobs g_af_knobs;
 

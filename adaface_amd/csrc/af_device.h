@@ -1,5 +1,5 @@
 // adaface_amd — device primitives shared by the kernel files (af_conv_gemm.hip with af_conv_gemm_pp_body.h, af_conv_s8.hip,
-// af_xattn_fused.hip, af_attention.hip): the asm / builtin wrappers whose exact form was learned the hard way, once each.
+// af_xattn_fused.hip, af_attention.hip, af_guidance.hip): the asm / builtin wrappers whose exact form was learned the hard way, once each.
 // Device code only: nothing on the host side includes this.  What looks alike but is not the same stays with its kernel
 // (ring::mma, the two max3f, xhalf_max / xgroup_max, lds_off, tile_coords, the site-specific "+v" pins).
 #pragma once
@@ -72,6 +72,14 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
 // one v_mfma_f32_16x16x32_bf16 on 16-byte fragments
 __device__ __forceinline__ f32x4 mma16(const u32x4& a, const u32x4& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// Sum over the 64 lanes of a wave, xor butterfly: fp32 addition commutes, so every lane ends with the same bits, and they
+// depend on the 64 values and their lanes alone.  All lanes of the wave must call it.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 1; off < AF_WAVE; off <<= 1) v += __shfl_xor(v, off, AF_WAVE);
+  return v;
 }
 
 // LayerNorm (mu, rstd) of a row from its sum and sum of squares.  The folded LayerNorm path is bit-identical to the

@@ -141,6 +141,22 @@ template <typename T>
 int af_launch_freeu(void* cat, int ld, int B, int H, int W, int Ch, int Cs, int version, float b, float s, bool backbone,
                     bool skip, void* ws, hipStream_t stream);
 
+// The guidance combine with PAG and rescale (af_guidance.hip, which also holds af_guidance itself).  The plan of one call: the
+// launcher follows it and af_guidance_plan_query reports it.  The values are part of that result.
+enum AfGuidanceKernel {
+  AF_GDK_REFUSED = 0,    // no sample, per_sample < 2 or beyond 2^31, more workgroups than a launch takes: -1 with a message
+  AF_GDK_COMBINE = 1,    // rescale off: guidance_combine_kernel, element-wise
+  AF_GDK_SINGLE = 2,     // rescale on, per_sample <= 1024: guidance_single_kernel, statistics and apply in one launch
+  AF_GDK_CHUNKED = 3     // rescale on: guidance_stats_kernel (one partial per 256-element chunk) + guidance_apply_kernel
+};
+struct AfGuidancePlan {
+  int kernel;         // AfGuidanceKernel
+  int launches;       // 1 / 1 / 2
+  long nchunk;        // 256-element chunks of a sample
+  long part_bytes;    // partials per sample, [nchunk][4] fp32 (CHUNKED only)
+};
+int af_plan_guidance(long n_samples, long per_sample, bool rescale_on, AfGuidancePlan* pl);
+
 template <typename T>
 int af_launch_nchw_to_nhwc(const float* x, void* y, int B, int Cn, int HW, int Cpad, float scale, hipStream_t s);
 template <typename T> int af_launch_nhwc_to_nchw(const void* x, float* y, int B, int Cn, int HW, int ld, hipStream_t s);

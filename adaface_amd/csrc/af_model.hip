@@ -55,7 +55,7 @@ AfKnobs g_af_knobs = {
     knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1), knob_env("AF_ATTN_SHORT", 1),
     knob_env("AF_GEMM_M128", 1),       knob_env("AF_SMALL_M_TILE64", 1),  knob_env("AF_GN_CONSUMER", 1),
     knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0),      knob_env("AF_FF8_MIN_K", 512),   knob_env("AF_FF8_MIN_ROWS", 0),
-    knob_env("AF_CONV_ATTN_SHORT", 1)};
+    knob_env("AF_CONV_ATTN_SHORT", 1), knob_env("AF_PAG_SHARE_PREFIX", 1)};
 static const AfKnobs g_af_knobs_initial = g_af_knobs;
 static int* knob_slot(const char* name) {
   static const struct { const char* n; int AfKnobs::*m; } tab[] = {
@@ -67,7 +67,7 @@ static int* knob_slot(const char* name) {
       {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"ablate", &AfKnobs::ablate}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4},
       {"attn_short", &AfKnobs::attn_short},
       {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}, {"ff8_min_k", &AfKnobs::ff8_min_k}, {"ff8_min_rows", &AfKnobs::ff8_min_rows},
-      {"conv_attn_short", &AfKnobs::conv_attn_short}};
+      {"conv_attn_short", &AfKnobs::conv_attn_short}, {"pag_share_prefix", &AfKnobs::pag_share_prefix}};
   if (!name) return nullptr;
   for (auto& t : tab)
     if (strcmp(t.n, name) == 0) return &(g_af_knobs.*(t.m));
@@ -360,6 +360,47 @@ struct af_handle {
       cur = out_shape(output_blocks[j], Shp{cur.C + sk.C, cur.ds});
     }
     return sites;
+  }
+
+  // Perturbed-attention guidance (af_set_pag): the self-attention layers (entries of ca_list, forward order) whose
+  // attention map is the identity on the third leg of af_unet_forward_pag.  Empty = off; the plain and twin forwards never look.
+  std::vector<char> pag_set;     // [ca_list.size()] once a set was given
+  bool pag_on() const { return std::find(pag_set.begin(), pag_set.end(), (char)1) != pag_set.end(); }
+  bool pag_site_set(int xi, int d) const {
+    for (size_t i = 0; i < ca_list.size() && i < pag_set.size(); ++i)
+      if (pag_set[i] && ca_list[i].first == xi && ca_list[i].second == d) return true;
+    return false;
+  }
+  // site -> {block in the tap numbering (input 0 .. n_in - 1, middle n_in, output n_in + 1 + j), depth index, downsample factor}
+  struct PagSite { int block, depth, ds; };
+  std::vector<PagSite> pag_sites() const {
+    std::vector<PagSite> sites(ca_list.size(), PagSite{-1, 0, 1});
+    int blk = 0;
+    auto walk = [&](const UBlock& ub) {
+      for (const auto& l : ub.layers)
+        if (l.kind == L_XFMR)
+          for (size_t i = 0; i < ca_list.size(); ++i)
+            if (ca_list[i].first == l.idx) sites[i] = PagSite{blk, ca_list[i].second, xf[l.idx].ds};
+      ++blk;
+    };
+    for (const auto& ub : input_blocks) walk(ub);
+    walk(middle_block);
+    for (const auto& ub : output_blocks) walk(ub);
+    return sites;
+  }
+  int pag_first_block() const {   // the first block (tap numbering) that holds a set site; -1: none
+    int first = -1;
+    const auto sites = pag_sites();
+    for (size_t i = 0; i < sites.size() && i < pag_set.size(); ++i)
+      if (pag_set[i] && sites[i].block >= 0 && (first < 0 || sites[i].block < first)) first = sites[i].block;
+    return first;
+  }
+  // input blocks that run on legs 0-1 only: of a full forward (depth <= 0) or of a DeepCache reuse step of that depth
+  int pag_two_leg_blocks(int depth) const {
+    const int first = pag_first_block();
+    if (first < 0 || !g_af_knobs.pag_share_prefix) return 0;
+    const int n_run = depth > 0 ? std::min(depth, (int)input_blocks.size()) : (int)input_blocks.size();
+    return std::min(first, n_run);
   }
 
   // DeepCache (af_unet_forward_cached): while that entry point runs, the concatenation buffer cat[n_out - depth] lives here
@@ -881,6 +922,7 @@ struct Runner {
   int dt;
   bool dry;
   Arena& A;
+  int pag_B = 0;   // af_unet_forward_pag: samples of one leg (the batch is 3 pag_B); 0 in every other forward
   Runner(af_handle* h_, hipStream_t s_) : h(h_), s(s_), dt(h_->dtype), dry(h_->arena.dry), A(h_->arena) {}
 
   Act alloc_act(int B, int H, int W, int C, int ld = 0) {
@@ -1306,6 +1348,11 @@ static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d
     if (site >= 0) return xfmr_self_attention_tome(X, blk, site, Bp, t, n, a, t1);
   }
   const int B = X.B, H = X.H, W = X.W, N = X.N, C = X.C;
+  const bool perturbed = R.pag_B > 0 && R.h->pag_site_set((int)(&X.w - R.h->xf.data()), (int)d);
+  if (perturbed && (Bp != 3 * R.pag_B || B != Bp)) {   // (the shared prefix ends in front of the first block with a set site)
+    af_set_error_msg("PAG: a set site runs on %d of %d samples, not on three legs of %d", Bp, B, R.pag_B);
+    return AF_ERR_STATE;
+  }
   auto pv = [&](Act v) { v.B = Bp; return v; };
   n = R.alloc_act(B, H, W, C);
   Act qkv = R.alloc_act(B, H, W, 3 * C);
@@ -1325,7 +1372,22 @@ static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d
   }
   a = R.alloc_act(B, H, W, C);
   Act ap = pv(a);
-  AF_TRY(R.attention(R.cols_of(qkv, 0, N), R.cols_of(qkv, C, N), R.cols_of(qkv, 2 * C, N), ap, N, N, X.w.heads, X.w.dh));
+  if (perturbed) {
+    // PAG: the attention map of leg 2 is the identity, so its attention output is its v.  The attention kernel runs on the
+    // batch window of legs 0-1 and leg 2's v columns are copied into its rows of a; q / k / v above and to_out below stay
+    // single launches over all three legs (and out1's LayerNorm partial sums cover every row).
+    const int Bl = R.pag_B;
+    AF_TRY(R.attention(R.cols_of(qkv, 0, N), R.cols_of(qkv, C, N), R.cols_of(qkv, 2 * C, N), ap, N, N, X.w.heads, X.w.dh, 0, 2 * Bl));
+    AF_TRY(R.check(qkv));
+    Act vsrc = qkv, adst = a;
+    vsrc.B = adst.B = Bl;
+    vsrc.C = C;
+    vsrc.p = R.elem_ptr(qkv.p, (long)2 * Bl * N * qkv.ld + 2 * C);
+    adst.p = R.elem_ptr(a.p, (long)2 * Bl * N * a.ld);
+    AF_TRY(R.copy_channels(vsrc, adst, 0));
+  } else {
+    AF_TRY(R.attention(R.cols_of(qkv, 0, N), R.cols_of(qkv, C, N), R.cols_of(qkv, 2 * C, N), ap, N, N, X.w.heads, X.w.dh));
+  }
   t1 = R.alloc_act(B, H, W, C);
   Act t1p = pv(t1);
   return R.conv(blk.out1, ap, t1p, X.producer().res(&tp));
@@ -1381,7 +1443,7 @@ static int xfmr_cross_attention_conv(const XfmrCtx& X, const CtxKV& kv, int S, c
   float* amap = lse;
   const Strided qv = R.cols_of(q, 0, N), kk = {kv.kv, 2 * C, (long)S * 2 * C};
   const Strided vv = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
-  const size_t vt_sample = B > 0 ? kv.vt_bytes / (size_t)B : 0;
+  const size_t vt_sample = h->ctx_Bf > 0 ? kv.vt_bytes / (size_t)h->ctx_Bf : 0;   // (the context's batch: B may be its first legs)
   const bool one_pass_on = g_af_knobs.conv_attn_short != 0 && g_af_knobs.attn_short != 0;
   for (int b0 = 0, b1; b0 < B; b0 = b1) {
     const int ng = groups(b0);
@@ -1422,7 +1484,10 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
   const int B = X.B, N = X.N, C = X.C;
   const CtxKV& kv = h->ctx_kv[w.ca_slot + d];
   const int S = h->ctx_tokens;
-  if (!R.dry && (!kv.kv || h->ctx_Bf != B)) {
+  // (PAG's shared prefix runs legs 0-1 of the three-leg context: its first 2 B samples, which every per-sample layout below
+  // holds in front; strides per sample therefore come from the context's batch, not from this launch's)
+  const bool pag_two_legs = R.pag_B > 0 && B == 2 * R.pag_B && h->ctx_Bf == 3 * R.pag_B;
+  if (!R.dry && (!kv.kv || (h->ctx_Bf != B && !pag_two_legs))) {
     af_set_error_msg("context not set for batch %d (af_set_context)", B);
     return AF_ERR_STATE;
   }
@@ -1450,7 +1515,8 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
     AF_TRY(xfmr_cross_attention_conv(X, kv, S, q, a));
   } else {
     const Strided k = {kv.kv, 2 * C, (long)S * 2 * C}, v = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
-    AF_TRY(R.attention(R.cols_of(q, 0, N), k, v, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt, B > 0 ? kv.vt_bytes / (size_t)B : 0));
+    AF_TRY(R.attention(R.cols_of(q, 0, N), k, v, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt,
+                       h->ctx_Bf > 0 ? kv.vt_bytes / (size_t)h->ctx_Bf : 0));
   }
   return R.conv(blk.out2, a, t2, X.producer().res(&t1));
 }
@@ -1672,7 +1738,13 @@ template <typename F> static int run_sized(af_handle* h, hipStream_t s, F&& run)
 // builds it (ddim.py:236-247: torch.cat([x] * 2), cond first).  The time embedding, conv_in, the first ResBlock and the
 // first transformer up to its cross-attention do not see the context: they run on Bf / 2 samples and are copied.
 static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, const int64_t* t_dev, float* eps_dev,
-                             int Bf, int H, int W, bool twin = false, int dc_mode = 0, int dc_depth = 0) {
+                             int Bf, int H, int W, int form = AF_UNET_FORM_PLAIN, int dc_mode = 0, int dc_depth = 0) {
+  // form: AF_UNET_FORM_PLAIN / _TWIN / _PAG.  PAG (af_unet_forward_pag): x_dev / t_dev hold Bf / 3 samples, the batch
+  // is [x; x; x] with legs (cond, uncond, perturbed).  Leg 2 is leg 0 except for the self-attention at the set sites, so every
+  // block in front of the first one that holds a set site runs on legs 0-1 (knob pag_share_prefix) and leg 0 is copied onto
+  // leg 2 -- the current h and the skip halves written so far -- just before the first block that needs three legs.  The twin
+  // forward's own shortcut (blocks 0-1 on one leg) is not taken here: legs 0-1 run every block they run as a full batch.
+  const bool twin = form == AF_UNET_FORM_TWIN, pag = form == AF_UNET_FORM_PAG;
   // dc_mode (af_unet_forward_cached): AF_DEEPCACHE_REFRESH = this walk with cat[n_out - dc_depth] in the handle's buffer;
   // AF_DEEPCACHE_REUSE = input_blocks[0 .. dc_depth-1], then output_blocks[n_out - dc_depth ..] from the h half kept there
   const bool dc_reuse = dc_mode == AF_DEEPCACHE_REUSE;
@@ -1681,7 +1753,18 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   const int dt = h->dtype;
   const int mc = c.model_channels, ted = 4 * mc;
   R.A.off = 0;
-  const int Bin = twin ? Bf / 2 : Bf;          // samples behind x_dev / t_dev
+  const int Bin = twin ? Bf / 2 : pag ? Bf / 3 : Bf;          // samples behind x_dev / t_dev
+  R.pag_B = pag ? Bin : 0;
+  const int pag_first = pag ? h->pag_first_block() : -1;       // (tap numbering; the entry point refused a forward without one)
+  // legs the blocks in front of pag_first compute; pag_wide: all three legs are live (from the start, or since the copy)
+  bool pag_wide = pag && !(g_af_knobs.pag_share_prefix && pag_first > 0);
+  // samples 0 .. Bin-1 of a Bf-sample buffer onto leg `leg`
+  auto copy_leg = [&](const Act& a, int leg) -> int {
+    Act src = a, dst = a;
+    src.B = dst.B = Bin;
+    dst.p = R.elem_ptr(a.p, (long)leg * Bin * a.H * a.W * a.ld);
+    return R.copy_channels(src, dst, 0);
+  };
   auto dup_half = [&](const Act& a) -> int {    // samples 0 .. Bin-1 of a full-batch buffer onto Bin .. Bf-1
     Act src = a, dst = a;
     src.B = dst.B = Bin;
@@ -1708,6 +1791,10 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     AF_TRY(AF_TYPED(dt, af_launch_timestep_embedding<Elem>((const long long*)t_dev, temb.p, Bin, mc, s)));
   }
   if (twin && !twin_prefix) AF_TRY(dup_half(x));   // other block structures: the whole network on [x; x]
+  if (pag && !R.dry)   // (x's rows are narrower than a 16-byte vector: converted once per leg, not copied)
+    for (int leg = 1; leg < (pag_wide ? 3 : 2); ++leg)
+      AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(x_dev, R.elem_ptr(x.p, (long)leg * Bin * H * W * x.ld), Bin, c.in_channels,
+                                                       H * W, x.ld, 1.0f, s)));
   {
     // (twin: the embeddings of the Bin distinct timesteps, then copied)
     Act tb = temb, e1b = e1, e2b = e2, eab = emb_all;
@@ -1718,6 +1805,10 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(e2.p, e2.p, (long)Bin * ted, s)));
     AF_TRY(R.conv(h->emb_all, e2b, eab));
     if (twin) AF_TRY(dup_half(emb_all));
+    if (pag) {   // (all three legs at once: a row per sample)
+      AF_TRY(copy_leg(emb_all, 1));
+      AF_TRY(copy_leg(emb_all, 2));
+    }
   }
 
   // `final_out` (optional): a pre-assigned view for the block's last layer (zero-copy skip concat, see below)
@@ -1831,12 +1922,34 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     return AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(a.p, h->tap_out, a.B, a.C, a.H * a.W, a.ld, s));
   };
   Act hcur = x;
+  // PAG with a shared prefix: in front of block `blk` (tap numbering), the first one at or behind pag_first that this walk
+  // runs, leg 0 is copied onto leg 2 in everything a later block reads -- hcur (unless it is one of the skips, or the block
+  // reads a concatenation) and the skip halves of the input blocks run so far.  GroupNorm partial sums that the producer of
+  // hcur left cover two legs only: the next GroupNorm sums for itself.
+  int pag_skips_done = 0;   // input blocks run
+  auto pag_widen = [&](int blk, Act* hc, int j_from = 0) -> int {   // (j_from: concatenations in front of it were consumed)
+    if (!pag || pag_wide || blk < pag_first) return 0;
+    pag_wide = true;
+    bool h_is_skip = hc == nullptr;
+    for (int i = 0; i < pag_skips_done; ++i) {
+      const int j = n_in - 1 - i;
+      if (j >= n_out || j < j_from) continue;
+      const Act sk = view(cat[j], ch_h[j], shp_in[i].C);
+      if (hc && sk.p == hc->p) h_is_skip = true;
+      AF_TRY(copy_leg(sk, 2));
+    }
+    if (!h_is_skip) AF_TRY(copy_leg(*hc, 2));
+    if (hc) { hc->B = Bf; hc->gn_part = nullptr; hc->gn_npart = 0; }
+    return 0;
+  };
+  const auto pag_nb = [&]() { return pag && !pag_wide ? 2 * Bin : Bf; };
   for (int i = 0; i < (dc_reuse ? dc_depth : n_in); ++i) {
     const int j = n_in - 1 - i;  // the output block that will consume this skip
     Act o;
+    AF_TRY(pag_widen(i, &hcur));
     // twin: block 0 (conv_in) on the first half, copied (it is a skip connection); block 1 = ResBlock on the first half +
     // the transformer, which returns the whole batch
-    const int nb = (twin_prefix && i < 2) ? Bin : Bf;
+    const int nb = (twin_prefix && i < 2) ? Bin : pag_nb();
     const bool twin_x = twin_prefix && i == 1;
     if (j < n_out) {
       const Act dst = view(cat[j], ch_h[j], shp_in[i].C);
@@ -1849,18 +1962,20 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
       o.B = Bf;
     }
     hcur = o;
+    pag_skips_done = i + 1;
     AF_TRY(tap(i, hcur));
   }
   if (!dc_reuse) {
     Act o;
     const Act dst = view(cat[0], 0, ch_h[0]);
-    AF_TRY(run_block(h->middle_block, hcur, o, n_out > 0 ? &dst : nullptr, Bf, false));
+    AF_TRY(pag_widen(n_in, &hcur));
+    AF_TRY(run_block(h->middle_block, hcur, o, n_out > 0 ? &dst : nullptr, pag_nb(), false));
     hcur = o;
     AF_TRY(tap(n_in, hcur));
   }
   // FreeU (af_set_freeu), in place on cat[j] just before its only reader.  The DeepCache feature D is the h half of
   // cat[n_out - dc_depth]: a refresh scales it where it is kept, so a reuse step filters that concatenation's fresh skip only.
-  auto freeu = [&](int j) -> int {
+  auto freeu = [&](int j, int nb) -> int {
     const int pair = h->freeu_version ? h->freeu_pair(ch_h[j]) : -1;
     if (pair < 0) return 0;
     const Act& a = cat[j];
@@ -1873,19 +1988,22 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     if (!ws) { af_set_error_msg("activation arena exhausted (FreeU, cap %zu)", R.A.cap); return AF_ERR_STATE; }
     int rc = 0;
     if (!R.dry)
-      rc = AF_TYPED(dt, af_launch_freeu<Elem>(a.p, a.ld, Bf, a.H, a.W, Ch, Cs, h->freeu_version, (float)h->freeu_b[pair],
+      rc = AF_TYPED(dt, af_launch_freeu<Elem>(a.p, a.ld, nb, a.H, a.W, Ch, Cs, h->freeu_version, (float)h->freeu_b[pair],
                                               (float)h->freeu_s[pair], !kept, true, ws, s));
     R.A.release(mk);
     return rc ? AF_ERR_INVALID : 0;
   };
   for (int j = dc_reuse ? n_out - dc_depth : 0; j < n_out; ++j) {
     Act o;
-    AF_TRY(freeu(j));
+    // (the h half of cat[j] is hcur, the previous block's output; a reuse step's first block reads the kept one instead)
+    AF_TRY(pag_widen(n_in + 1 + j, dc_reuse && j == n_out - dc_depth ? nullptr : &hcur, j));
+    const int nb = pag_nb();
+    AF_TRY(freeu(j, nb));
     if (j + 1 < n_out) {
       const Act dst = view(cat[j + 1], 0, ch_h[j + 1]);
-      AF_TRY(run_block(h->output_blocks[j], cat[j], o, &dst, Bf, false));
+      AF_TRY(run_block(h->output_blocks[j], cat[j], o, &dst, nb, false));
     } else {
-      AF_TRY(run_block(h->output_blocks[j], cat[j], o, nullptr, Bf, false));
+      AF_TRY(run_block(h->output_blocks[j], cat[j], o, nullptr, nb, false));
     }
     hcur = o;
     AF_TRY(tap(n_in + 1 + j, hcur));
@@ -2126,7 +2244,7 @@ static int clip_forward_impl(af_handle* h, hipStream_t s, const float* emb_dev, 
 extern "C" {
 
 const char* af_last_error(void) { return g_err; }
-int af_version(void) { return 1; }
+int af_version(void) { return 2; }
 
 int af_create(int device_id, const af_config* cfg, af_handle** out) {
   if (!cfg || !out) { af_set_error_msg("af_create: null argument"); return AF_ERR_INVALID; }
@@ -2431,10 +2549,22 @@ static int ensure_deepcache(af_handle* h, hipStream_t s) {
 }
 
 static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
-                              void* stream, bool twin, int dc_mode = 0, int dc_depth = 0) {
+                              void* stream, int form, int dc_mode = 0, int dc_depth = 0) {
   if (!h || !x_dev || !t_dev || !eps_dev) { af_set_error_msg("af_unet_forward: null argument"); return AF_ERR_INVALID; }
+  const bool twin = form == AF_UNET_FORM_TWIN, pag = form == AF_UNET_FORM_PAG;
+  if (!twin && !pag && form != AF_UNET_FORM_PLAIN) { af_set_error_msg("af_unet_forward: form %d (0 plain, 1 twin, 2 PAG)", form); return AF_ERR_INVALID; }
   if (twin && (Bf < 2 || Bf % 2)) { af_set_error_msg("af_unet_forward_twin: the batch [x; x] must be even, got %d", Bf); return AF_ERR_INVALID; }
+  if (pag && (Bf < 3 || Bf % 3)) { af_set_error_msg("af_unet_forward_pag: the batch [x; x; x] must be a multiple of 3, got %d", Bf); return AF_ERR_INVALID; }
   if (!h->cfg.build_unet) { af_set_error_msg("af_unet_forward: handle has no UNet"); return AF_ERR_STATE; }
+  if (pag) {
+    if (!h->pag_on()) { af_set_error_msg("af_unet_forward_pag: no site set (af_set_pag)"); return AF_ERR_STATE; }
+    for (size_t i = 0; i < h->pag_set.size() && i < h->ca_list.size(); ++i)
+      if (h->pag_set[i] && h->tome_merges(h->xf[h->ca_list[i].first])) {
+        af_set_error_msg("af_unet_forward_pag: site %d merges tokens (af_set_tome, max_downsample %d): a merged self-attention "
+                         "cannot be perturbed", (int)i, h->tome_max_down);
+        return AF_ERR_STATE;
+      }
+  }
   if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
   const int down = 1 << (h->cfg.n_channel_mult - 1);
   if (H % down || W % down) { af_set_error_msg("af_unet_forward: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
@@ -2453,10 +2583,10 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
       return AF_ERR_INVALID;
     }
     if (dc_mode == AF_DEEPCACHE_REUSE &&
-        !(dc.valid && dc.buf && dc.Bf == Bf && dc.H == H && dc.W == W && dc.twin == (int)twin && dc.depth == dc_depth &&
+        !(dc.valid && dc.buf && dc.Bf == Bf && dc.H == H && dc.W == W && dc.twin == form && dc.depth == dc_depth &&
           dc.fp8_on == (int)h->fp8_on && dc.fp8_scope == h->fp8_scope)) {
       af_set_error_msg("af_unet_forward_cached: no kept feature for (Bf %d, %dx%d, twin %d, depth %d) -- a refresh with exactly "
-                       "these arguments must come first", Bf, H, W, (int)twin, dc_depth);
+                       "these arguments must come first", Bf, H, W, form, dc_depth);
       return AF_ERR_STATE;
     }
   }
@@ -2465,7 +2595,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   AF_TRY(fold_layernorms(h, s));
   AF_TRY(ensure_fp8_twins(h, s));
   AF_TRY(ensure_up4_twins(h, s));
-  auto run = [&] { return unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, twin, dc_mode, dc_depth); };
+  auto run = [&] { return unet_forward_impl(h, s, x_dev, t_dev, eps_dev, Bf, H, W, form, dc_mode, dc_depth); };
   AF_TRY(run_sized(h, s, run));
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = false;                       // (until this refresh has been enqueued completely)
@@ -2477,7 +2607,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   if (const int rc = run()) { if (dc_mode) dc.valid = false; return rc; }
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = true;
-    dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = (int)twin; dc.depth = dc_depth;
+    dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = form; dc.depth = dc_depth;
     dc.fp8_on = (int)h->fp8_on; dc.fp8_scope = h->fp8_scope;
   }
   return 0;
@@ -2488,7 +2618,8 @@ int af_unet_forward_cached(af_handle* h, const float* x_dev, const int64_t* t_de
     af_set_error_msg("af_unet_forward_cached: mode %d is neither AF_DEEPCACHE_REFRESH nor AF_DEEPCACHE_REUSE", mode);
     return AF_ERR_INVALID;
   }
-  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, twin != 0, mode, depth);
+  if (twin < 0 || twin > AF_UNET_FORM_PAG) { af_set_error_msg("af_unet_forward_cached: twin %d (0 plain, 1 twin, 2 PAG)", twin); return AF_ERR_INVALID; }
+  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, twin, mode, depth);
 }
 int af_unet_cache_invalidate(af_handle* h) {
   if (!h) { af_set_error_msg("af_unet_cache_invalidate: null handle"); return AF_ERR_INVALID; }
@@ -2497,11 +2628,15 @@ int af_unet_cache_invalidate(af_handle* h) {
 }
 int af_unet_forward(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                     void* stream) {
-  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, false);
+  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, AF_UNET_FORM_PLAIN);
 }
 int af_unet_forward_twin(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                          void* stream) {
-  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, true);
+  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, AF_UNET_FORM_TWIN);
+}
+int af_unet_forward_pag(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
+                        void* stream) {
+  return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, AF_UNET_FORM_PAG);
 }
 
 int af_unet_num_blocks(af_handle* h) {
@@ -2605,6 +2740,43 @@ int af_freeu_plan_query(int dtype, int H, int W, int Ch, int Cs, int version, in
   AfFreeuPlan pl;
   if (af_plan_freeu(H, W, Ch, Cs, version, &pl)) return AF_ERR_INVALID;
   out[0] = pl.kernel; out[1] = pl.launches; out[2] = pl.nchunk; out[3] = pl.part_bytes;
+  return AF_OK;
+}
+
+int af_set_pag(af_handle* h, const int* sites, int n_sites) {
+  if (!h) { af_set_error_msg("af_set_pag: null handle"); return AF_ERR_INVALID; }
+  if (n_sites < 0 || (n_sites > 0 && !sites)) { af_set_error_msg("af_set_pag: %d sites without a list", n_sites); return AF_ERR_INVALID; }
+  const int n = h->cfg.build_unet ? (int)h->ca_list.size() : 0;
+  if (n_sites > 0 && !h->cfg.build_unet) { af_set_error_msg("af_set_pag: handle has no UNet"); return AF_ERR_STATE; }
+  std::vector<char> set((size_t)n, (char)0);
+  for (int i = 0; i < n_sites; ++i) {
+    if (sites[i] < 0 || sites[i] >= n) { af_set_error_msg("af_set_pag: site %d out of range (%d sites)", sites[i], n); return AF_ERR_INVALID; }
+    if (set[sites[i]]) { af_set_error_msg("af_set_pag: site %d given twice", sites[i]); return AF_ERR_INVALID; }
+    set[sites[i]] = 1;
+  }
+  if (n_sites == 0) set.clear();   // (off is the state of a handle that never heard of this call)
+  std::vector<char> before = h->pag_set;
+  if (!h->pag_on()) before.clear();
+  if (set != before) h->dc.valid = false;   // (a kept DeepCache feature belongs to the setting that wrote it)
+  h->pag_set = set;
+  return AF_OK;
+}
+int af_pag_num_sites(af_handle* h) { return (h && h->cfg.build_unet) ? (int)h->ca_list.size() : 0; }
+int af_pag_site(af_handle* h, int site, int out[4]) {
+  if (!h || !out) { af_set_error_msg("af_pag_site: null argument"); return AF_ERR_INVALID; }
+  if (site < 0 || site >= af_pag_num_sites(h)) { af_set_error_msg("af_pag_site: site %d out of range (%d sites)", site, af_pag_num_sites(h)); return AF_ERR_INVALID; }
+  const auto st = h->pag_sites()[site];
+  out[0] = st.block; out[1] = st.depth; out[2] = st.ds;
+  out[3] = (size_t)site < h->pag_set.size() && h->pag_set[site] ? 1 : 0;
+  return AF_OK;
+}
+int af_pag_plan_query(af_handle* h, int depth, int out[3]) {
+  if (!h || !out) { af_set_error_msg("af_pag_plan_query: null argument"); return AF_ERR_INVALID; }
+  if (!h->cfg.build_unet) { af_set_error_msg("af_pag_plan_query: handle has no UNet"); return AF_ERR_STATE; }
+  if (depth < 0 || depth > (int)h->input_blocks.size()) { af_set_error_msg("af_pag_plan_query: depth %d outside 0 .. %d", depth, (int)h->input_blocks.size()); return AF_ERR_INVALID; }
+  out[0] = h->pag_first_block();
+  out[1] = h->pag_two_leg_blocks(0);
+  out[2] = depth > 0 ? h->pag_two_leg_blocks(depth) : 0;
   return AF_OK;
 }
 

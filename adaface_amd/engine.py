@@ -44,6 +44,84 @@ def check_freeu_args(version, b1=1.0, b2=1.0, s1=1.0, s2=1.0):
     return (int(version), *vals)
 
 
+def pag_layout(unet_cfg) -> dict:
+    """The PAG sites of a UNetModel, from its constructor arguments alone (a dict or an object with channel_mult,
+    num_res_blocks, attention_resolutions[, transformer_depth]): {"n_sites", "blocks" (site -> block in the forward order
+    input blocks, middle block, output blocks), "ds" (site -> downsample factor of its map), "n_input_blocks", "names" (name ->
+    tuple of sites)}.  A site is the
+    self-attention of one transformer block in forward order; the names are diffusers': "mid", "down.blocks.L" (resolution
+    level L of the encoder) and "up.blocks.K" (decoder levels, K = 0 the deepest).  No GPU is needed."""
+    get = unet_cfg.get if isinstance(unet_cfg, dict) else (lambda k, d=None: getattr(unet_cfg, k, d))
+    mult, nres = list(get("channel_mult")), int(get("num_res_blocks"))
+    attn, depth = set(int(a) for a in get("attention_resolutions")), int(get("transformer_depth", 1) or 1)
+    nlev = len(mult)
+    blocks, factors, names = [], [], {}
+
+    def add(name, block):
+        names.setdefault(name, [])
+        for _ in range(depth):
+            names[name].append(len(blocks))
+            blocks.append(block)
+            factors.append(ds)
+    blk, ds = 1, 1                                   # (input block 0 is conv_in)
+    for lev in range(nlev):
+        for _ in range(nres):
+            if ds in attn:
+                add(f"down.blocks.{lev}", blk)
+            blk += 1
+        if lev != nlev - 1:
+            blk += 1                                 # (the downsample block)
+            ds *= 2
+    n_in = blk
+    add("mid", blk)
+    blk += 1
+    for lev in reversed(range(nlev)):
+        for i in range(nres + 1):
+            if ds in attn:
+                add(f"up.blocks.{nlev - 1 - lev}", blk)
+            blk += 1
+        if lev:
+            ds //= 2
+    return {"n_sites": len(blocks), "blocks": tuple(blocks), "ds": tuple(factors), "n_input_blocks": n_in, "names": {k: tuple(v) for k, v in names.items()}}
+
+
+def pag_sites_of(unet_cfg, layers) -> tuple:
+    """Names ("mid", "down.blocks.1", ...) and / or site numbers -> the sorted tuple of distinct sites; None or () = off.
+    ValueError for an unknown name, a site out of range or anything that is neither.  No GPU is needed."""
+    if layers is None:
+        return ()
+    if isinstance(layers, (str, int)) and not isinstance(layers, bool):
+        layers = (layers,)
+    lay = pag_layout(unet_cfg)
+    sites = set()
+    for item in layers:
+        if isinstance(item, str):
+            if item not in lay["names"]:
+                raise ValueError(f"PAG: layer {item!r} (one of {sorted(lay['names'])}, or a site number below {lay['n_sites']})")
+            sites.update(lay["names"][item])
+        elif isinstance(item, int) and not isinstance(item, bool):
+            if not 0 <= item < lay["n_sites"]:
+                raise ValueError(f"PAG: site {item} outside 0 .. {lay['n_sites'] - 1}")
+            sites.add(int(item))
+        else:
+            raise ValueError(f"PAG: layer {item!r} is neither a name nor a site number")
+    return tuple(sorted(sites))
+
+
+def pag_plan(unet_cfg, layers, depth: int = 0, share_prefix: bool = True) -> dict:
+    """What af_pag_plan_query reports, from the constructor arguments alone: the first block (forward order) with a set site
+    (-1: none), the input blocks a full forward runs on two legs, and those of a DeepCache reuse step of `depth`."""
+    lay, sites = pag_layout(unet_cfg), pag_sites_of(unet_cfg, layers)
+    first = min((lay["blocks"][s] for s in sites), default=-1)
+    full = min(first, lay["n_input_blocks"]) if first >= 0 and share_prefix else 0
+    return {"first_block": first, "two_leg_blocks": full, "two_leg_blocks_reuse": min(full, depth) if depth > 0 else 0}
+
+
+def pag_scale_at(t, pag_scale: float, pag_adaptive_scale: float = 0.0) -> float:
+    """The PAG scale of the step at timestep t, as diffusers' PAG pipelines compute it: max(s - a (1000 - t), 0)."""
+    return max(float(pag_scale) - float(pag_adaptive_scale) * (1000.0 - float(t)), 0.0)
+
+
 def _fill(arr, values: Sequence[int]):
     if len(values) > 8:
         raise ValueError("at most 8 entries supported")
@@ -197,22 +275,62 @@ class Engine:
               "af_unet_forward_twin")
         return out
 
-    def unet_forward_cached(self, x: torch.Tensor, t: torch.Tensor, *, depth: int, mode: str, twin: bool = False,
+    def set_pag(self, sites=()):
+        """af_set_pag: the self-attention layers whose attention map is the identity on the third leg of unet_forward_pag --
+        names ("mid", "down.blocks.2", "up.blocks.1", ...) and / or site numbers (pag_layout); None or () = off.  The plain and
+        twin forwards ignore the set.  Drops a kept DeepCache feature when the set changes."""
+        sites = pag_sites_of(self.unet_cfg, sites)
+        arr = (C.c_int * max(len(sites), 1))(*sites)
+        check(self._lib.af_set_pag(self._h, arr, len(sites)), "af_set_pag")
+        self.pag = sites
+
+    def pag_sites(self) -> list:
+        """[(block in forward order, depth index, downsample factor, set)] of every PAG site, as the handle reports them."""
+        out = (C.c_int * 4)()
+        sites = []
+        for i in range(int(self._lib.af_pag_num_sites(self._h))):
+            check(self._lib.af_pag_site(self._h, i, out), "af_pag_site")
+            sites.append((int(out[0]), int(out[1]), int(out[2]), bool(out[3])))
+        return sites
+
+    def pag_plan(self, depth: int = 0) -> dict:
+        """af_pag_plan_query: first block with a set site, input blocks on two legs in a full forward / in a reuse step."""
+        out = (C.c_int * 3)()
+        check(self._lib.af_pag_plan_query(self._h, int(depth), out), "af_pag_plan_query")
+        return {"first_block": int(out[0]), "two_leg_blocks": int(out[1]), "two_leg_blocks_reuse": int(out[2])}
+
+    def unet_forward_pag(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """af_unet_forward_pag: the UNet on [x; x; x], [t; t; t] with legs (cond, uncond, perturbed); the context was set for
+        3 * len(x) samples as [c; uc; c].  Leg 2 is leg 0 except that its self-attention at the set sites is the identity map.
+        Returns eps [3B, C, H, W]."""
+        x = x.contiguous().float()
+        t = t.contiguous().long()
+        B, _, H, W = x.shape
+        if out is None:
+            out = torch.empty(3 * B, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
+        check(self._lib.af_unet_forward_pag(self._h, ptr(x), ptr(t), ptr(out), 3 * B, H, W, stream_ptr()), "af_unet_forward_pag")
+        return out
+
+    def unet_forward_cached(self, x: torch.Tensor, t: torch.Tensor, *, depth: int, mode: str, twin=False,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """af_unet_forward_cached (DeepCache).  mode "refresh": unet_forward / unet_forward_twin bit for bit, which also keeps
         the output of output_blocks[n_out - depth - 1] in a buffer the handle owns.  mode "reuse": only input_blocks[:depth]
         and output_blocks[n_out - depth:] run, on that kept feature; AfError when no refresh with the same batch, latent size,
-        twin and depth came before.  twin: x, t hold B samples and eps 2 B, as unet_forward_twin.  set_context / set_conv_attn
+        twin and depth came before.  twin: x, t hold B samples and eps 2 B, as unet_forward_twin; twin="pag": eps 3 B, as
+        unet_forward_pag (the form is part of the kept feature's key).  set_context / set_conv_attn
         do not drop the kept feature: call unet_cache_invalidate when the conditioning changes."""
         if mode not in _lib.DEEPCACHE_MODES:
             raise ValueError(f"unet_forward_cached: mode {mode!r} (\"refresh\" or \"reuse\")")
         x = x.contiguous().float()
         t = t.contiguous().long()
         B, _, H, W = x.shape
-        Bf = 2 * B if twin else B
+        if twin not in _lib.UNET_FORMS:
+            raise ValueError(f"unet_forward_cached: twin {twin!r} (False, True or \"pag\")")
+        form = _lib.UNET_FORMS[twin]
+        Bf = _lib.UNET_FORM_LEGS[form] * B
         if out is None:
             out = torch.empty(Bf, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
-        check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, 1 if twin else 0, int(depth),
+        check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, form, int(depth),
                                                _lib.DEEPCACHE_MODES[mode], stream_ptr()), "af_unet_forward_cached")
         return out
 

@@ -59,6 +59,7 @@ class HipModule(nn.Module):
         object.__setattr__(self, "_fp8_scope", ("base",))     # kept here like the shifts: every fp8 engine gets it again
         object.__setattr__(self, "_tome", (0.0, 1))           # token merging (UNetModel.set_token_merging), kept the same way
         object.__setattr__(self, "_freeu", (0, 1.0, 1.0, 1.0, 1.0))   # FreeU (UNetModel.set_freeu), kept the same way
+        object.__setattr__(self, "_pag", ())                          # PAG sites (UNetModel.set_pag), kept the same way
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
@@ -139,6 +140,8 @@ class HipModule(nn.Module):
                     self._engine.set_tome(*self._tome)
                 if self._freeu[0]:
                     self._engine.set_freeu(*self._freeu)
+                if self._pag:
+                    self._engine.set_pag(self._pag)
             except Exception:
                 # (an engine whose configuration failed is not kept: the next call builds and configures again)
                 self._engine.close()

@@ -8,7 +8,9 @@ makes it MI355X-native and device-agnostic:
     step, so the UNet's hoisted cross-attention K/V stay cached across the 50 steps;
   * a scalar guidance_scale means "no annealing" instead of the reference's
     UnboundLocalError (ddim.py:169-173, SURVEY.md §8a a4);
-  * deep_cache_interval= / deep_cache_depth= (opt-in, not in the reference): DeepCache, see deep_cache.py.
+  * deep_cache_interval= / deep_cache_depth= (opt-in, not in the reference): DeepCache, see deep_cache.py;
+  * pag_scale= / pag_adaptive_scale= / guidance_rescale= (opt-in, not in the reference): perturbed-attention guidance and
+    guidance rescale, see guidance.py.  All zero: the calls below are the calls made without them.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
+from adaface_amd.ldm.models.diffusion import guidance as G
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
                                                            make_ddim_timesteps, noise_like)
@@ -75,11 +78,15 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
-               unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
+               unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2,
+               pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
         """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
         adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step).
         deep_cache_interval: None or 1 = off; N >= 2 = the full U-Net on loop indices i % N == 0 only, or an explicit
-        sequence of those indices (with 0); between them the outermost deep_cache_depth blocks run on the kept deep feature."""
+        sequence of those indices (with 0); between them the outermost deep_cache_depth blocks run on the kept deep feature.
+        pag_scale / pag_adaptive_scale: perturbed-attention guidance on the layers given to model.set_pag, every step a
+        three-leg forward; guidance_rescale in [0, 1]: the combined prediction rescaled towards the conditional one's standard
+        deviation (guidance.py)."""
         _check_noise_source(noise_source, noise_dropout)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -93,18 +100,24 @@ class DDIMSampler(object):
                                   log_every_t=log_every_t, guidance_scale=guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
                                   noise_source=noise_source, deep_cache_interval=deep_cache_interval,
-                                  deep_cache_depth=deep_cache_depth, **kwargs)
+                                  deep_cache_depth=deep_cache_depth, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
+                                  guidance_rescale=guidance_rescale, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None,
-                      deep_cache_interval=None, deep_cache_depth=2, **kwargs):
+                      deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
+                      **kwargs):
         """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
         code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
         step = the loop index."""
         _check_noise_source(noise_source, noise_dropout)
+        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
+        G.check_model(self.model, unconditional_conditioning, pag_scale)
+        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
+        self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
         if x_T is not None:
@@ -150,7 +163,9 @@ class DDIMSampler(object):
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
                                               corrector_kwargs=corrector_kwargs, guidance_scale=guide_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              noise_source=noise_source, noise_step=i, deep_cache_run=dc_run)
+                                              noise_source=noise_source, noise_step=i, deep_cache_run=dc_run,
+                                              pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
+                                              guidance_rescale=guidance_rescale, timestep=int(step))
             if callback:
                 callback(i)
             if img_callback:
@@ -180,15 +195,23 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0,
-                      deep_cache_run=None):
+                      deep_cache_run=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timestep=None):
         """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
         torch.randn; repeat_noise then gives every sample the first sample's id.  deep_cache_run: the loop's DeepCacheRun
-        (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse)."""
+        (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse).
+        pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes the model call and the combine, and the update
+        below takes its result as a plain eps; timestep: t as a host integer (None: read from t)."""
         _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
         single = unconditional_conditioning is None or guidance_scale == 1.
-        dc = None if deep_cache_run is None else deep_cache_run.step(noise_step, (not single, b, x.shape[2], x.shape[3]))
-        if single:
+        guided = G.is_on(pag_scale, guidance_rescale)
+        dc = None if deep_cache_run is None or guided else deep_cache_run.step(noise_step, (not single, b, x.shape[2], x.shape[3]))
+        if guided:
+            e_c = G.guided_eps(self, x, t, c, unconditional_conditioning, guidance_scale,
+                               int(t[0]) if timestep is None else timestep, pag_scale, pag_adaptive_scale, guidance_rescale,
+                               deep_cache_run, noise_step)
+            e_u = None
+        elif single:
             e_c = self.model.apply_model(x, t, c) if dc is None else self.model.apply_model(x, t, c, deep_cache=dc)
             e_u = None
         else:
@@ -257,9 +280,14 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, deep_cache_interval=None, deep_cache_depth=2):
+               use_original_steps=False, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0.,
+               guidance_rescale=0.):
         """ddim.py:315-350 (img2img tail): anneals guidance from `guidance_scale` to min(2, guidance_scale).
-        deep_cache_interval / deep_cache_depth: as sample()."""
+        deep_cache_interval / deep_cache_depth / pag_scale / pag_adaptive_scale / guidance_rescale: as sample()."""
+        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
+        G.check_model(self.model, unconditional_conditioning, pag_scale)
+        self.guidance_log = []
+        self._guided_twin_cache = None
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         time_range = np.flip(timesteps)
@@ -277,7 +305,9 @@ class DDIMSampler(object):
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
                                           guidance_scale=g, unconditional_conditioning=unconditional_conditioning,
-                                          noise_step=i, deep_cache_run=dc_run)
+                                          noise_step=i, deep_cache_run=dc_run, pag_scale=pag_scale,
+                                          pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
+                                          timestep=int(step))
             g = g - delta
         self._twin_cache = None
         return x_dec

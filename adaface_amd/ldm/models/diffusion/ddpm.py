@@ -31,7 +31,8 @@ class DiffusionWrapper(nn.Module):
         if conditioning_key not in (None, "crossattn"):
             raise NotImplementedError(f"conditioning_key '{conditioning_key}' is not used by SD-v1 txt2img")
 
-    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False, deep_cache=None):
+    def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False, deep_cache=None,
+                cfg_pag: bool = False):
         if self.conditioning_key is None:
             raise NotImplementedError("unconditional UNet is not on the path")
         c0 = c_crossattn[0]
@@ -39,6 +40,9 @@ class DiffusionWrapper(nn.Module):
             c_static_emb, c_in, extra_info = c0
         else:
             c_static_emb, c_in, extra_info = c0, None, None
+        if cfg_pag:                   # the three-leg call of perturbed-attention guidance (UNetModel.forward)
+            return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info, cfg_pag=True,
+                                        deep_cache=deep_cache)
         if deep_cache is not None:    # DeepCache refresh / reuse step (UNetModel.forward); None: the calls below, unchanged
             return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info,
                                         cfg_twin=bool(cfg_twin), deep_cache=deep_cache)
@@ -226,6 +230,22 @@ class LatentDiffusion(DDPM):
             return self.model(x_noisy, t, cfg_twin=True, deep_cache=deep_cache, **cond)
         return self.model(x_noisy, t, cfg_twin=True, **cond)
 
+    def apply_model_cfg_pag(self, x_noisy, t, cond_twin, deep_cache=None):
+        """The three-leg call of perturbed-attention guidance, beside apply_model_cfg_twin and with its arguments: `cond_twin`
+        is the condition of 2B samples (cond FIRST), x_noisy / t those of one leg.  Returns eps of 3B samples, legs (cond,
+        uncond, perturbed): the third leg is the first with the identity as the attention map of the self-attention layers
+        given to set_pag.  Not a reference method."""
+        cond = cond_twin
+        if not isinstance(cond, dict):
+            if not isinstance(cond, list):
+                cond = [cond]
+            cond = {'c_crossattn': cond}
+        if 'c_crossattn' not in cond:
+            raise NotImplementedError("apply_model_cfg_pag: perturbed-attention guidance needs a cross-attention condition")
+        if deep_cache is not None:
+            return self.model(x_noisy, t, cfg_pag=True, deep_cache=deep_cache, **cond)
+        return self.model(x_noisy, t, cfg_pag=True, **cond)
+
     # ---- decoder -----------------------------------------------------------------------------
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
@@ -294,6 +314,16 @@ class LatentDiffusion(DDPM):
         """UNetModel.set_freeu: opt-in FreeU backbone scaling and Fourier-filtered skips in the U-Net (version 0 = off)."""
         self.model.diffusion_model.set_freeu(version, b1, b2, s1, s2)
         return self
+
+    def set_pag(self, layers):
+        """UNetModel.set_pag: the self-attention layers perturbed on the third leg of apply_model_cfg_pag -- names ("mid",
+        "down.blocks.2", "up.blocks.1", ...) or site numbers; None or () = off."""
+        self.model.diffusion_model.set_pag(layers)
+        return self
+
+    @property
+    def pag(self) -> tuple:
+        return self.model.diffusion_model.pag
 
     def set_compute_dtype(self, dtype: str, fp8_scope: str = "base"):
         """'bf16' | 'f32' | 'f16' (alias 'fp16') | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
+from adaface_amd.ldm.models.diffusion import guidance as G
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
 from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
@@ -121,13 +122,15 @@ class DPMSolverSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, img_callback=None, mask=None, x0=None,
                x_T=None, verbose=True, log_every_t=100, guidance_scale=1., unconditional_guidance_scale=None,
                unconditional_conditioning=None, order=2, lower_order_final=True, skip_type="time_uniform", timesteps=None,
-               algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
+               algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
+               pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
         """(img, intermediates) as DDIMSampler.sample.  guidance_scale: a scalar or [max, min] (annealed as ddim_sampling
         does); unconditional_guidance_scale: the PLMS / CompVis spelling of the scalar.  timesteps: an explicit strictly
         increasing integer array, overriding S and skip_type.  algorithm: "dpmsolver++" (deterministic) or "sde-dpmsolver++"
         (one N(0, 1) draw per step, scaled by temperature=); noise_source: a PhiloxNoise for the SDE draws, the inpainting
         blend's q_sample noise and, with x_T None, the start code.  deep_cache_interval / deep_cache_depth: DeepCache, as
-        DDIMSampler.sample (deep_cache.py)."""
+        DDIMSampler.sample (deep_cache.py).  pag_scale / pag_adaptive_scale / guidance_rescale: perturbed-attention guidance
+        and guidance rescale, as DDIMSampler.sample (guidance.py)."""
         if algorithm not in ALGORITHMS:
             raise NotImplementedError(f'There is no DPM-Solver algorithm called "{algorithm}" ({", ".join(ALGORITHMS)})')
         sde = algorithm == "sde-dpmsolver++"
@@ -158,7 +161,8 @@ class DPMSolverSampler(object):
                                         img_callback=img_callback, mask=mask, x0=x0, log_every_t=log_every_t,
                                         unconditional_conditioning=unconditional_conditioning, noise_source=noise_source,
                                         temperature=temperature, deep_cache_interval=deep_cache_interval,
-                                        deep_cache_depth=deep_cache_depth)
+                                        deep_cache_depth=deep_cache_depth, pag_scale=pag_scale,
+                                        pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
 
     def _twin_condition(self, c, uc):
         """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
@@ -177,8 +181,14 @@ class DPMSolverSampler(object):
     @torch.no_grad()
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
                             log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.,
-                            deep_cache_interval=None, deep_cache_depth=2):
+                            deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0.,
+                            guidance_rescale=0.):
         """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update."""
+        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
+        G.check_model(self.model, unconditional_conditioning, pag_scale)
+        guided = G.is_on(pag_scale, guidance_rescale)
+        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
+        self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
         sde = schedule.shape[1] > COL_CN
@@ -210,8 +220,13 @@ class DPMSolverSampler(object):
                     img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
                 img = img_orig * mask + (1. - mask) * img
             single = unconditional_conditioning is None or guide_scale == 1.
-            dc = dc_run.step(i, (not single, b, img.shape[2], img.shape[3]))     # None: the full forward, as without DeepCache
-            if single:
+            # None: the full forward, as without DeepCache
+            dc = None if guided else dc_run.step(i, (not single, b, img.shape[2], img.shape[3]))
+            if guided:      # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
+                e_c = G.guided_eps(self, img, ts, cond, unconditional_conditioning, guide_scale, int(row[COL_T]), pag_scale,
+                                   pag_adaptive_scale, guidance_rescale, dc_run, i)
+                e_u = None
+            elif single:
                 e_c = self.model.apply_model(img, ts, cond) if dc is None else self.model.apply_model(img, ts, cond, deep_cache=dc)
                 e_u = None
             else:

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
+from adaface_amd.ldm.models.diffusion import guidance as G
 from adaface_amd.ldm.modules.diffusionmodules.util import (make_ddim_sampling_parameters, make_ddim_timesteps,
                                                             noise_like)
 
@@ -48,7 +49,10 @@ class PLMSSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, **kwargs):
+               unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
+               pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
+        """plms.py:71-117.  pag_scale / pag_adaptive_scale / guidance_rescale (not in the reference): perturbed-attention
+        guidance and guidance rescale on every model call of the run, see guidance.py."""
         from adaface_amd.ldm.models.diffusion.deep_cache import is_off
         if not is_off(deep_cache_interval):
             raise NotImplementedError("deep_cache_interval with the PLMS sampler: it calls the model twice in its first step and "
@@ -60,16 +64,21 @@ class PLMSSampler(object):
                                   noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, pag_scale=pag_scale,
+                                  pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None):
+                      unconditional_conditioning=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.):
         """plms.py:119-173."""
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps is not used by txt2img")
+        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
+        G.check_model(self.model, unconditional_conditioning, pag_scale)
+        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
+        self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T
@@ -95,7 +104,9 @@ class PLMSSampler(object):
                                                    score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
                                                    unconditional_guidance_scale=unconditional_guidance_scale,
                                                    unconditional_conditioning=unconditional_conditioning,
-                                                   old_eps=old_eps, t_next=ts_next)
+                                                   old_eps=old_eps, t_next=ts_next, pag_scale=pag_scale,
+                                                   pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
+                                                   timesteps=(int(step), int(time_range[min(i + 1, len(time_range) - 1)])))
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
@@ -126,14 +137,20 @@ class PLMSSampler(object):
     @torch.no_grad()
     def p_sample_plms(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, old_eps=None, t_next=None):
-        """plms.py:175-253."""
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, old_eps=None, t_next=None,
+                      pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timesteps=None):
+        """plms.py:175-253.  pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes every model call of the step
+        and its combine; timesteps: (t, t_next) as host integers (None: read from the tensors)."""
         if quantize_denoised or score_corrector is not None or use_original_steps:
             raise NotImplementedError("quantize_denoised / score_corrector / use_original_steps are not on the txt2img path")
         b = x.shape[0]
         f32 = lambda v: float(np.float32(float(v)))
 
         def get_model_output(xx, tt):
+            if G.is_on(pag_scale, guidance_rescale):
+                th = int(tt[0]) if timesteps is None else timesteps[0 if tt is t else 1]
+                return G.guided_eps(self, xx, tt, c, unconditional_conditioning, unconditional_guidance_scale, th, pag_scale,
+                                    pag_adaptive_scale, guidance_rescale)
             if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
                 return self.model.apply_model(xx, tt, c)
             twin = self._twin_condition(c, unconditional_conditioning)

@@ -145,6 +145,22 @@ class UNetModel(HipModule):
     def freeu(self) -> tuple:
         return self._freeu
 
+    def set_pag(self, layers):
+        """Perturbed-attention guidance (Ahn et al., ECCV 2024; not in the reference, off by default): the self-attention
+        layers whose attention map is the identity on the third leg of forward(cfg_pag=True) -- names ("mid", "down.blocks.0..2",
+        "up.blocks.1..3") and / or site numbers in forward order; None or () = off.  Every other forward ignores the set.  Kept
+        for every later engine; a live one is switched now.  Every compute dtype."""
+        from adaface_amd.engine import pag_sites_of
+        sites = pag_sites_of(self._layout_kwargs(), layers)
+        if self._engine is not None:
+            self._engine.set_pag(sites)
+        object.__setattr__(self, "_pag", sites)
+        return self
+
+    @property
+    def pag(self) -> tuple:
+        return self._pag
+
     @staticmethod
     def _conv_attn_spec(ks, placeholder2indices):
         """(ks, batch indices, token positions) for Engine.set_conv_attn from the reference's
@@ -175,7 +191,7 @@ class UNetModel(HipModule):
 
     @torch.no_grad()
     def forward(self, x, timesteps=None, context=None, y=None, context_in=None, extra_info=None, cfg_twin=False, deep_cache=None,
-                **kwargs):
+                cfg_pag=False, **kwargs):
         """x [B,C,H,W], timesteps [B], context [B*16,T,D] (layerwise) or [B,T,D]; returns eps [B,C,H,W] fp32.
         Mirrors openaimodel.py:827-1052 for inference: `extra_info` keys read at :849-859.
         cfg_twin (not in the reference; used by this package's samplers): x / timesteps are ONE half of the
@@ -184,7 +200,11 @@ class UNetModel(HipModule):
         deep_cache (not in the reference; DeepCache, set by this package's samplers): None = the plain forward;
         ("refresh", k) = the same forward, which also keeps the input of output_blocks[-k]; ("reuse", k) = only
         input_blocks[:k] and output_blocks[-k:] run, on the feature the last refresh kept.  A context or conv-attention spec
-        that differs from the previous call's drops the kept feature (a reuse then raises AfError)."""
+        that differs from the previous call's drops the kept feature (a reuse then raises AfError).
+        cfg_pag (not in the reference; perturbed-attention guidance, set_pag): x / timesteps are ONE leg, the context is the
+        twin condition of 2B samples (cond first), exactly what cfg_twin takes; returns eps for 3B samples, legs (cond, uncond,
+        perturbed).  The third leg's context is the first B samples' AFTER the compel-cfg weighting, with their layerwise
+        slices, and the conv-attention rows of the samples < B are repeated for the samples + 2B."""
         if y is not None:
             raise NotImplementedError("class-conditional UNet (num_classes) is not on the path")
         if timesteps is None or context is None:
@@ -197,11 +217,22 @@ class UNetModel(HipModule):
             raise NotImplementedError("img_mask / capture_distill_attn are training-time options")
         if info.get("iter_type", "normal_recon") == "mix_hijk":
             raise NotImplementedError("iter_type 'mix_hijk' (separate k/v contexts) is a training-time option")
+        if cfg_pag and cfg_twin:
+            raise ValueError("UNetModel.forward: cfg_pag and cfg_twin are two forms of one call; give one")
+        if cfg_pag and not self._pag:
+            raise ValueError("UNetModel.forward(cfg_pag=True): no PAG layer is set (set_pag)")
         eng = self.engine(x.device)
-        B = x.shape[0] * (2 if cfg_twin else 1)
+        B1 = x.shape[0]
+        B = B1 * (2 if (cfg_twin or cfg_pag) else 1)           # samples of the context as given
         cache_ok = True
+        given = context
         if layerwise and info.get("apply_compel_cfg_prob", 0) > 0:
             context, cache_ok = self._compel_cfg(context.to(x.device), B, info)
+        if cfg_pag:
+            B = 3 * B1
+            if conv[0]:
+                extra = [(b + 2 * B1, tok) for b, tok in zip(conv[1], conv[2]) if b < B1]
+                conv = (conv[0], conv[1] + tuple(b for b, _ in extra), conv[2] + tuple(tok for _, tok in extra))
         # Hoisted cross-attention K/V are cached per context TENSOR OBJECT: a reference to it is kept so that its
         # id / storage cannot be recycled for another prompt while the cache is live (data_ptr alone is unsafe).
         key = (id(context), getattr(context, "_version", 0), tuple(context.shape), layerwise, B, conv)
@@ -209,14 +240,20 @@ class UNetModel(HipModule):
             if key != self._ctx_key:
                 eng.unet_cache_invalidate()     # (the kept DeepCache feature was computed under the previous conditioning)
             eng.set_conv_attn(*conv)
-            eng.set_context(context.to(x.device), B, layerwise)
+            ctx = context.to(x.device)
+            if cfg_pag:                         # [c; uc] -> [c; uc; c]: whole samples (their 16 layer slices lie together)
+                per = ctx.shape[0] // (2 * B1)
+                ctx = torch.cat([ctx, ctx[:B1 * per]])
+            eng.set_context(ctx, B, layerwise)
             object.__setattr__(self, "_ctx_key", key if cache_ok else None)
-            object.__setattr__(self, "_ctx_ref", context)
+            object.__setattr__(self, "_ctx_ref", (context, given))
         if deep_cache is None:
-            out = (eng.unet_forward_twin if cfg_twin else eng.unet_forward)(x, timesteps.to(x.device))
+            fwd = eng.unet_forward_pag if cfg_pag else eng.unet_forward_twin if cfg_twin else eng.unet_forward
+            out = fwd(x, timesteps.to(x.device))
         else:
             mode, depth = deep_cache
-            out = eng.unet_forward_cached(x, timesteps.to(x.device), depth=int(depth), mode=mode, twin=bool(cfg_twin))
+            out = eng.unet_forward_cached(x, timesteps.to(x.device), depth=int(depth), mode=mode,
+                                          twin="pag" if cfg_pag else bool(cfg_twin))
         if extra_info is not None:
             # the reference writes the (here empty) distillation capture into the caller's dict (:1031-1035)
             extra_info["ca_layers_activations"] = {k: {} for k in ("outfeat", "attn", "attnscore", "q")}

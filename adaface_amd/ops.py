@@ -538,6 +538,32 @@ def dpmpp_sde_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x
     return x_next, x0_out
 
 
+def guidance(e_c, e_u, e_p, w, s, rescale=0.0, return_factor=False, out=None):
+    """af_guidance: e = e_u + w (e_c - e_u) + s (e_c - e_p), then guidance rescale e (phi f + 1 - phi) with
+    f = std(e_c) / std(e) per sample (dim 0 of e_c; unbiased).  e_u None: no w term; e_p None (or s = 0): no s term; rescale 0:
+    no statistics.  out: a contiguous fp32 GPU tensor of e_c's size to write into, which may be e_c itself (no other overlap).
+    return_factor (rescale > 0): also the applied f, [n_samples].  The sampler steps then take the result as e_cond with
+    e_uncond None."""
+    lib = _lib.load()
+    e_c = _dev_f32(e_c)
+    eu = None if e_u is None else _dev_f32(e_u)
+    ep = None if e_p is None else _dev_f32(e_p)
+    for name, t in (("e_u", eu), ("e_p", ep)):
+        if t is not None and t.numel() != e_c.numel():
+            raise ValueError(f"guidance: {name} has {t.numel()} elements, e_c has {e_c.numel()}")
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == e_c.numel()):
+        raise ValueError("guidance: out must be a contiguous fp32 GPU tensor of e_c's size")
+    if return_factor and not float(rescale) > 0.0:
+        raise ValueError("guidance: the factor exists only with rescale > 0")
+    n_samples = e_c.shape[0] if e_c.dim() > 1 else 1
+    if out is None:
+        out = torch.empty_like(e_c)
+    factor = torch.empty(n_samples, device=e_c.device, dtype=torch.float32) if return_factor else None
+    check(lib.af_guidance(ptr(e_c), ptr(eu), ptr(ep), n_samples, e_c.numel() // max(n_samples, 1), float(w), float(s),
+                          float(rescale), ptr(out), ptr(factor), stream_ptr()), "af_guidance")
+    return (out, factor) if return_factor else out
+
+
 def lincomb(terms, cfg=False):
     """sum_i w_i * x_i over up to four (tensor, weight) pairs; cfg=True: terms = [(e_cond, g), (e_uncond, _)] ->
     e_uncond + g * (e_cond - e_uncond)."""

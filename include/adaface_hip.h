@@ -129,6 +129,9 @@ int af_unet_forward_twin(af_handle* h, const float* x_dev, const int64_t* t_dev,
  * caller may re-set an identical context every step): whoever changes the conditioning between a refresh and a reuse
  * invalidates.  Other forwards, VAE and CLIP calls leave D alone.  In reuse mode the diagnostic tap writes only blocks that ran. */
 enum { AF_DEEPCACHE_REFRESH = 1, AF_DEEPCACHE_REUSE = 2 };
+/* The `twin` argument names the form of the forward: 0 and 1 as above, AF_UNET_FORM_PAG = the three-leg forward of
+ * af_unet_forward_pag (Bf = 3 B; the kept feature is 3 B wide and the form is part of its validity key). */
+enum { AF_UNET_FORM_PLAIN = 0, AF_UNET_FORM_TWIN = 1, AF_UNET_FORM_PAG = 2 };
 int af_unet_forward_cached(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                            int twin, int depth, int mode, void* stream);
 int af_unet_cache_invalidate(af_handle* h);
@@ -191,6 +194,32 @@ int af_freeu_plan_query(int dtype, int H, int W, int Ch, int Cs, int version, in
 int af_op_freeu(int dtype, const float* h_dev, const float* skip_dev, int B, int Ch, int Cs, int H, int W, int version, double b,
                 double s, float* h_out_dev, float* skip_out_dev, void* stream);
 
+/* Perturbed-attention guidance (Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance", ECCV 2024;
+ * the SD-1.5 PAG pipelines of diffusers), opt-in.  A site is the self-attention (attn1) of one transformer block, numbered in
+ * forward order: input blocks, middle block, output blocks (SD-1.5 and the tiny config: 16; 0-5 in input blocks 1, 2, 4, 5, 7, 8,
+ * 6 the middle block, 7-15 in output blocks 3-11).  For a perturbed sample at a set site attn1(n) = to_out(to_v(n)), n = norm1(x):
+ * the attention map is the identity; the residual, attn2 and the FeedForward are unchanged.
+ * af_set_pag: the set of sites; 0 sites = off.  A duplicate or out-of-range site: AF_ERR_INVALID.  A change of the set drops a kept
+ * DeepCache feature.  The plain and twin forwards ignore the set entirely.
+ * af_pag_site: out = {the site's block in the tap numbering (af_unet_set_tap), depth index in its transformer, downsample factor
+ * of its map, 1 if set}.
+ * af_unet_forward_pag: x_dev / t_dev hold B samples, the batch is [x; x; x], [t; t; t], Bf = 3 B, legs (cond, uncond, perturbed)
+ * in eps_dev [3 B].  The context is what af_set_context got for Bf samples: the caller passes [c; uc; c], and leg 2 is leg 0 in
+ * everything (context, cached K / V, conv-attention rows) except the self-attention at the set sites.  There q / k / v, the
+ * LayerNorm handling and to_out stay single launches over the three legs, the attention kernel runs on legs 0-1, and leg 2's v
+ * columns are copied into the attention output.  Every block in front of the first block that holds a set site runs on legs 0-1
+ * only; just before that block leg 0 is copied onto leg 2 (the current h and the skip halves of the pending concatenations).
+ * Knob pag_share_prefix = 0 computes all three legs from conv_in on.  Bf % 3 != 0: AF_ERR_INVALID; no site set, or a set site
+ * that also merges tokens (af_set_tome): AF_ERR_STATE; nothing is launched in either case.  Every handle dtype and the fp8 mode.
+ * af_pag_plan_query (host only): out = {first block with a set site (tap numbering, -1: none), input blocks that run on two
+ * legs in a full forward, ... in a DeepCache reuse step of `depth` (0: not asked)}. */
+int af_set_pag(af_handle* h, const int* sites, int n_sites);
+int af_pag_num_sites(af_handle* h);
+int af_pag_site(af_handle* h, int site, int out[4]);
+int af_pag_plan_query(af_handle* h, int depth, int out[3]);
+int af_unet_forward_pag(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
+                        void* stream);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the
@@ -245,6 +274,23 @@ int af_dpmpp_coeffs(double acp_t, double acp_prev, double h_last, double out[8])
 int af_dpmpp_step(const float* x_dev, const float* eps_cond_dev, const float* eps_uncond_dev, const float* x0_prev_dev, int64_t n,
                   float guidance, float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev,
                   float* x_next_dev, float* x0_out_dev, void* stream);
+
+/* The guidance combine of a sampler step with PAG and guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample
+ * Steps are Flawed", WACV 2024, section 3.4; guidance_rescale of diffusers), fp32, n_samples samples of per_sample elements:
+ *     e = e_u + w (e_c - e_u) + s (e_c - e_p);   f = std(e_c) / std(e) per sample (unbiased, as torch.std);
+ *     out = e (rescale f + 1 - rescale).
+ * eps_pag_dev NULL (or pag_scale = 0): no s term; eps_uncond_dev NULL: no w term.  rescale in [0, 1]; 0: one element-wise launch,
+ * no statistics.  rescale > 0: fp32 (mean, M2) partials per 256-element chunk, merged in ascending chunk order (Chan's update),
+ * then the apply pass, which recomputes e; samples of <= 1024 elements take one launch.  No atomics: a sample's bits depend on
+ * that sample alone.  No guard for std(e) = 0, as the reference formula.  factor_dev (NULL ok, rescale > 0 only): [n_samples], the
+ * applied f.  per_sample >= 2 and any alignment are accepted; 16-byte aligned items take float4 accesses, with the same bits.
+ * out_dev may be eps_cond_dev exactly; any other overlap is AF_ERR_INVALID.  The sampler steps (af_ddim_step, af_dpmpp_step,
+ * af_dpmpp_sde_step, af_lincomb) then take the result as eps_cond with eps_uncond NULL.
+ * af_guidance_plan_query (host only): out = {kernel form (1 element-wise, 2 one launch with statistics, 3 statistics + apply),
+ * launches, chunks per sample, partial bytes per sample}. */
+int af_guidance(const float* eps_cond_dev, const float* eps_uncond_dev, const float* eps_pag_dev, int64_t n_samples,
+                int64_t per_sample, float guidance, float pag_scale, float rescale, float* out_dev, float* factor_dev, void* stream);
+int af_guidance_plan_query(int64_t n_samples, int64_t per_sample, int rescale_on, int64_t out[4]);
 
 /* Seed-stable noise: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), keyed so that a sample's noise is a pure function of
  * its identity, never of the rank, the batch position or the launch (the contract, stated in csrc/af_philox.h):
@@ -310,8 +356,9 @@ int64_t af_arena_bytes(af_handle* h);
  * 8 conv_gemm_pp_kernel<*,*,0,true> (fp8 operands, af_set_fp8), 9 conv3x3_halo8_kernel (3x3 / stride-1 convolutions with an
  * LDS-resident input halo: the largest single kernel of a bf16 step); 10-15 the token-merging kernels (af_set_tome), one class per
  * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual; 16-19 the FreeU kernels (af_set_freeu): hidden
- * mean + min / max, low-band sums, apply, the single-launch small-map form.  A caller that asks af_prof_collect for the first 10
- * or 16 classes gets what it got before the later ones existed.
+ * mean + min / max, low-band sums, apply, the single-launch small-map form; 20-21 the guidance kernels (af_guidance): chunk
+ * statistics, and every form that writes the output.  A caller that asks af_prof_collect for the first 10, 16 or 20 classes gets
+ * what it got before the later ones existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */
 int af_prof_enable(int class_mask); /* bit c set = time class c; 0 = off */
@@ -371,10 +418,10 @@ int af_norm_plan_query(int kind, int dtype, int B, int64_t n, int C, int pre_npa
  * AF_* environment variables when the library is loaded (AF_GEMM_PP_MINFILL -> "gemm_pp_minfill", ...); nothing on the
  * launch path reads the environment.  The parity tests use af_knob_set to reach a kernel variant regardless of the
  * planner's choice and af_knob_reset to restore the load-time values.  No knob changes results beyond the summation
- * order of the chosen tiling (ff8_min_k / ff8_min_rows: which transformer blocks the fp8 mode's FeedForward scope covers).  The 25 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
+ * order of the chosen tiling (ff8_min_k / ff8_min_rows: which transformer blocks the fp8 mode's FeedForward scope covers).  The 26 names (adaface_amd/csrc/af_common.h, struct AfKnobs): splitk_target, conv_halo, gemm_pp,
  * gemm_pp_minfill, gemm_tile, gemm_splitk, gemm_groupm, gemm_dma, attn_ring, gn_small, ln_fuse, geglu_rowpanel, conv_halo8,
  * ablate (lab builds only), gn_producer, conv_up_phase4, attn_short, gemm_m128, small_m_tile64, gn_consumer, xattn_fused, plan_log,
- * ff8_min_k, ff8_min_rows, conv_attn_short.
+ * ff8_min_k, ff8_min_rows, conv_attn_short, pag_share_prefix (the only one about WHAT is computed where: af_unet_forward_pag).
  * Round 4 removed the six that selected a measured-neutral or slower variant or nothing at all (gn_reduce, splitk_inlaunch,
  * rowpanel_deep, gn_fold, attn_w4, gemm_pp_geglu_minkt), and after it the four variant switches of the ping-pong kernel went
  * the same way (schedule, K order, stagger, forced epilogue; its tap-mask switch became ablate); numbers in DESIGN.md section 5. */

@@ -76,6 +76,17 @@ def parse_args(argv=None):
                          "version 2: 1.3 1.4 0.9 0.2); composes with every sampler, --dtype, --deep_cache, --tome and --gpus")
     ap.add_argument("--freeu_version", type=int, default=1, choices=[1, 2],
                     help="--freeu: 1 = a constant backbone factor, 2 = the factor follows the backbone's channel mean")
+    ap.add_argument("--pag_scale", type=float, default=0.0, metavar="S",
+                    help="perturbed-attention guidance: e += S (e_cond - e_perturbed), a third U-Net leg per step whose "
+                         "self-attention maps at --pag_layers are the identity (0 = off; diffusers' SD-1.5 default is 3); composes "
+                         "with every sampler, --dtype, --deep_cache, --freeu, --gpus, and --tome where no merging level is a PAG layer")
+    ap.add_argument("--pag_layers", type=str, nargs="+", default=None, metavar="LAYER",
+                    help="--pag_scale: mid, down.blocks.0..2, up.blocks.1..3 or site numbers 0..15 (default: mid)")
+    ap.add_argument("--pag_adaptive_scale", type=float, default=0.0, metavar="A",
+                    help="--pag_scale: the scale of the step at timestep t is max(S - A (1000 - t), 0)")
+    ap.add_argument("--guidance_rescale", type=float, default=0.0, metavar="PHI",
+                    help="guidance rescale, 0 .. 1 (0 = off): the combined prediction is scaled towards the conditional one's "
+                         "standard deviation, the remedy for over-exposure at high guidance; every sampler")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -108,6 +119,27 @@ def parse_args(argv=None):
             ap.error("--freeu B1 B2 S1 S2: 1 <= B1, B2 <= 2")
         if not (0.0 <= s1 <= 1.0 and 0.0 <= s2 <= 1.0):
             ap.error("--freeu B1 B2 S1 S2: 0 <= S1, S2 <= 1")
+    if opt.pag_scale < 0.0 or opt.pag_adaptive_scale < 0.0:
+        ap.error("--pag_scale S, --pag_adaptive_scale A: S, A >= 0")
+    if not 0.0 <= opt.guidance_rescale <= 1.0:
+        ap.error("--guidance_rescale PHI: 0 <= PHI <= 1")
+    if opt.pag_scale == 0.0 and (opt.pag_layers is not None or opt.pag_adaptive_scale > 0.0):
+        ap.error("--pag_layers / --pag_adaptive_scale: give --pag_scale S > 0 too")
+    if opt.pag_scale > 0.0:
+        from adaface_amd.configs import sd15_config
+        from adaface_amd.engine import pag_layout, pag_sites_of
+        layers = [int(v) if v.lstrip("-").isdigit() else v for v in (opt.pag_layers or ["mid"])]
+        if not opt.config:        # (a --config names its own U-Net: its layers are checked when the model is built)
+            unet = sd15_config()["model"]["params"]["unet_config"]["params"]
+            try:
+                sites = pag_sites_of(unet, layers)
+            except ValueError as e:
+                ap.error(f"--pag_layers: {e}")
+            lay = pag_layout(unet)
+            merging = [s for s in sites if opt.tome > 0.0 and lay["ds"][s] <= opt.tome_max_downsample]
+            if merging:
+                ap.error(f"--pag_layers: --tome merges tokens at sites {merging}; a merged self-attention cannot be perturbed")
+        opt.pag_layers = layers
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     return opt
@@ -161,6 +193,8 @@ def main():
         model.set_token_merging(opt.tome, opt.tome_max_downsample)
     if opt.freeu is not None:
         model.set_freeu(opt.freeu_version, *opt.freeu)
+    if opt.pag_scale > 0.0:
+        model.set_pag(opt.pag_layers)
     if not opt.ckpt:  # seeded synthetic weights (identical on every rank)
         g = torch.Generator(device=device).manual_seed(1234)
         with torch.no_grad():
@@ -269,12 +303,16 @@ def main():
                 if opt.init_img_paths:
                     x_T = shard_batch(start_code, rank, world).to(device) + x_T * (1.0 - opt.init_img_weight)
             kw = {} if noise_source is None else dict(noise_source=noise_source)
+            guided = {}
+            if opt.pag_scale > 0.0 or opt.guidance_rescale > 0.0:
+                guided = dict(pag_scale=opt.pag_scale, pag_adaptive_scale=opt.pag_adaptive_scale, guidance_rescale=opt.guidance_rescale)
+            kw.update(guided)
             if opt.deep_cache not in (None, 1):
                 kw.update(deep_cache_interval=opt.deep_cache, deep_cache_depth=opt.deep_cache_depth)
             if opt.plms:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
-                                            eta=opt.ddim_eta, x_T=x_T)
+                                            eta=opt.ddim_eta, x_T=x_T, **guided)
             elif opt.dpm_solver:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,

@@ -94,6 +94,8 @@ _SIGS = [
     ("af_gemm_plan_counts_reset", C.c_int, []),
     ("af_gemm_plan_query", C.c_int, [C.c_int, C.c_int64] + [C.c_int] * 16 + [C.POINTER(C.c_int64)]),
     ("af_norm_plan_query", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    ("af_attn_plan_query", C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int64)]),
+    ("af_attn_plan_counts", C.c_int, [C.POINTER(C.c_int64)]),
     ("af_knob_set", C.c_int, [C.c_char_p, C.c_int]),
     ("af_knob_get", C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
     ("af_knob_reset", C.c_int, []),
@@ -134,6 +136,7 @@ _SIGS = [
     ("af_op_layernorm_fp8_rec", C.c_int, [_P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     ("af_op_layernorm", C.c_int, [C.c_int, _P, _P, _P, C.c_float, _P, C.c_int64, C.c_int, _P]),
     ("af_op_attention", C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    ("af_op_attention_ex", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [C.c_float] + [C.c_int] * 6 + [_P]),
     ("af_clip_embed_tokens", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("af_clip_text_forward", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
     ("af_clip_text_forward3", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P]),
@@ -206,7 +209,9 @@ def plan_counts(reset: bool = False) -> dict:
     tile0..tile5 by the plan's tile (row-panel and 128 x 160 GEMM launches under the tile of the tiled kernel they replace),
     halo (four-wave LDS-halo, not under a tile), splitk (launches that ran more than one K slice), ln_consumer / ln_producer,
     fp8 and up_phase4 (neither under a tile), ff8, halo8 (also under tile5), rowpanel (row-panel and 128 x 160 GEMM launches),
-    gn_producer / gn_consumer; attention: attn_short, xattn_fused, conv_attn_short."""
+    gn_producer / gn_consumer.  Attention, by the kernel af_launch_attention's plan named (ATTN_KERNELS, AfAttnKernel): attn_flash,
+    attn_w4, attn_ring40, attn_ring80, attn_short; the kernels with launchers of their own: xattn_fused, conv_attn_short (neither
+    is counted under the five before).  reset=True zeroes all of them."""
     lib = load()
     c = (C.c_int64 * 10)()
     check(lib.af_gemm_plan_counts(c), "af_gemm_plan_counts")
@@ -218,7 +223,10 @@ def plan_counts(reset: bool = False) -> dict:
     out["rowpanel"] = int(lib.af_rowpanel_launches())
     out["up_phase4"] = int(lib.af_up_phase4_launches())
     out["gn_producer"] = int(lib.af_gn_producer_launches())
-    out["attn_short"] = int(lib.af_attn_short_launches())
+    a = (C.c_int64 * len(ATTN_KERNELS))()
+    check(lib.af_attn_plan_counts(a), "af_attn_plan_counts")
+    for i, name in enumerate(ATTN_KERNELS[1:], 1):
+        out["attn_" + name] = int(a[i])
     out["gn_consumer"] = int(lib.af_gn_consumer_launches())
     out["xattn_fused"] = int(lib.af_xattn_fused_launches())
     out["conv_attn_short"] = int(lib.af_conv_attn_short_launches())
@@ -288,6 +296,22 @@ def norm_plan_query(kind, dtype, B=1, HW=None, C=None, pre_npart=0, rows=None) -
         check(load().af_norm_plan_query(1, dt, 1, int(rows), int(C), 0, out), "af_norm_plan_query")
         return {"kernel": LN_KERNELS[out[0]], "nv": int(out[1]), "rows_per_block": int(out[2])}
     raise ValueError(f"norm_plan_query: kind {kind!r}")
+
+
+ATTN_KERNELS = ("refused", "flash", "w4", "ring40", "ring80", "short")   # AfAttnKernel (csrc/af_kernels.h)
+
+
+def attn_plan_query(dtype, dh, Nk, ldq, ldk=None, ldv=None, ldo=None, causal=False, lse=False, vt_pack=False) -> dict:
+    """af_attn_plan_query: the kernel an attention launch with this head dim, key count, row pitches (elements; ldk, ldv and
+    ldo default to ldq) and flags reaches, {"kernel": one of ATTN_KERNELS}.  Honours the knobs attn_ring and attn_short.  Host
+    only: no GPU is needed.  dtype: a name or an AF_DTYPE_* value."""
+    dt = DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+    ldk = ldq if ldk is None else ldk
+    flags = (1 if causal else 0) | (2 if lse else 0) | (4 if vt_pack else 0)
+    out = C.c_int64()
+    check(load().af_attn_plan_query(dt, int(dh), int(Nk), int(ldq), int(ldk), int(ldk if ldv is None else ldv),
+                                    int(ldq if ldo is None else ldo), flags, C.byref(out)), "af_attn_plan_query")
+    return {"kernel": ATTN_KERNELS[out.value]}
 
 
 def check(rc: int, what: str = "") -> None:

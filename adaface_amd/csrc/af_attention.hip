@@ -26,6 +26,7 @@
 //   * dh is padded in LDS only: QK^T K-dim to a multiple of 32 bytes, O to
 //     32-row blocks; HBM traffic is exactly the unpadded Q, K, V, O.
 #include "af_device.h"
+#include "af_kernels.h"
 #include <math.h>
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -816,26 +817,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   attn_body<T, DH>(p);
 }
 
-template <typename T, int DH> static int launch_attn(const AttnParams& p, int B, hipStream_t stream) {
+// The plan of an attention launch (AfAttnKernel, af_kernels.h): every condition that decides the kernel, and nothing else.
+AfAttnKernel af_plan_attention(AfStorage st, int dh, int Nk, int ldq, int ldk, int ldv, int ldo, bool causal, bool has_lse,
+                               bool has_vt_pack) {
+  const int epc = st == AF_ST_F32 ? 4 : 8;   // elements per 16-byte chunk: what the staging loads and the LDS-DMA move
+  if (ldq % epc || ldk % epc || ldv % epc || ldo % 4 || Nk <= 0) return AF_ATK_REFUSED;
+  switch (dh) {
+    case 8: case 16: case 32: case 40: case 64: case 80: case 128: case 160: break;
+    default: return AF_ATK_REFUSED;
+  }
+  const bool bf = st == AF_ST_BF16;
+  // short key list with the V^T fragments packed by the caller: the register-resident cross-attention kernel
+  if (bf && has_vt_pack && g_af_knobs.attn_short && !causal && !has_lse && Nk <= xs::SMAX && (dh == 40 || dh == 80))
+    return AF_ATK_SHORT;
+  if (bf && dh == 40)   // eight-wave LDS-DMA ring kernel (the 64x64 level); it has no causal mask
+    return ((g_af_knobs.attn_ring & 1) && !causal) ? AF_ATK_RING40 : AF_ATK_FLASH_W4;
+  // 80-wide heads (the 32x32 level; bit 2: tests force it for short key lists)
+  if (bf && dh == 80 && (g_af_knobs.attn_ring & 2) && !causal && (Nk >= 256 || (g_af_knobs.attn_ring & 4))) return AF_ATK_RING80;
+  return AF_ATK_FLASH;
+}
+std::atomic<long> g_af_attn_launches[AF_ATK_COUNT] = {};
+
+template <typename T, int DH> static int launch_attn(AfAttnKernel kern, const AttnParams& p, int B, hipStream_t stream) {
   using C = AttnCfg<T, DH>;
-  if constexpr (C::IS_BF16 && DH == 40) {
-    if ((g_af_knobs.attn_ring & 1) && !p.causal) {   // eight-wave LDS-DMA ring kernel (the 64x64 level)
-      constexpr int lds40 = ring::Cfg<40>::LDS_BYTES;
-      return af_launch_lds<ring::attn_ring40_kernel>(dim3((p.Nq + 255) / 256, p.H, B), dim3(512), lds40, lds40, stream, p);
-    }
+  const dim3 grid((p.Nq + 127) / 128, p.H, B);
+  switch (kern) {
+    case AF_ATK_RING40:
+      if constexpr (C::IS_BF16 && DH == 40) {
+        constexpr int lds40 = ring::Cfg<40>::LDS_BYTES;
+        return af_launch_lds<ring::attn_ring40_kernel>(dim3((p.Nq + 255) / 256, p.H, B), dim3(512), lds40, lds40, stream, p);
+      }
+      break;
+    case AF_ATK_RING80:
+      if constexpr (C::IS_BF16 && DH == 80) {
+        constexpr int lds80 = ring::Cfg<80, 4>::LDS_BYTES;
+        return af_launch_lds<ring::attn_ring80_kernel>(dim3((p.Nq + 127) / 128, p.H, B), dim3(256), lds80, lds80, stream, p);
+      }
+      break;
+    case AF_ATK_FLASH_W4:
+      // (the 128-VGPR cap was sized for the bf16 dh-40 body: fp16 has no such instantiation; every other T / DH keeps its
+      // own, as it always has)
+      if constexpr (!std::is_same_v<T, f16>) return af_launch_lds<attn_kernel_w4<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
+      break;
+    case AF_ATK_FLASH:
+      return af_launch_lds<attn_kernel<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
+    default:
+      break;
   }
-  if constexpr (C::IS_BF16 && DH == 80) {
-    if ((g_af_knobs.attn_ring & 2) && !p.causal && (p.Nk >= 256 || (g_af_knobs.attn_ring & 4))) {   // 80-wide heads (the 32x32 level; bit 2: tests force it for short key lists)
-      constexpr int lds80 = ring::Cfg<80, 4>::LDS_BYTES;
-      return af_launch_lds<ring::attn_ring80_kernel>(dim3((p.Nq + 127) / 128, p.H, B), dim3(256), lds80, lds80, stream, p);
-    }
-  }
-  dim3 grid((p.Nq + 127) / 128, p.H, B);
-  if constexpr (!std::is_same_v<T, f16>) {   // (the 128-VGPR cap was sized for the bf16 dh-40 body: fp16 has no such instantiation)
-    // (a plain `if`: both kernels stay instantiated for every other T / DH, as they have always been)
-    if (C::IS_BF16 && DH == 40) return af_launch_lds<attn_kernel_w4<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
-  }
-  return af_launch_lds<attn_kernel<T, DH>>(grid, dim3(256), C::LDS_BYTES, C::LDS_BYTES, stream, p);
+  af_set_error_msg("attention: plan %d has no kernel for head dim %d in this storage type", (int)kern, DH);
+  return -1;
 }
 
 // packed V^T fragments for xs::xattn_short_kernel (elements; 0 = this (dtype, dh, Nk) has no short-key kernel)
@@ -863,8 +893,6 @@ int af_launch_attn_short_pack(const void* v, int ldv, long bsv, int Nk, int H, i
     return -1;
   }
 }
-std::atomic<long> g_af_attn_short_launches{0};
-
 template <int DH> static int launch_xattn_short(const AttnParams& p, int B, hipStream_t stream) {
   const int nblk = (p.Nq + 31) / 32;
   // blocks of 32 queries per wave: the launch should fit the chip in ONE round of workgroups (every wave pays the load of its
@@ -877,7 +905,6 @@ template <int DH> static int launch_xattn_short(const AttnParams& p, int B, hipS
   dim3 grid((nblk + bpw - 1) / bpw, (p.H + 3) / 4, B);
   hipLaunchKernelGGL((xs::xattn_short_kernel<DH>), grid, dim3(256), 0, stream, p, reinterpret_cast<const bf16*>(p.vt_pack), bpw);
   HIP_CHECK_RET(hipGetLastError());
-  ++g_af_attn_short_launches;
   return 0;
 }
 
@@ -928,32 +955,34 @@ int af_launch_conv_attn_short(const AttnParams& p, int B, int dh, int ks, int gr
 }
 
 template <typename T> int af_launch_attention(const AttnParams& p, int B, int dh, hipStream_t stream) {
-  constexpr int EPC = 16 / sizeof(T);
-  if (p.ldq % EPC || p.ldk % EPC || p.ldv % EPC || p.ldo % 4 || p.Nk <= 0) {
-    af_set_error_msg("attention: row strides must be multiples of %d elements", EPC);
+  const AfAttnKernel kern = af_plan_attention(StorageOf<T>::value, dh, p.Nk, p.ldq, p.ldk, p.ldv, p.ldo, p.causal != 0,
+                                              p.lse != nullptr, p.vt_pack != nullptr);
+  if (kern == AF_ATK_REFUSED) {
+    af_set_error_msg("attention: no kernel for head dim %d, %d keys, row strides %d / %d / %d / %d (head dim 8, 16, 32, 40, 64, 80, "
+                     "128 or 160; q / k / v strides multiples of %d elements, the output's of 4)", dh, p.Nk, p.ldq, p.ldk, p.ldv,
+                     p.ldo, (int)(16 / sizeof(T)));
     return -1;
   }
   if (p.Nq <= 0 || B <= 0) return 0;
   AfProfScope prof(AF_K_ATTENTION, stream, 4.0 * B * p.H * (double)p.Nq * p.Nk * dh,
                    (2.0 * p.Nq + 2.0 * p.Nk) * B * p.H * dh * sizeof(T));
-  if constexpr (std::is_same_v<T, bf16>) {
-    // short key list with the V^T fragments packed by the caller: the register-resident cross-attention kernel
-    if (p.vt_pack && g_af_knobs.attn_short && !p.causal && !p.lse && p.Nk <= xs::SMAX && (dh == 40 || dh == 80))
-      return dh == 40 ? launch_xattn_short<40>(p, B, stream) : launch_xattn_short<80>(p, B, stream);
+  int rc = -1;
+  if (kern == AF_ATK_SHORT) {
+    if constexpr (std::is_same_v<T, bf16>) rc = dh == 40 ? launch_xattn_short<40>(p, B, stream) : launch_xattn_short<80>(p, B, stream);
+  } else {
+    switch (dh) {
+      case 8: rc = launch_attn<T, 8>(kern, p, B, stream); break;
+      case 16: rc = launch_attn<T, 16>(kern, p, B, stream); break;
+      case 32: rc = launch_attn<T, 32>(kern, p, B, stream); break;
+      case 40: rc = launch_attn<T, 40>(kern, p, B, stream); break;
+      case 64: rc = launch_attn<T, 64>(kern, p, B, stream); break;
+      case 80: rc = launch_attn<T, 80>(kern, p, B, stream); break;
+      case 128: rc = launch_attn<T, 128>(kern, p, B, stream); break;
+      case 160: rc = launch_attn<T, 160>(kern, p, B, stream); break;
+    }
   }
-  switch (dh) {
-    case 8: return launch_attn<T, 8>(p, B, stream);
-    case 16: return launch_attn<T, 16>(p, B, stream);
-    case 32: return launch_attn<T, 32>(p, B, stream);
-    case 40: return launch_attn<T, 40>(p, B, stream);
-    case 64: return launch_attn<T, 64>(p, B, stream);
-    case 80: return launch_attn<T, 80>(p, B, stream);
-    case 128: return launch_attn<T, 128>(p, B, stream);
-    case 160: return launch_attn<T, 160>(p, B, stream);
-    default:
-      af_set_error_msg("attention: unsupported head dim %d", dh);
-      return -1;
-  }
+  if (rc == 0) ++g_af_attn_launches[kern];
+  return rc;
 }
 
 template int af_launch_attention<bf16>(const AttnParams&, int, int, hipStream_t);

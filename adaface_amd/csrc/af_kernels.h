@@ -9,13 +9,29 @@ AfGemmPlan af_plan_conv_gemm(const ConvGemmParams& p, int batch, AfStorage st, b
 template <typename T>
 int af_launch_conv_gemm(const ConvGemmParams& p, int batch, hipStream_t stream, const AfGemmPlan* plan = nullptr,
                         void* ws = nullptr);
+// The plan of an attention launch (af_attention.hip): which kernel runs.  af_launch_attention follows it and af_attn_plan_query
+// reports it, so a test knows on the CPU which kernel a shape, pitch and flag set reaches.  The values are part of that result.
+enum AfAttnKernel {
+  AF_ATK_REFUSED = 0,    // a head dim outside {8, 16, 32, 40, 64, 80, 128, 160}, a q / k / v pitch that is no whole number of
+                         // 16-byte chunks, an output pitch % 4, no key: the launcher fails, nothing runs
+  AF_ATK_FLASH = 1,      // attn_kernel<T, DH>: four waves, K / V staged through registers
+  AF_ATK_FLASH_W4 = 2,   // attn_kernel_w4<bf16, 40>: the same body capped at 128 VGPRs (bf16 dh 40 without the ring kernel)
+  AF_ATK_RING40 = 3,     // ring::attn_ring40_kernel: eight waves, LDS-DMA staging (bf16 dh 40, knob attn_ring bit 0, not causal)
+  AF_ATK_RING80 = 4,     // ring::attn_ring80_kernel (bf16 dh 80, attn_ring bit 1, not causal, >= 256 keys or attn_ring bit 2)
+  AF_ATK_SHORT = 5,      // xs::xattn_short_kernel (bf16 dh 40 / 80, <= 96 keys, V^T pack present, knob attn_short, no mask, no lse)
+  AF_ATK_COUNT = 6
+};
+AfAttnKernel af_plan_attention(AfStorage st, int dh, int Nk, int ldq, int ldk, int ldv, int ldo, bool causal, bool has_lse,
+                               bool has_vt_pack);
+// launches per AfAttnKernel since af_gemm_plan_counts_reset, counted where af_launch_attention followed the plan
+extern std::atomic<long> g_af_attn_launches[AF_ATK_COUNT];
+// Nq <= 0 or B <= 0: nothing to do, 0.  A refused plan: -1 with a message
 template <typename T> int af_launch_attention(const AttnParams& p, int B, int dh, hipStream_t stream);
 // V packed as the resident MFMA fragments of the short-key cross-attention kernel (bf16; Nk <= 96, dh 40 / 80): elements
 // needed (0 = no such kernel for this case) and the pack launch; AttnParams::vt_pack then selects the kernel
 template <typename T> long af_attn_short_pack_elems(int B, int H, int dh, int Nk);
 template <typename T>
 int af_launch_attn_short_pack(const void* v, int ldv, long bsv, int Nk, int H, int dh, int B, void* vt, hipStream_t stream);
-extern std::atomic<long> g_af_attn_short_launches;
 // Subject-token conv attention in ONE pass of the short-key kernel (bf16, dh 40 / 80, <= 96 keys with their V^T pack, ks 2..4):
 // p covers ALL Nk keys, the groups * ks^2 subject rows at their end (af_set_context's order); amap = the conv maps
 // [groups][B][H][Hh * Ww] fp32 + the zero word of af_launch_conv_attn_map.  The predicate is the planner's and the launcher's.

@@ -2972,8 +2972,13 @@ int af_gemm_plan_counts(int64_t* counts10) {
   for (int i = 0; i < 10; ++i) counts10[i] = g_af_plan_counts[i];
   return AF_OK;
 }
+int af_attn_plan_counts(int64_t* counts6) {
+  if (!counts6) { af_set_error_msg("af_attn_plan_counts: null argument"); return AF_ERR_INVALID; }
+  for (int i = 0; i < AF_ATK_COUNT; ++i) counts6[i] = g_af_attn_launches[i];
+  return AF_OK;
+}
 int af_gemm_plan_counts_reset(void) {
-  g_af_attn_short_launches = 0;
+  for (int i = 0; i < AF_ATK_COUNT; ++i) g_af_attn_launches[i] = 0;
   g_af_xattn_fused_launches = 0;
   g_af_conv_attn_short_launches = 0;
   g_af_gn_consumer_launches = 0;
@@ -2987,7 +2992,7 @@ int64_t af_halo8_launches(void) { return g_af_plan_counts[AF_PC_HALO8]; }
 int64_t af_rowpanel_launches(void) { return g_af_plan_counts[AF_PC_ROWPANEL]; }
 int64_t af_up_phase4_launches(void) { return g_af_plan_counts[AF_PC_UP_PHASE4]; }
 int64_t af_gn_producer_launches(void) { return g_af_plan_counts[AF_PC_GN_PRODUCER]; }
-int64_t af_attn_short_launches(void) { return g_af_attn_short_launches; }
+int64_t af_attn_short_launches(void) { return g_af_attn_launches[AF_ATK_SHORT]; }
 int64_t af_xattn_fused_launches(void) { return g_af_xattn_fused_launches; }
 int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches; }
 int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }

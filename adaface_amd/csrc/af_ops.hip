@@ -679,45 +679,104 @@ int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const
   return 0;
 }
 
-int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Nq,
-                    int Nk, int heads, int dh, float scale, int causal, void* stream) {   // causal = flags: bit 0 causal, bit 1 NaN guard rows
+// af_op_attention in the forms of AttnParams only the model states (Runner::attn_params, af_model.hip): q | k | v as columns of
+// one [B][N][3C] buffer (layout AF_ATTN_QKV), k | v as columns of the cached context [B][Nk][2C] with the V^T pack made from it
+// (AF_ATTN_CTX), row pitches wider than the channel count (ld_slack), a log-sum-exp output, a window [b0, b0 + nb) of the batch
+// and a key list cut short (drop_keys).  Test hooks, always on: every input buffer holds 0xFF bytes (NaN) wherever no operand
+// is -- slack columns, 128 tail rows -- and the output buffer and lse_dev hold them before the launch; o_dev receives the whole
+// pitched output, float [B][Nq][C + ld_slack].
+int af_op_attention_ex(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, float* lse_dev, int B,
+                       int Nq, int Nk, int heads, int dh, float scale, int flags, int layout, int ld_slack, int b0, int nb,
+                       int drop_keys, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;
-  const int C = heads * dh;
-  const long nq = (long)B * Nq * C, nk = (long)B * Nk * C;
-  OP_ALLOC(qn, (size_t)nq * esize(dtype), false);
-  // flags bit 1 (test hook): K and V are the heads of larger allocations whose 128 tail rows hold NaNs, so a kernel that
-  // reads rows >= Nk of the last sample's last key tile (instead of having them zero-filled) shows up as NaN in O
-  const bool guard = (causal & 2) != 0;
-  causal &= 1;
-  const size_t tail = guard ? (size_t)128 * C * esize(dtype) : 0;
-  OP_ALLOC(kn, (size_t)nk * esize(dtype) + tail, false);
-  OP_ALLOC(vn, (size_t)nk * esize(dtype) + tail, false);
-  if (guard) {
-    if (hipMemsetAsync((char*)kn + (size_t)nk * esize(dtype), 0xFF, tail, s) != hipSuccess ||   // 0xFFFF / 0xFFFFFFFF: NaN
-        hipMemsetAsync((char*)vn + (size_t)nk * esize(dtype), 0xFF, tail, s) != hipSuccess) return AF_ERR_HIP;
+  if (nb < 0) nb = B - b0;
+  if ((dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) || !q_dev || !k_dev || !v_dev || !o_dev || B <= 0 ||
+      Nq <= 0 || Nk <= 0 || heads <= 0 || dh <= 0 || dh % 8 || layout < AF_ATTN_DENSE || layout > AF_ATTN_CTX || ld_slack < 0 ||
+      ld_slack % 8 || b0 < 0 || nb < 0 || b0 + nb > B || drop_keys < 0 || drop_keys >= Nk || (layout == AF_ATTN_QKV && Nq != Nk)) {
+    af_set_error_msg("af_op_attention_ex: dtype=%d B=%d Nq=%d Nk=%d heads=%d dh=%d layout=%d ld_slack=%d window (%d, %d) drop_keys=%d "
+                     "(dh and ld_slack multiples of 8; the qkv layout needs Nq == Nk)", dtype, B, Nq, Nk, heads, dh, layout, ld_slack,
+                     b0, nb, drop_keys);
+    return AF_ERR_INVALID;
   }
-  OP_ALLOC(on, (size_t)nq * esize(dtype), true);
-  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(q_dev, qn, nq, s)));
-  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(k_dev, kn, nk, s)));
-  AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(v_dev, vn, nk, s)));
+  const bool causal = (flags & 1) != 0;
+  const size_t es = esize(dtype);
+  const int C = heads * dh, nkeys = Nk - drop_keys;
+  const int ldo = C + ld_slack;
+  const int ldq = (layout == AF_ATTN_QKV ? 3 * C : C) + ld_slack;
+  const int ldk = (layout == AF_ATTN_QKV ? 3 * C : layout == AF_ATTN_CTX ? 2 * C : C) + ld_slack;
+  const long rq = (long)B * Nq, rk = (long)B * Nk, tail_rows = 128;
+  // a [rows + 128 tail rows][ld] buffer of NaN bytes
+  auto nan_buf = [&](long rows, int ld) -> void* {
+    const size_t bytes = (size_t)(rows + tail_rows) * ld * es;
+    void* b = tmp.get(bytes, false);
+    if (b && hipMemsetAsync(b, 0xFF, bytes, s) != hipSuccess) return nullptr;   // 0xFFFF / 0xFFFFFFFF: NaN
+    return b;
+  };
+  // fp32 [rows][C] -> columns [off, off + C) of a [rows][ld] buffer of the storage type
+  auto put = [&](const float* src, long rows, void* dst, int ld, int off) -> int {
+    void* dense = tmp.get((size_t)rows * C * es, false);
+    if (!dense) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
+    AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(src, dense, rows * C, s)));
+    AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(dense, C, dst, ld, off, C, rows, s)));
+    return 0;
+  };
+  void *qn = nullptr, *kn = nullptr, *vn = nullptr;
+  if (layout == AF_ATTN_QKV) {
+    qn = nan_buf(rq, ldq);
+    if (!qn) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
+    kn = (char*)qn + (size_t)C * es;
+    vn = (char*)qn + (size_t)2 * C * es;
+  } else {
+    qn = nan_buf(rq, ldq);
+    kn = nan_buf(rk, ldk);
+    vn = layout == AF_ATTN_CTX ? (kn ? (void*)((char*)kn + (size_t)C * es) : nullptr) : nan_buf(rk, ldk);
+    if (!qn || !kn || !vn) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
+  }
+  AF_TRY(put(q_dev, rq, qn, ldq, 0));
+  AF_TRY(put(k_dev, rk, layout == AF_ATTN_QKV ? qn : kn, ldk, layout == AF_ATTN_QKV ? C : 0));
+  AF_TRY(put(v_dev, rk, layout == AF_ATTN_DENSE ? vn : layout == AF_ATTN_QKV ? qn : kn, ldk, layout == AF_ATTN_DENSE ? 0 : layout == AF_ATTN_QKV ? 2 * C : C));
+  const size_t o_bytes = (size_t)rq * ldo * es;
+  OP_ALLOC(on, o_bytes, false);
+  if (hipMemsetAsync(on, 0xFF, o_bytes, s) != hipSuccess) return AF_ERR_HIP;
+  if (lse_dev && hipMemsetAsync(lse_dev, 0xFF, (size_t)B * heads * Nq * sizeof(float), s) != hipSuccess) return AF_ERR_HIP;
+  // the window: as Runner::attn_params moves the pointers
   AttnParams p;
-  p.q = qn; p.k = kn; p.v = vn; p.o = on; p.lse = nullptr; p.causal = causal;
-  p.ldq = p.ldk = p.ldv = p.ldo = C;
-  p.bsq = (long)Nq * C; p.bso = (long)Nq * C; p.bsk = (long)Nk * C; p.bsv = (long)Nk * C;
-  p.Nq = Nq; p.Nk = Nk; p.H = heads; p.scale = scale;
+  p.ldq = ldq; p.ldk = p.ldv = ldk; p.ldo = ldo;
+  p.bsq = (long)Nq * ldq; p.bso = (long)Nq * ldo; p.bsk = p.bsv = (long)Nk * ldk;
+  p.q = (char*)qn + (size_t)b0 * p.bsq * es; p.k = (char*)kn + (size_t)b0 * p.bsk * es;
+  p.v = (char*)vn + (size_t)b0 * p.bsv * es; p.o = (char*)on + (size_t)b0 * p.bso * es;
+  p.lse = lse_dev ? lse_dev + (size_t)b0 * heads * Nq : nullptr;
+  p.causal = causal ? 1 : 0;
+  p.Nq = Nq; p.Nk = nkeys; p.H = heads; p.scale = scale;
   p.vt_pack = nullptr;
-  if (dtype == AF_DTYPE_BF16 && !causal) {   // as af_set_context does for the cached cross-attention K / V
-    const long pe = af_attn_short_pack_elems<bf16>(B, heads, dh, Nk);
+  if (dtype == AF_DTYPE_BF16 && !causal && !lse_dev && layout != AF_ATTN_QKV) {   // as af_set_context does for the cached cross-attention K / V
+    const long pe = af_attn_short_pack_elems<bf16>(B, heads, dh, nkeys);
     if (pe > 0) {
       OP_ALLOC(vt, (size_t)pe * 2, false);
-      AF_TRY(af_launch_attn_short_pack<bf16>(vn, C, (long)Nk * C, Nk, heads, dh, B, vt, s));
-      p.vt_pack = vt;
+      AF_TRY(af_launch_attn_short_pack<bf16>(vn, ldk, p.bsv, nkeys, heads, dh, B, vt, s));
+      p.vt_pack = (char*)vt + (size_t)b0 * (size_t)(pe / B) * 2;
     }
   }
-  AF_TRY(AF_TYPED(dtype, af_launch_attention<Elem>(p, B, dh, s)));
-  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, nq, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_attention<Elem>(p, nb, dh, s)));
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, rq * ldo, s)));
   return 0;
+}
+int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Nq,
+                    int Nk, int heads, int dh, float scale, int causal, void* stream) {   // causal = flags: bit 0 causal, bit 1 NaN guard rows
+  return af_op_attention_ex(dtype, q_dev, k_dev, v_dev, o_dev, nullptr, B, Nq, Nk, heads, dh, scale, causal, AF_ATTN_DENSE, 0, 0, -1, 0,
+                            stream);
+}
+
+// Host-only diagnostic: the kernel af_launch_attention would run (AfAttnKernel); no device is touched
+int af_attn_plan_query(int dtype, int dh, int Nk, int ldq, int ldk, int ldv, int ldo, int flags, int64_t* out) {
+  if (!out || (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16)) {
+    af_set_error_msg("af_attn_plan_query: bad argument");
+    return AF_ERR_INVALID;
+  }
+  *out = af_plan_attention(storage_of(dtype), dh, Nk, ldq, ldk, ldv, ldo, (flags & AF_AQ_CAUSAL) != 0, (flags & AF_AQ_LSE) != 0,
+                           (flags & AF_AQ_VT_PACK) != 0);
+  return AF_OK;
 }
 
 // Cross-attention with subject-token conv attention, on the launches xfmr_cross_attention_conv (af_model.hip) makes for a run of

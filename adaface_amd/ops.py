@@ -303,20 +303,46 @@ def freeu(h, skip, version, b, s, dtype="bf16"):
     return h_out, skip_out
 
 
-def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=False):
+ATTN_LAYOUTS = {"dense": 0, "qkv": 1, "ctx": 2}     # AF_ATTN_* (include/adaface_hip.h)
+
+
+def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=False, *, layout="dense", ld_slack=0, lse=False,
+              batch_window=None, drop_keys=0):
     """softmax(q k^T * scale) v per head; q [B,N,heads*dh], k/v [B,S,heads*dh] (attention.py:197-243).  causal: query i
-    attends to keys <= i (the CLIP text tower's mask).  nan_guard (tests): K / V sit in front of 128 rows of NaNs."""
+    attends to keys <= i (the CLIP text tower's mask).  nan_guard (tests): K / V sit in front of 128 rows of NaNs.
+
+    The keyword-only arguments state the forms of AttnParams only the model builds (af_op_attention_ex); with all of them at
+    their defaults the call is af_op_attention as before and returns o [B,N,heads*dh].  With any of them set:
+      layout        "dense": three buffers; "qkv": q | k | v as columns of one [B][N][3C] buffer (self-attention, N == S);
+                    "ctx": k | v as columns of one [B][S][2C] buffer, the cached context, from which the short-key kernel's V^T
+                    pack is made (bf16, dh 40 / 80, <= 96 keys, no mask, no lse); "qkv" makes no pack, as the model's
+                    self-attention has none
+      ld_slack      elements (a multiple of 8) added to every row pitch, the output's included
+      lse           also return the log2-domain log-sum-exp of the scaled scores, fp32 [B, heads, N]; no V^T pack is made
+      batch_window  (b0, nb): samples [b0, b0 + nb) run, every pointer moved by b0 samples
+      drop_keys     the last drop_keys key rows are left out (the batch stride stays S rows)
+    and the return value is the WHOLE pitched output [B, N, heads*dh + ld_slack] (or the pair (o, lse)): every input buffer, the
+    output and lse hold NaN bytes before the launch, so slack columns and samples outside the window read NaN unless the kernel
+    wrote there, and a NaN inside the window is a read of a slack column or of a row behind the operands."""
     lib = _lib.load()
     q, k, v = _dev_f32(q), _dev_f32(k), _dev_f32(v)
     B, Nq, Cn = q.shape
     Nk = k.shape[1]
     dh = Cn // heads
     scale = dh ** -0.5 if scale is None else scale
-    o = torch.empty_like(q)
-    check(lib.af_op_attention(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(o), B, Nq, Nk, heads, dh, scale,
-                              (1 if causal else 0) | (2 if nan_guard else 0), stream_ptr()),
-          "af_op_attention")
-    return o
+    flags = (1 if causal else 0) | (2 if nan_guard else 0)
+    if layout == "dense" and ld_slack == 0 and not lse and batch_window is None and drop_keys == 0:
+        o = torch.empty_like(q)
+        check(lib.af_op_attention(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(o), B, Nq, Nk, heads, dh, scale, flags, stream_ptr()),
+              "af_op_attention")
+        return o
+    b0, nb = (0, -1) if batch_window is None else batch_window
+    o = torch.empty(B, Nq, Cn + ld_slack, dtype=torch.float32, device=q.device)
+    l = torch.empty(B, heads, Nq, dtype=torch.float32, device=q.device) if lse else None
+    check(lib.af_op_attention_ex(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(o), ptr(l), B, Nq, Nk, heads, dh, scale, flags,
+                                 ATTN_LAYOUTS[layout], int(ld_slack), int(b0), int(nb), int(drop_keys), stream_ptr()),
+          "af_op_attention_ex")
+    return (o, l) if lse else o
 
 
 CONV_ATTN_PATHS = {"auto": 0, "merge": 1, "one_pass": 2}

@@ -412,6 +412,18 @@ int af_gemm_plan_query(int dtype, int64_t M, int N, int K, int cin_pad, int ks, 
  * kind 1: n rows of C elements (B, pre_npart ignored).  out5 = {kernel, vectors per lane, rows per workgroup, 0, 0}.  kernel:
  *   0 refused, 1 one wave per row, 2 the row-group kernel (8 lanes per row on 16-bit storage, 16 on f32). */
 int af_norm_plan_query(int kind, int dtype, int B, int64_t n, int C, int pre_npart, int64_t* out5);
+/* Host-only diagnostic: the kernel an attention launch would run (no device is touched; honours af_knob_set "attn_ring" and
+ * "attn_short").  The launcher follows the same plan.  dh = head dim, Nk = keys, ldq / ldk / ldv / ldo = row pitches in elements;
+ * flags: bit 0 causal mask, bit 1 a log-sum-exp output is asked for, bit 2 the caller holds the packed V^T of the short-key
+ * kernel.  *out = 0 refused (the launch fails: head dim outside {8, 16, 32, 40, 64, 80, 128, 160}, a q / k / v pitch that is no
+ * whole number of 16-byte chunks, ldo % 4, Nk <= 0), 1 the four-wave flash kernel, 2 its 128-VGPR build (bf16 dh 40),
+ * 3 / 4 the LDS-DMA ring kernels for dh 40 / 80 (bf16, no mask), 5 the register-resident short-key kernel (bf16 dh 40 / 80,
+ * <= 96 keys, pack present, no mask, no log-sum-exp). */
+enum { AF_AQ_CAUSAL = 1, AF_AQ_LSE = 2, AF_AQ_VT_PACK = 4 };
+int af_attn_plan_query(int dtype, int dh, int Nk, int ldq, int ldk, int ldv, int ldo, int flags, int64_t* out);
+/* attention launches since af_gemm_plan_counts_reset by the kernel that ran, indexed as af_attn_plan_query's result
+ * (counts6[0] stays 0; counts6[5] = af_attn_short_launches) */
+int af_attn_plan_counts(int64_t* counts6);
 
 /* ---- tuning / diagnostic knobs ----
  * The planner thresholds and "force this kernel variant" switches live in one struct that is filled once from the
@@ -583,10 +595,30 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
 int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps,
                     float* y_dev, int64_t rows, int C, void* stream);
 /* multi-head attention on [B,N,heads*dh] / [B,S,heads*dh] tensors (attention.py:197-243); `causal` is a flag word:
- * bit 0: query i sees keys <= i (CLIP text tower); bit 1 (test hook): K and V are placed at the head of allocations
- * whose 128 tail rows hold NaNs, so reads past row S of the last sample become visible in the output. */
+ * bit 0: query i sees keys <= i (CLIP text tower); bit 1 (test hook, accepted; always in force since af_op_attention_ex): K
+ * and V are placed at the head of allocations whose 128 tail rows hold NaNs, so reads past row S of the last sample become
+ * visible in the output. */
 int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int B, int Nq,
                     int Nk, int heads, int dh, float scale, int causal, void* stream);
+/* af_op_attention in the forms of AttnParams only the model states (Runner::attn_params, af_model.hip); af_op_attention is this
+ * call with layout 0, no slack, no log-sum-exp, the whole batch and every key.  C = heads * dh.
+ * layout: AF_ATTN_DENSE q, k, v in three buffers of pitch C + ld_slack; AF_ATTN_QKV columns 0 / C / 2C of one
+ *   [B][N][3C + ld_slack] buffer (self-attention; Nq == Nk); AF_ATTN_CTX q [B][Nq][C + ld_slack], k / v columns 0 / C of one
+ *   [B][Nk][2C + ld_slack] buffer (the cached context) from which the short-key kernel's V^T pack is made with that pitch.
+ * ld_slack: a non-negative multiple of 8 elements added to every row pitch, the output's included.
+ * lse_dev: null or float [B][heads][Nq], the log2-domain log-sum-exp of the scaled scores; no V^T pack is made with it, nor with
+ *   the causal mask or AF_ATTN_QKV (the model has none for self-attention).
+ * b0, nb: samples [b0, b0 + nb) run (nb < 0: all from b0): every pointer, the pack's included, moves by b0 samples.
+ * drop_keys: the last drop_keys of the Nk key rows are left out (the batch stride stays Nk rows), as conv attention's flash part.
+ * flags: bit 0 causal (bit 1 of af_op_attention is accepted: the guards below are always there).
+ * Guards: every input buffer is filled with 0xFF bytes (NaN in all three storage types) before the casts, so the slack columns
+ * and 128 tail rows behind each buffer (AF_ATTN_QKV / _CTX: behind the whole fused buffer) hold NaN; the output buffer and
+ * lse_dev too.  o_dev receives the whole pitched output, float [B][Nq][C + ld_slack]: slack columns and samples outside the
+ * window still hold NaN unless something wrote there, and a NaN inside the window means a read of what should not be read. */
+enum { AF_ATTN_DENSE = 0, AF_ATTN_QKV = 1, AF_ATTN_CTX = 2 };
+int af_op_attention_ex(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, float* lse_dev, int B,
+                       int Nq, int Nk, int heads, int dh, float scale, int flags, int layout, int ld_slack, int b0, int nb,
+                       int drop_keys, void* stream);
 /* timestep_embedding (util.py:154-174): t [B] int64 -> y [B,dim] fp32. */
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream);
 

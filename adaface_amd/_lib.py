@@ -55,6 +55,10 @@ _SIGS = [
     ("af_destroy", None, [_P]),
     ("af_load_tensor", C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64)]),
     ("af_load_tensor_device", C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64)]),
+    ("af_load_tensor_lora", C.c_int, [_P, C.c_char_p, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(_P), C.POINTER(_P),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    ("af_op_lora_repack", C.c_int, [C.c_int, _P] + [C.c_int] * 8 + [C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int),
+                                                                    C.POINTER(C.c_float), _P, _P]),
     ("af_num_tensors", C.c_int, [_P]),
     ("af_tensor_name", C.c_char_p, [_P, C.c_int]),
     ("af_tensor_loaded", C.c_int, [_P, C.c_int]),
@@ -166,6 +170,9 @@ _SIGS = [
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGS]
 
+# AF_LORA_MAX_ADAPTERS / AF_LORA_MAX_RANK (include/adaface_hip.h)
+LORA_MAX_ADAPTERS = 8
+LORA_MAX_RANK = 256
 # the `mode` argument of af_unet_forward_cached (include/adaface_hip.h)
 DEEPCACHE_MODES = {"refresh": 1, "reuse": 2}
 # ... and its `twin` argument, the form of the forward (AF_UNET_FORM_*); False / True keep their meaning

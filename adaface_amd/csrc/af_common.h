@@ -161,6 +161,13 @@ template <> __device__ __forceinline__ bf16 from_f32<bf16>(float v) { return (bf
 // IEEE round-to-nearest-even (v_cvt_f16_f32); beyond +-65504 the result is +-inf, as torch.Tensor.half(): no saturating clamp
 template <> __device__ __forceinline__ f16 from_f32<f16>(float v) { return (f16)v; }
 
+// row of output feature n of a GEGLU projection in its repacked weight (value / gate groups of 16 interleaved, half = rows / 2):
+// shared by the weight repack kernels (af_elementwise.hip, af_lora.hip) and the bias permutation
+__device__ __forceinline__ int geglu_perm(int n, int half) {
+  const int j = n < half ? n : n - half;
+  return (j >> 4) * 32 + (n < half ? 0 : 16) + (j & 15);
+}
+
 // 16-byte vector of storage elements (8 bf16 / fp16 or 4 float)
 template <typename T> struct Vec16 {
   static constexpr int N = 16 / sizeof(T);

@@ -748,10 +748,6 @@ INST(f16)
 // ---------------------------------------------------------------------------
 // weight repack: [rows][cin][ks][ks] fp32 -> T [row_off + perm(n)][(ky,kx,c) with c padded to cin_pad]
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int geglu_perm(int n, int half) {
-  const int j = n < half ? n : n - half;
-  return (j >> 4) * 32 + (n < half ? 0 : 16) + (j & 15);
-}
 template <typename T>
 __global__ void repack_weight_kernel(const float* __restrict__ src, T* __restrict__ dst, int rows, int cin,
                                      int cin_pad, int ks, int ldw, int row_off, int perm) {

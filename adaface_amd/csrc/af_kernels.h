@@ -245,6 +245,14 @@ template <typename T>
 int af_launch_repack_weight(const float* src, void* dst, int rows, int cin, int cin_pad, int ks, int ldw, int row_off,
                             int perm, hipStream_t s);
 int af_launch_permute_bias(const float* src, float* dst, int rows, int perm, hipStream_t s);
+// ... with LoRA adapters merged while it repacks (af_lora.hip): dst = T(src + sum_a scales[a] * up[a] @ down[a]), fp32, rounded
+// once; up[a] fp32 [rows][ranks[a]], down[a] fp32 [ranks[a]][cin * ks * ks] on the device, the four arrays on the host (copied
+// into the kernel's arguments).  n_adapters 0 .. 8 (0: the bits of af_launch_repack_weight), ranks 1 .. 256.  A refused
+// argument: -1 with a message, nothing launched
+template <typename T>
+int af_launch_lora_repack(const float* src, void* dst, int rows, int cin, int cin_pad, int ks, int ldw, int row_off, int perm,
+                          int n_adapters, const float* const* up, const float* const* down, const int* ranks,
+                          const float* scales, hipStream_t s);
 // LayerNorm folded into a linear: Wf = W * gamma (rounded to T), colsum[n] = sum_k Wf[n][k], biasf = W beta + bias
 template <typename T>
 int af_launch_ln_fold(const void* W, void* Wf, const float* gamma, const float* beta, const float* bias, float* colsum,

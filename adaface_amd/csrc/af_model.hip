@@ -2320,16 +2320,35 @@ int af_tensor_shape(af_handle* h, int i, int64_t* shape4) {
   return (int)s.shape.size();
 }
 
+// the adapters of af_load_tensor_lora (host arrays of device pointers, ranks and factors), or null
+struct LoraSet {
+  int n;
+  const float* const* up;
+  const float* const* down;
+  const int* ranks;
+  const float* scales;
+};
 static int load_tensor_impl(af_handle* h, const char* name, const float* data, int ndim, const int64_t* shape,
-                            bool on_device);
+                            bool on_device, const LoraSet* lora = nullptr);
 int af_load_tensor(af_handle* h, const char* name, const float* host_data, int ndim, const int64_t* shape) {
   return load_tensor_impl(h, name, host_data, ndim, shape, false);
 }
 int af_load_tensor_device(af_handle* h, const char* name, const float* dev_data, int ndim, const int64_t* shape) {
   return load_tensor_impl(h, name, dev_data, ndim, shape, true);
 }
+int af_load_tensor_lora(af_handle* h, const char* name, const float* base, int base_on_device, int ndim, const int64_t* shape,
+                        int n_adapters, const float* const* up_dev, const float* const* down_dev, const int* ranks,
+                        const float* scales) {
+  if (n_adapters == 0) return load_tensor_impl(h, name, base, ndim, shape, base_on_device != 0);
+  if (n_adapters < 0 || n_adapters > AF_LORA_MAX_ADAPTERS || !up_dev || !down_dev || !ranks || !scales) {
+    af_set_error_msg("af_load_tensor_lora: %d adapters (0 .. %d, with their four arrays)", n_adapters, AF_LORA_MAX_ADAPTERS);
+    return AF_ERR_INVALID;
+  }
+  const LoraSet lora{n_adapters, up_dev, down_dev, ranks, scales};
+  return load_tensor_impl(h, name, base, ndim, shape, base_on_device != 0, &lora);
+}
 static int load_tensor_impl(af_handle* h, const char* name, const float* host_data, int ndim, const int64_t* shape,
-                            bool on_device) {
+                            bool on_device, const LoraSet* lora) {
   if (!h || !name || !host_data) { af_set_error_msg("af_load_tensor: null argument"); return AF_ERR_INVALID; }
   auto it = h->slots.find(name);
   if (it == h->slots.end()) { af_set_error_msg("af_load_tensor: unknown tensor '%s'", name); return AF_ERR_NAME; }
@@ -2345,12 +2364,24 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
                      name, (long long)n, (long long)shape[0], (long long)nexp, (long long)s.shape[0]);
     return AF_ERR_INVALID;
   }
+  if (lora) {   // adapters go into conv / linear weights only; their extents follow from the slot and the rank
+    if (s.kind != Slot::WEIGHT) {
+      af_set_error_msg("af_load_tensor_lora: '%s' is not a conv / linear weight (adapters merge into weights only)", name);
+      return AF_ERR_INVALID;
+    }
+    for (int i = 0; i < lora->n; ++i)
+      if (!lora->up[i] || !lora->down[i] || lora->ranks[i] < 1 || lora->ranks[i] > AF_LORA_MAX_RANK ||
+          lora->ranks[i] > INT32_MAX / (s.rows > s.cin * s.ks * s.ks ? s.rows : s.cin * s.ks * s.ks)) {
+        af_set_error_msg("af_load_tensor_lora: adapter %d of '%s': null matrix or rank %d outside 1 .. %d for a [%d][%d x %d x %d] weight",
+                         i, name, lora->ranks[i], AF_LORA_MAX_RANK, s.rows, s.cin, s.ks, s.ks);
+        return AF_ERR_INVALID;
+      }
+  }
   HIP_CHECK_RET(hipSetDevice(h->device));
   const size_t bytes = (size_t)n * sizeof(float);
   const float* srcp = host_data;
-  if (on_device) {
-    HIP_CHECK_RET(hipDeviceSynchronize());  // the caller's producer stream may differ from ours
-  } else if (bytes > h->stage_bytes) {
+  if (on_device || lora) HIP_CHECK_RET(hipDeviceSynchronize());  // the caller's producer stream may differ from ours
+  if (!on_device && bytes > h->stage_bytes) {
     if (h->stage) hipFree(h->stage);
     h->stage = nullptr;
     h->stage_bytes = 0;
@@ -2365,6 +2396,9 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
   }
   if (s.kind == Slot::TABLE) {
     AF_TRY(AF_TYPED(h->dtype, af_launch_cast_f32<Elem>(srcp, s.dst, (long)n, 0)));
+  } else if (s.kind == Slot::WEIGHT && lora) {
+    AF_TRY(AF_TYPED(h->dtype, af_launch_lora_repack<Elem>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off, s.perm,
+                                                          lora->n, lora->up, lora->down, lora->ranks, lora->scales, 0)));
   } else if (s.kind == Slot::WEIGHT) {
     AF_TRY(AF_TYPED(h->dtype, af_launch_repack_weight<Elem>(srcp, s.dst, s.rows, s.cin, s.cin_pad, s.ks, s.ldw, s.row_off,
                                                             s.perm, 0)));

@@ -1034,6 +1034,17 @@ int af_op_freeu(int dtype, const float* h_dev, const float* skip_dev, int B, int
   return AF_OK;
 }
 
+// The LoRA-merging weight repack (af_lora.hip) on caller-owned buffers: dst_dev holds elements of `dtype` and is written in place
+int af_op_lora_repack(int dtype, const float* base_dev, int rows, int cin, int cin_pad, int ks, int ldw, int row_off, int perm,
+                      int n_adapters, const float* const* up_dev, const float* const* down_dev, const int* ranks,
+                      const float* scales, void* dst_dev, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_op_lora_repack: storage type %d", dtype); return AF_ERR_INVALID; }
+  AF_TRY(AF_TYPED(dtype, af_launch_lora_repack<Elem>(base_dev, dst_dev, rows, cin, cin_pad, ks, ldw, row_off, perm != 0, n_adapters,
+                                                     up_dev, down_dev, ranks, scales, s)));
+  return AF_OK;
+}
+
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import AfConfig, DTYPES, check, ptr, stream_ptr
+from .lora import check_lora_pair
 
 UNET_PREFIX = "model.diffusion_model."
 VAE_PREFIX = "first_stage_model."
@@ -215,6 +216,32 @@ class Engine:
         shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
         fn = self._lib.af_load_tensor_device if t.is_cuda else self._lib.af_load_tensor
         check(fn(self._h, name.encode(), C.c_void_p(t.data_ptr()), t.dim(), shape), f"af_load_tensor({name})")
+
+    def load_tensor_lora(self, name: str, base: torch.Tensor, adapters):
+        """af_load_tensor_lora: load_tensor(name, base + sum_a s_a * up_a @ down_a), merged in fp32 by the repack kernel itself and
+        rounded once.  adapters: up to 8 of (up [rows, r(, 1, 1)], down [r, cin(, ks, ks)], s) -- s the whole factor
+        (scale * alpha / r); the matrices are moved to the engine's device.  Conv / linear weights only.  [] is load_tensor."""
+        adapters = list(adapters)
+        if not adapters:
+            return self.load_tensor(name, base)
+        if len(adapters) > _lib.LORA_MAX_ADAPTERS:
+            raise ValueError(f"load_tensor_lora({name}): {len(adapters)} adapters (at most {_lib.LORA_MAX_ADAPTERS})")
+        base = base.detach().to(torch.float32).contiguous()
+        rows, per_row = base.shape[0], base[0].numel() if base.dim() > 1 else 1
+        ups, downs, ranks, scales = [], [], [], []
+        for i, (up, down, s) in enumerate(adapters):
+            check_lora_pair(f"{name} (adapter {i})", tuple(base.shape), tuple(up.shape), tuple(down.shape))
+            ups.append(up.detach().to(self.device, torch.float32).contiguous())
+            downs.append(down.detach().to(self.device, torch.float32).contiguous())
+            ranks.append(int(down.shape[0]))
+            scales.append(float(s))
+        assert all(u.numel() == rows * r and d.numel() == r * per_row for u, d, r in zip(ups, downs, ranks))
+        n = len(adapters)
+        shape = (C.c_int64 * max(1, base.dim()))(*base.shape)
+        check(self._lib.af_load_tensor_lora(self._h, name.encode(), C.c_void_p(base.data_ptr()), 1 if base.is_cuda else 0, base.dim(),
+                                            shape, n, (C.c_void_p * n)(*[u.data_ptr() for u in ups]),
+                                            (C.c_void_p * n)(*[d.data_ptr() for d in downs]), (C.c_int * n)(*ranks),
+                                            (C.c_float * n)(*scales)), f"af_load_tensor_lora({name})")
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], prefix: str = "", strict: bool = True):
         """Feed every tensor the library expects from `sd` (keys = `prefix` + library name)."""

@@ -60,6 +60,7 @@ class HipModule(nn.Module):
         object.__setattr__(self, "_tome", (0.0, 1))           # token merging (UNetModel.set_token_merging), kept the same way
         object.__setattr__(self, "_freeu", (0, 1.0, 1.0, 1.0, 1.0))   # FreeU (UNetModel.set_freeu), kept the same way
         object.__setattr__(self, "_pag", ())                          # PAG sites (UNetModel.set_pag), kept the same way
+        object.__setattr__(self, "_lora", [])                         # LoRA adapters [(weights, scale)] (set_lora), kept the same way
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
@@ -201,15 +202,80 @@ class HipModule(nn.Module):
         return self.set_fp8_shifts(load_scales(path, eng.fp8_site_names()))
 
     def sync_weights(self):
-        """Upload (repack) every parameter into the engine."""
+        """Upload (repack) every parameter into the engine; the targets of set_lora go through the fused merge."""
         eng = self._engine
         if eng is None:
             return
         table = eng.tensor_table()
         sd = self.state_dict()
+        targets = set(self.lora_targets())
         for name in table:
             key = name[len(self._ckpt_prefix):] if name.startswith(self._ckpt_prefix) else name
             if key not in sd:
                 raise KeyError(f"engine expects tensor '{name}' but the module has no parameter '{key}'")
-            eng.load_tensor(name, sd[key])
+            if key.endswith(".weight") and key[:-len(".weight")] in targets:
+                eng.load_tensor_lora(name, sd[key], self._lora_of(key[:-len(".weight")]))
+            else:
+                eng.load_tensor(name, sd[key])
         object.__setattr__(self, "_weights_dirty", False)
+
+    # ---- LoRA adapters: an overlay on the engine's weights, never on the parameters --------------
+    def lora_targets(self) -> list:
+        """The sorted parameter names (without ".weight") the current adapter set touches."""
+        return sorted({name for weights, _ in self._lora for name in weights})
+
+    def _lora_of(self, pname: str) -> list:
+        """[(up, down, s)] of the adapters that touch `pname`, in list order, s = scale * alpha / r formed in double."""
+        from adaface_amd.lora import lora_factor
+        return [(w[pname][0], w[pname][1], lora_factor(scale, w[pname][2], w[pname][1].shape[0]))
+                for w, scale in self._lora if pname in w]
+
+    def _lora_changed(self):
+        """Hook: state outside the engine that depends on the weights (UNetModel: the hoisted context K / V)."""
+
+    def set_lora(self, adapters):
+        """LoRA adapters on top of this module's weights: `adapters` is a list of (weights, scale), at most 8, with weights =
+        {parameter name without ".weight": (up, down, alpha)} in this module's own names (adaface_amd.lora.split_lora makes
+        them from a file).  The engine's copy of each touched weight becomes W + sum_a scale_a * alpha_a / r_a * up_a @ down_a,
+        formed in fp32 by the repack kernel and rounded once; the module's parameters and state_dict() never change, so
+        set_lora([]) / clear_lora() give the base model back exactly.  Names and shapes are checked first (KeyError /
+        ValueError naming the key).  On a live engine only the weights in the union of the previous and the new target set are
+        loaded again (those that dropped out, plainly); everything the engine derives from weights is refreshed before the next
+        forward.  The list is kept for every later engine (device or compute-dtype change).  A change of the adapter set drops
+        calibrated fp8 shifts, as a checkpoint load does: calibrate or load_fp8_scales after set_lora."""
+        import math
+        from adaface_amd.lora import check_adapter_list, check_lora_pair
+        adapters = check_adapter_list(adapters)
+        params = dict(self.named_parameters())
+        for i, (weights, _scale) in enumerate(adapters):
+            for pname, entry in weights.items():
+                p = params.get(f"{pname}.weight") if isinstance(pname, str) else None
+                if p is None or p.dim() < 2:
+                    raise KeyError(f"{type(self).__name__}.set_lora: adapter {i} names {pname!r}, which is no conv / linear weight "
+                                   "of this module")
+                if not isinstance(entry, (tuple, list)) or len(entry) != 3:
+                    raise ValueError(f"{type(self).__name__}.set_lora: adapter {i}, {pname!r}: expected (up, down, alpha)")
+                up, down, alpha = entry
+                check_lora_pair(f"adapter {i}, {pname!r}", tuple(p.shape), tuple(up.shape), tuple(down.shape))
+                if not math.isfinite(float(alpha)):
+                    raise ValueError(f"{type(self).__name__}.set_lora: adapter {i}, {pname!r}: alpha {alpha!r} is not finite")
+        old = set(self.lora_targets())
+        if not old and not any(w for w, _ in adapters):
+            object.__setattr__(self, "_lora", adapters)
+            return self
+        object.__setattr__(self, "_lora", adapters)
+        touched = sorted(old | set(self.lora_targets()))
+        self.set_fp8_shifts(None)
+        self._lora_changed()
+        eng = self._engine
+        if eng is not None and not self._weights_dirty:
+            table = eng.tensor_table()
+            for pname in touched:
+                key = f"{pname}.weight"
+                name = self._ckpt_prefix + key if self._ckpt_prefix + key in table else key
+                eng.load_tensor_lora(name, params[key], self._lora_of(pname))
+        return self
+
+    def clear_lora(self):
+        """set_lora([]): back to the base weights."""
+        return self.set_lora([])

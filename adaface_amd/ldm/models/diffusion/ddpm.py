@@ -325,6 +325,27 @@ class LatentDiffusion(DDPM):
     def pag(self) -> tuple:
         return self.model.diffusion_model.pag
 
+    def set_lora(self, adapters):
+        """LoRA adapters on the U-Net and the text tower (HipModule.set_lora on each): `adapters` is a list of (split, scale), at
+        most 8, with split = {"unet": weights, "text": weights} as adaface_amd.lora.split_lora returns it (either key may be
+        missing).  [] restores the base model.  Call it before the prompt is encoded: a text-tower adapter changes the context.
+        Text weights without a HIP text tower in this model raise ValueError."""
+        adapters = list(adapters or ())
+        for i, item in enumerate(adapters):
+            if not isinstance(item, (tuple, list)) or len(item) != 2 or not isinstance(item[0], dict) or set(item[0]) - {"unet", "text", "unused"}:
+                raise ValueError(f"set_lora: adapter {i} is not a ({{'unet': ..., 'text': ...}}, scale) pair")
+        text = [(split.get("text") or {}, scale) for split, scale in adapters]
+        cond = self.cond_stage_model
+        if any(w for w, _ in text) and not hasattr(cond, "set_lora"):
+            raise ValueError("set_lora: the adapters hold text-tower weights but this model has no HIP text tower (cond_stage_model)")
+        self.model.diffusion_model.set_lora([(split.get("unet") or {}, scale) for split, scale in adapters])
+        if hasattr(cond, "set_lora"):
+            cond.set_lora(text)
+        return self
+
+    def clear_lora(self):
+        return self.set_lora([])
+
     def set_compute_dtype(self, dtype: str, fp8_scope: str = "base"):
         """'bf16' | 'f32' | 'f16' (alias 'fp16') | 'fp8' (the UNet's ResBlock convolutions in e4m3; VAE and text tower stay bf16).
         fp8_scope: 'base' (ResBlock convolutions and self-attention q / k / v) or 'base+ff' (also the transformer blocks'

@@ -74,6 +74,9 @@ class UNetModel(HipModule):
         super()._mark_dirty()
         object.__setattr__(self, "_ctx_key", None)  # cached K/V depend on the weights
 
+    def _lora_changed(self):
+        object.__setattr__(self, "_ctx_key", None)  # (set_lora: attn2.to_k / to_v may have changed, as in _mark_dirty)
+
     def _compel_cfg(self, context, B, info):
         """Inference-time compel cfg (openaimodel.py:898-916 + prob_apply_compel_cfg, util.py:2063-2094): per conditioned
         layer, with probability apply_compel_cfg_prob, the context of the FIRST half of the batch becomes

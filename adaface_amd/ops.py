@@ -8,6 +8,7 @@ same kernels internally with no conversions).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import torch
@@ -301,6 +302,45 @@ def freeu(h, skip, version, b, s, dtype="bf16"):
     check(lib.af_op_freeu(DTYPES[dtype], ptr(h), ptr(skip), B, Ch, skip.shape[1], H, W, int(version), float(b), float(s),
                           ptr(h_out), ptr(skip_out), stream_ptr()), "af_op_freeu")
     return h_out, skip_out
+
+
+STORAGE_TORCH = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
+
+
+def lora_repack(base, adapters=(), cin_pad=None, ldw=None, row_off=0, rows_total=None, perm=False, dtype="bf16", out=None):
+    """The weight repack with LoRA adapters merged (af_op_lora_repack): base [rows, cin(, ks, ks)] fp32 and adapters
+    [(up [rows, r(, 1, 1)], down [r, cin(, ks, ks)], s)] (at most 8, r <= 256) -> the packed buffer [rows_total, ldw] in the storage
+    type `dtype`, element (row_off + perm(o), tap * cin_pad + c) = base[o, c, tap] + sum_a s_a * (up_a @ down_a)[o, c * ks^2 + tap],
+    formed in fp32 and rounded once; columns cin <= c < cin_pad are zeros.  perm: the GEGLU row order.  Defaults: cin_pad = cin,
+    ldw = ks^2 * cin_pad, rows_total = row_off + rows.  out: a buffer of that shape and type to write into (what the kernel does
+    not own keeps its content); otherwise a zero-filled one."""
+    from .lora import check_lora_pair
+    lib = _lib.load()
+    base = _dev_f32(base)
+    rows, cin = base.shape[0], base.shape[1]
+    ks = base.shape[2] if base.dim() == 4 else 1
+    cin_pad = cin if cin_pad is None else int(cin_pad)
+    ldw = ks * ks * cin_pad if ldw is None else int(ldw)
+    rows_total = row_off + rows if rows_total is None else int(rows_total)
+    if row_off < 0 or row_off + rows > rows_total:
+        raise ValueError(f"lora_repack: rows {row_off} .. {row_off + rows} outside a buffer of {rows_total}")
+    if out is None:
+        out = torch.zeros(rows_total, ldw, device=base.device, dtype=STORAGE_TORCH[dtype])
+    elif tuple(out.shape) != (rows_total, ldw) or out.dtype != STORAGE_TORCH[dtype] or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"lora_repack: out must be a contiguous device tensor [{rows_total}, {ldw}] of {STORAGE_TORCH[dtype]}")
+    adapters = list(adapters)
+    n = len(adapters)
+    ups, downs = [], []
+    for i, (up, down, _s) in enumerate(adapters):
+        check_lora_pair(f"adapter {i}", tuple(base.shape), tuple(up.shape), tuple(down.shape))
+        ups.append(_dev_f32(up))
+        downs.append(_dev_f32(down))
+    arr = lambda t, vals: (t * max(n, 1))(*vals)
+    check(lib.af_op_lora_repack(DTYPES[dtype], ptr(base), rows, cin, cin_pad, ks, ldw, int(row_off), 1 if perm else 0, n,
+                                arr(C.c_void_p, [u.data_ptr() for u in ups]), arr(C.c_void_p, [d.data_ptr() for d in downs]),
+                                arr(C.c_int, [int(d.shape[0]) for d in downs]), arr(C.c_float, [float(a[2]) for a in adapters]),
+                                ptr(out), stream_ptr()), "af_op_lora_repack")
+    return out
 
 
 ATTN_LAYOUTS = {"dense": 0, "qkv": 1, "ctx": 2}     # AF_ATTN_* (include/adaface_hip.h)

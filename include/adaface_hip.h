@@ -88,6 +88,30 @@ const char* af_tensor_name(af_handle* h, int i);
 int af_tensor_loaded(af_handle* h, int i);
 int af_tensor_shape(af_handle* h, int i, int64_t* shape4 /* up to 4 dims, 0-terminated */);
 
+/* LoRA adapters (Hu et al., ICLR 2022; the kohya / diffusers file convention), opt-in: a conv / linear weight is loaded as
+ *   W + sum over adapters a ascending ( s_a * up_a @ down_a )
+ * formed in fp32 while the weight is repacked and rounded once to the storage type; no fp32 copy of the merged matrix exists
+ * (csrc/af_lora.hip: vector fp32 FMAs; per element acc_a = sum over r ascending up_a[o][r] * down_a[r][c * ks^2 + tap], then
+ * v = fmaf(s_a, acc_a, v) from v = W[o][c][tap]).  up_a = lora_up.weight [rows][r_a] (trailing dims 1), down_a = lora_down.weight
+ * flattened in its own order [r_a][cin][ks][ks]; fp32 DEVICE data, r_a in 1 .. AF_LORA_MAX_RANK, at most AF_LORA_MAX_ADAPTERS of
+ * them; s_a is the whole factor (scale * alpha / r, formed by the caller).
+ * af_load_tensor_lora: af_load_tensor (base_on_device = 0, fp32 host data) / af_load_tensor_device (1) of `name` with the
+ * adapters merged: the same validation, the same slot, the same derived state marked stale (LayerNorm-folded twins, fp8 twins,
+ * up-phase packs, a kept DeepCache feature; the hoisted context K / V are the caller's to drop: af_set_context).  Weight slots
+ * only: a bias, norm or table name is AF_ERR_INVALID.  The adapters' extents follow from the slot (rows, cin, ks) and r_a: the
+ * caller guarantees up_a holds rows * r_a and down_a r_a * cin * ks^2 elements.  n_adapters = 0 is the plain load.
+ * af_op_lora_repack: the kernel as an operator on caller-owned buffers: base_dev fp32 [rows][cin][ks][ks] -> dst_dev, elements
+ * of `dtype`, at [(row_off + perm(o)) * ldw + tap * cin_pad + c]; columns cin <= c < cin_pad are written as zeros, nothing else
+ * of dst_dev is touched (perm 1: the GEGLU row order of ff.net.0.proj, rows % 32 == 0).  n_adapters = 0: the bits of the plain
+ * repack. */
+enum { AF_LORA_MAX_ADAPTERS = 8, AF_LORA_MAX_RANK = 256 };
+int af_load_tensor_lora(af_handle* h, const char* name, const float* base, int base_on_device, int ndim, const int64_t* shape,
+                        int n_adapters, const float* const* up_dev, const float* const* down_dev, const int* ranks,
+                        const float* scales);
+int af_op_lora_repack(int dtype, const float* base_dev, int rows, int cin, int cin_pad, int ks, int ldw, int row_off, int perm,
+                      int n_adapters, const float* const* up_dev, const float* const* down_dev, const int* ranks,
+                      const float* scales, void* dst_dev, void* stream);
+
 /* Subject-token convolutional attention inside the UNet's cross-attention layers
  * (extra_info['use_conv_attn_kernel_size'] / ['placeholder2indices'], openaimodel.py:852-853,922-945;
  * CrossAttention.forward attention.py:208-216; replace_rows_by_conv_attn ldm/util.py:701-879).

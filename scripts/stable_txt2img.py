@@ -87,6 +87,11 @@ def parse_args(argv=None):
     ap.add_argument("--guidance_rescale", type=float, default=0.0, metavar="PHI",
                     help="guidance rescale, 0 .. 1 (0 = off): the combined prediction is scaled towards the conditional one's "
                          "standard deviation, the remedy for over-exposure at high guidance; every sampler")
+    ap.add_argument("--lora", type=str, action="append", default=None, metavar="PATH[:SCALE]",
+                    help="LoRA adapter file (.safetensors / .pt, kohya or native key names) merged into the U-Net's and the text "
+                         "tower's weights as they are repacked; repeatable, at most 8; SCALE defaults to 1; composes with every "
+                         "sampler, --dtype, --deep_cache, --tome, --freeu, --pag_scale and --gpus")
+    ap.add_argument("--lora_strict", action="store_true", help="--lora: refuse a file with keys that map onto no layer")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1,
@@ -142,6 +147,16 @@ def parse_args(argv=None):
         opt.pag_layers = layers
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
+    if opt.lora_strict and not opt.lora:
+        ap.error("--lora_strict: give --lora PATH[:SCALE] too")
+    if opt.lora:
+        from adaface_amd.lora import LORA_MAX_ADAPTERS, parse_lora_arg
+        if len(opt.lora) > LORA_MAX_ADAPTERS:
+            ap.error(f"--lora: at most {LORA_MAX_ADAPTERS} adapters")
+        opt.lora = [parse_lora_arg(spec) for spec in opt.lora]
+        for path, scale in opt.lora:
+            if scale != scale or scale in (float("inf"), float("-inf")):
+                ap.error(f"--lora {path}: the scale must be a finite number")
     return opt
 
 
@@ -206,6 +221,18 @@ def main():
                     p.copy_(torch.randn(p.shape, generator=g, device=device) * p[0].numel() ** -0.5)
         model.model.diffusion_model._mark_dirty()
         model.first_stage_model._mark_dirty()
+    if opt.lora:   # before any conditioning is made: a text-tower adapter changes the context; the same set on every rank
+        from adaface_amd.lora import load_lora_file, split_lora
+        unet = model.model.diffusion_model
+        adapters = []
+        for path, scale in opt.lora:
+            split = split_lora(load_lora_file(path), unet._layout_kwargs(), strict=opt.lora_strict)
+            if split["unused"] and rank == 0:
+                print(f"--lora {path}: {len(split['unused'])} keys map onto no layer and are ignored, e.g. {split['unused'][:3]}")
+            adapters.append((split, scale))
+        model.set_lora(adapters)
+        if rank == 0:
+            print(f"--lora: {len(adapters)} adapter(s) on {len(unet.lora_targets())} U-Net weights")
 
     B = opt.n_samples
     lo, hi = shard_range(B, rank, world)

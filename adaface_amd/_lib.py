@@ -163,6 +163,11 @@ _SIGS = [
     ("af_pag_site", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("af_pag_plan_query", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("af_unet_forward_pag", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_tgate_set", C.c_int, [_P, C.c_int]),
+    ("af_tgate_num_sites", C.c_int, [_P]),
+    ("af_tgate_state", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("af_tgate_read_site", C.c_int, [_P, C.c_int, _P, _P]),
+    ("af_op_tgate_add", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     ("af_guidance", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     ("af_guidance_plan_query", C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("af_flops_issued", C.c_double, [C.c_int]),
@@ -178,6 +183,8 @@ DEEPCACHE_MODES = {"refresh": 1, "reuse": 2}
 # ... and its `twin` argument, the form of the forward (AF_UNET_FORM_*); False / True keep their meaning
 UNET_FORMS = {False: 0, True: 1, "plain": 0, "twin": 1, "pag": 2}
 UNET_FORM_LEGS = {0: 1, 1: 2, 2: 3}
+# the mode of af_tgate_set (AF_TGATE_*)
+TGATE_MODES = {None: 0, "capture": 1, "replay": 2}
 
 
 def lib_path() -> Path:

@@ -71,7 +71,9 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        // the FreeU kernels, one class each (af_freeu.hip; scripts/freeu_mode.py)
        AF_K_FREEU_MEAN = 16, AF_K_FREEU_SUMS = 17, AF_K_FREEU_APPLY = 18, AF_K_FREEU_SMALL = 19,
        // the guidance kernels (af_guidance.hip; scripts/pag_mode.py): the chunk statistics, and every form that writes the output
-       AF_K_GUIDANCE_STATS = 20, AF_K_GUIDANCE_APPLY = 21, AF_K_COUNT = 22 };
+       AF_K_GUIDANCE_STATS = 20, AF_K_GUIDANCE_APPLY = 21,
+       // the T-GATE add kernel (af_tgate.hip; scripts/tgate_mode.py)
+       AF_K_TGATE_ADD = 22, AF_K_COUNT = 23 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)

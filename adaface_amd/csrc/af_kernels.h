@@ -137,6 +137,13 @@ template <typename T>
 int af_launch_tome_unmerge_add(const void* o, int ldo, const void* res, int ldr, const int* map, int B, int N, int Np, int C,
                                void* y, int ldy, float* ln_stats_out, int ln_parts, hipStream_t s);
 
+// T-GATE (af_tgate.hip), all three storage types.  t2 [L B][N][ld2] = t1 + src, src [L B][N][lds]; cache (optional)
+// [B][N][ldc] = mean over the L legs (1 or 2) of src; ln_stats_out (optional): LayerNorm partial sums [ln_parts][L B N][2] of t2's
+// rows.  t2 may be src.  16-byte accesses where every pointer and row stride allows them, element accesses otherwise.
+template <typename T>
+int af_launch_tgate_add(const void* t1, int ld1, const void* src, int lds, void* t2, int ld2, void* cache, int ldc, int L, int B,
+                        int N, int C, float* ln_stats_out, int ln_parts, hipStream_t s);
+
 // FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
 // types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
 enum AfFreeuKernel {

@@ -412,7 +412,28 @@ struct af_handle {
     size_t bytes = 0, need = 0;       // need: what the dry run of a cached forward asks for
     bool valid = false;
     int Bf = 0, H = 0, W = 0, twin = 0, depth = 0, fp8_on = 0, fp8_scope = 0;   // the refresh that wrote D (dtype is the handle's)
+    int tgate = 0;                    // ... and the T-GATE mode of that refresh
   } dc;
+
+  // T-GATE (af_tgate_set): per cross-attention site (the order of ca_list) the leg-mean A of attn2's output, storage
+  // dtype, [B][N][C] each, one after the other in a handle-owned buffer.  The layout follows from the block structure and
+  // (B, H, W) alone, so a DeepCache reuse step that runs only some sites finds theirs.
+  struct TGate {
+    int mode = 0;                     // AF_TGATE_*: what the next forwards do
+    void* buf = nullptr;
+    size_t bytes = 0;
+    bool valid = false;
+    int B = 0, H = 0, W = 0;          // the capture that wrote the cache
+  } tg;
+  // elements in front of site `site` for a capture of B samples at H x W latents (site = ca_list.size(): all of them)
+  size_t tgate_offset(int site, int B, int H, int W) const {
+    size_t off = 0;
+    for (int i = 0; i < site && i < (int)ca_list.size(); ++i) {
+      const XfmrW& x = xf[ca_list[i].first];
+      off += (size_t)B * (H / x.ds) * (W / x.ds) * (x.heads * x.dh);
+    }
+    return off;
+  }
 
   // runtime state
   Arena arena;
@@ -923,6 +944,9 @@ struct Runner {
   bool dry;
   Arena& A;
   int pag_B = 0;   // af_unet_forward_pag: samples of one leg (the batch is 3 pag_B); 0 in every other forward
+  // T-GATE (set by unet_forward_impl only; the VAE and CLIP runners never look): AF_TGATE_* of this forward, the legs a capture
+  // averages, and the latent's sides (the cache layout's key)
+  int tgate = 0, tg_legs = 1, tg_H = 0, tg_W = 0;
   Runner(af_handle* h_, hipStream_t s_) : h(h_), s(s_), dt(h_->dtype), dry(h_->arena.dry), A(h_->arena) {}
 
   Act alloc_act(int B, int H, int W, int C, int ld = 0) {
@@ -1475,6 +1499,35 @@ static int xfmr_cross_attention_conv(const XfmrCtx& X, const CtxKV& kv, int S, c
   return 0;
 }
 
+// T-GATE, one launch of af_tgate.hip at cross-attention site `site`.  capture: src = attn2's output o for the R.tg_legs
+// legs of the batch, A[site] = their mean into the handle's cache and t2 = t1 + o; replay: src = A[site], t2 = t1 + A[site].
+// Either way t2's LayerNorm partial sums go where out2's producer epilogue leaves them, so the FeedForward keeps its folded route.
+static int xfmr_tgate_add(const XfmrCtx& X, int site, const Act& t1, const Act& src, Act& t2, bool capture) {
+  Runner& R = X.R;
+  af_handle* h = R.h;
+  AF_TRY(R.check(t2));
+  if (R.dry) return 0;
+  const int L = capture ? R.tg_legs : 1;
+  const int Bl = X.B / L;
+  af_handle::TGate& tg = h->tg;
+  const size_t off = h->tgate_offset(site, Bl, R.tg_H, R.tg_W), end = h->tgate_offset(site + 1, Bl, R.tg_H, R.tg_W);
+  if (X.B % L || !tg.buf || end - off != (size_t)Bl * X.N * X.C || end * esize(R.dt) > tg.bytes) {
+    af_set_error_msg("T-GATE: site %d ([%d, %d, %d]) does not fit the cache", site, Bl, X.N, X.C);
+    return AF_ERR_STATE;
+  }
+  void* A = R.elem_ptr(tg.buf, (long)off);
+  float* st = X.ln_parts ? X.st_part : nullptr;
+  const int rc = capture ? AF_TYPED(R.dt, af_launch_tgate_add<Elem>(t1.p, t1.ld, src.p, src.ld, t2.p, t2.ld, A, X.C, L, Bl, X.N, X.C,
+                                                                    st, X.ln_parts, R.s))
+                         : AF_TYPED(R.dt, af_launch_tgate_add<Elem>(t1.p, t1.ld, A, X.C, t2.p, t2.ld, nullptr, 0, 1, Bl, X.N, X.C,
+                                                                    st, X.ln_parts, R.s));
+  return rc ? AF_ERR_INVALID : 0;
+}
+static int xfmr_tgate_replay(const XfmrCtx& X, int site, const Act& t1, Act& t2) {
+  t2 = X.R.alloc_act(X.B, X.H, X.W, X.C);
+  return xfmr_tgate_add(X, site, t1, t1, t2, false);
+}
+
 // x = x + attn2(norm2(x), context): t1 -> t2 (block d of the transformer; pre: t1's statistics cover the first half only)
 static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d, bool pre, const Act& t1, Act& n, Act& a,
                                 Act& t2) {
@@ -1482,6 +1535,7 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
   af_handle* h = R.h;
   const XfmrW& w = X.w;
   const int B = X.B, N = X.N, C = X.C;
+  if (R.tgate == AF_TGATE_REPLAY) return xfmr_tgate_replay(X, w.ca_slot + (int)d, t1, t2);
   const CtxKV& kv = h->ctx_kv[w.ca_slot + d];
   const int S = h->ctx_tokens;
   // (PAG's shared prefix runs legs 0-1 of the three-leg context: its first 2 B samples, which every per-sample layout below
@@ -1499,7 +1553,8 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
   // The fused single launch: bf16, C = 320 / 8 heads x 40, <= 80 keys, LayerNorm folded (the 64x64 level).  Decided from the
   // shape and the weights alone, so that the sizing pass and the run agree; the pack exists whenever the context was set for
   // such a layer
-  if (g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && X.ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
+  // (a T-GATE capture needs attn2's output by itself: never the fused launch)
+  if (!R.tgate && g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && X.ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
       t1.ld == C && t2.ld == C && af_xattn_fused_ok(B * N, N, C, w.heads, w.dh, S > 0 ? S : 77))
     return xfmr_cross_attention_fused(X, blk, pre, kv, S, t1, t2);
   if (!X.ln_parts) {
@@ -1517,6 +1572,11 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
     const Strided k = {kv.kv, 2 * C, (long)S * 2 * C}, v = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
     AF_TRY(R.attention(R.cols_of(q, 0, N), k, v, a, N, S, w.heads, w.dh, 0, -1, nullptr, 0, kv.vt,
                        h->ctx_Bf > 0 ? kv.vt_bytes / (size_t)h->ctx_Bf : 0));
+  }
+  if (R.tgate == AF_TGATE_CAPTURE) {
+    // to_out + bias without the residual into t2, then one launch: A[site] = leg mean, t2 = t1 + o in place (+ row sums)
+    AF_TRY(R.conv(blk.out2, a, t2));
+    return xfmr_tgate_add(X, w.ca_slot + (int)d, t1, t2, t2, true);
   }
   return R.conv(blk.out2, a, t2, X.producer().res(&t1));
 }
@@ -1755,6 +1815,7 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   R.A.off = 0;
   const int Bin = twin ? Bf / 2 : pag ? Bf / 3 : Bf;          // samples behind x_dev / t_dev
   R.pag_B = pag ? Bin : 0;
+  R.tgate = h->tg.mode; R.tg_legs = twin ? 2 : 1; R.tg_H = H; R.tg_W = W;
   const int pag_first = pag ? h->pag_first_block() : -1;       // (tap numbering; the entry point refused a forward without one)
   // legs the blocks in front of pag_first compute; pag_wide: all three legs are live (from the start, or since the copy)
   bool pag_wide = pag && !(g_af_knobs.pag_share_prefix && pag_first > 0);
@@ -2299,6 +2360,7 @@ void af_destroy(af_handle* h) {
   if (h->ctx_rowmap) hipFree(h->ctx_rowmap);
   if (h->ctx_cast) hipFree(h->ctx_cast);
   if (h->dc.buf) hipFree(h->dc.buf);
+  if (h->tg.buf) hipFree(h->tg.buf);
   if (h->arena.base) hipFree(h->arena.base);
   if (h->stage) hipFree(h->stage);
   delete h;
@@ -2408,6 +2470,7 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
   HIP_CHECK_RET(hipStreamSynchronize(0));
   s.loaded = true;
   h->dc.valid = false;
+  h->tg.valid = false;
   h->ln_fold_dirty = true;
   h->fp8_dirty = true;
   h->up4_dirty = true;
@@ -2582,6 +2645,24 @@ static int ensure_deepcache(af_handle* h, hipStream_t s) {
   return 0;
 }
 
+// the T-GATE cache for a capture of B samples at H x W latents; growing it drops what it held
+static int ensure_tgate(af_handle* h, hipStream_t s, int B, int H, int W) {
+  const size_t need = h->tgate_offset((int)h->ca_list.size(), B, H, W) * esize(h->dtype) + 4096;   // (slack: as ensure_deepcache)
+  if (need <= h->tg.bytes) return 0;
+  HIP_CHECK_RET(hipStreamSynchronize(s));
+  if (h->tg.buf) hipFree(h->tg.buf);
+  h->tg.buf = nullptr;
+  h->tg.bytes = 0;
+  h->tg.valid = false;
+  if (hipMalloc(&h->tg.buf, need) != hipSuccess) {
+    h->tg.buf = nullptr;
+    af_set_error_msg("hipMalloc of the %zu-byte T-GATE cache failed", need);
+    return AF_ERR_HIP;
+  }
+  h->tg.bytes = need;
+  return 0;
+}
+
 static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                               void* stream, int form, int dc_mode = 0, int dc_depth = 0) {
   if (!h || !x_dev || !t_dev || !eps_dev) { af_set_error_msg("af_unet_forward: null argument"); return AF_ERR_INVALID; }
@@ -2599,7 +2680,22 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
         return AF_ERR_STATE;
       }
   }
-  if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
+  af_handle::TGate& tg = h->tg;
+  if (tg.mode) {   // T-GATE (af_tgate_set): everything it refuses, before anything is enqueued
+    const bool replay = tg.mode == AF_TGATE_REPLAY;
+    const char* who = replay ? "replay" : "capture";
+    if (pag) { af_set_error_msg("T-GATE %s: the PAG form is not supported", who); return AF_ERR_INVALID; }
+    if (h->fp8_on) { af_set_error_msg("T-GATE %s: the fp8 mode is not supported", who); return AF_ERR_STATE; }
+    if (replay && twin) { af_set_error_msg("T-GATE replay runs one leg: the plain form only"); return AF_ERR_INVALID; }
+    if (!replay && dc_mode == AF_DEEPCACHE_REUSE) { af_set_error_msg("T-GATE capture needs every site: not on a DeepCache reuse step"); return AF_ERR_INVALID; }
+    if (replay && !(tg.valid && tg.buf)) { af_set_error_msg("T-GATE replay: no valid cache (a capture forward must come first)"); return AF_ERR_STATE; }
+    if (replay && (tg.B != Bf || tg.H != H || tg.W != W)) {
+      af_set_error_msg("T-GATE replay: (B %d, %dx%d) but the capture was (B %d, %dx%d)", Bf, H, W, tg.B, tg.H, tg.W);
+      return AF_ERR_STATE;
+    }
+    if (replay) AF_TRY(check_loaded(h, "model.diffusion_model."));   // (af_set_context, which a replay does not need, checks this otherwise)
+  }
+  if (tg.mode != AF_TGATE_REPLAY && (!h->ctx_set || h->ctx_Bf != Bf)) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
   const int down = 1 << (h->cfg.n_channel_mult - 1);
   if (H % down || W % down) { af_set_error_msg("af_unet_forward: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
   if (h->freeu_version)   // (before anything is enqueued: the closed form of the Fourier filter needs two rows and two columns)
@@ -2618,7 +2714,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     }
     if (dc_mode == AF_DEEPCACHE_REUSE &&
         !(dc.valid && dc.buf && dc.Bf == Bf && dc.H == H && dc.W == W && dc.twin == form && dc.depth == dc_depth &&
-          dc.fp8_on == (int)h->fp8_on && dc.fp8_scope == h->fp8_scope)) {
+          dc.fp8_on == (int)h->fp8_on && dc.fp8_scope == h->fp8_scope && dc.tgate == tg.mode)) {
       af_set_error_msg("af_unet_forward_cached: no kept feature for (Bf %d, %dx%d, twin %d, depth %d) -- a refresh with exactly "
                        "these arguments must come first", Bf, H, W, form, dc_depth);
       return AF_ERR_STATE;
@@ -2638,11 +2734,20 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     af_set_error_msg("af_unet_forward_cached: the kept feature does not fit this forward");   // (cannot happen for a valid entry)
     return AF_ERR_STATE;
   }
-  if (const int rc = run()) { if (dc_mode) dc.valid = false; return rc; }
+  if (tg.mode == AF_TGATE_CAPTURE) {
+    tg.valid = false;                       // (until this capture has been enqueued completely)
+    AF_TRY(ensure_tgate(h, s, twin ? Bf / 2 : Bf, H, W));
+  }
+  if (const int rc = run()) { if (dc_mode) dc.valid = false; if (tg.mode == AF_TGATE_CAPTURE) tg.valid = false; return rc; }
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = true;
     dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = form; dc.depth = dc_depth;
     dc.fp8_on = (int)h->fp8_on; dc.fp8_scope = h->fp8_scope;
+    dc.tgate = tg.mode;
+  }
+  if (tg.mode == AF_TGATE_CAPTURE) {
+    tg.valid = true;
+    tg.B = twin ? Bf / 2 : Bf; tg.H = H; tg.W = W;
   }
   return 0;
 }
@@ -2811,6 +2916,33 @@ int af_pag_plan_query(af_handle* h, int depth, int out[3]) {
   out[0] = h->pag_first_block();
   out[1] = h->pag_two_leg_blocks(0);
   out[2] = depth > 0 ? h->pag_two_leg_blocks(depth) : 0;
+  return AF_OK;
+}
+
+int af_tgate_set(af_handle* h, int mode) {
+  if (!h) { af_set_error_msg("af_tgate_set: null handle"); return AF_ERR_INVALID; }
+  if (mode != AF_TGATE_OFF && mode != AF_TGATE_CAPTURE && mode != AF_TGATE_REPLAY) { af_set_error_msg("af_tgate_set: mode %d (0 off, 1 capture, 2 replay)", mode); return AF_ERR_INVALID; }
+  if (mode && !h->cfg.build_unet) { af_set_error_msg("af_tgate_set: handle has no UNet"); return AF_ERR_STATE; }
+  h->tg.mode = mode;
+  return AF_OK;
+}
+int af_tgate_num_sites(af_handle* h) { return (h && h->cfg.build_unet) ? (int)h->ca_list.size() : 0; }
+int af_tgate_state(af_handle* h, int out[4]) {
+  if (!h || !out) { af_set_error_msg("af_tgate_state: null argument"); return AF_ERR_INVALID; }
+  const bool v = h->tg.valid && h->tg.buf;
+  out[0] = v ? 1 : 0; out[1] = v ? h->tg.B : 0; out[2] = v ? h->tg.H : 0; out[3] = v ? h->tg.W : 0;
+  return AF_OK;
+}
+int af_tgate_read_site(af_handle* h, int site, float* out_dev, void* stream) {
+  if (!h || !out_dev) { af_set_error_msg("af_tgate_read_site: null argument"); return AF_ERR_INVALID; }
+  if (site < 0 || site >= af_tgate_num_sites(h)) { af_set_error_msg("af_tgate_read_site: site %d out of range (%d sites)", site, af_tgate_num_sites(h)); return AF_ERR_INVALID; }
+  const af_handle::TGate& tg = h->tg;
+  if (!tg.valid || !tg.buf) { af_set_error_msg("af_tgate_read_site: no valid cache"); return AF_ERR_STATE; }
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  const size_t off = h->tgate_offset(site, tg.B, tg.H, tg.W), end = h->tgate_offset(site + 1, tg.B, tg.H, tg.W);
+  if (end * esize(h->dtype) > tg.bytes) { af_set_error_msg("af_tgate_read_site: the cache does not hold site %d", site); return AF_ERR_STATE; }
+  const void* src = reinterpret_cast<const char*>(tg.buf) + off * esize(h->dtype);
+  AF_TRY(AF_TYPED(h->dtype, af_launch_cast_to_f32<Elem>(src, out_dev, (long)(end - off), reinterpret_cast<hipStream_t>(stream))));
   return AF_OK;
 }
 

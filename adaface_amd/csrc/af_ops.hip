@@ -1045,6 +1045,18 @@ int af_op_lora_repack(int dtype, const float* base_dev, int rows, int cin, int c
   return AF_OK;
 }
 
+// The T-GATE add (af_tgate.hip) on caller-owned buffers of `dtype` elements, rows and strides as given
+int af_op_tgate_add(int dtype, const void* t1_dev, const void* src_dev, void* t2_dev, void* cache_dev, float* stats_dev, int parts,
+                    int L, int B, int N, int C, int ld_t1, int ld_src, int ld_t2, int ld_cache, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_op_tgate_add: storage type %d", dtype); return AF_ERR_INVALID; }
+  if (B <= 0) { af_set_error_msg("af_op_tgate_add: bad argument"); return AF_ERR_INVALID; }
+  if (AF_TYPED(dtype, af_launch_tgate_add<Elem>(t1_dev, ld_t1, src_dev, ld_src, t2_dev, ld_t2, cache_dev, ld_cache, L, B, N, C,
+                                                stats_dev, parts, s)))
+    return AF_ERR_INVALID;
+  return AF_OK;
+}
+
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;

@@ -281,25 +281,68 @@ class Engine:
         check(self._lib.af_set_conv_attn(self._h, int(ks), n, bi, ti), "af_set_conv_attn")
         self._ctx_key = None
 
-    def unet_forward(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    @contextlib.contextmanager
+    def _tgate(self, tgate):
+        """af_tgate_set around one forward: the mode is OFF again afterwards, also on error.  None costs nothing."""
+        if tgate not in _lib.TGATE_MODES:
+            raise ValueError(f"tgate {tgate!r} (None, \"capture\" or \"replay\")")
+        if tgate is None:
+            yield
+            return
+        check(self._lib.af_tgate_set(self._h, _lib.TGATE_MODES[tgate]), "af_tgate_set")
+        try:
+            yield
+        finally:
+            self._lib.af_tgate_set(self._h, 0)
+
+    def unet_forward(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None, tgate=None) -> torch.Tensor:
+        """tgate (T-GATE): "capture" = this forward, which also keeps the cross-attention outputs per site; "replay" = every
+        cross-attention replaced by the kept output (no context needed); None = off."""
         x = x.contiguous().float()
         t = t.contiguous().long()
         Bf, _, H, W = x.shape
         if out is None:
             out = torch.empty(Bf, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
-        check(self._lib.af_unet_forward(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, stream_ptr()), "af_unet_forward")
+        with self._tgate(tgate):
+            check(self._lib.af_unet_forward(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, stream_ptr()), "af_unet_forward")
         return out
 
-    def unet_forward_twin(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def unet_forward_twin(self, x: torch.Tensor, t: torch.Tensor, out: Optional[torch.Tensor] = None, tgate=None) -> torch.Tensor:
         """af_unet_forward_twin: the UNet on the CFG batch [x; x], [t; t] (context set for 2 * len(x) samples, cond first)
-        without materialising the concatenation; the context-independent prefix runs once.  Returns eps [2B, C, H, W]."""
+        without materialising the concatenation; the context-independent prefix runs once.  Returns eps [2B, C, H, W].
+        tgate="capture": the kept cross-attention outputs are the means over the two legs."""
         x = x.contiguous().float()
         t = t.contiguous().long()
         B, _, H, W = x.shape
         if out is None:
             out = torch.empty(2 * B, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
-        check(self._lib.af_unet_forward_twin(self._h, ptr(x), ptr(t), ptr(out), 2 * B, H, W, stream_ptr()),
-              "af_unet_forward_twin")
+        with self._tgate(tgate):
+            check(self._lib.af_unet_forward_twin(self._h, ptr(x), ptr(t), ptr(out), 2 * B, H, W, stream_ptr()),
+                  "af_unet_forward_twin")
+        return out
+
+    def tgate_num_sites(self) -> int:
+        """Cross-attention sites of the U-Net (forward order, the numbering of pag_sites)."""
+        return int(self._lib.af_tgate_num_sites(self._h))
+
+    def tgate_state(self) -> dict:
+        """af_tgate_state: {"valid", "B", "H", "W"} of the T-GATE cache (the capture that wrote it)."""
+        out = (C.c_int * 4)()
+        check(self._lib.af_tgate_state(self._h, out), "af_tgate_state")
+        return {"valid": bool(out[0]), "B": int(out[1]), "H": int(out[2]), "W": int(out[3])}
+
+    def tgate_site(self, i: int) -> torch.Tensor:
+        """af_tgate_read_site: the kept cross-attention output of site i as fp32 [B, N, C].  Tests and scripts."""
+        st = self.tgate_state()
+        if not st["valid"]:
+            raise _lib.AfError("tgate_site: no valid cache (a capture forward must come first)")
+        if not 0 <= int(i) < self.tgate_num_sites():
+            raise ValueError(f"tgate_site: site {i} outside 0 .. {self.tgate_num_sites() - 1}")
+        ds = self.pag_sites()[int(i)][2]
+        mc, mult = self.unet_cfg["model_channels"], list(self.unet_cfg["channel_mult"])
+        lvl = ds.bit_length() - 1
+        out = torch.empty(st["B"], (st["H"] // ds) * (st["W"] // ds), mc * mult[lvl], device=self.device, dtype=torch.float32)
+        check(self._lib.af_tgate_read_site(self._h, int(i), ptr(out), stream_ptr()), "af_tgate_read_site")
         return out
 
     def set_pag(self, sites=()):
@@ -339,13 +382,14 @@ class Engine:
         return out
 
     def unet_forward_cached(self, x: torch.Tensor, t: torch.Tensor, *, depth: int, mode: str, twin=False,
-                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            out: Optional[torch.Tensor] = None, tgate=None) -> torch.Tensor:
         """af_unet_forward_cached (DeepCache).  mode "refresh": unet_forward / unet_forward_twin bit for bit, which also keeps
         the output of output_blocks[n_out - depth - 1] in a buffer the handle owns.  mode "reuse": only input_blocks[:depth]
         and output_blocks[n_out - depth:] run, on that kept feature; AfError when no refresh with the same batch, latent size,
         twin and depth came before.  twin: x, t hold B samples and eps 2 B, as unet_forward_twin; twin="pag": eps 3 B, as
         unet_forward_pag (the form is part of the kept feature's key).  set_context / set_conv_attn
-        do not drop the kept feature: call unet_cache_invalidate when the conditioning changes."""
+        do not drop the kept feature: call unet_cache_invalidate when the conditioning changes.  tgate: as unet_forward
+        ("capture" with a refresh only; "replay" on the plain form); the mode is part of the kept feature's key."""
         if mode not in _lib.DEEPCACHE_MODES:
             raise ValueError(f"unet_forward_cached: mode {mode!r} (\"refresh\" or \"reuse\")")
         x = x.contiguous().float()
@@ -357,8 +401,9 @@ class Engine:
         Bf = _lib.UNET_FORM_LEGS[form] * B
         if out is None:
             out = torch.empty(Bf, self.unet_cfg["out_channels"], H, W, device=x.device, dtype=torch.float32)
-        check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, form, int(depth),
-                                               _lib.DEEPCACHE_MODES[mode], stream_ptr()), "af_unet_forward_cached")
+        with self._tgate(tgate):
+            check(self._lib.af_unet_forward_cached(self._h, ptr(x), ptr(t), ptr(out), Bf, H, W, form, int(depth),
+                                                   _lib.DEEPCACHE_MODES[mode], stream_ptr()), "af_unet_forward_cached")
         return out
 
     def set_tome(self, ratio: float, max_downsample: int = 1):

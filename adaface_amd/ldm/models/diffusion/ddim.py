@@ -20,6 +20,7 @@ import torch
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
+from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
                                                            make_ddim_timesteps, noise_like)
 from adaface_amd.noise import STREAM_QSAMPLE, STREAM_STEP, STREAM_XT
@@ -39,6 +40,7 @@ class DDIMSampler(object):
         self.schedule = schedule
         self._twin_cache = None
         self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
+        self.tgate_log = []           # None / "capture" / "replay" per step of the last run
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -79,14 +81,16 @@ class DDIMSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
                unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2,
-               pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
+               pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
         """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
         adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step).
         deep_cache_interval: None or 1 = off; N >= 2 = the full U-Net on loop indices i % N == 0 only, or an explicit
         sequence of those indices (with 0); between them the outermost deep_cache_depth blocks run on the kept deep feature.
         pag_scale / pag_adaptive_scale: perturbed-attention guidance on the layers given to model.set_pag, every step a
         three-leg forward; guidance_rescale in [0, 1]: the combined prediction rescaled towards the conditional one's standard
-        deviation (guidance.py)."""
+        deviation (guidance.py).
+        tgate_step: None or 0 = off; g in 1 .. S - 1 = T-GATE (tgate.py): loop index g - 1 also keeps the cross-attention
+        outputs, from loop index g on the U-Net runs on one leg with them and without guidance."""
         _check_noise_source(noise_source, noise_dropout)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -101,7 +105,7 @@ class DDIMSampler(object):
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
                                   noise_source=noise_source, deep_cache_interval=deep_cache_interval,
                                   deep_cache_depth=deep_cache_depth, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
-                                  guidance_rescale=guidance_rescale, **kwargs)
+                                  guidance_rescale=guidance_rescale, tgate_step=tgate_step, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
@@ -109,13 +113,14 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None,
                       deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
-                      **kwargs):
+                      tgate_step=None, **kwargs):
         """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
         code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
         step = the loop index."""
         _check_noise_source(noise_source, noise_dropout)
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
+        refuse_guided(tgate_step, pag_scale, guidance_rescale)
         self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
         self._guided_twin_cache = None
         device = self.model.betas.device
@@ -147,6 +152,8 @@ class DDIMSampler(object):
         self._twin_cache = None
         dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
         self.deep_cache_log = dc_run.log
+        tg_run = TGateRun(self.model, total_steps, tgate_step)
+        self.tgate_log = tg_run.log
 
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
@@ -165,7 +172,8 @@ class DDIMSampler(object):
                                               unconditional_conditioning=unconditional_conditioning,
                                               noise_source=noise_source, noise_step=i, deep_cache_run=dc_run,
                                               pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
-                                              guidance_rescale=guidance_rescale, timestep=int(step))
+                                              guidance_rescale=guidance_rescale, timestep=int(step),
+                                              tgate_run=tg_run)
             if callback:
                 callback(i)
             if img_callback:
@@ -195,18 +203,30 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0,
-                      deep_cache_run=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timestep=None):
+                      deep_cache_run=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timestep=None,
+                      tgate_run=None):
         """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
         torch.randn; repeat_noise then gives every sample the first sample's id.  deep_cache_run: the loop's DeepCacheRun
         (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse).
         pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes the model call and the combine, and the update
-        below takes its result as a plain eps; timestep: t as a host integer (None: read from t)."""
+        below takes its result as a plain eps; timestep: t as a host integer (None: read from t).  tgate_run: the loop's
+        TGateRun (tgate.py) -- it names this step's phase from noise_step; a replay step is a single-leg call."""
         _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
         single = unconditional_conditioning is None or guidance_scale == 1.
         guided = G.is_on(pag_scale, guidance_rescale)
-        dc = None if deep_cache_run is None or guided else deep_cache_run.step(noise_step, (not single, b, x.shape[2], x.shape[3]))
-        if guided:
+        phase = None
+        form = (not single, b, x.shape[2], x.shape[3])
+        if tgate_run is not None:
+            if guided and tgate_run.active:
+                refuse_guided(1, pag_scale, guidance_rescale)
+            phase = tgate_run.step(noise_step)
+            single = single or phase == "replay"
+            form = tgate_run.form((not single, b, x.shape[2], x.shape[3]), phase)
+        dc = None if deep_cache_run is None or guided else deep_cache_run.step(noise_step, form)
+        if phase is not None:
+            e_c, e_u = gated_eps(self, x, t, c, unconditional_conditioning, single, phase, dc)
+        elif guided:
             e_c = G.guided_eps(self, x, t, c, unconditional_conditioning, guidance_scale,
                                int(t[0]) if timestep is None else timestep, pag_scale, pag_adaptive_scale, guidance_rescale,
                                deep_cache_run, noise_step)

@@ -32,9 +32,14 @@ class DiffusionWrapper(nn.Module):
             raise NotImplementedError(f"conditioning_key '{conditioning_key}' is not used by SD-v1 txt2img")
 
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False, deep_cache=None,
-                cfg_pag: bool = False):
+                cfg_pag: bool = False, tgate=None):
         if self.conditioning_key is None:
             raise NotImplementedError("unconditional UNet is not on the path")
+        if tgate is not None:         # T-GATE capture / replay step (UNetModel.forward); None: the calls below, unchanged
+            c0 = c_crossattn[0]
+            c_static_emb, c_in, extra_info = c0 if isinstance(c0, tuple) else (c0, None, None)
+            return self.diffusion_model(x, t, context=c_static_emb, context_in=c_in, extra_info=extra_info,
+                                        cfg_twin=bool(cfg_twin), cfg_pag=bool(cfg_pag), deep_cache=deep_cache, tgate=tgate)
         c0 = c_crossattn[0]
         if isinstance(c0, tuple):
             c_static_emb, c_in, extra_info = c0
@@ -109,6 +114,7 @@ class DDPM(nn.Module):
 
 class LatentDiffusion(DDPM):
     """ddpm.py:712-5396, inference subset."""
+    supports_tgate = True         # apply_model / apply_model_cfg_twin take tgate= (samplers: tgate.py)
     supports_deep_cache = True    # apply_model / apply_model_cfg_twin take deep_cache= (samplers: deep_cache.py)
 
     def __init__(self, first_stage_config, cond_stage_config=None, personalization_config=None,
@@ -201,20 +207,24 @@ class LatentDiffusion(DDPM):
         return emb.unsqueeze(1).expand(B, n_layers, T, D).reshape(B * n_layers, T, D).contiguous()
 
     # ---- denoiser ----------------------------------------------------------------------------
-    def apply_model(self, x_noisy, t, cond, return_ids=False, deep_cache=None):
+    def apply_model(self, x_noisy, t, cond, return_ids=False, deep_cache=None, tgate=None):
         """ddpm.py:2192-2297 (the split_input_params patch mode is never active: SURVEY.md §8a a6).
-        deep_cache (not in the reference): None, ("refresh", k) or ("reuse", k), see UNetModel.forward."""
+        deep_cache (not in the reference): None, ("refresh", k) or ("reuse", k), see UNetModel.forward.
+        tgate (not in the reference): None, "capture" or "replay" (T-GATE, tgate.py), see UNetModel.forward."""
         if not isinstance(cond, dict):
             if not isinstance(cond, list):
                 cond = [cond]
             key = 'c_concat' if self.model.conditioning_key == 'concat' else 'c_crossattn'
             cond = {key: cond}
-        x_recon = self.model(x_noisy, t, **cond) if deep_cache is None else self.model(x_noisy, t, deep_cache=deep_cache, **cond)
+        if tgate is not None:
+            x_recon = self.model(x_noisy, t, deep_cache=deep_cache, tgate=tgate, **cond)
+        else:
+            x_recon = self.model(x_noisy, t, **cond) if deep_cache is None else self.model(x_noisy, t, deep_cache=deep_cache, **cond)
         if isinstance(x_recon, tuple) and not return_ids:
             return x_recon[0]
         return x_recon
 
-    def apply_model_cfg_twin(self, x_noisy, t, cond_twin, deep_cache=None):
+    def apply_model_cfg_twin(self, x_noisy, t, cond_twin, deep_cache=None, tgate=None):
         """apply_model(torch.cat([x] * 2), torch.cat([t] * 2), cond_twin) -- the classifier-free-guidance call of
         p_sample_ddim / p_sample_plms (ddim.py:236-247) -- without the concatenation: `cond_twin` is the condition of the
         2B samples (cond first), x_noisy / t those of one half.  Returns eps of the 2B samples.  Not a reference method: the
@@ -224,6 +234,10 @@ class LatentDiffusion(DDPM):
             if not isinstance(cond, list):
                 cond = [cond]
             cond = {'c_crossattn': cond}
+        if tgate is not None:         # (T-GATE capture on the twin form: the kept outputs are the means over the two legs)
+            if 'c_crossattn' not in cond:
+                raise NotImplementedError("apply_model_cfg_twin: T-GATE needs a cross-attention condition")
+            return self.model(x_noisy, t, cfg_twin=True, deep_cache=deep_cache, tgate=tgate, **cond)
         if 'c_crossattn' not in cond:
             return self.apply_model(torch.cat([x_noisy] * 2), torch.cat([t] * 2), cond_twin)
         if deep_cache is not None:

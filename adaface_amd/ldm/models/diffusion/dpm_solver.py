@@ -26,6 +26,7 @@ import torch
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
+from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
 from adaface_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
 from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
 
@@ -112,6 +113,7 @@ class DPMSolverSampler(object):
         self.ddpm_num_timesteps = model.num_timesteps
         self._twin_cache = None
         self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
+        self.tgate_log = []           # None / "capture" / "replay" per step of the last run
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -123,14 +125,14 @@ class DPMSolverSampler(object):
                x_T=None, verbose=True, log_every_t=100, guidance_scale=1., unconditional_guidance_scale=None,
                unconditional_conditioning=None, order=2, lower_order_final=True, skip_type="time_uniform", timesteps=None,
                algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
-               pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
+               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
         """(img, intermediates) as DDIMSampler.sample.  guidance_scale: a scalar or [max, min] (annealed as ddim_sampling
         does); unconditional_guidance_scale: the PLMS / CompVis spelling of the scalar.  timesteps: an explicit strictly
         increasing integer array, overriding S and skip_type.  algorithm: "dpmsolver++" (deterministic) or "sde-dpmsolver++"
         (one N(0, 1) draw per step, scaled by temperature=); noise_source: a PhiloxNoise for the SDE draws, the inpainting
         blend's q_sample noise and, with x_T None, the start code.  deep_cache_interval / deep_cache_depth: DeepCache, as
         DDIMSampler.sample (deep_cache.py).  pag_scale / pag_adaptive_scale / guidance_rescale: perturbed-attention guidance
-        and guidance rescale, as DDIMSampler.sample (guidance.py)."""
+        and guidance rescale, as DDIMSampler.sample (guidance.py).  tgate_step: T-GATE, as DDIMSampler.sample (tgate.py)."""
         if algorithm not in ALGORITHMS:
             raise NotImplementedError(f'There is no DPM-Solver algorithm called "{algorithm}" ({", ".join(ALGORITHMS)})')
         sde = algorithm == "sde-dpmsolver++"
@@ -162,7 +164,8 @@ class DPMSolverSampler(object):
                                         unconditional_conditioning=unconditional_conditioning, noise_source=noise_source,
                                         temperature=temperature, deep_cache_interval=deep_cache_interval,
                                         deep_cache_depth=deep_cache_depth, pag_scale=pag_scale,
-                                        pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
+                                        pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
+                                        tgate_step=tgate_step)
 
     def _twin_condition(self, c, uc):
         """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
@@ -182,10 +185,11 @@ class DPMSolverSampler(object):
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
                             log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.,
                             deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0.,
-                            guidance_rescale=0.):
+                            guidance_rescale=0., tgate_step=None):
         """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update."""
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
+        refuse_guided(tgate_step, pag_scale, guidance_rescale)
         guided = G.is_on(pag_scale, guidance_rescale)
         self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
         self._guided_twin_cache = None
@@ -208,6 +212,8 @@ class DPMSolverSampler(object):
         self._twin_cache = None
         dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
         self.deep_cache_log = dc_run.log
+        tg_run = TGateRun(self.model, total_steps, tgate_step)
+        self.tgate_log = tg_run.log
         for i, row in enumerate(schedule):
             index = total_steps - i - 1
             guide_scale = float(row[COL_G])
@@ -220,9 +226,13 @@ class DPMSolverSampler(object):
                     img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
                 img = img_orig * mask + (1. - mask) * img
             single = unconditional_conditioning is None or guide_scale == 1.
+            phase = tg_run.step(i)
+            single = single or phase == "replay"      # (T-GATE: one leg from the gate on)
             # None: the full forward, as without DeepCache
-            dc = None if guided else dc_run.step(i, (not single, b, img.shape[2], img.shape[3]))
-            if guided:      # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
+            dc = None if guided else dc_run.step(i, tg_run.form((not single, b, img.shape[2], img.shape[3]), phase))
+            if phase is not None:
+                e_c, e_u = gated_eps(self, img, ts, cond, unconditional_conditioning, single, phase, dc)
+            elif guided:      # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
                 e_c = G.guided_eps(self, img, ts, cond, unconditional_conditioning, guide_scale, int(row[COL_T]), pag_scale,
                                    pag_adaptive_scale, guidance_rescale, dc_run, i)
                 e_u = None

@@ -50,13 +50,16 @@ class PLMSSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
-               pag_adaptive_scale=0., guidance_rescale=0., **kwargs):
+               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
         """plms.py:71-117.  pag_scale / pag_adaptive_scale / guidance_rescale (not in the reference): perturbed-attention
         guidance and guidance rescale on every model call of the run, see guidance.py."""
         from adaface_amd.ldm.models.diffusion.deep_cache import is_off
         if not is_off(deep_cache_interval):
             raise NotImplementedError("deep_cache_interval with the PLMS sampler: it calls the model twice in its first step and "
                                       "extrapolates from an eps history (use DDIMSampler or DPMSolverSampler)")
+        if tgate_step not in (None, 0) or isinstance(tgate_step, bool):
+            raise NotImplementedError("tgate_step with the PLMS sampler: its eps history mixes predictions from before and after "
+                                      "the gate, which T-GATE does not define (use DDIMSampler or DPMSolverSampler)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         return self.plms_sampling(conditioning, (batch_size, C, H, W), callback=callback, img_callback=img_callback,

@@ -194,7 +194,7 @@ class UNetModel(HipModule):
 
     @torch.no_grad()
     def forward(self, x, timesteps=None, context=None, y=None, context_in=None, extra_info=None, cfg_twin=False, deep_cache=None,
-                cfg_pag=False, **kwargs):
+                cfg_pag=False, tgate=None, **kwargs):
         """x [B,C,H,W], timesteps [B], context [B*16,T,D] (layerwise) or [B,T,D]; returns eps [B,C,H,W] fp32.
         Mirrors openaimodel.py:827-1052 for inference: `extra_info` keys read at :849-859.
         cfg_twin (not in the reference; used by this package's samplers): x / timesteps are ONE half of the
@@ -207,9 +207,30 @@ class UNetModel(HipModule):
         cfg_pag (not in the reference; perturbed-attention guidance, set_pag): x / timesteps are ONE leg, the context is the
         twin condition of 2B samples (cond first), exactly what cfg_twin takes; returns eps for 3B samples, legs (cond, uncond,
         perturbed).  The third leg's context is the first B samples' AFTER the compel-cfg weighting, with their layerwise
-        slices, and the conv-attention rows of the samples < B are repeated for the samples + 2B."""
+        slices, and the conv-attention rows of the samples < B are repeated for the samples + 2B.
+        tgate (not in the reference; T-GATE, set by this package's samplers, tgate.py): None = off; "capture" = this forward
+        (plain or cfg_twin), which also keeps every cross-attention output, averaged over the legs; "replay" = the plain
+        forward with every cross-attention replaced by what the capture kept -- the context is neither set nor read."""
         if y is not None:
             raise NotImplementedError("class-conditional UNet (num_classes) is not on the path")
+        if tgate not in (None, "capture", "replay"):
+            raise ValueError(f"UNetModel.forward: tgate {tgate!r} (None, \"capture\" or \"replay\")")
+        if tgate is not None and cfg_pag:
+            raise NotImplementedError("UNetModel.forward: T-GATE with the PAG form (the third leg has no cached counterpart)")
+        if tgate == "replay":
+            if cfg_twin:
+                raise ValueError("UNetModel.forward: a T-GATE replay runs one leg (no cfg_twin)")
+            if timesteps is None:
+                raise ValueError("UNetModel.forward needs timesteps")
+            eng = self.engine(x.device)
+            if deep_cache is None:
+                out = eng.unet_forward(x, timesteps.to(x.device), tgate="replay")
+            else:
+                mode, depth = deep_cache
+                out = eng.unet_forward_cached(x, timesteps.to(x.device), depth=int(depth), mode=mode, twin=False, tgate="replay")
+            if extra_info is not None:
+                extra_info["ca_layers_activations"] = {k: {} for k in ("outfeat", "attn", "attnscore", "q")}
+            return out.type(x.dtype) if x.dtype != torch.float32 else out
         if timesteps is None or context is None:
             raise ValueError("UNetModel.forward needs timesteps and context")
         info = extra_info if extra_info is not None else {}
@@ -250,13 +271,14 @@ class UNetModel(HipModule):
             eng.set_context(ctx, B, layerwise)
             object.__setattr__(self, "_ctx_key", key if cache_ok else None)
             object.__setattr__(self, "_ctx_ref", (context, given))
+        tg = {} if tgate is None else {"tgate": tgate}
         if deep_cache is None:
             fwd = eng.unet_forward_pag if cfg_pag else eng.unet_forward_twin if cfg_twin else eng.unet_forward
-            out = fwd(x, timesteps.to(x.device))
+            out = fwd(x, timesteps.to(x.device), **tg)
         else:
             mode, depth = deep_cache
             out = eng.unet_forward_cached(x, timesteps.to(x.device), depth=int(depth), mode=mode,
-                                          twin="pag" if cfg_pag else bool(cfg_twin))
+                                          twin="pag" if cfg_pag else bool(cfg_twin), **tg)
         if extra_info is not None:
             # the reference writes the (here empty) distillation capture into the caller's dict (:1031-1035)
             extra_info["ca_layers_activations"] = {k: {} for k in ("outfeat", "attn", "attnscore", "q")}

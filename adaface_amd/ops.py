@@ -307,6 +307,47 @@ def freeu(h, skip, version, b, s, dtype="bf16"):
 STORAGE_TORCH = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
 
 
+def _rows_ld(name, t, shape):
+    """Row stride (elements) of a [B', N, C] device view whose rows are C contiguous elements ld apart, samples N * ld apart."""
+    if not t.is_cuda or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"tgate_add: {name} must be a device tensor of shape {tuple(shape)}, got {tuple(t.shape)}")
+    ld = t.stride(1) if t.shape[1] > 1 else (t.stride(0) // max(t.shape[1], 1) if t.shape[0] > 1 else t.shape[2])
+    if t.stride(2) != 1 or ld < t.shape[2] or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld):
+        raise ValueError(f"tgate_add: {name} has strides {t.stride()}: rows must be contiguous and evenly spaced")
+    return int(ld)
+
+
+def tgate_add(t1, src, legs=1, cache=False, stats_parts=0, out=None, cache_out=None):
+    """The T-GATE add (af_op_tgate_add) on the caller's own buffers, all of one storage dtype (bf16, fp16 or f32), nothing
+    converted or copied: t2 = t1 + src for [legs * B, N, C] views (rows of C contiguous elements, any row stride and alignment),
+    fp32 add, rounded once; cache: also the mean of src over the legs (1 or 2; sample b with b + B), [B, N, C]; stats_parts > 0:
+    also fp32 [stats_parts, legs * B * N, 2], the sum and the sum of squares of every t2 row's rounded values in part 0.
+    out: where t2 goes (may be src itself); cache_out: where the mean goes.  Returns (t2, cache or None, stats or None)."""
+    lib = _lib.load()
+    names = {v: k for k, v in STORAGE_TORCH.items()}
+    if t1.dtype not in names or src.dtype != t1.dtype:
+        raise ValueError(f"tgate_add: storage dtypes {t1.dtype} / {src.dtype}")
+    if legs not in (1, 2) or t1.dim() != 3 or t1.shape[0] % legs:
+        raise ValueError(f"tgate_add: {legs} legs for a batch of {tuple(t1.shape)}")
+    LB, N, Cn = t1.shape
+    B = LB // legs
+    ld1, lds = _rows_ld("t1", t1, t1.shape), _rows_ld("src", src, t1.shape)
+    if out is None:
+        out = torch.empty(LB, N, Cn, device=t1.device, dtype=t1.dtype)
+    ld2 = _rows_ld("out", out, t1.shape)
+    if cache and cache_out is None:
+        cache_out = torch.empty(B, N, Cn, device=t1.device, dtype=t1.dtype)
+    ldc = 0
+    if cache_out is not None:
+        if cache_out.dtype != t1.dtype:
+            raise ValueError("tgate_add: cache_out has another dtype")
+        ldc = _rows_ld("cache_out", cache_out, (B, N, Cn))
+    stats = torch.empty(int(stats_parts), LB * N, 2, device=t1.device, dtype=torch.float32) if stats_parts > 0 else None
+    check(lib.af_op_tgate_add(DTYPES[names[t1.dtype]], ptr(t1), ptr(src), ptr(out), ptr(cache_out), ptr(stats), int(stats_parts),
+                              int(legs), B, N, Cn, ld1, lds, ld2, ldc, stream_ptr()), "af_op_tgate_add")
+    return out, cache_out, stats
+
+
 def lora_repack(base, adapters=(), cin_pad=None, ldw=None, row_off=0, rows_total=None, perm=False, dtype="bf16", out=None):
     """The weight repack with LoRA adapters merged (af_op_lora_repack): base [rows, cin(, ks, ks)] fp32 and adapters
     [(up [rows, r(, 1, 1)], down [r, cin(, ks, ks)], s)] (at most 8, r <= 256) -> the packed buffer [rows_total, ldw] in the storage

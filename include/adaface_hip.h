@@ -244,6 +244,35 @@ int af_pag_plan_query(af_handle* h, int depth, int out[3]);
 int af_unet_forward_pag(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                         void* stream);
 
+/* T-GATE (Zhang et al., "Cross-Attention Makes Inference Cumbersome in Text-to-Image Diffusion Models", 2024), opt-in.  A site
+ * is the cross-attention (attn2) of one transformer block, numbered as the PAG sites are (af_pag_site).
+ * af_tgate_set: the mode of the forwards that follow, through every U-Net entry point:
+ *   AF_TGATE_OFF      the forwards are what they are without this call: launch for launch, bit for bit.
+ *   AF_TGATE_CAPTURE  the forward (plain or twin form; DeepCache mode none or REFRESH) also keeps, per site,
+ *                     A = mean over the L legs of attn2's output (to_out + bias, before the residual), fp32, rounded once to the
+ *                     storage dtype, [B][N][C]: L = 2 for the twin form (sample b with b + B), 1 for the plain form.  A site
+ *                     never takes the fused cross-attention launch here: attn2's output is rounded to storage before the
+ *                     residual add, so eps differs from the OFF forward in rounding.  A new capture overwrites the cache.
+ *   AF_TGATE_REPLAY   the plain form on the B samples of the capture (DeepCache mode none, REFRESH or REUSE): every site
+ *                     computes t1 + A[site]; no q projection, attention, out projection or context is needed, and
+ *                     af_set_context need not have been called for this batch.
+ * Refused on the host with a message before any launch: the PAG form, CAPTURE with a REUSE step and REPLAY with the twin form
+ * (AF_ERR_INVALID); the fp8 mode, REPLAY with no valid cache or with another B, H or W than the capture (AF_ERR_STATE).  The
+ * cache belongs to the handle (not the arena) and is dropped by every af_load_tensor*.
+ * af_tgate_state: out = {cache valid, B, H, W of the capture}.  af_tgate_read_site: A[site] as fp32 [B][N][C].
+ * af_op_tgate_add: the kernel as an operator on caller buffers of `dtype` elements (nothing is converted or copied):
+ *   t2 [L B][N][ld_t2] = t1 [L B][N][ld_t1] + src [L B][N][ld_src], fp32 add, rounded once; cache_dev (optional)
+ *   [B][N][ld_cache] = mean over the L legs (1 or 2) of src; stats_dev (optional) fp32 [parts][L B N][2]: the sum and the sum of
+ *   squares of the rounded t2 values of every row in part 0, zeros in the other parts.  t2_dev may be src_dev.  Any alignment:
+ *   16-byte accesses where every pointer and row stride allows them. */
+enum { AF_TGATE_OFF = 0, AF_TGATE_CAPTURE = 1, AF_TGATE_REPLAY = 2 };
+int af_tgate_set(af_handle* h, int mode);
+int af_tgate_num_sites(af_handle* h);
+int af_tgate_state(af_handle* h, int out[4]);
+int af_tgate_read_site(af_handle* h, int site, float* out_dev, void* stream);
+int af_op_tgate_add(int dtype, const void* t1_dev, const void* src_dev, void* t2_dev, void* cache_dev, float* stats_dev, int parts,
+                    int L, int B, int N, int C, int ld_t1, int ld_src, int ld_t2, int ld_cache, void* stream);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the
@@ -381,7 +410,8 @@ int64_t af_arena_bytes(af_handle* h);
  * LDS-resident input halo: the largest single kernel of a bf16 step); 10-15 the token-merging kernels (af_set_tome), one class per
  * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual; 16-19 the FreeU kernels (af_set_freeu): hidden
  * mean + min / max, low-band sums, apply, the single-launch small-map form; 20-21 the guidance kernels (af_guidance): chunk
- * statistics, and every form that writes the output.  A caller that asks af_prof_collect for the first 10, 16 or 20 classes gets
+ * statistics, and every form that writes the output; 22 the T-GATE add kernel (af_tgate_set).  A caller that asks af_prof_collect for
+ * the first 10, 16, 20 or 22 classes gets
  * what it got before the later ones existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */

@@ -87,6 +87,11 @@ def parse_args(argv=None):
     ap.add_argument("--guidance_rescale", type=float, default=0.0, metavar="PHI",
                     help="guidance rescale, 0 .. 1 (0 = off): the combined prediction is scaled towards the conditional one's "
                          "standard deviation, the remedy for over-exposure at high guidance; every sampler")
+    ap.add_argument("--tgate", type=int, default=None, metavar="G",
+                    help="T-GATE: step G - 1 also keeps the cross-attention outputs (averaged over the guidance legs); from step G "
+                         "on the U-Net runs on one leg with them, without cross-attention or guidance; 1 <= G <= steps - 1 "
+                         "(0 = off).  DDIM and --dpm_solver; composes with --deep_cache, --tome, --freeu, --lora and --gpus; not "
+                         "with --plms, --pag_scale, --guidance_rescale or --dtype fp8")
     ap.add_argument("--lora", type=str, action="append", default=None, metavar="PATH[:SCALE]",
                     help="LoRA adapter file (.safetensors / .pt, kohya or native key names) merged into the U-Net's and the text "
                          "tower's weights as they are repacked; repeatable, at most 8; SCALE defaults to 1; composes with every "
@@ -145,6 +150,15 @@ def parse_args(argv=None):
             if merging:
                 ap.error(f"--pag_layers: --tome merges tokens at sites {merging}; a merged self-attention cannot be perturbed")
         opt.pag_layers = layers
+    if opt.tgate is not None and opt.tgate < 0:
+        ap.error("--tgate G: G >= 1 (0 = off)")
+    if opt.tgate:
+        if opt.plms:
+            ap.error("--tgate: PLMS keeps an eps history across the gate (use DDIM or --dpm_solver)")
+        if opt.pag_scale > 0.0 or opt.guidance_rescale > 0.0:
+            ap.error("--tgate: after the gate no guidance combine is made, so --pag_scale / --guidance_rescale have nothing to act on")
+        if opt.dtype == "fp8":
+            ap.error("--tgate: not built for --dtype fp8")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     if opt.lora_strict and not opt.lora:
@@ -336,6 +350,8 @@ def main():
             kw.update(guided)
             if opt.deep_cache not in (None, 1):
                 kw.update(deep_cache_interval=opt.deep_cache, deep_cache_depth=opt.deep_cache_depth)
+            if opt.tgate:
+                kw.update(tgate_step=opt.tgate)
             if opt.plms:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,

@@ -146,6 +146,8 @@ _SIGS = [
     ("af_clip_text_forward3", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P]),
     ("af_op_timestep_embedding", C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     ("af_op_gn_conv1x1", C.c_int, [_P, _P, _P, C.c_float, _P, _P, _P, _P] + [C.c_int] * 5 + [_P]),
+    ("af_op_ln_chain", C.c_int, [C.c_int] + [_P] * 6 + [C.c_float, _P, _P, C.c_int64] + [C.c_int] * 7 + [_P] * 8 +
+                                [C.POINTER(C.c_int), _P]),
     ("af_set_tome", C.c_int, [_P, C.c_double, C.c_int]),
     ("af_tome_plan_query", C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64)]),
     ("af_tome_num_sites", C.c_int, [_P]),

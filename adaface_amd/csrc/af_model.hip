@@ -1093,16 +1093,7 @@ struct Runner {
     if (x.f8 && (!L.w8 || ln)) { af_set_error_msg("conv: e4m3 input without an fp8 weight twin"); return AF_ERR_STATE; }
     const AfGemmPlan pl = af_plan_conv_gemm(p, 1, storage_of(dt));
     if (x.f8 && pl.kernel != AF_GK_PP_FP8) { af_set_error_msg("conv: e4m3 input on a shape without an fp8 plan"); return AF_ERR_STATE; }
-    if (ln_parts_pending) {
-      if (pl.kernel == AF_GK_ROWPANEL || pl.kernel == AF_GK_M128) {   // (these sum the partial statistics of their rows themselves)
-        p.ln_stats = ln->parts_in;
-        p.ln_parts_n = ln->parts_n;
-        p.ln_inv_count = 1.0f / (float)ln->count;
-        p.ln_eps = ln->eps;
-      } else {
-        AF_TRY(ln_finalize(ln->parts_in, ln->parts_n, (long)p.M, ln->count, ln->eps, ln->stats_buf));
-      }
-    }
+    if (ln_parts_pending) AF_TRY(af_ln_consumer_stats(p, pl, ln->parts_in, ln->parts_n, ln->count, ln->eps, ln->stats_buf, dry, s));
     // (only here does a tensor get gn_part, so only tensors of a bf16 handle ever carry one: groupnorm() relies on it)
     if (o.want_gn && dt == AF_DTYPE_BF16 && out.C % 32 == 0 && out.C == p.N && af_conv_gn_stats_ok(p, pl, out.C / 32)) {
       const int npart = out.H * out.W / 64;

@@ -589,6 +589,165 @@ int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* be
   return 0;
 }
 
+// One producer GEMM -> LayerNorm -> consumer GEMM pair of a transformer block with the LayerNorm folded into the two GEMMs, on
+// the launches run_xfmr (af_model.hip) makes, every intermediate returned: t = a Wp^T + bp + res with ln_stats_out, the folded
+// consumer weight (af_launch_ln_fold), the consumer on the partial sums or on finalised statistics as af_ln_consumer_stats
+// (af_host.h, Runner::conv's own decision) says, and the unfolded route (af_launch_layernorm on t, then the plain GEMM) beside
+// it.  Both launches are planned on aligned dummies first, so a shape that cannot fold is refused before the device is touched.
+// Test hooks: the sentinel in the whole t and y buffers (guard_rows rows behind the M valid ones included) and NaN in all
+// parts_cap slabs before the launches.
+int af_op_ln_chain(int dtype, const float* a_dev, const float* wp_dev, const float* bp_dev, const float* res_dev,
+                   const float* gamma_dev, const float* beta_dev, float eps, const float* wc_dev, const float* bc_dev, int64_t M,
+                   int Kp, int C, int N, int geglu, int parts_n, int parts_cap, int guard_rows, float* wf_dev, float* colsum_dev,
+                   float* biasf_dev, float* t_dev, float* parts_dev, float* stats_dev, float* y_folded_dev, float* y_plain_dev,
+                   int* plans10, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype != AF_DTYPE_BF16) {
+    af_set_error_msg("af_op_ln_chain: LayerNorm-fused launches exist for bf16 storage only (dtype %d)", dtype);
+    return AF_ERR_INVALID;
+  }
+  const int rows = geglu ? 2 * N : N;   // consumer weight rows
+  if (M <= 0 || M + guard_rows > 0x7fffffff || guard_rows < 0 || Kp <= 0 || Kp % 64 != 0 || C <= 0 || C % 64 != 0 || N <= 0 ||
+      N % 4 != 0 || (geglu && rows % 64 != 0) || parts_cap <= 0) {
+    af_set_error_msg("af_op_ln_chain: M=%lld Kp=%d C=%d N=%d geglu=%d (Kp, C: multiples of 64; N: of 4, GEGLU: of 32)", (long long)M,
+                     Kp, C, N, geglu);
+    return AF_ERR_INVALID;
+  }
+  const int rows_pad_p = round_up(C, 128), rows_pad_c = round_up(rows, 128);
+  const long Mg = (long)M + guard_rows;
+  alignas(16) static char dummy[16];
+  ConvGemmParams pp, pc;
+  memset(&pp, 0, sizeof(pp));
+  pp.src = dummy; pp.src_batch_stride = (long)M * Kp; pp.ldc = Kp; pp.Cin = Kp;
+  pp.Hs = 1; pp.Ws = (int)M; pp.Hi = 1; pp.Wi = (int)M; pp.Ho = 1; pp.Wo = (int)M;
+  pp.ks = 1; pp.stride = 1; pp.pad = 0;
+  pp.W = dummy; pp.ldw = Kp; pp.Wrows = rows_pad_p;
+  pp.M = (int)M; pp.N = C; pp.K = Kp; pp.k_logical = Kp;
+  pp.bias = bp_dev ? reinterpret_cast<const float*>(dummy) : nullptr;
+  pp.residual = res_dev ? dummy : nullptr; pp.ldr = C;
+  pp.out = dummy; pp.ldo = C; pp.alpha = 1.f;
+  pp.ln_stats_out = reinterpret_cast<float*>(dummy);
+  pc = pp;
+  pc.src_batch_stride = (long)M * C; pc.ldc = C; pc.Cin = C;
+  pc.ldw = C; pc.Wrows = rows_pad_c;
+  pc.N = rows; pc.K = C; pc.k_logical = C;
+  pc.bias = reinterpret_cast<const float*>(dummy);
+  pc.residual = nullptr; pc.ldr = 0;
+  pc.ldo = N;
+  pc.epilogue = geglu ? AF_EPI_GEGLU : AF_EPI_NONE;
+  pc.ln_stats_out = nullptr;
+  pc.ln_stats = reinterpret_cast<const float*>(dummy); pc.ln_colsum = reinterpret_cast<const float*>(dummy);
+  ConvGemmParams pu = pc;   // the unfolded consumer
+  pu.ln_stats = nullptr; pu.ln_colsum = nullptr;
+  pu.bias = bc_dev ? reinterpret_cast<const float*>(dummy) : nullptr;
+  // the model's refusals (xfmr_ln_parts): both launches must plan a LayerNorm epilogue -- asked as Runner::ln_capable asks, of the
+  // launch without its LayerNorm arguments and residual -- and the consumer is handed the producer's slab count
+  int slabs = 0;
+  {
+    ConvGemmParams qa = pp, qb = pc;
+    qa.ln_stats_out = nullptr; qa.residual = nullptr; qa.ldr = 0;
+    qb.ln_stats = nullptr; qb.ln_colsum = nullptr;
+    const AfGemmPlan a = af_plan_conv_gemm(qa, 1, AF_ST_BF16), b = af_plan_conv_gemm(qb, 1, AF_ST_BF16);
+    slabs = a.ln_slabs;
+    if (a.ln_slabs <= 0 || b.ln_slabs <= 0) {
+      af_set_error_msg("af_op_ln_chain: the %s [%lld, %d] -> %d plans no LayerNorm epilogue (kernel %d, %d K slices)",
+                       a.ln_slabs <= 0 ? "producer" : "consumer", (long long)M, a.ln_slabs <= 0 ? Kp : C, a.ln_slabs <= 0 ? C : rows,
+                       a.ln_slabs <= 0 ? a.kernel : b.kernel, a.ln_slabs <= 0 ? a.splitk : b.splitk);
+      return AF_ERR_INVALID;
+    }
+    if (af_plan_conv_gemm(pp, 1, AF_ST_BF16).ln_slabs != slabs || af_plan_conv_gemm(pc, 1, AF_ST_BF16).ln_slabs <= 0) {
+      af_set_error_msg("af_op_ln_chain: the launches with their LayerNorm arguments plan other statistics slabs than the bare ones (%d)", slabs);
+      return AF_ERR_INVALID;
+    }
+    if ((parts_n > 0 ? parts_n : a.ln_slabs) != a.ln_slabs) {
+      af_set_error_msg("af_op_ln_chain: the producer writes %d statistics slabs, the consumer is handed %d", a.ln_slabs, parts_n);
+      return AF_ERR_INVALID;
+    }
+    if (a.ln_slabs > parts_cap) {
+      af_set_error_msg("af_op_ln_chain: %d statistics slabs, room for %d", a.ln_slabs, parts_cap);
+      return AF_ERR_INVALID;
+    }
+  }
+  Tmp tmp;
+  OP_ALLOC(an, (size_t)M * Kp * 2, false);
+  OP_ALLOC(wpn, (size_t)rows_pad_p * Kp * 2, true);
+  OP_ALLOC(wcn, (size_t)rows_pad_c * C * 2, true);
+  OP_ALLOC(wcf, (size_t)rows_pad_c * C * 2, true);
+  OP_ALLOC(cs, (size_t)rows_pad_c * 4, true);
+  OP_ALLOC(bf, (size_t)rows_pad_c * 4, true);
+  OP_ALLOC(tn, (size_t)Mg * C * 2, false);
+  OP_ALLOC(tl, (size_t)M * C * 2, false);
+  OP_ALLOC(y0, (size_t)Mg * N * 2, false);
+  OP_ALLOC(y1, (size_t)Mg * N * 2, false);
+  OP_ALLOC(parts, (size_t)parts_cap * M * 2 * sizeof(float), false);
+  OP_ALLOC(st_own, (size_t)M * 2 * sizeof(float), true);
+  OP_ALLOC(st_tap, (size_t)M * 2 * sizeof(float), true);
+  float *bpn = nullptr, *bcn = nullptr;
+  void* rn = nullptr;
+  AF_TRY(fill_cols_dt(dtype, tn, Mg, C, 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(dtype, y0, Mg, N, 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(dtype, y1, Mg, N, 0, OP_SENTINEL, s));
+  AF_TRY(fill_cols_dt(AF_DTYPE_F32, parts, (long)parts_cap * M, 2, 0, OP_NAN, s));
+  AF_TRY(af_launch_cast_f32<bf16>(a_dev, an, (long)M * Kp, s));
+  AF_TRY(af_launch_repack_weight<bf16>(wp_dev, wpn, C, Kp, Kp, 1, Kp, 0, 0, s));
+  AF_TRY(af_launch_repack_weight<bf16>(wc_dev, wcn, rows, C, C, 1, C, 0, geglu ? 1 : 0, s));
+  if (bp_dev) {
+    bpn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad_p * 4, true));
+    if (!bpn) return AF_ERR_HIP;
+    AF_TRY(af_launch_permute_bias(bp_dev, bpn, C, 0, s));
+  }
+  if (bc_dev) {
+    bcn = reinterpret_cast<float*>(tmp.get((size_t)rows_pad_c * 4, true));
+    if (!bcn) return AF_ERR_HIP;
+    AF_TRY(af_launch_permute_bias(bc_dev, bcn, rows, geglu ? 1 : 0, s));
+  }
+  if (res_dev) {
+    rn = tmp.get((size_t)M * C * 2, false);
+    if (!rn) return AF_ERR_HIP;
+    AF_TRY(af_launch_cast_f32<bf16>(res_dev, rn, (long)M * C, s));
+  }
+  AF_TRY(af_launch_ln_fold<bf16>(wcn, wcf, gamma_dev, beta_dev, bcn, (float*)cs, (float*)bf, rows_pad_c, C, C, s));
+  // producer
+  pp.src = an; pp.W = wpn; pp.bias = bpn; pp.residual = rn; pp.out = tn;
+  pp.ln_stats_out = (float*)parts;
+  const AfGemmPlan plp = af_plan_conv_gemm(pp, 1, AF_ST_BF16);
+  // folded consumer: planned with the finalised statistics' buffer, which af_ln_consumer_stats fills or replaces
+  pc.src = tn; pc.W = wcf; pc.bias = (const float*)bf; pc.out = y1;
+  pc.ln_colsum = (const float*)cs; pc.ln_stats = (const float*)st_own;
+  const AfGemmPlan plc = af_plan_conv_gemm(pc, 1, AF_ST_BF16);
+  if (plp.ln_slabs != slabs || plc.ln_slabs <= 0) {
+    af_set_error_msg("af_op_ln_chain: the launches as stated plan %d / %d statistics slabs, the bare ones %d", plp.ln_slabs,
+                     plc.ln_slabs, slabs);
+    return AF_ERR_INVALID;
+  }
+  AF_TRY(af_launch_conv_gemm<bf16>(pp, 1, s, &plp, nullptr));
+  AF_TRY(af_launch_ln_finalize((const float*)parts, slabs, (int)M, C, eps, (float*)st_tap, s));
+  AF_TRY(af_ln_consumer_stats(pc, plc, (const float*)parts, slabs, C, eps, (float*)st_own, false, s));
+  AF_TRY(af_launch_conv_gemm<bf16>(pc, 1, s, &plc, nullptr));
+  // the unfolded route on the same t
+  AF_TRY(af_launch_layernorm<bf16>(tn, C, (long)M, C, gamma_dev, beta_dev, eps, tl, C, s));
+  pu.src = tl; pu.W = wcn; pu.bias = bcn; pu.out = y0;
+  {
+    const AfGemmPlan pl = af_plan_conv_gemm(pu, 1, AF_ST_BF16);
+    void* wsk = nullptr;
+    if (pl.splitk > 1) { wsk = tmp.get(pl.ws_bytes, false); if (!wsk) return AF_ERR_HIP; }
+    AF_TRY(af_launch_conv_gemm<bf16>(pu, 1, s, &pl, wsk));
+  }
+  if (plans10) {
+    const int o[10] = {plp.kernel, plp.rowpanel, plp.tile, plp.splitk, plp.ln_slabs, plc.kernel, plc.rowpanel, plc.tile, plc.splitk, plc.ln_slabs};
+    memcpy(plans10, o, sizeof(o));
+  }
+  if (wf_dev) AF_TRY(af_launch_cast_to_f32<bf16>(wcf, wf_dev, (long)rows * C, s));
+  if (colsum_dev) HIP_CHECK_RET(hipMemcpyAsync(colsum_dev, cs, (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
+  if (biasf_dev) HIP_CHECK_RET(hipMemcpyAsync(biasf_dev, bf, (size_t)rows * 4, hipMemcpyDeviceToDevice, s));
+  if (t_dev) AF_TRY(af_launch_cast_to_f32<bf16>(tn, t_dev, Mg * C, s));
+  if (parts_dev) HIP_CHECK_RET(hipMemcpyAsync(parts_dev, parts, (size_t)parts_cap * M * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (stats_dev) HIP_CHECK_RET(hipMemcpyAsync(stats_dev, st_tap, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (y_folded_dev) AF_TRY(af_launch_cast_to_f32<bf16>(y1, y_folded_dev, Mg * N, s));
+  if (y_plain_dev) AF_TRY(af_launch_cast_to_f32<bf16>(y0, y_plain_dev, Mg * N, s));
+  return 0;
+}
+
 int af_op_groupnorm(int dtype, const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, int silu,
                     float* y_dev, int B, int C, int H, int W, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

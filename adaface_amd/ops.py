@@ -234,6 +234,59 @@ def gn_conv1x1(x, gamma, beta, w, bias=None, eps=1e-6):
     return y0, y1
 
 
+LN_CHAIN_PARTS_CAP = 20     # statistics slabs ln_chain leaves room for: 16 of C = 1280 and spare ones that must stay unwritten
+LN_CHAIN_GUARD_ROWS = 256   # rows behind the M valid ones of t and y: one row panel
+
+
+def geglu_row_perm(rows):
+    """Row of output feature n of a GEGLU projection [2 N, K] (value rows, then gate rows) in the kernels' repacked weight:
+    value / gate groups of 16 interleaved (geglu_perm, csrc/af_common.h).  A LongTensor p with packed[p[n]] = w[n]."""
+    n = torch.arange(rows)
+    half = rows // 2
+    j = torch.where(n < half, n, n - half)
+    return (j // 16) * 32 + torch.where(n < half, 0, 16) + (j % 16)
+
+
+def ln_chain(a, wp, gamma, beta, wc, bp=None, res=None, bc=None, eps=1e-5, geglu=False, dtype="bf16", parts_n=0):
+    """One producer GEMM -> LayerNorm -> consumer GEMM pair with the LayerNorm folded into the GEMMs, as the transformer blocks
+    run it in bf16 (af_op_ln_chain), every intermediate returned.  a [M, Kp], wp [C, Kp], bp [C], res [M, C], gamma / beta [C],
+    wc [N, C] ([2 N, C] with geglu), bc [N] ([2 N]).  Returns a dict of fp32 tensors:
+      Wf [rows, C], colsum [rows], biasf [rows]  the folded consumer weight, its row sums and W beta + b, in wc's row order
+      t [M, C]            the producer's stored output;  t_guard: the LN_CHAIN_GUARD_ROWS rows behind it
+      parts [slabs, M, 2] (sum, sum of squares) per statistics slab;  parts_spare: the slabs behind them (NaN unless written)
+      stats [M, 2]        (mu, rstd) from ln_finalize_kernel
+      y_folded, y_plain [M, N]  the folded consumer / LayerNorm launch + plain GEMM;  y_folded_guard, y_plain_guard
+    and plans = two dicts (kernel by its GEMM_KERNELS name, rowpanel, tile, splitk, ln_slabs) of the producer and the folded
+    consumer.  AfError where a launch plans no LayerNorm epilogue, for parts_n > 0 that is not the producer's slab count and
+    for a dtype other than bf16."""
+    lib = _lib.load()
+    M, Kp = a.shape
+    Cn = wp.shape[0]
+    rows = wc.shape[0]
+    N = rows // 2 if geglu else rows
+    if wp.shape[1] != Kp or wc.shape[1] != Cn or (res is not None and tuple(res.shape) != (M, Cn)):
+        raise ValueError(f"ln_chain: a {tuple(a.shape)}, wp {tuple(wp.shape)}, wc {tuple(wc.shape)} do not chain")
+    plans = (C.c_int * 10)()
+    dev, G, cap = a.device, LN_CHAIN_GUARD_ROWS, LN_CHAIN_PARTS_CAP
+    f = dict(device=dev, dtype=torch.float32)
+    wf, cs, bf = torch.empty(rows, Cn, **f), torch.empty(rows, **f), torch.empty(rows, **f)
+    t, parts, stats = torch.empty(M + G, Cn, **f), torch.empty(cap, M, 2, **f), torch.empty(M, 2, **f)
+    y1, y0 = torch.empty(M + G, N, **f), torch.empty(M + G, N, **f)
+    opt = lambda v: None if v is None else ptr(_dev_f32(v))   # noqa: E731
+    check(lib.af_op_ln_chain(DTYPES[dtype], ptr(_dev_f32(a)), ptr(_dev_f32(wp)), opt(bp), opt(res), ptr(_dev_f32(gamma)),
+                             ptr(_dev_f32(beta)), eps, ptr(_dev_f32(wc)), opt(bc), M, Kp, Cn, N, int(geglu), parts_n, cap, G,
+                             ptr(wf), ptr(cs), ptr(bf), ptr(t), ptr(parts), ptr(stats), ptr(y1), ptr(y0), plans, stream_ptr()),
+          "af_op_ln_chain")
+    pl = tuple(dict(kernel=GEMM_KERNELS.get(int(plans[5 * i]), int(plans[5 * i])), rowpanel=int(plans[5 * i + 1]),
+                    tile=int(plans[5 * i + 2]), splitk=int(plans[5 * i + 3]), ln_slabs=int(plans[5 * i + 4])) for i in range(2))
+    if geglu:   # back to wc's row order
+        p = geglu_row_perm(rows).to(dev)
+        wf, cs, bf = wf[p], cs[p], bf[p]
+    slabs = pl[0]["ln_slabs"]
+    return {"Wf": wf, "colsum": cs, "biasf": bf, "t": t[:M], "t_guard": t[M:], "parts": parts[:slabs], "parts_spare": parts[slabs:],
+            "stats": stats, "y_folded": y1[:M], "y_folded_guard": y1[M:], "y_plain": y0[:M], "y_plain_guard": y0[M:], "plans": pl}
+
+
 def layer_norm(x, weight, bias, eps=1e-5, dtype="bf16"):
     lib = _lib.load()
     x = _dev_f32(x)

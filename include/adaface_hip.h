@@ -645,6 +645,27 @@ int af_op_layernorm_fp8_rec(const float* x_dev, const float* gamma_dev, const fl
 int af_op_gn_conv1x1(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, const float* w_dev,
                      const float* bias_dev, float* y_plain_dev, float* y_fused_dev, int B, int C, int H, int W, int N,
                      void* stream);
+/* One producer GEMM -> LayerNorm -> consumer GEMM pair of a transformer block with the LayerNorm folded into the two GEMMs
+ * (bf16 only: AF_ERR_INVALID for another dtype), on the model's launchers, every intermediate returned.  Inputs fp32 device:
+ * a [M, Kp], producer weight wp [C, Kp], bias bp [C] or null, residual res [M, C] or null, gamma / beta [C], consumer weight wc
+ * [N, C] ([2N, C] with geglu: value rows, then gate rows) and bias bc or null.  Kp and C multiples of 64, N of 4 (geglu: 32).
+ *   t = a wp^T + bp + res, whose GEMM also writes per-row partial sums; the consumer multiplies t by wc * gamma and applies
+ *   rstd (acc - mu colsum) + (wc beta + bc) in its epilogue: on the partial sums where its kernel keeps its rows for all of N
+ *   (row-panel, 128 x 160 tile GEMM), on an ln_finalize launch's (mu, rstd) otherwise -- the model's own decision.
+ * Refused with AF_ERR_INVALID and a message before the device is touched: a producer or consumer whose plan has no LayerNorm
+ * epilogue, parts_n > 0 that differs from the producer's slab count (parts_n <= 0: the consumer is handed the producer's),
+ * more slabs than parts_cap.
+ * Outputs fp32 device, each optional.  rows = N (geglu: 2N), in the kernel's row order (geglu: value / gate groups of 16
+ * interleaved): wf [rows, C] = bf16(wc * gamma), colsum [rows], biasf [rows].  t [M + guard_rows, C]: the stored producer output.
+ * parts [parts_cap, M, 2]: (sum, sum of squares) per statistics slab (slabs the launch does not write keep NaN).  stats [M, 2] =
+ * (mu, rstd), always from ln_finalize_kernel.  y_folded / y_plain [M + guard_rows, N]: the folded consumer / af_launch_layernorm
+ * on t and the plain GEMM on wc.  Rows behind M of t and y hold 49152 unless a launch wrote there.  plans10 (host) = {kernel,
+ * row-panel kind, tile, splitk, statistics slabs} of the producer, then of the folded consumer (as af_gemm_plan_query). */
+int af_op_ln_chain(int dtype, const float* a_dev, const float* wp_dev, const float* bp_dev, const float* res_dev,
+                   const float* gamma_dev, const float* beta_dev, float eps, const float* wc_dev, const float* bc_dev, int64_t M,
+                   int Kp, int C, int N, int geglu, int parts_n, int parts_cap, int guard_rows, float* wf_dev, float* colsum_dev,
+                   float* biasf_dev, float* t_dev, float* parts_dev, float* stats_dev, float* y_folded_dev, float* y_plain_dev,
+                   int* plans10, void* stream);
 /* F.layer_norm over the last dim of [rows, C]. */
 int af_op_layernorm(int dtype, const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps,
                     float* y_dev, int64_t rows, int C, void* stream);

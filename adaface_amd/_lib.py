@@ -37,6 +37,7 @@ class AfConfig(C.Structure):
         ("build_clip", C.c_int),
         ("clip_vocab", C.c_int), ("clip_hidden", C.c_int), ("clip_layers", C.c_int), ("clip_heads", C.c_int),
         ("clip_intermediate", C.c_int), ("clip_max_pos", C.c_int),
+        ("build_controlnet", C.c_int), ("hint_channels", C.c_int),
     ]
 
 
@@ -170,6 +171,15 @@ _SIGS = [
     ("af_tgate_state", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("af_tgate_read_site", C.c_int, [_P, C.c_int, _P, _P]),
     ("af_op_tgate_add", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
+    ("af_control_set_hint", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_control_num_residuals", C.c_int, [_P]),
+    ("af_control_forward", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("af_unet_set_control", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),
+    ("af_control_plan_query", C.c_int, [C.POINTER(AfConfig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    ("af_control_stats", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("af_control_add_launches", C.c_int64, []),
+    ("af_op_control_add", C.c_int, [C.c_int, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_float), C.c_int, C.c_int, _P]),
     ("af_guidance", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     ("af_guidance_plan_query", C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("af_flops_issued", C.c_double, [C.c_int]),
@@ -187,6 +197,8 @@ UNET_FORMS = {False: 0, True: 1, "plain": 0, "twin": 1, "pag": 2}
 UNET_FORM_LEGS = {0: 1, 1: 2, 2: 3}
 # the mode of af_tgate_set (AF_TGATE_*)
 TGATE_MODES = {None: 0, "capture": 1, "replay": 2}
+# AF_CONTROL_MAX_SEGMENTS (csrc/af_kernels.h): segments of one ControlNet residual add launch
+CONTROL_MAX_SEGMENTS = 16
 
 
 def lib_path() -> Path:
@@ -269,6 +281,43 @@ def tome_plan_query(H, W, ratio) -> tuple:
     out = (C.c_int64 * 4)()
     check(load().af_tome_plan_query(int(H), int(W), float(ratio), out), "af_tome_plan_query")
     return tuple(int(v) for v in out)
+
+
+def fill_unet_config(cfg: AfConfig, unet: dict) -> AfConfig:
+    """The U-Net fields of af_config from UNetModel constructor arguments (Engine and control_plan_query share it)."""
+    ar, cm = list(unet["attention_resolutions"]), list(unet["channel_mult"])
+    if len(ar) > 8 or len(cm) > 8:
+        raise ValueError("at most 8 entries supported")
+    cfg.in_channels = unet["in_channels"]
+    cfg.model_channels = unet["model_channels"]
+    cfg.out_channels = unet.get("out_channels", unet["in_channels"])
+    cfg.num_res_blocks = unet["num_res_blocks"]
+    cfg.n_attention_resolutions = len(ar)
+    for i, v in enumerate(ar):
+        cfg.attention_resolutions[i] = int(v)
+    cfg.n_channel_mult = len(cm)
+    for i, v in enumerate(cm):
+        cfg.channel_mult[i] = int(v)
+    cfg.num_heads = unet["num_heads"]
+    cfg.context_dim = unet["context_dim"]
+    cfg.transformer_depth = unet.get("transformer_depth", 1)
+    cfg.n_context_layers = unet.get("n_context_layers", 16)
+    return cfg
+
+
+def control_plan_query(unet: dict, H: int, W: int) -> list:
+    """af_control_plan_query: [(C, H, W, element offset for one sample)] of the ControlNet residuals of an H x W latent, in block
+    order (input blocks, then the middle block), from the constructor arguments alone.  Host only: no GPU is needed."""
+    cfg = fill_unet_config(AfConfig(), unet)
+    out = (C.c_int64 * (4 * 64))()
+    n = C.c_int()
+    check(load().af_control_plan_query(C.byref(cfg), int(H), int(W), 64, out, C.byref(n)), "af_control_plan_query")
+    return [tuple(int(out[4 * i + k]) for k in range(4)) for i in range(n.value)]
+
+
+def control_add_launches() -> int:
+    """Launches of the ControlNet residual add kernel since the library was loaded (not part of plan_counts)."""
+    return int(load().af_control_add_launches())
 
 
 FREEU_KERNELS = ("refused", "single", "chunked")           # AfFreeuKernel (csrc/af_kernels.h)

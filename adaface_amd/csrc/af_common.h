@@ -73,7 +73,9 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        // the guidance kernels (af_guidance.hip; scripts/pag_mode.py): the chunk statistics, and every form that writes the output
        AF_K_GUIDANCE_STATS = 20, AF_K_GUIDANCE_APPLY = 21,
        // the T-GATE add kernel (af_tgate.hip; scripts/tgate_mode.py)
-       AF_K_TGATE_ADD = 22, AF_K_COUNT = 23 };
+       AF_K_TGATE_ADD = 22,
+       // the ControlNet residual add kernel (af_controlnet.hip; scripts/controlnet_mode.py)
+       AF_K_CONTROL_ADD = 23, AF_K_COUNT = 24 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)

@@ -144,6 +144,16 @@ template <typename T>
 int af_launch_tgate_add(const void* t1, int ld1, const void* src, int lds, void* t2, int ld2, void* cache, int ldc, int L, int B,
                         int N, int C, float* ln_stats_out, int ln_parts, hipStream_t s);
 
+// ControlNet residual injection (af_controlnet.hip), all three storage types: ONE launch applies up to
+// AF_CONTROL_MAX_SEGMENTS segments dst[r][0 .. C) = round(dst[r][c] + round32(scale * src[r][c])), r < rows -- dst rows ld >= C
+// elements apart (a channel range of a concatenation buffer), src dense.  Product and sum are separate fp32 roundings (no fma).
+// 16-byte accesses per segment where its pointers and row stride allow them, element accesses otherwise.  Nothing outside the
+// addressed channel ranges is read or written.  A refused argument: -1 with a message, nothing launched.
+enum { AF_CONTROL_MAX_SEGMENTS = 16 };
+struct AfControlSeg { void* dst; const void* src; long rows; int C, ld; float scale; };
+template <typename T> int af_launch_control_add(const AfControlSeg* segs, int n, hipStream_t s);
+extern std::atomic<long> g_af_control_add_launches;   // launches since the library was loaded
+
 // FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
 // types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
 enum AfFreeuKernel {

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <string>
@@ -435,6 +436,28 @@ struct af_handle {
     return off;
   }
 
+  // ControlNet.  A control handle (cfg.build_controlnet) is the U-Net's encoder under unet_prefix = "control_model."
+  // -- time_embed, conv_in, input_blocks, middle_block, emb_all, ca_list / ctx_kv as above, no output blocks and no out --
+  // plus the hint network, one 1x1 "zero" convolution per input block and one behind the middle block.  g = the hint network's
+  // output [hint_B][hint_H][hint_W][model_channels] (af_control_set_hint), handle-owned.
+  bool is_control = false;
+  std::string unet_prefix = "model.diffusion_model.";
+  Linear hint_convs[8];
+  std::vector<Linear> zero_convs;
+  Linear mid_out;
+  void* hint_g = nullptr;
+  size_t hint_g_bytes = 0;
+  int hint_B = 0, hint_H = 0, hint_W = 0;
+  // ... and on a U-Net handle the residuals attached by af_unet_set_control: n of them for Bs samples, dense NHWC, back to back
+  // in block order (control_layout), the caller's buffer; stats of the last forward (af_control_stats)
+  struct Control {
+    const void* res = nullptr;
+    int n = 0, Bs = 0, H = 0, W = 0;
+    float scales[AF_CONTROL_MAX_SEGMENTS] = {};
+    bool cond_only = false;
+    int last_launches = 0, last_segments = 0;
+  } ctl;
+
   // runtime state
   Arena arena;
   float* stage = nullptr;  // fp32 staging for weight upload
@@ -604,12 +627,13 @@ static bool in_list(const int* a, int n, int v) {
   return false;
 }
 
-// mirrors UNetModel.__init__ (openaimodel.py:517-697)
-static int build_unet(Builder& b) {
+// mirrors UNetModel.__init__ (openaimodel.py:517-697).  encoder_only (a control handle): time_embed, input_blocks
+// and middle_block under the handle's prefix, no output blocks and no out -- ControlNet.__init__ (cldm.py) builds exactly these.
+static int build_unet(Builder& b, bool encoder_only = false) {
   af_handle* h = b.h;
   const af_config& c = h->cfg;
   const int mc = c.model_channels, ted = mc * 4;
-  const std::string P = "model.diffusion_model.";
+  const std::string P = h->unet_prefix;
   if (mc % bk_of(h->dtype) != 0 || c.context_dim % bk_of(h->dtype) != 0 || c.num_heads <= 0) {
     af_set_error_msg("unet: model_channels (%d) and context_dim (%d) must be multiples of %d", mc, c.context_dim,
                      bk_of(h->dtype));
@@ -665,7 +689,7 @@ static int build_unet(Builder& b) {
     int r2 = make_unet_resblock(b, P + "middle_block.2", ch, ch);
     ub.layers.push_back({L_RES, r2});
   }
-  for (int level = c.n_channel_mult - 1; level >= 0; --level) {
+  for (int level = c.n_channel_mult - 1; level >= 0 && !encoder_only; --level) {
     const int mult = c.channel_mult[level];
     for (int i = 0; i < c.num_res_blocks + 1; ++i) {
       UBlock ub;
@@ -690,8 +714,10 @@ static int build_unet(Builder& b) {
       h->output_blocks.push_back(ub);
     }
   }
-  b.make_norm(h->out_norm, P + "out.0", ch, 1e-5f);
-  b.make_conv(h->out_conv, P + "out.2", mc, c.out_channels, 3);
+  if (!encoder_only) {
+    b.make_norm(h->out_norm, P + "out.0", ch, 1e-5f);
+    b.make_conv(h->out_conv, P + "out.2", mc, c.out_channels, 3);
+  }
 
   // fused emb_layers.1 of every ResBlock: one [emb_total, ted] linear
   b.alloc_linear(h->emb_all, ted, h->emb_total, 1, false);
@@ -721,6 +747,42 @@ static int build_unet(Builder& b) {
   collect_ca(h->middle_block);
   for (auto& ub : h->output_blocks) collect_ca(ub);
   h->ctx_kv.resize(h->ca_list.size());
+  return b.rc;
+}
+
+// the channels of the skip input block i leaves (i = n_in: of the middle block's output), from the block structure alone
+static std::vector<int> unet_skip_channels(const af_handle* h) {
+  std::vector<int> out;
+  int C = h->cfg.in_channels;
+  auto walk = [&](const UBlock& ub) {
+    for (const auto& l : ub.layers) {
+      if (l.kind == L_CONV_IN) C = h->cfg.model_channels;
+      else if (l.kind == L_RES) C = h->res[l.idx].cout;
+    }
+    out.push_back(C);
+  };
+  for (const auto& ub : h->input_blocks) walk(ub);
+  walk(h->middle_block);
+  return out;
+}
+
+// ControlNet.__init__ (cldm.py): the encoder of build_unet, input_hint_block.{0,2,..,14}, zero_convs.i.0, middle_block_out.0
+static int build_controlnet(Builder& b) {
+  af_handle* h = b.h;
+  const af_config& c = h->cfg;
+  h->is_control = true;
+  h->unet_prefix = "control_model.";
+  if (c.hint_channels <= 0) { af_set_error_msg("controlnet: hint_channels %d", c.hint_channels); return AF_ERR_INVALID; }
+  if (const int rc = build_unet(b, true)) return rc;
+  const std::string P = h->unet_prefix;
+  const int chans[9] = {c.hint_channels, 16, 16, 32, 32, 96, 96, 256, c.model_channels};
+  for (int k = 0; k < 8; ++k)   // (every width is padded to the K tile: the activations between them carry zero pad channels)
+    b.make_conv(h->hint_convs[k], P + "input_hint_block." + std::to_string(2 * k), chans[k], chans[k + 1], 3, true, true, /*pad_cin=*/true);
+  const std::vector<int> sk = unet_skip_channels(h);
+  h->zero_convs.resize(h->input_blocks.size());
+  for (size_t i = 0; i < h->input_blocks.size(); ++i)
+    b.make_conv(h->zero_convs[i], P + "zero_convs." + std::to_string(i) + ".0", sk[i], sk[i], 1);
+  b.make_conv(h->mid_out, P + "middle_block_out.0", sk.back(), sk.back(), 1);
   return b.rc;
 }
 
@@ -1939,6 +2001,7 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   Shp cur = {c.in_channels, H, W};
   for (int i = 0; i < n_in; ++i) shp_in[i] = cur = out_shape(h->input_blocks[i], cur);
   Shp hshape = out_shape(h->middle_block, cur);
+  const Shp mid_shape = hshape;
   std::vector<Act> cat(n_out);
   std::vector<int> ch_h(n_out);
   for (int j = 0; j < n_out; ++j) {
@@ -2025,6 +2088,35 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     hcur = o;
     AF_TRY(tap(n_in, hcur));
   }
+  // ControlNet residuals (af_unet_set_control): s_i r_i onto the skip of input block i where its output block will
+  // read it, s_mid r_mid onto the middle block's output, ONE launch.  Every reader of the unmodified skips (the input blocks and
+  // the middle block) has been enqueued; FreeU below filters the controlled skip.  A reuse step of depth k touches the k skips
+  // it rewrote (the middle residual is inside the kept feature).  cond_only: the first half of the batch only.
+  if (!R.dry) h->ctl.last_launches = h->ctl.last_segments = 0;
+  if (h->ctl.res) {
+    const af_handle::Control& ct = h->ctl;
+    const long Bs = ct.cond_only ? Bf / 2 : Bf;
+    const int n_apply = dc_reuse ? dc_depth : n_in + 1;
+    AfControlSeg segs[AF_CONTROL_MAX_SEGMENTS];
+    int ns = 0;
+    size_t off = 0;     // elements of the residual buffer in front of residual i
+    for (int i = 0; i < n_apply && i < ct.n && ns < AF_CONTROL_MAX_SEGMENTS; ++i) {
+      const bool mid = i == n_in;
+      const Shp sp = mid ? mid_shape : shp_in[i];
+      const int j = mid ? 0 : n_in - 1 - i;
+      const long rows = Bs * sp.H * sp.W;
+      if (j < n_out) {
+        const Act dst = mid ? view(cat[0], 0, ch_h[0]) : view(cat[j], ch_h[j], sp.C);
+        segs[ns++] = AfControlSeg{dst.p, reinterpret_cast<const char*>(ct.res) + off * esize(dt), rows, sp.C, dst.ld, ct.scales[i]};
+      }
+      off += (size_t)rows * sp.C;
+    }
+    if (!R.dry && ns) {
+      if (AF_TYPED(dt, af_launch_control_add<Elem>(segs, ns, s))) return AF_ERR_INVALID;
+      h->ctl.last_launches = 1;
+      h->ctl.last_segments = ns;
+    }
+  }
   // FreeU (af_set_freeu), in place on cat[j] just before its only reader.  The DeepCache feature D is the h half of
   // cat[n_out - dc_depth]: a refresh scales it where it is kept, so a reuse step filters that concatenation's fresh skip only.
   auto freeu = [&](int j, int nb) -> int {
@@ -2068,6 +2160,138 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
   AF_TRY(R.conv(h->out_conv, g, e));
   if (!R.dry)
     AF_TRY(AF_TYPED(dt, af_launch_nhwc_to_nchw<Elem>(e.p, eps_dev, Bf, c.out_channels, H * W, e.ld, s)));
+  return 0;
+}
+
+// ControlNet.forward (cldm.py) on Bf samples with the handle's g (control_hint_impl): the input-block walk of unet_forward_impl
+// in its plain form, g added by conv_in's residual epilogue, a 1x1 convolution behind every block straight into the caller's
+// residual buffer (storage dtype, dense NHWC, back to back).  n_blocks <= n_in stops after input block n_blocks - 1.
+static int control_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, const int64_t* t_dev, int Bf, int H, int W,
+                                int n_blocks, void* out_dev) {
+  Runner R(h, s);
+  const af_config& c = h->cfg;
+  const int dt = h->dtype;
+  const int mc = c.model_channels, ted = 4 * mc;
+  R.A.off = 0;
+  Act x = R.alloc_act(Bf, H, W, c.in_channels, h->conv_in.cin_pad);
+  Act temb = R.alloc_act(Bf, 1, 1, mc);
+  Act e1 = R.alloc_act(Bf, 1, 1, ted);
+  Act e2 = R.alloc_act(Bf, 1, 1, ted);
+  Act emb_all = R.alloc_act(Bf, 1, 1, h->emb_total);
+  AF_TRY(R.check(x));
+  AF_TRY(R.check(emb_all));
+  if (!R.dry) {
+    AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(x_dev, x.p, Bf, c.in_channels, H * W, x.ld, 1.0f, s)));
+    AF_TRY(AF_TYPED(dt, af_launch_timestep_embedding<Elem>((const long long*)t_dev, temb.p, Bf, mc, s)));
+  }
+  AF_TRY(R.conv(h->time_embed0, temb, e1));
+  if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(e1.p, e1.p, (long)Bf * ted, s)));
+  AF_TRY(R.conv(h->time_embed2, e1, e2));
+  if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(e2.p, e2.p, (long)Bf * ted, s)));
+  AF_TRY(R.conv(h->emb_all, e2, emb_all));
+  // g of sample b is g[b mod Bh]: one hint for all samples, or one per sample repeated per guidance leg
+  Act g;
+  g.p = h->hint_g; g.B = Bf; g.H = H; g.W = W; g.C = g.ld = mc;
+  if (h->hint_B != Bf) {
+    Act gx = R.alloc_act(Bf, H, W, mc);
+    AF_TRY(R.check(gx));
+    for (int b0 = 0; b0 < Bf; b0 += h->hint_B) {
+      Act src = g, dst = gx;
+      src.B = dst.B = h->hint_B;
+      dst.p = R.elem_ptr(gx.p, (long)b0 * H * W * mc);
+      AF_TRY(R.copy_channels(src, dst, 0));
+    }
+    g = gx;
+  }
+  size_t off = 0;   // elements of out_dev written so far
+  auto emit = [&](const Linear& zc, const Act& hh) -> int {
+    Act r;
+    r.B = hh.B; r.H = hh.H; r.W = hh.W; r.C = r.ld = hh.C;
+    r.p = R.elem_ptr(out_dev, (long)off);
+    off += (size_t)r.npix() * r.C;
+    return R.conv(zc, hh, r);
+  };
+  auto run_block = [&](const UBlock& ub, Act& hcur) -> int {
+    for (const LayerRef& l : ub.layers) {
+      Act out;
+      switch (l.kind) {
+        case L_CONV_IN: {
+          out = R.alloc_act(Bf, hcur.H, hcur.W, mc);
+          Act xin = hcur;
+          xin.C = h->conv_in.cin;  // logical channels; ld carries the padding
+          AF_TRY(R.conv(h->conv_in, xin, out, ConvOpt().res(&g)));
+        } break;
+        case L_RES: {
+          const ResBlockW& w = h->res[l.idx];
+          out = R.alloc_act(Bf, hcur.H, hcur.W, w.cout);
+          AF_TRY(run_resblock(R, w, hcur, out, emb_all.p, emb_all.ld));
+        } break;
+        case L_XFMR: {
+          out = R.alloc_act(Bf, hcur.H, hcur.W, hcur.C);
+          AF_TRY(run_xfmr(R, h->xf[l.idx], hcur, out));
+        } break;
+        case L_DOWN: {
+          out = R.alloc_act(Bf, hcur.H / 2, hcur.W / 2, hcur.C);
+          AF_TRY(R.conv(h->updown[l.idx], hcur, out, ConvOpt().strided(2)));
+        } break;
+        case L_UP:
+          af_set_error_msg("controlnet: an upsampling layer in the encoder");
+          return AF_ERR_STATE;
+      }
+      hcur = out;
+    }
+    return 0;
+  };
+  const int n_in = (int)h->input_blocks.size();
+  Act hcur = x;
+  for (int i = 0; i < std::min(n_blocks, n_in); ++i) {
+    AF_TRY(run_block(h->input_blocks[i], hcur));
+    AF_TRY(emit(h->zero_convs[i], hcur));
+  }
+  if (n_blocks > n_in) {
+    AF_TRY(run_block(h->middle_block, hcur));
+    AF_TRY(emit(h->mid_out, hcur));
+  }
+  return 0;
+}
+
+// input_hint_block (cldm.py): eight 3x3 convolutions, SiLU between them, three of them stride 2 -> g_out [Bh][H8/8][W8/8][mc].
+// The activations ping-pong between two arena buffers; their rows are as wide as the next layer's padded K, pad channels zero.
+static int control_hint_impl(af_handle* h, hipStream_t s, const float* hint_dev, int Bh, int H8, int W8, void* g_out) {
+  Runner R(h, s);
+  const af_config& c = h->cfg;
+  const int dt = h->dtype;
+  R.A.off = 0;
+  const Linear* L = h->hint_convs;
+  size_t maxb = 0;
+  {
+    int Hc = H8, Wc = W8;
+    maxb = (size_t)Bh * Hc * Wc * L[0].cin_pad;
+    for (int k = 0; k < 7; ++k) {
+      if (k == 2 || k == 4 || k == 6) { Hc /= 2; Wc /= 2; }
+      maxb = std::max(maxb, (size_t)Bh * Hc * Wc * L[k + 1].cin_pad);
+    }
+    maxb *= esize(dt);
+  }
+  void* buf[2] = {R.A.alloc(maxb), R.A.alloc(maxb)};
+  if (!buf[0] || !buf[1]) { af_set_error_msg("activation arena exhausted (hint network, cap %zu)", R.A.cap); return AF_ERR_STATE; }
+  Act a;
+  a.p = buf[0]; a.B = Bh; a.H = H8; a.W = W8; a.C = c.hint_channels; a.ld = L[0].cin_pad;
+  if (!R.dry) AF_TRY(AF_TYPED(dt, af_launch_nchw_to_nhwc<Elem>(hint_dev, a.p, Bh, c.hint_channels, H8 * W8, a.ld, 1.0f, s)));
+  for (int k = 0; k < 8; ++k) {
+    const int stride = (k == 2 || k == 4 || k == 6) ? 2 : 1;
+    Act o;
+    o.B = Bh; o.H = a.H / stride; o.W = a.W / stride; o.C = L[k].cout;
+    o.ld = k < 7 ? L[k + 1].cin_pad : L[k].cout;
+    o.p = k < 7 ? buf[(k + 1) & 1] : g_out;
+    const size_t bytes = (size_t)o.npix() * o.ld * esize(dt);
+    if (!R.dry && o.ld != o.C) HIP_CHECK_RET(hipMemsetAsync(o.p, 0, bytes, s));
+    Act xin = a;
+    xin.C = L[k].cin;
+    AF_TRY(R.conv(L[k], xin, o, ConvOpt().strided(stride)));
+    if (k < 7 && !R.dry) AF_TRY(AF_TYPED(dt, af_launch_silu<Elem>(o.p, o.p, (long)o.npix() * o.ld, s)));
+    a = o;
+  }
   return 0;
 }
 
@@ -2307,14 +2531,25 @@ int af_create(int device_id, const af_config* cfg, af_handle** out) {
   h->cfg = *cfg;
   h->dtype = cfg->dtype;
   Builder b{h.get()};
-  if (cfg->build_unet) {
+  if (cfg->build_controlnet && (cfg->build_unet || cfg->build_vae || cfg->build_clip)) {
+    af_set_error_msg("af_create: a ControlNet is a handle of its own (build_controlnet with no other build_* flag)");
+    af_destroy(h.release());
+    return AF_ERR_INVALID;
+  }
+  if (cfg->build_unet || cfg->build_controlnet) {
     if (cfg->n_channel_mult <= 0 || cfg->n_channel_mult > 8 || cfg->n_attention_resolutions > 8) {
       af_set_error_msg("af_create: bad channel_mult / attention_resolutions");
       af_destroy(h.release());
       return AF_ERR_INVALID;
     }
-    int rc = build_unet(b);
-    if (!rc) rc = register_fp8_sites(b);
+    int rc;
+    if (cfg->build_controlnet) {
+      rc = build_controlnet(b);
+      h->cfg.build_unet = 1;     // (the encoder is a U-Net's: af_set_context and the weight loaders treat the handle as one)
+    } else {
+      rc = build_unet(b);
+      if (!rc) rc = register_fp8_sites(b);
+    }
     if (rc) { af_destroy(h.release()); return rc; }
   }
   if (cfg->build_vae) {
@@ -2352,6 +2587,7 @@ void af_destroy(af_handle* h) {
   if (h->ctx_cast) hipFree(h->ctx_cast);
   if (h->dc.buf) hipFree(h->dc.buf);
   if (h->tg.buf) hipFree(h->tg.buf);
+  if (h->hint_g) hipFree(h->hint_g);
   if (h->arena.base) hipFree(h->arena.base);
   if (h->stage) hipFree(h->stage);
   delete h;
@@ -2462,6 +2698,7 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
   s.loaded = true;
   h->dc.valid = false;
   h->tg.valid = false;
+  h->hint_B = 0;               // (a control handle's hint feature was made with the weights as they were: af_control_set_hint again)
   h->ln_fold_dirty = true;
   h->fp8_dirty = true;
   h->up4_dirty = true;
@@ -2497,7 +2734,7 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
   if (!h || !ctx_dev || Bf <= 0 || n_tokens <= 0) { af_set_error_msg("af_set_context: bad argument"); return AF_ERR_INVALID; }
   if (!h->cfg.build_unet) { af_set_error_msg("af_set_context: handle has no UNet"); return AF_ERR_STATE; }
   HIP_CHECK_RET(hipSetDevice(h->device));
-  AF_TRY(check_loaded(h, "model.diffusion_model."));
+  AF_TRY(check_loaded(h, h->unet_prefix.c_str()));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int dt = h->dtype, D = h->cfg.context_dim;
   const int L = layerwise ? h->cfg.n_context_layers : 1;
@@ -2662,6 +2899,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
   if (twin && (Bf < 2 || Bf % 2)) { af_set_error_msg("af_unet_forward_twin: the batch [x; x] must be even, got %d", Bf); return AF_ERR_INVALID; }
   if (pag && (Bf < 3 || Bf % 3)) { af_set_error_msg("af_unet_forward_pag: the batch [x; x; x] must be a multiple of 3, got %d", Bf); return AF_ERR_INVALID; }
   if (!h->cfg.build_unet) { af_set_error_msg("af_unet_forward: handle has no UNet"); return AF_ERR_STATE; }
+  if (h->is_control) { af_set_error_msg("af_unet_forward: a control handle has no output blocks (af_control_forward)"); return AF_ERR_STATE; }
   if (pag) {
     if (!h->pag_on()) { af_set_error_msg("af_unet_forward_pag: no site set (af_set_pag)"); return AF_ERR_STATE; }
     for (size_t i = 0; i < h->pag_set.size() && i < h->ca_list.size(); ++i)
@@ -2685,6 +2923,23 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
       return AF_ERR_STATE;
     }
     if (replay) AF_TRY(check_loaded(h, "model.diffusion_model."));   // (af_set_context, which a replay does not need, checks this otherwise)
+  }
+  if (h->ctl.res) {   // ControlNet residuals (af_unet_set_control): everything they refuse, before anything is enqueued
+    const int n_in = (int)h->input_blocks.size(), n_out = (int)h->output_blocks.size();
+    const int need = dc_mode == AF_DEEPCACHE_REUSE ? dc_depth : n_in + 1;
+    if (pag) { af_set_error_msg("ControlNet: the PAG form is not supported (detach with af_unet_set_control(NULL))"); return AF_ERR_INVALID; }
+    if (tg.mode) { af_set_error_msg("ControlNet: T-GATE capture / replay is not supported"); return AF_ERR_INVALID; }
+    if (h->ctl.cond_only && !twin) { af_set_error_msg("ControlNet: cond_only needs the twin form"); return AF_ERR_INVALID; }
+    if (h->ctl.Bs != (h->ctl.cond_only ? Bf / 2 : Bf) || h->ctl.H != H || h->ctl.W != W) {
+      af_set_error_msg("ControlNet: the residuals are laid out for %d samples of %d x %d, this forward adds to %d samples of %d x %d",
+                       h->ctl.Bs, h->ctl.H, h->ctl.W, h->ctl.cond_only ? Bf / 2 : Bf, H, W);
+      return AF_ERR_INVALID;
+    }
+    if (n_in != n_out || n_in + 1 > AF_CONTROL_MAX_SEGMENTS) { af_set_error_msg("ControlNet: %d input and %d output blocks (equal, at most %d)", n_in, n_out, AF_CONTROL_MAX_SEGMENTS - 1); return AF_ERR_INVALID; }
+    if (dc_mode == AF_DEEPCACHE_REUSE ? h->ctl.n < need : h->ctl.n != need) {
+      af_set_error_msg("ControlNet: %d residuals attached, this forward takes %s%d", h->ctl.n, dc_mode == AF_DEEPCACHE_REUSE ? "the first " : "", need);
+      return AF_ERR_INVALID;
+    }
   }
   if (tg.mode != AF_TGATE_REPLAY && (!h->ctx_set || h->ctx_Bf != Bf)) { af_set_error_msg("af_unet_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
   const int down = 1 << (h->cfg.n_channel_mult - 1);
@@ -2769,6 +3024,104 @@ int af_unet_forward_pag(af_handle* h, const float* x_dev, const int64_t* t_dev, 
   return unet_forward_entry(h, x_dev, t_dev, eps_dev, Bf, H, W, stream, AF_UNET_FORM_PAG);
 }
 
+// ---- ControlNet ----
+int af_control_num_residuals(af_handle* h) { return (h && h->is_control) ? (int)h->input_blocks.size() + 1 : 0; }
+
+int af_control_set_hint(af_handle* h, const float* hint_dev, int Bh, int H8, int W8, void* stream) {
+  if (!h || !hint_dev) { af_set_error_msg("af_control_set_hint: null argument"); return AF_ERR_INVALID; }
+  if (!h->is_control) { af_set_error_msg("af_control_set_hint: not a control handle (af_config.build_controlnet)"); return AF_ERR_STATE; }
+  if (Bh <= 0 || H8 <= 0 || W8 <= 0 || H8 % 8 || W8 % 8) { af_set_error_msg("af_control_set_hint: hint batch %d, %d x %d (sides must be multiples of 8)", Bh, H8, W8); return AF_ERR_INVALID; }
+  if ((long)Bh * H8 * W8 > 0x7fffffffL) { af_set_error_msg("af_control_set_hint: %d x %d x %d pixels exceed one launch", Bh, H8, W8); return AF_ERR_INVALID; }
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  AF_TRY(check_loaded(h, h->unet_prefix.c_str()));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  h->hint_B = 0;      // (until the network has been enqueued completely)
+  const size_t need = (size_t)Bh * (H8 / 8) * (W8 / 8) * h->cfg.model_channels * esize(h->dtype) + 4096;   // (slack: as ensure_deepcache)
+  if (need > h->hint_g_bytes) {
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if (h->hint_g) hipFree(h->hint_g);
+    h->hint_g = nullptr;
+    h->hint_g_bytes = 0;
+    if (hipMalloc(&h->hint_g, need) != hipSuccess) { h->hint_g = nullptr; af_set_error_msg("hipMalloc of the %zu-byte hint feature failed", need); return AF_ERR_HIP; }
+    h->hint_g_bytes = need;
+  }
+  auto run = [&] { return control_hint_impl(h, s, hint_dev, Bh, H8, W8, h->hint_g); };
+  AF_TRY(run_sized(h, s, run));
+  AF_TRY(run());
+  h->hint_B = Bh; h->hint_H = H8 / 8; h->hint_W = W8 / 8;
+  return AF_OK;
+}
+
+int af_control_forward(af_handle* h, const float* x_dev, const int64_t* t_dev, int Bf, int H, int W, int n_blocks, void* out_dev,
+                       void* stream) {
+  if (!h || !x_dev || !t_dev || !out_dev) { af_set_error_msg("af_control_forward: null argument"); return AF_ERR_INVALID; }
+  if (!h->is_control) { af_set_error_msg("af_control_forward: not a control handle (af_config.build_controlnet)"); return AF_ERR_STATE; }
+  const int n_in = (int)h->input_blocks.size();
+  if (Bf <= 0 || n_blocks < 1 || n_blocks > n_in + 1) { af_set_error_msg("af_control_forward: batch %d, n_blocks %d outside 1 .. %d", Bf, n_blocks, n_in + 1); return AF_ERR_INVALID; }
+  const int down = 1 << (h->cfg.n_channel_mult - 1);
+  if (H <= 0 || W <= 0 || H % down || W % down) { af_set_error_msg("af_control_forward: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
+  if (!h->hint_g || h->hint_B <= 0) { af_set_error_msg("af_control_forward: no hint (af_control_set_hint)"); return AF_ERR_STATE; }
+  if (h->hint_H != H || h->hint_W != W) { af_set_error_msg("af_control_forward: the hint is %d x %d, 8 times a %d x %d latent, not %d x %d", 8 * h->hint_H, 8 * h->hint_W, h->hint_H, h->hint_W, H, W); return AF_ERR_INVALID; }
+  if (Bf % h->hint_B) { af_set_error_msg("af_control_forward: hint batch %d does not divide the batch %d", h->hint_B, Bf); return AF_ERR_INVALID; }
+  if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_control_forward: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  AF_TRY(fold_layernorms(h, s));
+  auto run = [&] { return control_forward_impl(h, s, x_dev, t_dev, Bf, H, W, n_blocks, out_dev); };
+  AF_TRY(run_sized(h, s, run));
+  return run();
+}
+
+int af_unet_set_control(af_handle* h, const void* res_dev, int Bs, int H, int W, int n, const float* scales, int cond_only) {
+  if (!h) { af_set_error_msg("af_unet_set_control: null handle"); return AF_ERR_INVALID; }
+  if (!res_dev) { h->ctl.res = nullptr; h->ctl.n = 0; h->ctl.cond_only = false; return AF_OK; }
+  if (!h->cfg.build_unet || h->is_control) { af_set_error_msg("af_unet_set_control: not a U-Net handle"); return AF_ERR_STATE; }
+  if (n < 1 || n > AF_CONTROL_MAX_SEGMENTS || n > (int)h->input_blocks.size() + 1 || !scales) {
+    af_set_error_msg("af_unet_set_control: %d residuals (1 .. %d) with their scales", n, std::min((int)AF_CONTROL_MAX_SEGMENTS, (int)h->input_blocks.size() + 1));
+    return AF_ERR_INVALID;
+  }
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(scales[i])) { af_set_error_msg("af_unet_set_control: scale %d is not finite", i); return AF_ERR_INVALID; }
+  if (Bs <= 0 || H <= 0 || W <= 0) { af_set_error_msg("af_unet_set_control: residuals for %d samples of %d x %d", Bs, H, W); return AF_ERR_INVALID; }
+  h->ctl.res = res_dev;
+  h->ctl.n = n; h->ctl.Bs = Bs; h->ctl.H = H; h->ctl.W = W;
+  h->ctl.cond_only = cond_only != 0;
+  for (int i = 0; i < n; ++i) h->ctl.scales[i] = scales[i];
+  return AF_OK;
+}
+
+int af_control_plan_query(const af_config* cfg, int H, int W, int max_n, int64_t* out, int* n_out) {
+  if (!cfg || !out || !n_out) { af_set_error_msg("af_control_plan_query: null argument"); return AF_ERR_INVALID; }
+  if (cfg->n_channel_mult <= 0 || cfg->n_channel_mult > 8 || cfg->num_res_blocks <= 0 || cfg->model_channels <= 0) { af_set_error_msg("af_control_plan_query: bad channel_mult / num_res_blocks"); return AF_ERR_INVALID; }
+  const int down = 1 << (cfg->n_channel_mult - 1);
+  if (H <= 0 || W <= 0 || H % down || W % down) { af_set_error_msg("af_control_plan_query: H,W must be multiples of %d", down); return AF_ERR_INVALID; }
+  // (the walk of build_unet, shapes only: conv_in, num_res_blocks blocks per level, a downsample between levels, the middle block)
+  std::vector<std::array<int64_t, 3>> r;
+  int ch = cfg->model_channels, hh = H, ww = W;
+  r.push_back({ch, hh, ww});
+  for (int level = 0; level < cfg->n_channel_mult; ++level) {
+    ch = cfg->channel_mult[level] * cfg->model_channels;
+    for (int k = 0; k < cfg->num_res_blocks; ++k) r.push_back({ch, hh, ww});
+    if (level != cfg->n_channel_mult - 1) { hh /= 2; ww /= 2; r.push_back({ch, hh, ww}); }
+  }
+  r.push_back({ch, hh, ww});
+  *n_out = (int)r.size();
+  if ((int)r.size() > max_n) { af_set_error_msg("af_control_plan_query: %d residuals, room for %d", (int)r.size(), max_n); return AF_ERR_INVALID; }
+  int64_t off = 0;
+  for (size_t i = 0; i < r.size(); ++i) {
+    out[4 * i] = r[i][0]; out[4 * i + 1] = r[i][1]; out[4 * i + 2] = r[i][2]; out[4 * i + 3] = off;
+    off += r[i][0] * r[i][1] * r[i][2];
+  }
+  return AF_OK;
+}
+
+int af_control_stats(af_handle* h, int out[2]) {
+  if (!h || !out) { af_set_error_msg("af_control_stats: null argument"); return AF_ERR_INVALID; }
+  out[0] = h->ctl.last_launches; out[1] = h->ctl.last_segments;
+  return AF_OK;
+}
+int64_t af_control_add_launches(void) { return g_af_control_add_launches; }
+
 int af_unet_num_blocks(af_handle* h) {
   return (h && h->cfg.build_unet) ? (int)(h->input_blocks.size() + 1 + h->output_blocks.size()) : 0;
 }
@@ -2811,6 +3164,7 @@ int af_set_tome(af_handle* h, double ratio, int max_downsample) {
   if (max_downsample != 1 && max_downsample != 2) { af_set_error_msg("af_set_tome: max_downsample %d is neither 1 nor 2", max_downsample); return AF_ERR_INVALID; }
   if (ratio > 0.0) {
     if (!h->cfg.build_unet) { af_set_error_msg("af_set_tome: handle has no UNet"); return AF_ERR_STATE; }
+    if (h->is_control) { af_set_error_msg("af_set_tome: a control handle does not merge tokens"); return AF_ERR_STATE; }
     if (h->dtype == AF_DTYPE_F16) { af_set_error_msg("af_set_tome: token merging takes bf16 and f32 handles (handle is f16)"); return AF_ERR_STATE; }
     if (h->fp8_on) { af_set_error_msg("af_set_tome: token merging does not combine with the fp8 mode (af_set_fp8)"); return AF_ERR_STATE; }
   }
@@ -2878,6 +3232,7 @@ int af_set_pag(af_handle* h, const int* sites, int n_sites) {
   if (n_sites < 0 || (n_sites > 0 && !sites)) { af_set_error_msg("af_set_pag: %d sites without a list", n_sites); return AF_ERR_INVALID; }
   const int n = h->cfg.build_unet ? (int)h->ca_list.size() : 0;
   if (n_sites > 0 && !h->cfg.build_unet) { af_set_error_msg("af_set_pag: handle has no UNet"); return AF_ERR_STATE; }
+  if (n_sites > 0 && h->is_control) { af_set_error_msg("af_set_pag: a control handle has no PAG form"); return AF_ERR_STATE; }
   std::vector<char> set((size_t)n, (char)0);
   for (int i = 0; i < n_sites; ++i) {
     if (sites[i] < 0 || sites[i] >= n) { af_set_error_msg("af_set_pag: site %d out of range (%d sites)", sites[i], n); return AF_ERR_INVALID; }
@@ -2914,6 +3269,7 @@ int af_tgate_set(af_handle* h, int mode) {
   if (!h) { af_set_error_msg("af_tgate_set: null handle"); return AF_ERR_INVALID; }
   if (mode != AF_TGATE_OFF && mode != AF_TGATE_CAPTURE && mode != AF_TGATE_REPLAY) { af_set_error_msg("af_tgate_set: mode %d (0 off, 1 capture, 2 replay)", mode); return AF_ERR_INVALID; }
   if (mode && !h->cfg.build_unet) { af_set_error_msg("af_tgate_set: handle has no UNet"); return AF_ERR_STATE; }
+  if (mode && h->is_control) { af_set_error_msg("af_tgate_set: a control handle has no T-GATE mode"); return AF_ERR_STATE; }
   h->tg.mode = mode;
   return AF_OK;
 }
@@ -3155,6 +3511,7 @@ int64_t af_conv_attn_short_launches(void) { return g_af_conv_attn_short_launches
 int64_t af_gn_consumer_launches(void) { return g_af_gn_consumer_launches; }
 int af_set_fp8(af_handle* h, int on) {
   if (!h) { af_set_error_msg("af_set_fp8: null handle"); return AF_ERR_INVALID; }
+  if (on && h->is_control) { af_set_error_msg("af_set_fp8: the fp8 mode is not built for a control handle (run it in bf16)"); return AF_ERR_STATE; }
   if (on && h->tome_ratio > 0.0) { af_set_error_msg("af_set_fp8: the fp8 mode does not combine with token merging (af_set_tome)"); return AF_ERR_STATE; }
   if (on && h->dtype != AF_DTYPE_BF16) { af_set_error_msg("af_set_fp8: the fp8 convolutions extend the bf16 mode (handle is %s)", h->dtype == AF_DTYPE_F16 ? "f16" : "f32"); return AF_ERR_STATE; }
   if (h->fp8_on != (on != 0)) h->dc.valid = false;   // (a kept DeepCache feature belongs to the mode that wrote it)

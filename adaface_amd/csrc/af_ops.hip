@@ -1216,6 +1216,23 @@ int af_op_tgate_add(int dtype, const void* t1_dev, const void* src_dev, void* t2
   return AF_OK;
 }
 
+// The ControlNet residual add (af_controlnet.hip) on caller-owned buffers of `dtype` elements: one launch for all n segments
+int af_op_control_add(int dtype, int n, void* const* dst_dev, const void* const* src_dev, const int* C, const int* ld,
+                      const int64_t* rows_per_sample, const float* scales, int Bs, int Bd, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_op_control_add: storage type %d", dtype); return AF_ERR_INVALID; }
+  if (n < 1 || n > AF_CONTROL_MAX_SEGMENTS) { af_set_error_msg("af_op_control_add: %d segments (1 .. %d)", n, (int)AF_CONTROL_MAX_SEGMENTS); return AF_ERR_INVALID; }
+  if (!dst_dev || !src_dev || !C || !ld || !rows_per_sample || !scales) { af_set_error_msg("af_op_control_add: null argument"); return AF_ERR_INVALID; }
+  if (Bs <= 0 || (Bd != Bs && Bd != 2 * Bs)) { af_set_error_msg("af_op_control_add: dst batch %d for a src batch of %d (equal, or twice it)", Bd, Bs); return AF_ERR_INVALID; }
+  AfControlSeg segs[AF_CONTROL_MAX_SEGMENTS];
+  for (int k = 0; k < n; ++k) {
+    if (rows_per_sample[k] <= 0) { af_set_error_msg("af_op_control_add: segment %d has %lld rows per sample", k, (long long)rows_per_sample[k]); return AF_ERR_INVALID; }
+    segs[k] = AfControlSeg{dst_dev[k], src_dev[k], (long)Bs * rows_per_sample[k], C[k], ld[k], scales[k]};
+  }
+  if (AF_TYPED(dtype, af_launch_control_add<Elem>(segs, n, s))) return AF_ERR_INVALID;
+  return AF_OK;
+}
+
 int af_op_timestep_embedding(int dtype, const int64_t* t_dev, float* y_dev, int B, int dim, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Tmp tmp;

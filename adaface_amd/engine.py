@@ -123,6 +123,63 @@ def pag_scale_at(t, pag_scale: float, pag_adaptive_scale: float = 0.0) -> float:
     return max(float(pag_scale) - float(pag_adaptive_scale) * (1000.0 - float(t)), 0.0)
 
 
+def check_control_scales(scale=1.0, scales=None, n: int = 13) -> tuple:
+    """The n per-residual scales of ControlNet: `scale` on every residual, or the caller's list of exactly n finite numbers
+    (cldm's guess mode is the list scale * 0.825 ** (n - 1 - i)).  ValueError for anything else.  No GPU is needed."""
+    import math
+    if scales is None:
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(float(scale)):
+            raise ValueError(f"ControlNet: scale {scale!r} (a finite number)")
+        return (float(scale),) * n
+    scales = list(scales)
+    if len(scales) != n:
+        raise ValueError(f"ControlNet: {len(scales)} scales for {n} residuals")
+    for i, v in enumerate(scales):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+            raise ValueError(f"ControlNet: scale {i} is {v!r} (a finite number)")
+    return tuple(float(v) for v in scales)
+
+
+def check_control_window(t_range) -> tuple:
+    """(t_lo, t_hi) of the control window in DDPM timesteps; None = always (0, 999).  ValueError for anything else."""
+    if t_range is None:
+        return (0, 999)
+    try:
+        lo, hi = t_range
+        lo, hi = int(lo), int(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"ControlNet: t_range {t_range!r} (a pair (t_lo, t_hi) of timesteps)") from None
+    if lo > hi:
+        raise ValueError(f"ControlNet: t_range ({lo}, {hi}) is empty")
+    return (lo, hi)
+
+
+def control_window_from_fractions(start: float = 0.0, end: float = 1.0) -> tuple:
+    """Fractions of the schedule (0 = the first, noisiest step, 1 = the last) -> (t_lo, t_hi) = (999 (1 - end), 999 (1 - start)),
+    rounded to the nearest timestep."""
+    for name, v in (("start", start), ("end", end)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"ControlNet: control {name} {v!r} (a fraction in [0, 1])")
+    if float(start) > float(end):
+        raise ValueError(f"ControlNet: control start {start} is behind control end {end}")
+    return (int(round(999 * (1.0 - float(end)))), int(round(999 * (1.0 - float(start)))))
+
+
+def control_active(t, window) -> bool:
+    """Is control on at this call?  Iff t_lo <= t <= t_hi for EVERY timestep of the batch."""
+    ts = [int(v) for v in (t.reshape(-1).tolist() if hasattr(t, "reshape") else list(t))]
+    return all(window[0] <= v <= window[1] for v in ts)
+
+
+def control_plan(unet_cfg, H: int, W: int) -> list:
+    """[(C, H, W, element offset for one sample)] of the 13 (SD-1.5) ControlNet residuals of an H x W latent, from the
+    constructor arguments alone (af_control_plan_query).  No GPU is needed."""
+    get = unet_cfg.get if isinstance(unet_cfg, dict) else (lambda k, d=None: getattr(unet_cfg, k, d))
+    kw = {k: get(k) for k in ("in_channels", "model_channels", "num_res_blocks", "attention_resolutions", "channel_mult",
+                              "num_heads", "context_dim")}
+    return _lib.control_plan_query(kw, H, W)
+
+
 def _fill(arr, values: Sequence[int]):
     if len(values) > 8:
         raise ValueError("at most 8 entries supported")
@@ -132,10 +189,11 @@ def _fill(arr, values: Sequence[int]):
 
 class Engine:
     def __init__(self, *, dtype: str = "bf16", device: int = 0, unet: Optional[dict] = None, vae: Optional[dict] = None,
-                 clip: Optional[dict] = None):
+                 clip: Optional[dict] = None, controlnet: Optional[dict] = None):
         """unet: UNetModel ctor kwargs (in_channels, model_channels, out_channels, num_res_blocks,
         attention_resolutions, channel_mult, num_heads, context_dim, transformer_depth);
-        vae: Decoder ddconfig (ch, out_ch, ch_mult, num_res_blocks, z_channels) + embed_dim."""
+        vae: Decoder ddconfig (ch, out_ch, ch_mult, num_res_blocks, z_channels) + embed_dim;
+        controlnet: cldm ControlNet ctor kwargs (the U-Net's, plus hint_channels): a control handle, a handle of its own."""
         self._lib = _lib.load()
         self._h = C.c_void_p()
         if not torch.cuda.is_available():
@@ -146,20 +204,7 @@ class Engine:
         self.device = torch.device("cuda", device)
         if unet is not None:
             cfg.build_unet = 1
-            cfg.in_channels = unet["in_channels"]
-            cfg.model_channels = unet["model_channels"]
-            cfg.out_channels = unet["out_channels"]
-            cfg.num_res_blocks = unet["num_res_blocks"]
-            ar = list(unet["attention_resolutions"])
-            cm = list(unet["channel_mult"])
-            cfg.n_attention_resolutions = len(ar)
-            _fill(cfg.attention_resolutions, ar)
-            cfg.n_channel_mult = len(cm)
-            _fill(cfg.channel_mult, cm)
-            cfg.num_heads = unet["num_heads"]
-            cfg.context_dim = unet["context_dim"]
-            cfg.transformer_depth = unet.get("transformer_depth", 1)
-            cfg.n_context_layers = unet.get("n_context_layers", 16)
+            _lib.fill_unet_config(cfg, unet)
         if vae is not None:
             cfg.build_vae = 1
             cfg.vae_ch = vae["ch"]
@@ -177,7 +222,16 @@ class Engine:
             cfg.build_clip = 1
             cfg.clip_vocab, cfg.clip_hidden, cfg.clip_layers = clip["vocab"], clip["hidden"], clip["layers"]
             cfg.clip_heads, cfg.clip_intermediate, cfg.clip_max_pos = clip["heads"], clip["intermediate"], clip["max_pos"]
+        if controlnet is not None:
+            if unet is not None or vae is not None or clip is not None:
+                raise ValueError("Engine: a ControlNet is an engine of its own (controlnet= with nothing else)")
+            cfg.build_controlnet = 1
+            _lib.fill_unet_config(cfg, controlnet)
+            cfg.hint_channels = controlnet.get("hint_channels", 3)
+            unet = dict(controlnet)         # (set_context and the plan read the U-Net fields)
         self.unet_cfg, self.vae_cfg, self.clip_cfg = unet, vae, clip
+        self.is_control = controlnet is not None
+        self._control_ref = None            # (set_control: the residual buffer the handle points into stays alive here)
         torch.cuda.init()
         check(self._lib.af_create(device, C.byref(cfg), C.byref(self._h)), "af_create")
         self._ctx_key = None
@@ -320,6 +374,93 @@ class Engine:
             check(self._lib.af_unet_forward_twin(self._h, ptr(x), ptr(t), ptr(out), 2 * B, H, W, stream_ptr()),
                   "af_unet_forward_twin")
         return out
+
+    # -- ControlNet (DESIGN 2r) ---------------------------------------------------------------
+    def control_plan(self, H: int, W: int) -> list:
+        """[(C, H, W, element offset for one sample)] of the residuals of an H x W latent (af_control_plan_query)."""
+        return control_plan(self.unet_cfg, H, W)
+
+    def control_set_hint(self, hint: torch.Tensor):
+        """af_control_set_hint (a control engine): hint fp32 [Bh, hint_channels, 8 H, 8 W], values in [0, 1], through the hint
+        network once; the forwards that follow read the kept feature (Bh = 1: one hint for every sample)."""
+        if not hint.is_cuda or hint.dim() != 4:
+            raise ValueError("control_set_hint: the hint must be a device tensor [Bh, C, 8 H, 8 W]")
+        hint = hint.contiguous().float()
+        Bh, Ch, H8, W8 = hint.shape
+        if Ch != self.unet_cfg.get("hint_channels", 3):
+            raise ValueError(f"control_set_hint: {Ch} hint channels, the ControlNet takes {self.unet_cfg.get('hint_channels', 3)}")
+        if H8 % 8 or W8 % 8:
+            raise ValueError(f"control_set_hint: hint sides {H8} x {W8} must be multiples of 8")
+        check(self._lib.af_control_set_hint(self._h, ptr(hint), Bh, H8, W8, stream_ptr()), "af_control_set_hint")
+        self.hint_shape = (Bh, H8, W8)
+
+    def control_forward(self, x: torch.Tensor, t: torch.Tensor, n_blocks: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """af_control_forward (a control engine; context set for len(x) samples, hint set): the residuals of the first n_blocks
+        blocks (None: all, input blocks and middle block) as ONE flat tensor in the engine's storage dtype -- residual i of the
+        batch is out[B * off_i : B * (off_i + C_i H_i W_i)] viewed [B, H_i, W_i, C_i] (control_plan; control_residuals splits)."""
+        x = x.contiguous().float()
+        t = t.contiguous().long()
+        B, _, H, W = x.shape
+        plan = self.control_plan(H, W)
+        n = len(plan) if n_blocks is None else int(n_blocks)
+        if not 1 <= n <= len(plan):
+            raise ValueError(f"control_forward: n_blocks {n_blocks!r} outside 1 .. {len(plan)}")
+        total = B * sum(c * hh * ww for c, hh, ww, _ in plan[:n])
+        from .ops import STORAGE_TORCH
+        dt = next(v for k, v in STORAGE_TORCH.items() if DTYPES[k] == DTYPES[self.dtype])
+        if out is None:
+            out = torch.empty(total, device=x.device, dtype=dt)
+        elif out.dtype != dt or out.numel() < total or not out.is_contiguous():
+            raise ValueError("control_forward: out must be a contiguous tensor of the storage dtype with room for the residuals")
+        check(self._lib.af_control_forward(self._h, ptr(x), ptr(t), B, H, W, n, ptr(out), stream_ptr()), "af_control_forward")
+        return out
+
+    def control_residuals(self, flat: torch.Tensor, B: int, H: int, W: int, n_blocks: Optional[int] = None) -> list:
+        """Views [B, H_i, W_i, C_i] (NHWC) of the residuals inside control_forward's flat result."""
+        plan = self.control_plan(H, W)
+        n = len(plan) if n_blocks is None else int(n_blocks)
+        return [flat[B * off: B * (off + c * hh * ww)].view(B, hh, ww, c) for c, hh, ww, off in plan[:n]]
+
+    def set_control(self, residuals: Optional[torch.Tensor], scales=None, cond_only: bool = False, source=None, shape=None):
+        """af_unet_set_control (a U-Net engine): attach control_forward's flat result (its first len(scales) residuals) to the
+        forwards that follow; None detaches.  shape = (B, H, W) of the x that control_forward ran on.  source: the control engine that made them -- its storage dtype and device must be
+        this engine's (ValueError otherwise).  The buffer is kept alive until it is replaced or detached."""
+        if residuals is None:
+            check(self._lib.af_unet_set_control(self._h, None, 0, 0, 0, 0, None, 0), "af_unet_set_control")
+            self._control_ref = None
+            return
+        from .ops import STORAGE_TORCH
+        if source is not None:
+            if DTYPES[source.dtype] != DTYPES[self.dtype]:
+                raise ValueError(f"set_control: the control engine's dtype {source.dtype!r} is not this engine's storage dtype {self.dtype!r}")
+            if source.device != self.device:
+                raise ValueError(f"set_control: the control engine lives on {source.device}, this engine on {self.device}")
+        names = {v: k for k, v in STORAGE_TORCH.items()}
+        if not residuals.is_cuda or residuals.device != self.device or not residuals.is_contiguous():
+            raise ValueError(f"set_control: the residuals must be a contiguous tensor on {self.device}")
+        if residuals.dtype not in names or DTYPES[names[residuals.dtype]] != DTYPES[self.dtype]:
+            raise ValueError(f"set_control: residuals of {residuals.dtype}, this engine stores {self.dtype!r}")
+        scales = [float(v) for v in scales]
+        if shape is None:
+            raise ValueError("set_control: shape=(B, H, W) of the control forward is needed")
+        B, H, W = (int(v) for v in shape)
+        plan = self.control_plan(H, W)
+        if not 1 <= len(scales) <= len(plan):
+            raise ValueError(f"set_control: {len(scales)} scales for at most {len(plan)} residuals")
+        need = B * sum(c * hh * ww for c, hh, ww, _ in plan[:len(scales)])
+        if residuals.numel() < need:
+            raise ValueError(f"set_control: {residuals.numel()} elements, {len(scales)} residuals of {B} x {H} x {W} take {need}")
+        arr = (C.c_float * len(scales))(*scales)
+        check(self._lib.af_unet_set_control(self._h, ptr(residuals), B, H, W, len(scales), arr, 1 if cond_only else 0),
+              "af_unet_set_control")
+        self._control_ref = residuals
+
+    def control_stats(self) -> dict:
+        """af_control_stats: {"launches", "segments"} of the residual add in the last U-Net forward."""
+        out = (C.c_int * 2)()
+        check(self._lib.af_control_stats(self._h, out), "af_control_stats")
+        return {"launches": int(out[0]), "segments": int(out[1])}
 
     def tgate_num_sites(self) -> int:
         """Cross-attention sites of the U-Net (forward order, the numbering of pag_sites)."""

@@ -111,6 +111,41 @@ def unet_param_shapes(*, in_channels, model_channels, out_channels, num_res_bloc
     return shapes
 
 
+HINT_CHANNELS = (16, 16, 32, 32, 96, 96, 256)     # input_hint_block of cldm's ControlNet; strides 1 1 2 1 2 1 2 1
+HINT_STRIDES = (1, 1, 2, 1, 2, 1, 2, 1)
+
+
+def controlnet_param_shapes(*, in_channels, model_channels, num_res_blocks, attention_resolutions, channel_mult, context_dim,
+                            hint_channels=3, transformer_depth=1, **_unused) -> Dict[str, Shape]:
+    """Keys relative to `control_model.`, exactly as cldm/cldm.py's ControlNet registers them: the U-Net's time_embed,
+    input_blocks and middle_block, input_hint_block.{0,2,..,14} (3x3 convolutions hint_channels -> 16 -> 16 -> 32 -> 32 -> 96 ->
+    96 -> 256 -> model_channels), zero_convs.i.0 (1x1, one per input block) and middle_block_out.0."""
+    unet = unet_param_shapes(in_channels=in_channels, model_channels=model_channels, out_channels=in_channels,
+                             num_res_blocks=num_res_blocks, attention_resolutions=attention_resolutions,
+                             channel_mult=channel_mult, context_dim=context_dim, transformer_depth=transformer_depth)
+    shapes = {k: v for k, v in unet.items() if k.startswith(("time_embed.", "input_blocks.", "middle_block."))}
+    chans = (hint_channels,) + HINT_CHANNELS + (model_channels,)
+    for k in range(8):
+        shapes[f"input_hint_block.{2 * k}.weight"] = (chans[k + 1], chans[k], 3, 3)
+        shapes[f"input_hint_block.{2 * k}.bias"] = (chans[k + 1],)
+    inputs, middle, _ = unet_blocks(model_channels, channel_mult, num_res_blocks, attention_resolutions, in_channels)
+    ch = model_channels
+    for i, layers in enumerate(inputs):
+        for d in layers:
+            if d[0] in ("conv_in", "res"):
+                ch = d[2]
+        shapes[f"zero_convs.{i}.0.weight"] = (ch, ch, 1, 1)
+        shapes[f"zero_convs.{i}.0.bias"] = (ch,)
+    shapes["middle_block_out.0.weight"] = (ch, ch, 1, 1)
+    shapes["middle_block_out.0.bias"] = (ch,)
+    return shapes
+
+
+def controlnet_zero_init_names(shapes: Dict[str, Shape]) -> List[str]:
+    """What cldm zero-initialises: the U-Net part's zero modules, every zero_conv, middle_block_out and the last hint conv."""
+    return unet_zero_init_names(shapes) + [k for k in shapes if k.startswith(("zero_convs.", "middle_block_out.", "input_hint_block.14."))]
+
+
 # tensors the reference zero-initialises (zero_module: openaimodel.py:233,696; attention.py:313)
 def unet_zero_init_names(shapes: Dict[str, Shape]) -> List[str]:
     out = []

@@ -58,6 +58,7 @@ class UNetModel(HipModule):
         shapes = layout.unet_param_shapes(**self._layout_kwargs())
         build_param_tree(self, shapes, zero_init=layout.unet_zero_init_names(shapes))
         object.__setattr__(self, "_ctx_key", None)
+        object.__setattr__(self, "_control", None)     # ControlNet (set_control)
 
     def _layout_kwargs(self):
         return dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
@@ -164,6 +165,81 @@ class UNetModel(HipModule):
     def pag(self) -> tuple:
         return self._pag
 
+    def set_control(self, controlnet, hint=None, scale=1.0, scales=None, t_range=None, cond_only=False):
+        """ControlNet (Zhang et al., ICCV 2023; not in the reference, off by default): every forward whose timesteps ALL lie in
+        t_range = (t_lo, t_hi) (DDPM timesteps; None = always) also runs `controlnet` (a ControlNet module of this U-Net's
+        layout and storage dtype) on (x, t, the context this forward uses, hint) and adds its 13 residuals, times `scale` or the
+        per-residual list `scales`, to the skip connections where the decoder reads them and to the middle block's output.
+        hint: [1 or B, 3, 8 H, 8 W] in [0, 1]; its features are computed once.  Under cfg_twin the control branch runs on both
+        legs; cond_only=True runs it on the conditional samples only and leaves the unconditional leg bit for bit as it is
+        without control.  Outside the window the forward is exactly the uncontrolled one.  deep_cache composes (a reuse step of
+        depth k runs the first k control blocks only); cfg_pag and tgate are refused.  set_control(None) switches it off."""
+        from adaface_amd.engine import check_control_scales, check_control_window
+        if controlnet is None:
+            object.__setattr__(self, "_control", None)
+            if self._engine is not None:
+                self._engine.set_control(None)
+            return self
+        from adaface_amd.ldm.modules.diffusionmodules.controlnet import ControlNet
+        if not isinstance(controlnet, ControlNet):
+            raise TypeError(f"set_control: a ControlNet module is needed, got {type(controlnet).__name__}")
+        mine, theirs = self._layout_kwargs(), controlnet._layout_kwargs()
+        for k in ("in_channels", "model_channels", "num_res_blocks", "attention_resolutions", "channel_mult", "context_dim",
+                  "transformer_depth"):
+            if mine[k] != theirs[k]:
+                raise ValueError(f"set_control: the ControlNet's {k} = {theirs[k]!r}, this U-Net's {mine[k]!r}")
+        if hint is None or hint.dim() != 4 or hint.shape[1] != controlnet.hint_channels:
+            raise ValueError(f"set_control: hint [1 or B, {controlnet.hint_channels}, 8 H, 8 W] is needed")
+        if hint.shape[2] % 8 or hint.shape[3] % 8:
+            raise ValueError(f"set_control: hint sides {tuple(hint.shape[2:])} must be multiples of 8")
+        n = len(layout.unet_blocks(self.model_channels, self.channel_mult, self.num_res_blocks, self.attention_resolutions,
+                                   self.in_channels)[0]) + 1
+        ctl = dict(net=controlnet, hint=hint, scales=check_control_scales(scale, scales, n), window=check_control_window(t_range),
+                   cond_only=bool(cond_only))
+        object.__setattr__(self, "_control", ctl)
+        return self
+
+    @property
+    def control(self):
+        return self._control
+
+    def _apply_control(self, eng, x, timesteps, ctx, given, B1, layerwise, cfg_twin, deep_cache):
+        """Run the control branch for this forward and attach its residuals to `eng` (or detach, outside the window)."""
+        from adaface_amd.engine import control_active
+        ctl = self._control
+        if ctl is None:
+            return
+        if not control_active(timesteps, ctl["window"]):
+            eng.set_control(None)
+            return
+        net, hint = ctl["net"], ctl["hint"]
+        H, W = x.shape[2], x.shape[3]
+        storage = lambda d: "bf16" if d == "fp8" else d
+        if storage(net.compute_dtype) != storage(self.compute_dtype):
+            raise ValueError(f"ControlNet: its compute dtype {net.compute_dtype!r} is not this U-Net's storage dtype "
+                             f"{storage(self.compute_dtype)!r} (set_compute_dtype on the ControlNet)")
+        if tuple(hint.shape[2:]) != (8 * H, 8 * W):
+            raise ValueError(f"ControlNet: the hint is {tuple(hint.shape[2:])}, 8 times the {H} x {W} latent is {(8 * H, 8 * W)}")
+        if hint.shape[0] not in (1, B1):
+            raise ValueError(f"ControlNet: hint batch {hint.shape[0]} for {B1} samples (1 or {B1})")
+        ceng = net.engine(x.device)
+        cond_only = ctl["cond_only"] and cfg_twin
+        both = cfg_twin and not cond_only
+        Bc = 2 * B1 if both else B1
+        if cfg_twin and not both:                       # the conditional samples' context: whole samples, their layer slices together
+            per = ctx.shape[0] // (2 * B1)
+            ctx = ctx[:B1 * per]
+        net._set_hint(ceng, hint)
+        net._set_context(ceng, ctx, (given, Bc), Bc, layerwise)
+        xc = torch.cat([x, x]) if both else x
+        tc = torch.cat([timesteps, timesteps]) if both else timesteps
+        n_blocks, scales = None, ctl["scales"]
+        if deep_cache is not None and deep_cache[0] == "reuse":
+            n_blocks = int(deep_cache[1])
+            scales = scales[:n_blocks]
+        flat = ceng.control_forward(xc, tc.to(x.device), n_blocks)
+        eng.set_control(flat, scales, cond_only=cond_only, source=ceng, shape=(Bc, H, W))
+
     @staticmethod
     def _conv_attn_spec(ks, placeholder2indices):
         """(ks, batch indices, token positions) for Engine.set_conv_attn from the reference's
@@ -210,13 +286,18 @@ class UNetModel(HipModule):
         slices, and the conv-attention rows of the samples < B are repeated for the samples + 2B.
         tgate (not in the reference; T-GATE, set by this package's samplers, tgate.py): None = off; "capture" = this forward
         (plain or cfg_twin), which also keeps every cross-attention output, averaged over the legs; "replay" = the plain
-        forward with every cross-attention replaced by what the capture kept -- the context is neither set nor read."""
+        forward with every cross-attention replaced by what the capture kept -- the context is neither set nor read.
+        With a ControlNet set (set_control) and every timestep inside its window, the control branch runs first on the same x,
+        timesteps and context (after the compel-cfg weighting) and its residuals are added inside this forward; cfg_pag and
+        tgate then raise NotImplementedError."""
         if y is not None:
             raise NotImplementedError("class-conditional UNet (num_classes) is not on the path")
         if tgate not in (None, "capture", "replay"):
             raise ValueError(f"UNetModel.forward: tgate {tgate!r} (None, \"capture\" or \"replay\")")
         if tgate is not None and cfg_pag:
             raise NotImplementedError("UNetModel.forward: T-GATE with the PAG form (the third leg has no cached counterpart)")
+        if self._control is not None and (cfg_pag or tgate is not None):
+            raise NotImplementedError("UNetModel.forward: ControlNet does not combine with the PAG form or T-GATE (set_control(None))")
         if tgate == "replay":
             if cfg_twin:
                 raise ValueError("UNetModel.forward: a T-GATE replay runs one leg (no cfg_twin)")
@@ -271,6 +352,9 @@ class UNetModel(HipModule):
             eng.set_context(ctx, B, layerwise)
             object.__setattr__(self, "_ctx_key", key if cache_ok else None)
             object.__setattr__(self, "_ctx_ref", (context, given))
+        if self._control is not None:
+            # (the context AFTER the compel-cfg weighting, and that tensor object as the key of the control branch's K / V)
+            self._apply_control(eng, x, timesteps.to(x.device), context.to(x.device), context, B1, layerwise, bool(cfg_twin), deep_cache)
         tg = {} if tgate is None else {"tgate": tgate}
         if deep_cache is None:
             fwd = eng.unet_forward_pag if cfg_pag else eng.unet_forward_twin if cfg_twin else eng.unet_forward

@@ -401,6 +401,43 @@ def tgate_add(t1, src, legs=1, cache=False, stats_parts=0, out=None, cache_out=N
     return out, cache_out, stats
 
 
+def control_add(dsts, srcs, scales, cond_only=False):
+    """The ControlNet residual add (af_op_control_add) on the caller's own buffers, in place, ONE launch for all segments:
+    dsts[k] [Bd, P_k, C_k] (rows of C_k contiguous elements, any row stride and alignment: a channel range of a wider buffer)
+    += scales[k] * srcs[k] [Bs, P_k, C_k] (dense), fp32 product rounded, fp32 sum rounded, then the storage rounding.  Bd = Bs,
+    or cond_only: Bd = 2 Bs and only the samples < Bs are touched.  All of one storage dtype (bf16, fp16 or f32); at most 16
+    segments.  Nothing outside the addressed channel ranges is read or written.  Returns dsts."""
+    lib = _lib.load()
+    names = {v: k for k, v in STORAGE_TORCH.items()}
+    dsts, srcs, scales = list(dsts), list(srcs), [float(v) for v in scales]
+    n = len(dsts)
+    if not (n == len(srcs) == len(scales)) or n < 1:
+        raise ValueError(f"control_add: {n} dsts, {len(srcs)} srcs, {len(scales)} scales")
+    if n > _lib.CONTROL_MAX_SEGMENTS:
+        raise ValueError(f"control_add: {n} segments (at most {_lib.CONTROL_MAX_SEGMENTS})")
+    dt = dsts[0].dtype
+    if dt not in names or any(t.dtype != dt for t in dsts + srcs):
+        raise ValueError(f"control_add: one storage dtype for every operand, got {sorted({str(t.dtype) for t in dsts + srcs})}")
+    if any(t.dim() != 3 for t in dsts + srcs):
+        raise ValueError("control_add: operands are [B, P, C] views")
+    Bs, Bd = srcs[0].shape[0], dsts[0].shape[0]
+    if Bd != (2 * Bs if cond_only else Bs):
+        raise ValueError(f"control_add: dst batch {Bd} for a src batch of {Bs} (cond_only={bool(cond_only)})")
+    lds = []
+    for k, (d, s) in enumerate(zip(dsts, srcs)):
+        if s.shape[0] != Bs or d.shape[0] != Bd or tuple(s.shape[1:]) != tuple(d.shape[1:]):
+            raise ValueError(f"control_add: segment {k}: dst {tuple(d.shape)} against src {tuple(s.shape)}")
+        if not s.is_cuda or not s.is_contiguous():
+            raise ValueError(f"control_add: segment {k}: src must be a dense device tensor (strides {s.stride()})")
+        lds.append(_rows_ld(f"dsts[{k}]", d, d.shape))
+    P = _lib.C.c_void_p
+    check(lib.af_op_control_add(DTYPES[names[dt]], n, (P * n)(*[d.data_ptr() for d in dsts]), (P * n)(*[s.data_ptr() for s in srcs]),
+                                (_lib.C.c_int * n)(*[int(d.shape[2]) for d in dsts]), (_lib.C.c_int * n)(*lds),
+                                (_lib.C.c_int64 * n)(*[int(d.shape[1]) for d in dsts]), (_lib.C.c_float * n)(*scales),
+                                int(Bs), int(Bd), stream_ptr()), "af_op_control_add")
+    return dsts
+
+
 def lora_repack(base, adapters=(), cin_pad=None, ldw=None, row_off=0, rows_total=None, perm=False, dtype="bf16", out=None):
     """The weight repack with LoRA adapters merged (af_op_lora_repack): base [rows, cin(, ks, ks)] fp32 and adapters
     [(up [rows, r(, 1, 1)], down [r, cin(, ks, ks)], s)] (at most 8, r <= 256) -> the packed buffer [rows_total, ldw] in the storage

@@ -68,6 +68,10 @@ typedef struct af_config {
    * 77 positions, quick_gelu) — the conditioning producer in front of the path */
   int build_clip;
   int clip_vocab, clip_hidden, clip_layers, clip_heads, clip_intermediate, clip_max_pos;
+  /* ControlNet (cldm.py ControlNet; names "control_model.<k>"): the U-Net's encoder and middle block under the U-Net fields
+   * above, plus input_hint_block, zero_convs and middle_block_out.  A handle of its own: not together with build_unet. */
+  int build_controlnet;
+  int hint_channels;              /* 3 */
 } af_config;
 
 const char* af_last_error(void);
@@ -273,6 +277,48 @@ int af_tgate_read_site(af_handle* h, int site, float* out_dev, void* stream);
 int af_op_tgate_add(int dtype, const void* t1_dev, const void* src_dev, void* t2_dev, void* cache_dev, float* stats_dev, int parts,
                     int L, int B, int N, int C, int ld_t1, int ld_src, int ld_t2, int ld_cache, void* stream);
 
+/* ControlNet (Zhang, Rao, Agrawala, ICCV 2023; cldm/cldm.py of lllyasviel/ControlNet), opt-in.  A control handle
+ * (af_config.build_controlnet) owns time_embed, input_blocks, middle_block, input_hint_block, zero_convs and middle_block_out
+ * under "control_model."; af_load_tensor* and af_set_context work on it as on a U-Net handle (its 7 cross-attention layers read
+ * the layer slices 0 .. 6).  It has no output blocks: the af_unet_forward* entry points, af_set_fp8, af_set_tome, af_set_pag and
+ * af_tgate_set refuse it (AF_ERR_STATE).
+ * af_control_set_hint: hint_dev fp32 NCHW [Bh][hint_channels][H8][W8] (values in [0, 1]; H8, W8 multiples of 8) through
+ *   input_hint_block (3x3 convolutions hint_channels -> 16 -> 16 -> 32/2 -> 32 -> 96/2 -> 96 -> 256/2 -> model_channels, SiLU
+ *   between them) into a handle-owned g [Bh][H8 / 8][W8 / 8][model_channels], once; the forwards only read it.  Every af_load_tensor* drops it.
+ * af_control_forward: the walk emb = time_embed(t); h = x; for block i: h = block_i(h, emb, ctx), after block 0 h += g;
+ *   r_i = zero_convs.i.0(h); r_mid = middle_block_out.0(middle_block(h)) on Bf samples (the context was set for Bf).  g's sample
+ *   for sample b is b mod Bh (Bh must divide Bf; 8 H = H8, 8 W = W8).  n_blocks = n_in + 1 (af_control_num_residuals) is the
+ *   full set; n_blocks = k <= n_in stops after input block k - 1.  out_dev receives the residuals unscaled, in the handle's
+ *   storage dtype, dense NHWC [Bf][H_i][W_i][C_i], back to back in block order (af_control_plan_query: the layout).
+ * af_unet_set_control (a U-Net handle): res_dev = such a buffer of n residuals for Bs samples of an H x W latent (the layout
+ *   af_control_forward(Bf = Bs, H, W, n_blocks = n) wrote), in this handle's storage dtype;
+ *   scales[n]; the forwards that follow add s_i r_i to the skip connection of input block i where the decoder reads it, and
+ *   s_mid r_mid to the middle block's output, in ONE launch (csrc/af_controlnet.hip) between the middle block and the first
+ *   output block -- the encoder itself sees the unmodified skips; FreeU filters the controlled skip.  Bs = Bf, or cond_only:
+ *   the twin form with Bs = Bf / 2, where only the first half of the batch is touched and the second is bit for bit what it is
+ *   without control.  A full forward or a DeepCache refresh needs n = n_in + 1; a reuse step of depth k applies residuals
+ *   0 .. k - 1 (n >= k; the middle residual is inside the kept feature).  res_dev = NULL detaches: the forwards are then what
+ *   they are without this call, launch for launch, bit for bit.  Refused on the host with a message before any launch
+ *   (AF_ERR_INVALID): the PAG form, a T-GATE mode, cond_only on another form than the twin, n, Bs, H or W that do not match the forward,
+ *   more than 16 residuals, a scale that is not finite.
+ * af_control_plan_query (host only): out[4 i .. 4 i + 3] = {C_i, H_i, W_i, element offset per sample batch of one} of residual
+ *   i for an H x W latent (offsets for B samples are B times these); *n_out = n_in + 1.  max_n: room in out, in residuals.
+ * af_control_stats: out = {control-add launches (0 or 1), segments applied} of the handle's last U-Net forward.
+ * af_control_add_launches: launches of the add kernel since the library was loaded.
+ * af_op_control_add: the kernel as an operator on caller buffers of `dtype` elements: segment k is dst_dev[k] [Bd][P_k][ld_k]
+ *   (C_k <= ld_k) += scales[k] * src_dev[k] [Bs][P_k][C_k] (dense), fp32 product rounded, fp32 sum rounded, storage rounding;
+ *   Bd = Bs, or Bd = 2 Bs (only the samples < Bs are touched).  n <= 16.  Any alignment. */
+int af_control_set_hint(af_handle* h, const float* hint_dev, int Bh, int H8, int W8, void* stream);
+int af_control_num_residuals(af_handle* h);
+int af_control_forward(af_handle* h, const float* x_dev, const int64_t* t_dev, int Bf, int H, int W, int n_blocks, void* out_dev,
+                       void* stream);
+int af_unet_set_control(af_handle* h, const void* res_dev, int Bs, int H, int W, int n, const float* scales, int cond_only);
+int af_control_plan_query(const af_config* cfg, int H, int W, int max_n, int64_t* out, int* n_out);
+int af_control_stats(af_handle* h, int out[2]);
+int64_t af_control_add_launches(void);
+int af_op_control_add(int dtype, int n, void* const* dst_dev, const void* const* src_dev, const int* C, const int* ld,
+                      const int64_t* rows_per_sample, const float* scales, int Bs, int Bd, void* stream);
+
 /* ---- conditioning producer: CLIP text tower (names "cond_stage_model.transformer.text_model.<k>") ----
  * af_clip_embed_tokens = CLIPTextEmbeddings.token_embedding (encoders/modules.py:207-208): ids_dev [n] int64 ->
  *   emb_dev [n, hidden] fp32.  The caller (EmbeddingManager.forward, embedding_manager.py:1292-1584) patches the
@@ -410,8 +456,9 @@ int64_t af_arena_bytes(af_handle* h);
  * LDS-resident input halo: the largest single kernel of a bf16 step); 10-15 the token-merging kernels (af_set_tome), one class per
  * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual; 16-19 the FreeU kernels (af_set_freeu): hidden
  * mean + min / max, low-band sums, apply, the single-launch small-map form; 20-21 the guidance kernels (af_guidance): chunk
- * statistics, and every form that writes the output; 22 the T-GATE add kernel (af_tgate_set).  A caller that asks af_prof_collect for
- * the first 10, 16, 20 or 22 classes gets
+ * statistics, and every form that writes the output; 22 the T-GATE add kernel (af_tgate_set); 23 the ControlNet residual add kernel
+ * (af_unet_set_control).  A caller that asks af_prof_collect for
+ * the first 10, 16, 20, 22 or 23 classes gets
  * what it got before the later ones existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */

@@ -96,6 +96,19 @@ def parse_args(argv=None):
                     help="LoRA adapter file (.safetensors / .pt, kohya or native key names) merged into the U-Net's and the text "
                          "tower's weights as they are repacked; repeatable, at most 8; SCALE defaults to 1; composes with every "
                          "sampler, --dtype, --deep_cache, --tome, --freeu, --pag_scale and --gpus")
+    ap.add_argument("--controlnet", type=str, default=None, metavar="PATH[:SCALE]",
+                    help="ControlNet checkpoint (control_sd15_*.pth / control_v11p_sd15_*.pth|.safetensors, keys with or without "
+                         "control_model.), or `synthetic` for seeded synthetic weights; SCALE (default 1) multiplies every residual.  "
+                         "Composes with every sampler, --lora (not applied to the control branch), --tome (U-Net only), --freeu, "
+                         "--deep_cache, --gpus and every --dtype (fp8: the control branch runs in bf16); not with --pag_scale or --tgate")
+    ap.add_argument("--control_image", type=str, nargs="+", default=None, metavar="PATH",
+                    help="--controlnet: the hint image(s), resized to H x W: one for all samples, or one per global sample index")
+    ap.add_argument("--control_start", type=float, default=0.0, metavar="F",
+                    help="--controlnet: control is on from this fraction of the schedule (0 = the first step) ...")
+    ap.add_argument("--control_end", type=float, default=1.0, metavar="F",
+                    help="... to this one (1 = the last step): timesteps 999 (1 - END) .. 999 (1 - START)")
+    ap.add_argument("--control_cond_only", action="store_true",
+                    help="--controlnet: control on the conditional guidance leg only (the unconditional leg is left as it is)")
     ap.add_argument("--lora_strict", action="store_true", help="--lora: refuse a file with keys that map onto no layer")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
@@ -159,6 +172,28 @@ def parse_args(argv=None):
             ap.error("--tgate: after the gate no guidance combine is made, so --pag_scale / --guidance_rescale have nothing to act on")
         if opt.dtype == "fp8":
             ap.error("--tgate: not built for --dtype fp8")
+    control_extras = opt.control_image is not None or opt.control_cond_only or opt.control_start != 0.0 or opt.control_end != 1.0
+    if control_extras and not opt.controlnet:
+        ap.error("--control_image / --control_start / --control_end / --control_cond_only: give --controlnet PATH[:SCALE] too")
+    if opt.controlnet:
+        from adaface_amd.engine import control_window_from_fractions
+        from adaface_amd.lora import parse_lora_arg
+        if opt.pag_scale > 0.0:
+            ap.error("--controlnet: not built for the PAG form (--pag_scale)")
+        if opt.tgate:
+            ap.error("--controlnet: not built for T-GATE (--tgate)")
+        path, scale = parse_lora_arg(opt.controlnet)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            ap.error(f"--controlnet {path}: the scale must be a finite number")
+        if path != "synthetic" and not opt.control_image:
+            ap.error("--controlnet: give --control_image PATH [PATH ...] (only `synthetic` makes its own hint)")
+        if opt.control_image and len(opt.control_image) not in (1, opt.n_samples):
+            ap.error(f"--control_image: one image, or one per sample ({opt.n_samples}), got {len(opt.control_image)}")
+        try:
+            opt.control_t_range = control_window_from_fractions(opt.control_start, opt.control_end)
+        except ValueError as e:
+            ap.error(f"--control_start / --control_end: {e}")
+        opt.controlnet = (path, scale)
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     if opt.lora_strict and not opt.lora:
@@ -181,6 +216,13 @@ def load_img(path, h, w):
     w, h = (x - x % 32 for x in (w, h))
     image = np.array(image.resize((w, h), resample=Image.LANCZOS)).astype(np.float32) / 255.0
     return 2.0 * torch.from_numpy(image[None].transpose(0, 3, 1, 2)) - 1.0
+
+
+def load_hint(path, h, w):
+    """A ControlNet hint image: RGB, resized to h x w, [0, 1], NCHW."""
+    from PIL import Image
+    image = np.array(Image.open(path).convert("RGB").resize((w, h), resample=Image.LANCZOS)).astype(np.float32) / 255.0
+    return torch.from_numpy(image[None].transpose(0, 3, 1, 2)).clamp(0.0, 1.0)
 
 
 def load_emb(path, n, device):
@@ -251,6 +293,28 @@ def main():
     B = opt.n_samples
     lo, hi = shard_range(B, rank, world)
     b = hi - lo
+    if opt.controlnet:   # identity from the model, pose from the ControlNet: its own engine, bf16 beside an fp8 U-Net
+        from adaface_amd import layout
+        from adaface_amd.ldm.modules.diffusionmodules.controlnet import SD15_CONTROLNET, ControlNet
+        from adaface_amd.synth import synth_controlnet_state_dict, synth_hint
+        unet = model.model.diffusion_model
+        path, scale = opt.controlnet
+        ctor = {**SD15_CONTROLNET, **{k: v for k, v in unet._layout_kwargs().items() if k != "out_channels"}, "num_heads": unet.num_heads}
+        if path == "synthetic":
+            cnet = ControlNet(**ctor)
+            cnet.load_control_state_dict(synth_controlnet_state_dict(layout.controlnet_param_shapes(**cnet._layout_kwargs()), seed=4321))
+        else:
+            cnet = ControlNet.from_file(path, **{k: v for k, v in ctor.items() if k not in SD15_CONTROLNET or SD15_CONTROLNET[k] != v})
+        cnet = cnet.to(device).set_compute_dtype("bf16" if opt.dtype == "fp8" else opt.dtype)
+        if opt.control_image:
+            hints = torch.cat([load_hint(p, opt.H, opt.W) for p in opt.control_image])
+        else:
+            hints = synth_hint(1, opt.seed + 4, opt.H, opt.W)
+        hint = hints if hints.shape[0] == 1 else hints[lo:hi]      # (one per GLOBAL sample index: this rank's)
+        unet.set_control(cnet, hint.to(device), scale=scale, t_range=opt.control_t_range, cond_only=opt.control_cond_only)
+        if rank == 0:
+            print(f"--controlnet: {path} x {scale:g}, timesteps {opt.control_t_range[0]} .. {opt.control_t_range[1]}"
+                  f"{', conditional leg only' if opt.control_cond_only else ''}")
     if opt.prompt_emb:
         c_all = load_emb(opt.prompt_emb, B, "cpu")
         uc_all = load_emb(opt.neg_prompt_emb, B, "cpu") if opt.neg_prompt_emb else torch.zeros_like(c_all)

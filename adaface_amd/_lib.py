@@ -78,6 +78,9 @@ _SIGS = [
     ("af_dpmpp_sde_coeffs", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     ("af_dpmpp_sde_step", C.c_int, [_P, _P, _P, _P, C.c_int64] + [C.c_float] * 7 + [_P, _P, C.c_float, _P, C.c_int64, _P, C.c_int64,
                                     C.c_uint64, C.c_uint32, _P]),
+    ("af_noise_blend", C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, _P, C.c_int64,
+                                 C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    ("af_noise_blend_launches", C.c_int64, []),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -318,6 +321,11 @@ def control_plan_query(unet: dict, H: int, W: int) -> list:
 def control_add_launches() -> int:
     """Launches of the ControlNet residual add kernel since the library was loaded (not part of plan_counts)."""
     return int(load().af_control_add_launches())
+
+
+def noise_blend_launches() -> int:
+    """Launches of the noising + inpainting blend kernel since the library was loaded (not part of plan_counts)."""
+    return int(load().af_noise_blend_launches())
 
 
 FREEU_KERNELS = ("refused", "single", "chunked")           # AfFreeuKernel (csrc/af_kernels.h)

@@ -75,7 +75,9 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        // the T-GATE add kernel (af_tgate.hip; scripts/tgate_mode.py)
        AF_K_TGATE_ADD = 22,
        // the ControlNet residual add kernel (af_controlnet.hip; scripts/controlnet_mode.py)
-       AF_K_CONTROL_ADD = 23, AF_K_COUNT = 24 };
+       AF_K_CONTROL_ADD = 23,
+       // the noising + inpainting blend kernel (af_inpaint.hip; scripts/inpaint_mode.py)
+       AF_K_NOISE_BLEND = 24, AF_K_COUNT = 25 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)

@@ -154,6 +154,10 @@ struct AfControlSeg { void* dst; const void* src; long rows; int C, ld; float sc
 template <typename T> int af_launch_control_add(const AfControlSeg* segs, int n, hipStream_t s);
 extern std::atomic<long> g_af_control_add_launches;   // launches since the library was loaded
 
+// Noising + inpainting blend (af_inpaint.hip): fp32 only, the whole of it behind the ABI's af_noise_blend (which
+// checks its arguments on the host and launches ONE kernel); af_noise_blend_launches reads this counter.
+extern std::atomic<long> g_af_noise_blend_launches;   // launches since the library was loaded
+
 // FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
 // types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
 enum AfFreeuKernel {

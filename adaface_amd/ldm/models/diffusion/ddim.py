@@ -11,6 +11,8 @@ makes it MI355X-native and device-agnostic:
   * deep_cache_interval= / deep_cache_depth= (opt-in, not in the reference): DeepCache, see deep_cache.py;
   * pag_scale= / pag_adaptive_scale= / guidance_rescale= (opt-in, not in the reference): perturbed-attention guidance and
     guidance rescale, see guidance.py.  All zero: the calls below are the calls made without them.
+  * strength= / fused_blend= (opt-in, not in the reference): img2img by strength and the one-launch inpainting blend, see
+    blend.py.  None / False: the calls below are the calls made without them.
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ import torch
 
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
+from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
@@ -81,7 +84,8 @@ class DDIMSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
                unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2,
-               pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
+               pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False,
+               **kwargs):
         """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
         adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step).
         deep_cache_interval: None or 1 = off; N >= 2 = the full U-Net on loop indices i % N == 0 only, or an explicit
@@ -90,8 +94,12 @@ class DDIMSampler(object):
         three-leg forward; guidance_rescale in [0, 1]: the combined prediction rescaled towards the conditional one's standard
         deviation (guidance.py).
         tgate_step: None or 0 = off; g in 1 .. S - 1 = T-GATE (tgate.py): loop index g - 1 also keeps the cross-attention
-        outputs, from loop index g on the U-Net runs on one leg with them and without guidance."""
+        outputs, from loop index g on the U-Net runs on one leg with them and without guidance.
+        strength: None = off; a number in (0, 1] (needs x0) = img2img, the run executes the n = max(1, int(len * strength))
+        smallest of the grid's timesteps from x0 noised to the largest of them (blend.py); S in the other arguments' rules
+        above is then n.  fused_blend: the blend of mask= / x0= in front of each step as one launch with the same bits."""
         _check_noise_source(noise_source, noise_dropout)
+        check_strength(strength, x0)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -105,7 +113,8 @@ class DDIMSampler(object):
                                   unconditional_conditioning=unconditional_conditioning, verbose=verbose,
                                   noise_source=noise_source, deep_cache_interval=deep_cache_interval,
                                   deep_cache_depth=deep_cache_depth, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
-                                  guidance_rescale=guidance_rescale, tgate_step=tgate_step, **kwargs)
+                                  guidance_rescale=guidance_rescale, tgate_step=tgate_step, strength=strength,
+                                  fused_blend=fused_blend, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
@@ -113,10 +122,11 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None,
                       deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
-                      tgate_step=None, **kwargs):
+                      tgate_step=None, strength=None, fused_blend=False, **kwargs):
         """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
         code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
-        step = the loop index."""
+        step = the loop index.  strength / fused_blend: as sample(); with strength, x_T is the noise added to x0."""
+        check_strength(strength, x0, timesteps=timesteps, ddim_use_original_steps=ddim_use_original_steps)
         _check_noise_source(noise_source, noise_dropout)
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
@@ -125,17 +135,22 @@ class DDIMSampler(object):
         self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
-        if x_T is not None:
+        if strength is not None:
+            # the n smallest timesteps of the grid; the per-index tables are read by index < n, as in a full run
+            timesteps = strength_timesteps(self.ddim_timesteps, strength)
+        elif timesteps is None:
+            timesteps = self.ddpm_num_timesteps if ddim_use_original_steps else self.ddim_timesteps
+        elif not ddim_use_original_steps:
+            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
+            timesteps = self.ddim_timesteps[:subset_end]
+        if strength is not None:
+            img = start_code(self.model, x0, int(timesteps[-1]), x_T, noise_source)
+        elif x_T is not None:
             img = x_T
         elif noise_source is None:
             img = torch.randn(shape, device=device)
         else:
             img = noise_source.randn(shape, STREAM_XT, 0, device)
-        if timesteps is None:
-            timesteps = self.ddpm_num_timesteps if ddim_use_original_steps else self.ddim_timesteps
-        elif not ddim_use_original_steps:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = reversed(range(0, timesteps)) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
@@ -154,11 +169,14 @@ class DDIMSampler(object):
         self.deep_cache_log = dc_run.log
         tg_run = TGateRun(self.model, total_steps, tgate_step)
         self.tgate_log = tg_run.log
+        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
 
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
-            if mask is not None:
+            if blend is not None:
+                img = blend(img, int(step), i)
+            elif mask is not None:
                 assert x0 is not None
                 if noise_source is None:
                     img_orig = self.model.q_sample(x0, ts)

@@ -22,19 +22,33 @@ from adaface_amd.ldm.util import instantiate_from_config
 
 
 class DiffusionWrapper(nn.Module):
-    """ddpm.py:5477-5516: routes (x, t, c_crossattn=[(emb, prompts, extra_info)]) to the UNet."""
+    """ddpm.py:5477-5516: routes (x, t, c_crossattn=[(emb, prompts, extra_info)]) to the UNet.  conditioning_key "hybrid"
+    (the sd-v1-5-inpainting checkpoint: a 9-channel conv_in) also concatenates c_concat onto x along the channels."""
 
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
         self.diffusion_model = instantiate_from_config(diff_model_config)
         self.conditioning_key = conditioning_key
-        if conditioning_key not in (None, "crossattn"):
-            raise NotImplementedError(f"conditioning_key '{conditioning_key}' is not used by SD-v1 txt2img")
+        if conditioning_key not in (None, "crossattn", "hybrid"):
+            raise NotImplementedError(f"conditioning_key '{conditioning_key}' is not used by SD-v1 txt2img / inpainting")
 
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, cfg_twin: bool = False, deep_cache=None,
                 cfg_pag: bool = False, tgate=None):
         if self.conditioning_key is None:
             raise NotImplementedError("unconditional UNet is not on the path")
+        if self.conditioning_key == "hybrid":
+            # ddpm.py:5503-5506: unet(cat([x] + c_concat, 1), t, context=cat(c_crossattn, 1)).  Under cfg_twin / cfg_pag x and
+            # c_concat are those of ONE leg, so the legs still share one concatenated x
+            if not c_concat:
+                raise ValueError("conditioning_key 'hybrid' needs c_concat (LatentDiffusion.set_concat_cond, or the dict form)")
+            x = torch.cat([x] + [c.to(x.device, x.dtype) for c in c_concat], dim=1)
+            want = getattr(self.diffusion_model, "in_channels", x.shape[1])
+            if x.shape[1] != want:
+                raise ValueError(f"hybrid conditioning: x and c_concat have {x.shape[1]} channels together, the U-Net takes {want}")
+            if len(c_crossattn) > 1:
+                if not all(isinstance(c, torch.Tensor) for c in c_crossattn):
+                    raise NotImplementedError("hybrid conditioning: several c_crossattn entries must be plain tensors")
+                c_crossattn = [torch.cat(list(c_crossattn), dim=1)]
         if tgate is not None:         # T-GATE capture / replay step (UNetModel.forward); None: the calls below, unchanged
             c0 = c_crossattn[0]
             c_static_emb, c_in, extra_info = c0 if isinstance(c0, tuple) else (c0, None, None)
@@ -151,6 +165,7 @@ class LatentDiffusion(DDPM):
         self.compel_cfg_weight_level_range = None
         self.apply_compel_cfg_prob = 0
         self.empty_context = None
+        self._concat_cond = None      # set_concat_cond (hybrid models)
 
     # ---- conditioning ------------------------------------------------------------------------
     def get_learned_conditioning(self, cond_in, zs_clip_features=None, zs_id_embs=None,
@@ -207,6 +222,38 @@ class LatentDiffusion(DDPM):
         return emb.unsqueeze(1).expand(B, n_layers, T, D).reshape(B * n_layers, T, D).contiguous()
 
     # ---- denoiser ----------------------------------------------------------------------------
+    def set_concat_cond(self, c_concat):
+        """The channels a hybrid model (conditioning_key "hybrid": the 9-channel inpainting U-Net) concatenates onto x_noisy
+        in every apply_model / apply_model_cfg_twin / apply_model_cfg_pag whose condition carries no c_concat of its own:
+        [1 or B, Cc, H, W] (adaface_amd.img2img.concat_cond), or None to clear.  The samplers stay unaware of it.  Not a
+        reference method."""
+        if self.model.conditioning_key != "hybrid":
+            raise ValueError(f"set_concat_cond: conditioning_key is {self.model.conditioning_key!r}; only a 'hybrid' model "
+                             "concatenates a condition onto its input")
+        if c_concat is not None:
+            unet = self.model.diffusion_model
+            want = unet.in_channels - unet.out_channels
+            if not isinstance(c_concat, torch.Tensor) or c_concat.dim() != 4 or c_concat.shape[1] != want:
+                raise ValueError(f"set_concat_cond: a tensor [1 or B, {want}, H, W] is needed")
+        self._concat_cond = c_concat
+        return self
+
+    def _with_concat(self, cond: dict, x_noisy):
+        """cond with the stored c_concat (hybrid models, when cond has none), fitted to x_noisy's batch."""
+        if self.model.conditioning_key != "hybrid" or "c_concat" in cond:
+            return cond
+        cc = self._concat_cond
+        if cc is None:
+            raise ValueError("a hybrid model needs its concatenated condition: set_concat_cond, or cond = {c_concat, c_crossattn}")
+        B = x_noisy.shape[0]
+        if cc.shape[0] != B:
+            if B % cc.shape[0] != 0:
+                raise ValueError(f"set_concat_cond: {cc.shape[0]} samples for a batch of {B}")
+            cc = cc.repeat(B // cc.shape[0], 1, 1, 1)     # (a batch [x; x] takes [cc; cc])
+        if tuple(cc.shape[2:]) != tuple(x_noisy.shape[2:]):
+            raise ValueError(f"set_concat_cond: the condition is {tuple(cc.shape[2:])}, the latent {tuple(x_noisy.shape[2:])}")
+        return dict(cond, c_concat=[cc])
+
     def apply_model(self, x_noisy, t, cond, return_ids=False, deep_cache=None, tgate=None):
         """ddpm.py:2192-2297 (the split_input_params patch mode is never active: SURVEY.md §8a a6).
         deep_cache (not in the reference): None, ("refresh", k) or ("reuse", k), see UNetModel.forward.
@@ -216,6 +263,7 @@ class LatentDiffusion(DDPM):
                 cond = [cond]
             key = 'c_concat' if self.model.conditioning_key == 'concat' else 'c_crossattn'
             cond = {key: cond}
+        cond = self._with_concat(cond, x_noisy)
         if tgate is not None:
             x_recon = self.model(x_noisy, t, deep_cache=deep_cache, tgate=tgate, **cond)
         else:
@@ -234,6 +282,8 @@ class LatentDiffusion(DDPM):
             if not isinstance(cond, list):
                 cond = [cond]
             cond = {'c_crossattn': cond}
+        if 'c_crossattn' in cond:
+            cond = self._with_concat(cond, x_noisy)
         if tgate is not None:         # (T-GATE capture on the twin form: the kept outputs are the means over the two legs)
             if 'c_crossattn' not in cond:
                 raise NotImplementedError("apply_model_cfg_twin: T-GATE needs a cross-attention condition")
@@ -256,6 +306,7 @@ class LatentDiffusion(DDPM):
             cond = {'c_crossattn': cond}
         if 'c_crossattn' not in cond:
             raise NotImplementedError("apply_model_cfg_pag: perturbed-attention guidance needs a cross-attention condition")
+        cond = self._with_concat(cond, x_noisy)
         if deep_cache is not None:
             return self.model(x_noisy, t, cfg_pag=True, deep_cache=deep_cache, **cond)
         return self.model(x_noisy, t, cfg_pag=True, **cond)
@@ -300,7 +351,7 @@ class LatentDiffusion(DDPM):
         from adaface_amd.ldm.models.diffusion.ddim import DDIMSampler
         unet = self.model.diffusion_model
         if shape is None:
-            shape = [unet.in_channels, unet.image_size, unet.image_size]
+            shape = [unet.out_channels, unet.image_size, unet.image_size]     # (the latent: a hybrid U-Net takes more)
         if x_T is None:
             x_T = torch.randn(batch_size, *shape, generator=torch.Generator().manual_seed(0)).to(self.device)
         sampler = DDIMSampler(self)

@@ -25,6 +25,7 @@ import torch
 
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
+from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
 from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
 from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
 from adaface_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
@@ -125,14 +126,18 @@ class DPMSolverSampler(object):
                x_T=None, verbose=True, log_every_t=100, guidance_scale=1., unconditional_guidance_scale=None,
                unconditional_conditioning=None, order=2, lower_order_final=True, skip_type="time_uniform", timesteps=None,
                algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
-               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
+               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False, **kwargs):
         """(img, intermediates) as DDIMSampler.sample.  guidance_scale: a scalar or [max, min] (annealed as ddim_sampling
         does); unconditional_guidance_scale: the PLMS / CompVis spelling of the scalar.  timesteps: an explicit strictly
         increasing integer array, overriding S and skip_type.  algorithm: "dpmsolver++" (deterministic) or "sde-dpmsolver++"
         (one N(0, 1) draw per step, scaled by temperature=); noise_source: a PhiloxNoise for the SDE draws, the inpainting
         blend's q_sample noise and, with x_T None, the start code.  deep_cache_interval / deep_cache_depth: DeepCache, as
         DDIMSampler.sample (deep_cache.py).  pag_scale / pag_adaptive_scale / guidance_rescale: perturbed-attention guidance
-        and guidance rescale, as DDIMSampler.sample (guidance.py).  tgate_step: T-GATE, as DDIMSampler.sample (tgate.py)."""
+        and guidance rescale, as DDIMSampler.sample (guidance.py).  tgate_step: T-GATE, as DDIMSampler.sample (tgate.py).
+        strength / fused_blend: img2img by strength and the one-launch inpainting blend, as DDIMSampler.sample (blend.py).
+        The schedule of a run by strength is dpmpp_schedule on its n executed timesteps: its first step is first order, and
+        the n < 15 rule of lower_order_final applies to n."""
+        check_strength(strength, x0)
         if algorithm not in ALGORITHMS:
             raise NotImplementedError(f'There is no DPM-Solver algorithm called "{algorithm}" ({", ".join(ALGORITHMS)})')
         sde = algorithm == "sde-dpmsolver++"
@@ -152,6 +157,8 @@ class DPMSolverSampler(object):
         acp = self.model.alphas_cumprod.detach().double().cpu().numpy()
         assert acp.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
         ts = dpmpp_timesteps(acp, S, skip_type) if timesteps is None else np.asarray(timesteps)
+        if strength is not None:
+            ts = strength_timesteps(ts, strength)
         self.timesteps = ts
         self.schedule = dpmpp_schedule(acp, ts, order=order, lower_order_final=lower_order_final, guidance=guidance_scale,
                                        sde=sde)
@@ -165,7 +172,7 @@ class DPMSolverSampler(object):
                                         temperature=temperature, deep_cache_interval=deep_cache_interval,
                                         deep_cache_depth=deep_cache_depth, pag_scale=pag_scale,
                                         pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
-                                        tgate_step=tgate_step)
+                                        tgate_step=tgate_step, strength=strength, fused_blend=fused_blend)
 
     def _twin_condition(self, c, uc):
         """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
@@ -185,8 +192,11 @@ class DPMSolverSampler(object):
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
                             log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.,
                             deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0.,
-                            guidance_rescale=0., tgate_step=None):
-        """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update."""
+                            guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False):
+        """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update.  strength not None: the table is
+        that of the executed steps already (sample() builds it), and the run starts from x0 noised to its first timestep
+        with x_T as the noise; fused_blend: as sample()."""
+        check_strength(strength, x0)
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
         refuse_guided(tgate_step, pag_scale, guidance_rescale)
@@ -196,7 +206,9 @@ class DPMSolverSampler(object):
         device = self.model.betas.device
         b = shape[0]
         sde = schedule.shape[1] > COL_CN
-        if x_T is not None:
+        if strength is not None:
+            img = start_code(self.model, x0, int(schedule[0, COL_T]), x_T, noise_source)
+        elif x_T is not None:
             img = x_T
         elif noise_source is None:
             img = torch.randn(shape, device=device)
@@ -214,11 +226,14 @@ class DPMSolverSampler(object):
         self.deep_cache_log = dc_run.log
         tg_run = TGateRun(self.model, total_steps, tgate_step)
         self.tgate_log = tg_run.log
+        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
         for i, row in enumerate(schedule):
             index = total_steps - i - 1
             guide_scale = float(row[COL_G])
             ts = torch.full((b,), int(row[COL_T]), device=device, dtype=torch.long)
-            if mask is not None:
+            if blend is not None:
+                img = blend(img, int(row[COL_T]), i)
+            elif mask is not None:
                 assert x0 is not None
                 if noise_source is None:
                     img_orig = self.model.q_sample(x0, ts)

@@ -11,8 +11,10 @@ import torch
 
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
+from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
 from adaface_amd.ldm.modules.diffusionmodules.util import (make_ddim_sampling_parameters, make_ddim_timesteps,
                                                             noise_like)
+from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
 
 
 class PLMSSampler(object):
@@ -50,10 +52,16 @@ class PLMSSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
-               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, **kwargs):
+               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, noise_source=None, strength=None,
+               fused_blend=False, **kwargs):
         """plms.py:71-117.  pag_scale / pag_adaptive_scale / guidance_rescale (not in the reference): perturbed-attention
-        guidance and guidance rescale on every model call of the run, see guidance.py."""
+        guidance and guidance rescale on every model call of the run, see guidance.py.  noise_source (not in the reference):
+        an adaface_amd.noise.PhiloxNoise for the start code (stream 0) and the blend's q_sample noise (stream 2) -- nothing
+        else: the eta = 0 update has no noise of its own.  strength / fused_blend (not in the reference): img2img by strength
+        and the one-launch inpainting blend, as DDIMSampler.sample (blend.py); a run by strength starts an eps history of its
+        own, so its first executed step is the two-call one."""
         from adaface_amd.ldm.models.diffusion.deep_cache import is_off
+        check_strength(strength, x0)
         if not is_off(deep_cache_interval):
             raise NotImplementedError("deep_cache_interval with the PLMS sampler: it calls the model twice in its first step and "
                                       "extrapolates from an eps history (use DDIMSampler or DPMSolverSampler)")
@@ -68,14 +76,17 @@ class PLMSSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, pag_scale=pag_scale,
-                                  pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale)
+                                  pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
+                                  noise_source=noise_source, strength=strength, fused_blend=fused_blend)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.):
-        """plms.py:119-173."""
+                      unconditional_conditioning=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
+                      noise_source=None, strength=None, fused_blend=False):
+        """plms.py:119-173.  noise_source / strength / fused_blend: as sample(); with strength, x_T is the noise added to x0."""
+        check_strength(strength, x0, timesteps=timesteps)
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps is not used by txt2img")
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
@@ -84,24 +95,40 @@ class PLMSSampler(object):
         self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
-        if timesteps is None:
+        if strength is not None:
+            timesteps = strength_timesteps(self.ddim_timesteps, strength)
+        elif timesteps is None:
             timesteps = self.ddim_timesteps
         else:
             subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
             timesteps = self.ddim_timesteps[:subset_end]
+        if strength is not None:
+            img = start_code(self.model, x0, int(timesteps[-1]), x_T, noise_source)
+        elif x_T is not None:
+            img = x_T
+        elif noise_source is None:
+            img = torch.randn(shape, device=device)
+        else:
+            img = noise_source.randn(shape, STREAM_XT, 0, device)
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
         old_eps = []
         self._twin_cache = None
+        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, len(time_range) - 1)]), device=device, dtype=torch.long)
-            if mask is not None:
+            if blend is not None:
+                img = blend(img, int(step), i)
+            elif mask is not None:
                 assert x0 is not None
-                img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                if noise_source is None:
+                    img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                else:
+                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
+                    img = img_orig * mask + (1. - mask) * img
             img, pred_x0, e_t = self.p_sample_plms(img, cond, ts, index=index, quantize_denoised=quantize_denoised,
                                                    temperature=temperature, noise_dropout=noise_dropout,
                                                    score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,

@@ -183,6 +183,9 @@ class UNetModel(HipModule):
         from adaface_amd.ldm.modules.diffusionmodules.controlnet import ControlNet
         if not isinstance(controlnet, ControlNet):
             raise TypeError(f"set_control: a ControlNet module is needed, got {type(controlnet).__name__}")
+        if self.in_channels != self.out_channels:
+            raise NotImplementedError(f"set_control: ControlNet on a hybrid U-Net ({self.in_channels} input channels, "
+                                      f"{self.out_channels} latent channels) is not built")
         mine, theirs = self._layout_kwargs(), controlnet._layout_kwargs()
         for k in ("in_channels", "model_channels", "num_res_blocks", "attention_resolutions", "channel_mult", "context_dim",
                   "transformer_depth"):

@@ -735,6 +735,48 @@ def dpmpp_sde_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x
     return x_next, x0_out
 
 
+STREAM_QSAMPLE = 2    # noise.STREAM_QSAMPLE (csrc/af_philox.h), stated here because noise.py imports this module
+
+
+def noise_blend(x, x0, keep, sa, s1, noise=None, seed=0, stream=STREAM_QSAMPLE, step=0, sample_ids=None, first_id=0, out=None):
+    """af_noise_blend, one launch on fp32 latents [B, C, ...]: q = sa * x0 + s1 * z, then out = q * keep + (1 - keep) * x, every
+    product and sum rounded on its own -- the bits of LatentDiffusion.q_sample followed by the samplers' blend line.
+    keep: [B, 1 or C, ...] (1 = take the noised x0), or None: out = q, the stochastic encode (x may then be None).
+    noise: the z to use (x0's size); None: z is generated inside the kernel from (seed, sample id, stream, step, element), the
+    bits philox_randn gives (ids: sample_ids, an int64 GPU tensor, or first_id + i).  s1 == 0: no noise is read or generated.
+    out: a contiguous fp32 GPU tensor of x0's size to write into, which may be x itself (no other overlap); allocated when None."""
+    lib = _lib.load()
+    x0 = _dev_f32(x0)
+    if x0.dim() < 2:
+        raise ValueError("noise_blend: x0 must be [B, C, ...]")
+    B, Cc = x0.shape[0], x0.shape[1]
+    HW = x0.numel() // max(B * Cc, 1)
+    xx = None if x is None else _dev_f32(x)
+    nz = None if noise is None else _dev_f32(noise)
+    for name, t in (("x", xx), ("noise", nz)):
+        if t is not None and t.shape != x0.shape:
+            raise ValueError(f"noise_blend: {name} has shape {tuple(t.shape)}, x0 has {tuple(x0.shape)}")
+    kc, kp = 1, None
+    if keep is not None:
+        if xx is None:
+            raise ValueError("noise_blend: a keep mask needs x, the latent to blend into")
+        if keep.dim() != x0.dim() or keep.shape[1] not in (1, Cc) or keep.shape[2:] != x0.shape[2:] or keep.shape[0] not in (1, B):
+            raise ValueError(f"noise_blend: keep has shape {tuple(keep.shape)}; [B, 1 or C, ...] of x0's {tuple(x0.shape)} expected")
+        kc = int(keep.shape[1])
+        kp = _dev_f32(keep if keep.shape[0] == B else keep.expand(B, *keep.shape[1:]))
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x0.shape):
+        raise ValueError("noise_blend: out must be a contiguous fp32 GPU tensor of x0's shape")
+    if sample_ids is not None and not (sample_ids.is_cuda and sample_ids.dtype == torch.int64 and sample_ids.is_contiguous()
+                                       and sample_ids.numel() >= B):
+        raise ValueError("noise_blend: sample_ids must be a contiguous int64 GPU tensor of at least x0.shape[0] elements")
+    if out is None:
+        out = torch.empty_like(x0)
+    check(lib.af_noise_blend(ptr(xx), ptr(x0), ptr(kp), kc, ptr(nz), B, Cc, HW, float(sa), float(s1), ptr(sample_ids),
+                             int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(step), ptr(out), stream_ptr()),
+          "af_noise_blend")
+    return out
+
+
 def guidance(e_c, e_u, e_p, w, s, rescale=0.0, return_factor=False, out=None):
     """af_guidance: e = e_u + w (e_c - e_u) + s (e_c - e_p), then guidance rescale e (phi f + 1 - phi) with
     f = std(e_c) / std(e) per sample (dim 0 of e_c; unbiased).  e_u None: no w term; e_p None (or s = 0): no s term; rescale 0:

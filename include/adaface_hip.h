@@ -421,6 +421,24 @@ int af_dpmpp_sde_step(const float* x_dev, const float* eps_cond_dev, const float
                       float guidance, float alpha_t, float sigma_t, float c_x, float c_d, float w_cur, float w_prev,
                       float* x_next_dev, float* x0_out_dev, float c_n, const float* noise_dev, int64_t per_sample,
                       const int64_t* sample_ids_dev, int64_t first_id, uint64_t seed, uint32_t step, void* stream);
+/* The noising of a clean latent and the inpainting blend in front of a sampler step (af_inpaint.hip), ONE launch,
+ * fp32 NCHW latents [n_samples][C][HW].  For sample b, channel c, pixel p, with e = c * HW + p:
+ *     z   = noise_dev[b][e]                                  (noise_dev non-NULL; the key arguments then select nothing)
+ *         | the Philox normal of (seed, id_b, stream_id, step, e)   (noise_dev NULL: the bits af_philox_randn gives)
+ *     q   = fl( fl(sa * x0) + fl(s1 * z) )                   (s1 == 0: no noise is generated or read, q = fl(sa * x0))
+ *     out = q                                                (keep_dev NULL: the stochastic encode; x_dev may be NULL)
+ *         | fl( fl(q * m) + fl( fl(1 - m) * x ) ),  m = keep_dev[b][keep_channels == 1 ? 0 : c][p]
+ * Every product and sum is rounded to fp32 on its own (nothing is contracted into an fma): the bits of the torch composition
+ * q_sample(x0, t, z) * keep + (1. - keep) * x with sa, s1 the two fp32 table values of t.  ids as af_dpmpp_sde_step
+ * (sample_ids_dev NULL: first_id + b).  Any alignment and any C * HW >= 1 are accepted; 16-byte aligned pointers with
+ * HW % 4 == 0 take a four-element path, and both paths give the same bits for an element, which do not depend on what else is
+ * in the launch.  out_dev may be x_dev exactly; any other overlap of out_dev with an input, keep_channels not in {1, C},
+ * x_dev NULL with keep_dev non-NULL, step >= 2^24, stream_id >= 256 or an id < 0: AF_ERR_INVALID before any launch. */
+int af_noise_blend(const float* x_dev, const float* x0_dev, const float* keep_dev, int keep_channels, const float* noise_dev,
+                   int64_t n_samples, int C, int64_t HW, float sa, float s1, const int64_t* sample_ids_dev, int64_t first_id,
+                   uint64_t seed, uint32_t stream_id, uint32_t step, float* out_dev, void* stream);
+/* launches of its kernel since the library was loaded */
+int64_t af_noise_blend_launches(void);
 
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */

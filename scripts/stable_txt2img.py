@@ -6,6 +6,7 @@ Keeps the reference's flag names for everything that reaches the denoising path
 --seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --noise --deep_cache --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
+Not in the reference: --img2img / --strength / --inpaint_mask (img2img by strength and inpainting, adaface_amd/img2img.py).
 
     python scripts/stable_txt2img.py --synthetic --n_samples 8 --ddim_steps 50 --skip_save
     python scripts/stable_txt2img.py --synthetic --n_samples 64 --gpus 8      # starts the 8 ranks itself
@@ -109,6 +110,18 @@ def parse_args(argv=None):
                     help="... to this one (1 = the last step): timesteps 999 (1 - END) .. 999 (1 - START)")
     ap.add_argument("--control_cond_only", action="store_true",
                     help="--controlnet: control on the conditional guidance leg only (the unconditional leg is left as it is)")
+    ap.add_argument("--img2img", type=str, nargs="+", default=None, metavar="PATH",
+                    help="img2img by strength: the image(s) to start from, resized to H x W: one for all samples, or one per "
+                         "global sample index.  The run executes the last --strength share of the schedule from the noised "
+                         "encoding.  Composes with every sampler, --dtype, --noise, --deep_cache, --tome, --freeu, --lora, "
+                         "--gpus and --controlnet; not with --init_img_paths")
+    ap.add_argument("--strength", type=float, default=None, metavar="F",
+                    help="--img2img: in (0, 1], the share of the steps that run (1 = all of them, from pure noise plus the "
+                         "image's trace; default 0.75)")
+    ap.add_argument("--inpaint_mask", type=str, nargs="+", default=None, metavar="PATH",
+                    help="--img2img: inpainting mask(s), white = repaint, resized to H x W: one for all samples, or one per "
+                         "global sample index.  A latent cell with any white pixel is repainted; the rest is the image's own "
+                         "encoding.  A checkpoint or config with a 9-channel U-Net (sd-v1-5-inpainting) needs it")
     ap.add_argument("--lora_strict", action="store_true", help="--lora: refuse a file with keys that map onto no layer")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
@@ -194,6 +207,21 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error(f"--control_start / --control_end: {e}")
         opt.controlnet = (path, scale)
+    if opt.strength is not None and not opt.img2img:
+        ap.error("--strength: give --img2img PATH [PATH ...] too")
+    if opt.inpaint_mask and not opt.img2img:
+        ap.error("--inpaint_mask: give --img2img PATH [PATH ...] too (the image whose unmasked region is kept)")
+    if opt.img2img:
+        if opt.init_img_paths:
+            ap.error("--img2img: not with --init_img_paths (that blends the encoding into the start code of a full run)")
+        opt.strength = 0.75 if opt.strength is None else opt.strength
+        if not 0.0 < opt.strength <= 1.0:
+            ap.error("--strength F: 0 < F <= 1")
+        for flag, paths in (("--img2img", opt.img2img), ("--inpaint_mask", opt.inpaint_mask)):
+            if paths and len(paths) not in (1, opt.n_samples):
+                ap.error(f"{flag}: one image, or one per sample ({opt.n_samples}), got {len(paths)}")
+        if opt.H % opt.f or opt.W % opt.f:
+            ap.error(f"--img2img: --H and --W must be multiples of --f ({opt.f})")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     if opt.lora_strict and not opt.lora:
@@ -207,6 +235,17 @@ def parse_args(argv=None):
             if scale != scale or scale in (float("inf"), float("-inf")):
                 ap.error(f"--lora {path}: the scale must be a finite number")
     return opt
+
+
+def hybrid_problem(opt, hybrid):
+    """What keeps a hybrid model (9-channel inpainting U-Net) from running with these options, as a message; None: nothing."""
+    if not hybrid:
+        return None
+    if not (opt.img2img and opt.inpaint_mask):
+        return "a 9-channel (inpainting) U-Net needs --img2img PATH and --inpaint_mask PATH: it reads the mask and the masked image"
+    if opt.controlnet:
+        return "--controlnet: not built for a 9-channel (inpainting) U-Net"
+    return None
 
 
 def load_img(path, h, w):
@@ -254,6 +293,11 @@ def main():
     from ldm.util import instantiate_from_config, load_config, load_model_from_config
 
     config = load_config(opt.config) if opt.config else sd15_config()
+    from adaface_amd import img2img as I2I
+    hybrid = I2I.select_hybrid(config, opt.ckpt)     # a 9-channel U-Net in the config or the checkpoint: the inpainting model
+    problem = hybrid_problem(opt, hybrid)
+    if problem:
+        raise SystemExit(problem)
     if opt.ckpt:
         model = load_model_from_config(config, opt.ckpt)
     else:
@@ -325,6 +369,23 @@ def main():
         raise SystemExit("give --prompt_emb (pre-computed CLIP/AdaFace embedding) or --synthetic")
     c = model.get_learned_conditioning(shard_batch(c_all, rank, world, per_sample=16).to(device))
     uc = model.get_learned_conditioning(shard_batch(uc_all, rank, world, per_sample=16).to(device))
+    i2i = {}
+    x0 = keep = None
+    if opt.img2img:
+        # this rank's images and masks, by GLOBAL sample index.  Before the fp8 calibration: its sample runs the model, and a
+        # hybrid model needs its concatenated condition for that
+        imgs = I2I.load_batch(opt.img2img, B, lo, hi, opt.H, opt.W, I2I.load_image, "--img2img").to(device)
+        x0 = I2I.encode_image(model, imgs)
+        i2i = dict(x0=x0, strength=opt.strength, fused_blend=True)
+        if opt.inpaint_mask:
+            repaint = I2I.load_batch(opt.inpaint_mask, B, lo, hi, opt.H, opt.W, I2I.load_mask, "--inpaint_mask").to(device)
+            keep = I2I.repaint_to_keep(repaint, opt.f)
+            i2i["mask"] = keep
+            if hybrid:
+                model.set_concat_cond(I2I.concat_cond(model, imgs, repaint, opt.f))
+        if rank == 0:
+            print(f"--img2img: strength {opt.strength:g}" + (f", inpainting ({float(1.0 - keep.mean()):.0%} of this rank's latent "
+                  f"cells repainted{', hybrid U-Net' if hybrid else ''})" if keep is not None else ""))
     if opt.dtype == "fp8":
         # static activation scales: from the file when it exists, else from a short calibration sample with this run's
         # conditioning.  With several ranks and a file to write, rank 0 calibrates on its shard and the others load what it
@@ -416,6 +477,8 @@ def main():
                 kw.update(deep_cache_interval=opt.deep_cache, deep_cache_depth=opt.deep_cache_depth)
             if opt.tgate:
                 kw.update(tgate_step=opt.tgate)
+            kw.update(i2i)        # (--img2img: x_T is then the noise added to x0, not a latent)
+            guided.update(i2i)
             if opt.plms:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
@@ -428,6 +491,8 @@ def main():
             else:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T, **kw)
+            if keep is not None:      # the kept region is the image's own encoding, without the last blend's noise
+                samples = I2I.finish(samples, x0, keep)
             frames = gather_frames(model.decode_first_stage_uint8(samples), global_batch=B)
             if rank == 0 and not opt.skip_save:
                 from PIL import Image

@@ -81,6 +81,10 @@ _SIGS = [
     ("af_noise_blend", C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, _P, C.c_int64,
                                  C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     ("af_noise_blend_launches", C.c_int64, []),
+    ("af_lcm_coeffs", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    ("af_lcm_step", C.c_int, [_P, _P, _P, C.c_int64] + [C.c_float] * 8 + [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_uint64,
+                              C.c_uint32, _P]),
+    ("af_lcm_step_launches", C.c_int64, []),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -158,6 +158,10 @@ extern std::atomic<long> g_af_control_add_launches;   // launches since the libr
 // checks its arguments on the host and launches ONE kernel); af_noise_blend_launches reads this counter.
 extern std::atomic<long> g_af_noise_blend_launches;   // launches since the library was loaded
 
+// LCM / TCD consistency step (af_lcm.hip): fp32 only, the whole of it behind the ABI's af_lcm_step (which checks its
+// arguments on the host and launches ONE kernel, instantiated on (CFG, noise source) alone); af_lcm_step_launches reads this.
+extern std::atomic<long> g_af_lcm_step_launches;      // launches since the library was loaded
+
 // FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
 // types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
 enum AfFreeuKernel {

@@ -390,6 +390,27 @@ class LatentDiffusion(DDPM):
     def pag(self) -> tuple:
         return self.model.diffusion_model.pag
 
+    @property
+    def has_guidance_embedding(self) -> bool:
+        return getattr(self.model.diffusion_model, "time_cond_proj_dim", None) is not None
+
+    @property
+    def guidance_embedding(self):
+        """The guidance scale set_guidance_embedding folded into the U-Net's time embedding, or None."""
+        return getattr(self.model.diffusion_model, "guidance_embedding", None)
+
+    def set_guidance_embedding(self, w):
+        """UNetModel.set_guidance_embedding: feed the guidance scale w through the guidance-scale embedding of a distilled LCM
+        checkpoint (U-Net config key time_cond_proj_dim) in every following forward; None = off.  LCMSampler.sample(
+        guidance_embedding=True) sets and removes it around a run."""
+        unet = self.model.diffusion_model
+        if not hasattr(unet, "set_guidance_embedding"):
+            if w is None:
+                return self
+            raise ValueError("set_guidance_embedding: this model's U-Net has no guidance-scale embedding")
+        unet.set_guidance_embedding(w)
+        return self
+
     def set_lora(self, adapters):
         """LoRA adapters on the U-Net and the text tower (HipModule.set_lora on each): `adapters` is a list of (split, scale), at
         most 8, with split = {"unet": weights, "text": weights} as adaface_amd.lora.split_lora returns it (either key may be

@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from adaface_amd import layout
-from adaface_amd.ldm._hipmodule import HipModule, build_param_tree
+from adaface_amd.ldm._hipmodule import HipModule, _Node, build_param_tree
 
 
 class UNetModel(HipModule):
@@ -19,7 +19,8 @@ class UNetModel(HipModule):
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None,
                  use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1, num_heads_upsample=-1,
                  use_scale_shift_norm=False, resblock_updown=False, use_new_attention_order=False,
-                 use_spatial_transformer=False, transformer_depth=1, context_dim=None, n_embed=None, legacy=True):
+                 use_spatial_transformer=False, transformer_depth=1, context_dim=None, n_embed=None, legacy=True,
+                 time_cond_proj_dim=None):
         super().__init__()
         # the SD-v1 family is the hot path (v1-inference-ada.yaml:35-50); other branches of the
         # reference constructor are training / legacy-LDM variants outside SURVEY.md §8
@@ -59,6 +60,26 @@ class UNetModel(HipModule):
         build_param_tree(self, shapes, zero_init=layout.unet_zero_init_names(shapes))
         object.__setattr__(self, "_ctx_key", None)
         object.__setattr__(self, "_control", None)     # ControlNet (set_control)
+        # the guidance-scale embedding of a distilled LCM checkpoint (not in the reference; None = absent, nothing changes):
+        # time_embed.cond_proj.weight [model_channels, dim], no bias.  The weight lives on the Python side only -- it is folded
+        # into the engine's time_embed.0.bias (set_guidance_embedding), never an engine tensor.  Zero until a checkpoint is loaded.
+        self.time_cond_proj_dim = None if time_cond_proj_dim is None else int(time_cond_proj_dim)
+        if self.time_cond_proj_dim is not None:
+            if self.time_cond_proj_dim < 4:
+                raise ValueError(f"UNetModel: time_cond_proj_dim {time_cond_proj_dim!r} (None, or at least 4)")
+            node = _Node()
+            node.register_parameter("weight", torch.nn.Parameter(torch.zeros(model_channels, self.time_cond_proj_dim),
+                                                                 requires_grad=False))
+            self.time_embed.add_module("cond_proj", node)
+            self._register_load_state_dict_pre_hook(self._accept_diffusers_cond_proj)
+        object.__setattr__(self, "_guidance_w", None)  # set_guidance_embedding
+
+    @staticmethod
+    def _accept_diffusers_cond_proj(state_dict, prefix, *args):
+        """diffusers names the weight time_embedding.cond_proj.weight; either name loads."""
+        theirs, ours = prefix + "time_embedding.cond_proj.weight", prefix + "time_embed.cond_proj.weight"
+        if theirs in state_dict and ours not in state_dict:
+            state_dict[ours] = state_dict.pop(theirs)
 
     def _layout_kwargs(self):
         return dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
@@ -77,6 +98,57 @@ class UNetModel(HipModule):
 
     def _lora_changed(self):
         object.__setattr__(self, "_ctx_key", None)  # (set_lora: attn2.to_k / to_v may have changed, as in _mark_dirty)
+        if self._guidance_w is not None and self._engine is not None and not self._weights_dirty:
+            self._load_time_bias()      # (the folded bias holds the merged time_embed.0 weight, which may have changed)
+
+    # ---- guidance-scale embedding (distilled LCM checkpoints) -------------------------------------
+    @property
+    def guidance_embedding(self):
+        """The guidance scale w folded into the time embedding, or None."""
+        return self._guidance_w
+
+    def folded_time_bias(self, w):
+        """time_embed.0.bias + W0 (Wc wemb(w)), a float64 host tensor: the bias under which time_embed.0(temb) equals
+        time_embed.0(temb + Wc wemb) (the engine takes it rounded once to fp32).  W0 is the
+        EFFECTIVE time_embed.0 weight, base plus the adapters of set_lora (adaface_amd.lora.merge_host).  The fold is exact: w is
+        constant over a run and time_embed.0 is linear."""
+        from adaface_amd.ldm.modules.diffusionmodules.util import guidance_scale_embedding
+        from adaface_amd.lora import merge_host
+        if self.time_cond_proj_dim is None:
+            raise ValueError("UNetModel: no guidance-scale embedding (built without time_cond_proj_dim: there is no "
+                             "time_embed.cond_proj.weight)")
+        params = dict(self.named_parameters())
+        wemb = torch.from_numpy(guidance_scale_embedding(w, self.time_cond_proj_dim))
+        W0 = merge_host(params["time_embed.0.weight"], self._lora_of("time_embed.0"))
+        Wc = params["time_embed.cond_proj.weight"].detach().double().cpu()
+        return params["time_embed.0.bias"].detach().double().cpu() + W0 @ (Wc @ wemb)
+
+    def _load_time_bias(self):
+        """The engine's time_embed.0.bias for the current setting: the folded one, or the parameter itself."""
+        eng = self._engine
+        bias = self.folded_time_bias(self._guidance_w) if self._guidance_w is not None else \
+            dict(self.named_parameters())["time_embed.0.bias"]
+        eng.load_tensor(self._ckpt_prefix + "time_embed.0.bias", bias)
+        eng.unet_cache_invalidate()     # (a kept DeepCache feature was computed under the previous time embedding)
+
+    def set_guidance_embedding(self, w):
+        """Feed the guidance scale w through the model's guidance-scale embedding in every following forward; None = off, which
+        restores the original bias exactly.  The embedding Wc wemb(w) is added in front of time_embed.0 by folding it into that
+        layer's bias (folded_time_bias) -- the forward itself does not change.  Kept for every later engine and re-applied
+        after set_lora and after every weight upload; a live engine is switched now."""
+        if w is not None:
+            self.folded_time_bias(w)                # (refuses a model without cond_proj, and a w that is no finite number)
+            w = float(w)
+        changed = w != self._guidance_w
+        object.__setattr__(self, "_guidance_w", w)
+        if changed and self._engine is not None and not self._weights_dirty:
+            self._load_time_bias()
+        return self
+
+    def sync_weights(self):
+        super().sync_weights()
+        if self._engine is not None and self._guidance_w is not None:
+            self._load_time_bias()
 
     def _compel_cfg(self, context, B, info):
         """Inference-time compel cfg (openaimodel.py:898-916 + prob_apply_compel_cfg, util.py:2063-2094): per conditioned

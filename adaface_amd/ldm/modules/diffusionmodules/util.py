@@ -67,6 +67,26 @@ def extract_into_tensor(a, t, x_shape):
     return out.reshape(b, *((1,) * (len(x_shape) - 1)))
 
 
+def guidance_scale_embedding(w, dim):
+    """The guidance-scale embedding of a distilled LCM checkpoint (w_embedding of the LCM authors' code; diffusers'
+    get_guidance_scale_embedding), float64 numpy [dim], host only: the sinusoid of (w - 1) * 1000 with
+    f_i = exp(-ln(10000) i / (half - 1)), half = dim // 2, laid out [sin | cos] and zero-padded to an odd dim.  Both the layout
+    and the divisor differ from timestep_embedding ([cos | sin], i / half)."""
+    import math
+    import numpy as np
+    dim = int(dim)
+    if dim < 4:
+        raise ValueError(f"guidance_scale_embedding: dim {dim} (at least 4: the frequencies divide by dim // 2 - 1)")
+    w = float(w)
+    if not math.isfinite(w):
+        raise ValueError(f"guidance_scale_embedding: w {w!r} is not finite")
+    half = dim // 2
+    freqs = np.exp(-math.log(10000.0) * np.arange(half, dtype=np.float64) / (half - 1))
+    args = (w - 1.0) * 1000.0 * freqs
+    emb = np.concatenate([np.sin(args), np.cos(args)])
+    return np.concatenate([emb, np.zeros(1)]) if dim % 2 else emb
+
+
 def timestep_embedding(timesteps, dim, max_period=10000, repeat_only=False, dtype="f32"):
     """util.py:154-174 through the HIP kernel (device tensors only)."""
     from adaface_amd import ops

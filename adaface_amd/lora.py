@@ -56,6 +56,18 @@ def lora_factor(scale: float, alpha: float, r: int) -> float:
     return float(scale) * float(alpha) / float(r)
 
 
+def merge_host(base: torch.Tensor, adapters) -> torch.Tensor:
+    """The effective weight base + sum_a s_a * up_a @ down_a on the host in float64, base's shape.  adapters: [(up, down, s)] as
+    HipModule._lora_of gives them, s taken as the fp32 value the library receives.  What the repack kernel forms in fp32 on the
+    device, for host-side arithmetic that needs the merged weight (the guidance-embedding fold)."""
+    out = base.detach().double().cpu().reshape(base.shape[0], -1).clone()
+    for up, down, s in adapters:
+        r = int(down.shape[0])
+        s32 = float(torch.tensor(float(s), dtype=torch.float32))
+        out += s32 * (up.detach().double().cpu().reshape(base.shape[0], r) @ down.detach().double().cpu().reshape(r, -1))
+    return out.reshape(base.shape)
+
+
 # ---------------------------------------------------------------------------------------------- names
 def _cfg_get(unet_cfg):
     return unet_cfg.get if isinstance(unet_cfg, dict) else (lambda k, d=None: getattr(unet_cfg, k, d))

@@ -735,6 +735,54 @@ def dpmpp_sde_step(x, e_cond, e_uncond, x0_prev, guidance, alpha_t, sigma_t, c_x
     return x_next, x0_out
 
 
+def lcm_coeffs(acp_t, acp_prev, acp_s=0.0, t=0, timestep_scaling=10.0, sigma_data=0.5):
+    """af_lcm_coeffs (host only, no GPU): the seven doubles (alpha_t, sigma_t, k_out, k_skip, c_x, c_0, c_n) of one consistency
+    step from alphas_cumprod acp_t to acp_prev (1.0: the final step, which returns the denoised sample).  acp_s <= 0: LCM, with
+    the boundary condition of integer timestep t; acp_s > 0: TCD with alphas_cumprod acp_s at the intermediate timestep."""
+    import ctypes
+    out = (ctypes.c_double * 7)()
+    check(_lib.load().af_lcm_coeffs(float(acp_t), float(acp_prev), float(acp_s), int(t), float(timestep_scaling),
+                                    float(sigma_data), out), "af_lcm_coeffs")
+    return tuple(float(v) for v in out)
+
+
+def lcm_step(x, e_cond, e_uncond, guidance, alpha_t, sigma_t, k_out, k_skip, c_x, c_0, c_n, noise=None, seed=0, step=0,
+             sample_ids=None, first_id=0, x_next=None, d_out=None, want_d=True):
+    """CFG combine + one LCM / TCD step (af_lcm_step), one launch; returns (x_next, D) with D = k_out x0 + k_skip x the denoised
+    sample and x_next = c_x x + c_0 x0 + c_n z.  e_uncond None: no guidance.  c_n == 0: no noise is read or generated; otherwise
+    noise is the z to use (x's size), or None: z is generated inside the kernel from (seed, sample id, stream 1, step, element),
+    x's dim 0 being the samples (ids: sample_ids, an int64 GPU tensor, or first_id + i).  x_next / d_out: fp32 contiguous tensors
+    to write into (x_next may be x itself, d_out neither), allocated when None; want_d=False with d_out None skips the D write."""
+    lib = _lib.load()
+    x, e_cond = _dev_f32(x), _dev_f32(e_cond)
+    eu = None if e_uncond is None else _dev_f32(e_uncond)
+    nz = None if noise is None else _dev_f32(noise)
+    for name, t in (("e_cond", e_cond), ("e_uncond", eu), ("noise", nz)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f"lcm_step: {name} has {t.numel()} elements, x has {x.numel()}")
+    for name, t in (("x_next", x_next), ("d_out", d_out)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == x.numel()):
+            raise ValueError(f"lcm_step: {name} must be a contiguous fp32 GPU tensor of x's size")
+    n_samples = x.shape[0] if x.dim() > 0 else 1
+    if sample_ids is not None and not (sample_ids.is_cuda and sample_ids.dtype == torch.int64 and sample_ids.is_contiguous()
+                                       and sample_ids.numel() >= n_samples):
+        raise ValueError("lcm_step: sample_ids must be a contiguous int64 GPU tensor of at least x.shape[0] elements")
+    if x_next is None:
+        x_next = torch.empty_like(x)
+    if d_out is None and want_d:
+        d_out = torch.empty_like(x)
+    check(lib.af_lcm_step(ptr(x), ptr(e_cond), ptr(eu), x.numel(), float(guidance), float(alpha_t), float(sigma_t), float(k_out),
+                          float(k_skip), float(c_x), float(c_0), float(c_n), ptr(x_next), ptr(d_out), ptr(nz),
+                          x.numel() // n_samples, ptr(sample_ids), int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step),
+                          stream_ptr()), "af_lcm_step")
+    return x_next, d_out
+
+
+def lcm_step_launches() -> int:
+    """Launches of the LCM / TCD step kernel since the library was loaded (not part of plan_counts)."""
+    return int(_lib.load().af_lcm_step_launches())
+
+
 STREAM_QSAMPLE = 2    # noise.STREAM_QSAMPLE (csrc/af_philox.h), stated here because noise.py imports this module
 
 

@@ -440,6 +440,35 @@ int af_noise_blend(const float* x_dev, const float* x0_dev, const float* keep_de
 /* launches of its kernel since the library was loaded */
 int64_t af_noise_blend_launches(void);
 
+/* Few-step sampling with consistency models (af_lcm.hip): the LCM update (Luo et al., "Latent Consistency Models",
+ * 2023) and TCD's strategic stochastic sampling (Zheng et al., "Trajectory Consistency Distillation", 2024), both as
+ *     x0 = (x - sigma_t e) / alpha_t,   D = k_out x0 + k_skip x,   x_next = c_x x + c_0 x0 + c_n z,   z ~ N(0, 1).
+ *
+ * af_lcm_coeffs: pure host function (no GPU, no handle), all in double; the only statement of the formulas.
+ * acp_t / acp_prev: alphas_cumprod at the step's start and end, 0 < acp_t < acp_prev <= 1; acp_prev == 1 is the final step,
+ * which returns the denoised sample (x_next = D, c_n = 0).  acp_s <= 0 selects LCM, with tau = t * timestep_scaling:
+ *     k_skip = sd^2 / (tau^2 + sd^2),  k_out = tau / sqrt(tau^2 + sd^2)             (sd = sigma_data; the boundary condition)
+ *     x_next = sqrt(acp_prev) D + sqrt(1 - acp_prev) z:  c_x = sqrt(acp_prev) k_skip, c_0 = sqrt(acp_prev) k_out.
+ * acp_s > 0 selects TCD, acp_s being alphas_cumprod at the intermediate timestep s (acp_prev <= acp_s <= 1):
+ *     D = x0 (k_out = 1, k_skip = 0),  pn = sqrt(acp_s) x0 + sqrt(1 - acp_s) e,  r^2 = acp_prev / acp_s,
+ *     x_next = r pn + sqrt(1 - r^2) z:  c_x = r sqrt(1 - acp_s) / sigma_t,  c_0 = r (sqrt(acp_s) - alpha_t sqrt(1 - acp_s) / sigma_t).
+ * out = { alpha_t, sigma_t, k_out, k_skip, c_x, c_0, c_n }.  Non-finite input, an acp outside (0, 1], acp_prev <= acp_t,
+ * acp_prev > acp_s in TCD mode, t < 0 or a scale that is not positive: AF_ERR_INVALID with a message. */
+int af_lcm_coeffs(double acp_t, double acp_prev, double acp_s, int64_t t, double timestep_scaling, double sigma_data,
+                  double out[7]);
+/* af_lcm_step: one launch per sampler step, fp32, n elements: e = e_u + g (e_c - e_u) (eps_uncond_dev NULL: e = e_c), x0, D to
+ * d_out_dev (NULL: not wanted) and x_next.  c_n == 0: no noise is read or generated.  Otherwise noise_dev non-NULL: z is read
+ * from it (n elements) and the key arguments are ignored; noise_dev NULL: z is generated in registers from (seed, id, stream 1,
+ * step, element), the bits af_philox_randn gives; n = n_samples * per_sample, ids from sample_ids_dev (NULL: first_id + i).  A
+ * temperature is folded into c_n by the caller.  x_next_dev may be x_dev; d_out_dev must overlap neither x_dev nor x_next_dev
+ * (AF_ERR_INVALID).  Any alignment is accepted; the wide and the scalar path give the same bits for an element. */
+int af_lcm_step(const float* x_dev, const float* eps_cond_dev, const float* eps_uncond_dev, int64_t n, float guidance, float alpha_t,
+                float sigma_t, float k_out, float k_skip, float c_x, float c_0, float c_n, float* x_next_dev, float* d_out_dev,
+                const float* noise_dev, int64_t per_sample, const int64_t* sample_ids_dev, int64_t first_id, uint64_t seed,
+                uint32_t step, void* stream);
+/* launches of its kernel since the library was loaded */
+int64_t af_lcm_step_launches(void);
+
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */
 int af_lincomb(float* out_dev, int64_t n, const float* x0_dev, float w0, const float* x1_dev, float w1,

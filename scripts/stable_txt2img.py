@@ -3,7 +3,7 @@
 
 Keeps the reference's flag names for everything that reaches the denoising path
 (stable_txt2img.py:38-310): --config --ckpt --n_samples --n_repeat --ddim_steps --ddim_eta --scale --H --W --C --f
---seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --noise --deep_cache --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
+--seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --lcm --tcd_gamma --noise --deep_cache --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
 Not in the reference: --img2img / --strength / --inpaint_mask (img2img by strength and inpainting, adaface_amd/img2img.py).
@@ -53,6 +53,16 @@ def parse_args(argv=None):
     smp.add_argument("--plms", action="store_true", help="PLMS sampler instead of DDIM (scalar --scale)")
     smp.add_argument("--dpm_solver", action="store_true",
                      help="DPM-Solver++(2M) sampler instead of DDIM: made for 15-25 --ddim_steps (eta must be 0)")
+    smp.add_argument("--lcm", action="store_true",
+                     help="LCM sampler instead of DDIM, for a consistency-distilled model or an LCM-LoRA (--lora lcm-lora.safetensors "
+                          "--scale 1.5): made for 2-8 --ddim_steps (eta must be 0)")
+    ap.add_argument("--lcm_original_steps", type=int, default=50, metavar="N",
+                    help="--lcm: the solver steps of the distillation; the grid is thinned from the N timesteps (i + 1) 1000 / N - 1")
+    ap.add_argument("--tcd_gamma", type=float, default=None, metavar="G",
+                    help="TCD sampling on the LCM grid, G in [0, 1]: 0 = deterministic (DDIM), 1 = the LCM re-noising; implies --lcm")
+    ap.add_argument("--lcm_guidance_embedding", action="store_true",
+                    help="--lcm: feed --scale (one number) through the checkpoint's guidance-scale embedding (a config with "
+                         "time_cond_proj_dim) and run one U-Net leg per step, as a fully distilled LCM checkpoint expects")
     ap.add_argument("--dpm_skip", choices=["time_uniform", "logSNR"], default="time_uniform",
                     help="--dpm_solver: the timestep grid; time_uniform = DDIM's, logSNR = uniform in log(alpha / sigma)")
     ap.add_argument("--dpm_sde", action="store_true",
@@ -141,6 +151,27 @@ def parse_args(argv=None):
     opt = ap.parse_args(argv)
     if opt.dpm_sde and not opt.dpm_solver:
         ap.error("--dpm_sde is a variant of --dpm_solver: give both")
+    if opt.tcd_gamma is not None:
+        if opt.plms or opt.dpm_solver:
+            ap.error("--tcd_gamma: implies --lcm, which is not allowed with --plms or --dpm_solver")
+        if not 0.0 <= opt.tcd_gamma <= 1.0:
+            ap.error("--tcd_gamma G: 0 <= G <= 1")
+        opt.lcm = True
+    if (opt.lcm_guidance_embedding or opt.lcm_original_steps != 50) and not opt.lcm:
+        ap.error("--lcm_guidance_embedding / --lcm_original_steps: give --lcm too")
+    if opt.lcm:
+        if not 1 <= opt.lcm_original_steps <= 1000:
+            ap.error("--lcm_original_steps N: 1 <= N <= 1000")
+        if not 1 <= opt.ddim_steps <= opt.lcm_original_steps:
+            ap.error(f"--lcm: 1 <= --ddim_steps <= --lcm_original_steps ({opt.lcm_original_steps})")
+        if opt.ddim_eta != 0.0:
+            ap.error("--lcm: --ddim_eta has no meaning for the consistency update (its noise is the sampler's own)")
+        if opt.deep_cache not in (None, 1) or opt.tgate:
+            ap.error("--lcm: --deep_cache and --tgate target long schedules and are not built for it")
+        if opt.lcm_guidance_embedding and len(opt.scale) != 1:
+            ap.error("--lcm_guidance_embedding: --scale must be one number (the embedding is constant over a run)")
+        if opt.lcm_guidance_embedding and (opt.pag_scale > 0.0 or opt.guidance_rescale > 0.0):
+            ap.error("--lcm_guidance_embedding: the run has one leg per step, so --pag_scale / --guidance_rescale have nothing to act on")
     if opt.deep_cache is not None and opt.deep_cache < 1:
         ap.error("--deep_cache N: N >= 1")
     if opt.deep_cache not in (None, 1) and opt.plms:
@@ -430,6 +461,12 @@ def main():
     elif opt.dpm_solver:
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler
         sampler = DPMSolverSampler(model)
+    elif opt.lcm:
+        from ldm.models.diffusion.lcm import LCMSampler
+        if opt.lcm_guidance_embedding and not model.has_guidance_embedding:
+            raise SystemExit("--lcm_guidance_embedding: this model has no guidance-scale embedding (a --config whose unet_config "
+                             "sets time_cond_proj_dim, and a checkpoint with time_embed.cond_proj.weight, are needed)")
+        sampler = LCMSampler(model)
     else:
         sampler = DDIMSampler(model)
     shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
@@ -488,6 +525,11 @@ def main():
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
                                             skip_type=opt.dpm_skip, algorithm="sde-dpmsolver++" if opt.dpm_sde else "dpmsolver++",
                                             **kw)
+            elif opt.lcm:
+                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                                            guidance_scale=gs, unconditional_conditioning=uc, x_T=x_T,
+                                            original_steps=opt.lcm_original_steps, tcd_gamma=opt.tcd_gamma,
+                                            guidance_embedding=opt.lcm_guidance_embedding, **kw)
             else:
                 samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                                             guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T, **kw)
@@ -503,7 +545,7 @@ def main():
     toc = time.time()
     if rank == 0:
         n_img = B * opt.n_repeat
-        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M) SDE' if opt.dpm_sde else 'DPM-Solver++(2M)' if opt.dpm_solver else 'DDIM'} steps in {toc - tic:.2f} s "
+        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M) SDE' if opt.dpm_sde else 'DPM-Solver++(2M)' if opt.dpm_solver else 'TCD' if opt.tcd_gamma is not None else 'LCM' if opt.lcm else 'DDIM'} steps in {toc - tic:.2f} s "
               f"({n_img / (toc - tic):.2f} images/s incl. first-call warm-up) on {world} GPU(s); outputs: {opt.outdir}")
     if dist.is_initialized():
         dist.destroy_process_group()

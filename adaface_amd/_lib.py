@@ -85,6 +85,12 @@ _SIGS = [
     ("af_lcm_step", C.c_int, [_P, _P, _P, C.c_int64] + [C.c_float] * 8 + [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_uint64,
                               C.c_uint32, _P]),
     ("af_lcm_step_launches", C.c_int64, []),
+    ("af_set_regions", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("af_region_state", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("af_region_plan_query", C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int64)]),
+    ("af_region_attn_launches", C.c_int64, []),
+    ("af_op_region_weights", C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, _P]),
+    ("af_op_region_attention", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, _P]),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

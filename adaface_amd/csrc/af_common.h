@@ -77,7 +77,10 @@ enum { AF_K_CONV_GEMM = 0, AF_K_ATTENTION = 1, AF_K_GROUPNORM = 2, AF_K_LAYERNOR
        // the ControlNet residual add kernel (af_controlnet.hip; scripts/controlnet_mode.py)
        AF_K_CONTROL_ADD = 23,
        // the noising + inpainting blend kernel (af_inpaint.hip; scripts/inpaint_mode.py)
-       AF_K_NOISE_BLEND = 24, AF_K_COUNT = 25 };
+       AF_K_NOISE_BLEND = 24,
+       // regional prompts (af_region_attn.hip; scripts/region_mode.py): the fused kernel by pyramid level (25 + level, the
+       // operator counts as level 0) and the composition's combine kernel
+       AF_K_REGION_ATTN = 25, AF_K_REGION_COMBINE = 29, AF_K_COUNT = 30 };
 // (process-wide diagnostics, updated by every launch: atomics, since distinct handles may be used from distinct host threads)
 extern int g_af_prof_enabled;
 extern int g_af_prof_stride;              // bracket only every stride-th launch of a class (>= 1)
@@ -150,6 +153,8 @@ struct AfKnobs {
   int pag_share_prefix;     // AF_PAG_SHARE_PREFIX     0 = af_unet_forward_pag computes all three legs from conv_in on; 1 = every block in
                             //                         front of the first one with a set site runs on legs 0-1 and leg 0 is copied onto
                             //                         leg 2: the A/B handle of that sharing
+  int region_fused;         // AF_REGION_FUSED         0 = regional cross-attention (af_set_regions) always as R attention launches on the
+                            //                         key segments + region_combine_kernel, never region_attn_kernel: its A/B handle
 };
 extern AfKnobs g_af_knobs;
 

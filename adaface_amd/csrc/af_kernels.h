@@ -162,6 +162,43 @@ extern std::atomic<long> g_af_noise_blend_launches;   // launches since the libr
 // arguments on the host and launches ONE kernel, instantiated on (CFG, noise source) alone); af_lcm_step_launches reads this.
 extern std::atomic<long> g_af_lcm_step_launches;      // launches since the library was loaded
 
+// Regional prompts (af_region_attn.hip): the context of a sample is R <= AF_REGION_MAX segments of T keys, a weight
+// pyramid says which regions a pixel of a site listens to.  The layout of the pyramid of an H x W map (sides multiples of 8):
+// level l (f = 2^l) holds w [Bf][R][N_l] fp32 at float w_off[l] and one word of active-region bits per (sample, 32-query
+// block) at word b_off[l]; -1 with a message for a shape it refuses.
+enum { AF_REGION_MAX = 8 };
+struct AfRegionLayout { long w_off[4], b_off[4], w_floats, b_words; int N[4], nblk[4]; };
+int af_region_layout(int Bf, int R, int H, int W, AfRegionLayout* L);
+// m [Bf][R][H][W] fp32 >= 0 -> the pyramid and the bits, ONE launch (region_weights_kernel)
+int af_launch_region_weights(const float* m, int Bf, int R, int H, int W, float* pyr, unsigned* bits, hipStream_t stream);
+// The plan of a regional cross-attention: the ONE decision, which xfmr_cross_attention and af_op_region_attention follow and
+// af_region_plan_query reports.  The values are part of that result.
+enum AfRegionKernel {
+  AF_RGK_REFUSED = 0,    // R outside 1 .. 8, no key, a head dim the attention kernels do not take
+  AF_RGK_COMPOSE = 1,    // R launches of af_launch_attention on the key segments + region_combine_kernel (f32, T > 96, other
+                         // head dims, knob region_fused = 0)
+  AF_RGK_FUSED = 2       // region_attn_kernel<T, DH>: bf16 / fp16, dh in {32, 40, 64, 80, 128, 160}, T <= 96
+};
+int af_plan_region_attention(AfStorage st, int dh, int T, int R);
+// V of the cached [B][R T][..] key list (row pitch ldv, sample stride bsv) as the fused kernel's per-segment V^T fragments:
+// elements needed (0 = no fused kernel for this case) and the pack launch
+template <typename T> long af_region_pack_elems(int B, int R, int H, int dh, int Tk);
+template <typename T>
+int af_launch_region_pack(const void* v, int ldv, long bsv, int Tk, int R, int H, int dh, int B, void* vt, hipStream_t stream);
+struct AfRegionAttnArgs {
+  const void* q; const void* k; void* o; const void* vt;   // k: [B][R T] rows of pitch ldk; vt: af_launch_region_pack
+  const float* w; const unsigned* bits;                    // this site's level: w [B][R][Nq], bits [B][ceil(Nq / 32)]
+  int ldq, ldk, ldo; long bsq, bsk, bso;                   // elements
+  int B, Nq, R, T, heads, dh; float scale;
+  int level;                                               // the pyramid level, for the profiler's class only (AF_K_REGION_ATTN + level)
+};
+template <typename T> int af_launch_region_attention(const AfRegionAttnArgs& a, hipStream_t stream);
+// out [B Nq][ldo] = sum_{r : w_r > 0} w_r src[r][B Nq][Cn] (src dense, rs elements between regions), fp32 sum, r ascending
+template <typename T>
+int af_launch_region_combine(const void* src, long rs, const float* w, void* out, int ldo, int B, int Nq, int Cn, int R,
+                             hipStream_t stream);
+extern std::atomic<long> g_af_region_attn_launches;   // fused launches since the library was loaded
+
 // FreeU in place on a concatenation buffer [B][H W][ld], pixel rows [h (Ch) | skip (Cs)] (af_freeu.hip).  All three storage
 // types.  The plan of one site: the launcher follows it and af_freeu_plan_query reports it.  The values are part of that result.
 enum AfFreeuKernel {

@@ -56,7 +56,7 @@ AfKnobs g_af_knobs = {
     knob_env("AF_GN_PRODUCER", 1),     knob_env("AF_CONV_UP_PHASE4", 1), knob_env("AF_ATTN_SHORT", 1),
     knob_env("AF_GEMM_M128", 1),       knob_env("AF_SMALL_M_TILE64", 1),  knob_env("AF_GN_CONSUMER", 1),
     knob_env("AF_XATTN_FUSED", 1),     knob_env("AF_PLAN_LOG", 0),      knob_env("AF_FF8_MIN_K", 512),   knob_env("AF_FF8_MIN_ROWS", 0),
-    knob_env("AF_CONV_ATTN_SHORT", 1), knob_env("AF_PAG_SHARE_PREFIX", 1)};
+    knob_env("AF_CONV_ATTN_SHORT", 1), knob_env("AF_PAG_SHARE_PREFIX", 1), knob_env("AF_REGION_FUSED", 1)};
 static const AfKnobs g_af_knobs_initial = g_af_knobs;
 static int* knob_slot(const char* name) {
   static const struct { const char* n; int AfKnobs::*m; } tab[] = {
@@ -68,7 +68,8 @@ static int* knob_slot(const char* name) {
       {"geglu_rowpanel", &AfKnobs::geglu_rowpanel}, {"conv_halo8", &AfKnobs::conv_halo8}, {"ablate", &AfKnobs::ablate}, {"gn_producer", &AfKnobs::gn_producer}, {"conv_up_phase4", &AfKnobs::conv_up_phase4},
       {"attn_short", &AfKnobs::attn_short},
       {"gemm_m128", &AfKnobs::gemm_m128}, {"small_m_tile64", &AfKnobs::small_m_tile64}, {"gn_consumer", &AfKnobs::gn_consumer}, {"xattn_fused", &AfKnobs::xattn_fused}, {"plan_log", &AfKnobs::plan_log}, {"ff8_min_k", &AfKnobs::ff8_min_k}, {"ff8_min_rows", &AfKnobs::ff8_min_rows},
-      {"conv_attn_short", &AfKnobs::conv_attn_short}, {"pag_share_prefix", &AfKnobs::pag_share_prefix}};
+      {"conv_attn_short", &AfKnobs::conv_attn_short}, {"pag_share_prefix", &AfKnobs::pag_share_prefix},
+      {"region_fused", &AfKnobs::region_fused}};
   if (!name) return nullptr;
   for (auto& t : tab)
     if (strcmp(t.n, name) == 0) return &(g_af_knobs.*(t.m));
@@ -457,6 +458,20 @@ struct af_handle {
     bool cond_only = false;
     int last_launches = 0, last_segments = 0;
   } ctl;
+
+  // Regional prompts (af_set_regions): the weight pyramid and the active-region bits of the (Bf, H, W) they were
+  // set for, handle-owned, and per cross-attention site (the order of ca_list) the per-segment V^T fragments of the fused kernel
+  // (null where the site runs the composition), remade by every af_set_context while regions are set.
+  struct Regions {
+    int R = 0, Bf = 0, H = 0, W = 0;  // R = 0: off
+    float* pyr = nullptr;
+    unsigned* bits = nullptr;
+    size_t pyr_bytes = 0, bits_bytes = 0;
+    AfRegionLayout L = {};
+    std::vector<void*> vt;            // per site
+    std::vector<size_t> vt_bytes;
+    int fused_sites = 0;              // of the last forward
+  } rg;
 
   // runtime state
   Arena arena;
@@ -1581,6 +1596,52 @@ static int xfmr_tgate_replay(const XfmrCtx& X, int site, const Act& t1, Act& t2)
   return xfmr_tgate_add(X, site, t1, t1, t2, false);
 }
 
+// Regional prompts (af_set_regions) at cross-attention site `site`: the S keys are R segments of T, this map's level
+// of the weight pyramid mixes the per-segment attention outputs.  One decision (af_plan_region_attention): the fused kernel, or
+// the composition -- R launches of R.attention on the key segments (a pointer offset of r T rows, Nk = T, the batch stride of
+// the whole list) into `parts`, then region_combine.  `parts` is reserved whichever path runs: the sizing pass must not depend
+// on the choice.
+static int xfmr_cross_attention_regions(const XfmrCtx& X, const CtxKV& kv, int site, int S, const Act& q, Act& a) {
+  Runner& R = X.R;
+  af_handle* h = R.h;
+  const XfmrW& w = X.w;
+  af_handle::Regions& rg = h->rg;
+  const int B = X.B, N = X.N, C = X.C, Rn = rg.R, T = S / Rn;
+  Act parts = R.alloc_act(B * Rn, X.H, X.W, C);
+  AF_TRY(R.check(parts));
+  AF_TRY(R.check(a));
+  if (R.dry) return 0;
+  int lvl = -1;
+  for (int l = 0; l < 4; ++l)
+    if ((rg.H >> l) == X.H && (rg.W >> l) == X.W) lvl = l;
+  if (lvl < 0 || B != rg.Bf || N != X.H * X.W || site < 0 || site >= (int)rg.vt.size()) {
+    af_set_error_msg("regions: set for %d samples of %d x %d, this site has %d samples of %d x %d (%d rows)", rg.Bf, rg.H, rg.W, B, X.H, X.W, N);
+    return AF_ERR_STATE;
+  }
+  const float* wl = rg.pyr + rg.L.w_off[lvl];
+  const int plan = af_plan_region_attention(storage_of(R.dt), w.dh, T, Rn);
+  if (plan == AF_RGK_REFUSED) { af_set_error_msg("regions: no kernel for head dim %d, %d regions of %d keys", w.dh, Rn, T); return AF_ERR_STATE; }
+  if (plan == AF_RGK_FUSED && rg.vt[site]) {
+    AfRegionAttnArgs g;
+    g.q = q.p; g.k = kv.kv; g.o = a.p; g.vt = rg.vt[site]; g.w = wl; g.bits = rg.bits + rg.L.b_off[lvl];
+    g.ldq = q.ld; g.ldk = 2 * C; g.ldo = a.ld;
+    g.bsq = (long)N * q.ld; g.bsk = (long)S * 2 * C; g.bso = (long)N * a.ld;
+    g.B = B; g.Nq = N; g.R = Rn; g.T = T; g.heads = w.heads; g.dh = w.dh; g.scale = 1.0f / sqrtf((float)w.dh); g.level = lvl;
+    AF_TRY(AF_TYPED(R.dt, af_launch_region_attention<Elem>(g, R.s)));
+    ++rg.fused_sites;
+    return 0;
+  }
+  for (int r = 0; r < Rn; ++r) {
+    const Strided k = {R.elem_ptr(kv.kv, (long)r * T * 2 * C), 2 * C, (long)S * 2 * C};
+    const Strided v = {R.elem_ptr(kv.kv, (long)r * T * 2 * C + C), 2 * C, (long)S * 2 * C};
+    Act o = parts;
+    o.B = B;
+    o.p = R.elem_ptr(parts.p, (long)r * B * N * C);
+    AF_TRY(R.attention(R.cols_of(q, 0, N), k, v, o, N, T, w.heads, w.dh));
+  }
+  return AF_TYPED(R.dt, af_launch_region_combine<Elem>(parts.p, (long)B * N * C, wl, a.p, a.ld, B, N, C, Rn, R.s));
+}
+
 // x = x + attn2(norm2(x), context): t1 -> t2 (block d of the transformer; pre: t1's statistics cover the first half only)
 static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d, bool pre, const Act& t1, Act& n, Act& a,
                                 Act& t2) {
@@ -1607,7 +1668,9 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
   // shape and the weights alone, so that the sizing pass and the run agree; the pack exists whenever the context was set for
   // such a layer
   // (a T-GATE capture needs attn2's output by itself: never the fused launch)
-  if (!R.tgate && g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && X.ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
+  // (regional prompts need the per-segment softmax: never the fused launch)
+  const bool regions = h->rg.R > 0;
+  if (!regions && !R.tgate && g_af_knobs.xattn_fused && R.dt == AF_DTYPE_BF16 && X.ln_parts == 4 && !conv_attn && blk.out2_perm && blk.q2_ln.w &&
       t1.ld == C && t2.ld == C && af_xattn_fused_ok(B * N, N, C, w.heads, w.dh, S > 0 ? S : 77))
     return xfmr_cross_attention_fused(X, blk, pre, kv, S, t1, t2);
   if (!X.ln_parts) {
@@ -1619,7 +1682,9 @@ static int xfmr_cross_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t 
   } else {
     AF_TRY(R.conv(blk.q2_ln, t1, q, X.consumer(blk.q2_cs, blk.ln2)));
   }
-  if (conv_attn) {
+  if (regions) {
+    AF_TRY(xfmr_cross_attention_regions(X, kv, w.ca_slot + (int)d, S, q, a));
+  } else if (conv_attn) {
     AF_TRY(xfmr_cross_attention_conv(X, kv, S, q, a));
   } else {
     const Strided k = {kv.kv, 2 * C, (long)S * 2 * C}, v = {R.dry ? nullptr : R.elem_ptr(kv.kv, C), 2 * C, (long)S * 2 * C};
@@ -2587,6 +2652,9 @@ void af_destroy(af_handle* h) {
   if (h->ctx_cast) hipFree(h->ctx_cast);
   if (h->dc.buf) hipFree(h->dc.buf);
   if (h->tg.buf) hipFree(h->tg.buf);
+  if (h->rg.pyr) hipFree(h->rg.pyr);
+  if (h->rg.bits) hipFree(h->rg.bits);
+  for (void* p : h->rg.vt) if (p) hipFree(p);
   if (h->hint_g) hipFree(h->hint_g);
   if (h->arena.base) hipFree(h->arena.base);
   if (h->stage) hipFree(h->stage);
@@ -2723,6 +2791,7 @@ int af_set_conv_attn(af_handle* h, int ks, int n_subj, const int* batch_idx, con
   }
   if (ks > 4) { af_set_error_msg("af_set_conv_attn: kernel size %d (the reference has 2, 3 and 4: ldm/util.py:747-760)", ks); return AF_ERR_INVALID; }
   if (!batch_idx || !token_idx) { af_set_error_msg("af_set_conv_attn: null index arrays"); return AF_ERR_INVALID; }
+  if (h->rg.R) { af_set_error_msg("af_set_conv_attn: regions are set (af_set_regions): conv attention with a subject is not supported with them"); return AF_ERR_STATE; }
   h->conv_ks = ks;
   h->conv_batch.assign(batch_idx, batch_idx + n_subj);
   h->conv_tokens.assign(token_idx, token_idx + (size_t)n_subj * ks * ks);
@@ -2730,9 +2799,82 @@ int af_set_conv_attn(af_handle* h, int ks, int n_subj, const int* batch_idx, con
   return AF_OK;
 }
 
+// ---- regional prompts ----
+static void regions_off(af_handle* h) {
+  af_handle::Regions& rg = h->rg;
+  if (rg.R) h->dc.valid = false;
+  rg.R = rg.Bf = rg.H = rg.W = 0;
+  rg.fused_sites = 0;
+}
+// the per-segment V^T fragments of every site the fused kernel can take, from the cached K | V as it now stands
+static int regions_pack(af_handle* h, hipStream_t s) {
+  af_handle::Regions& rg = h->rg;
+  const int dt = h->dtype, S = h->ctx_tokens, T = S / rg.R;
+  rg.vt.resize(h->ca_list.size(), nullptr);
+  rg.vt_bytes.resize(h->ca_list.size(), 0);
+  for (size_t i = 0; i < h->ca_list.size(); ++i) {
+    const XfmrW& x = h->xf[h->ca_list[i].first];
+    const int C = x.heads * x.dh;
+    const size_t need = (size_t)AF_TYPED(dt, (int)af_region_pack_elems<Elem>(rg.Bf, rg.R, x.heads, x.dh, T)) * esize(dt);
+    if (need != rg.vt_bytes[i]) {
+      HIP_CHECK_RET(hipStreamSynchronize(s));
+      if (rg.vt[i]) hipFree(rg.vt[i]);
+      rg.vt[i] = nullptr;
+      rg.vt_bytes[i] = 0;
+      if (need) HIP_CHECK_RET(hipMalloc(&rg.vt[i], need));
+      rg.vt_bytes[i] = need;
+    }
+    if (need)
+      AF_TRY(AF_TYPED(dt, af_launch_region_pack<Elem>(reinterpret_cast<char*>(h->ctx_kv[i].kv) + (size_t)C * esize(dt), 2 * C,
+                                                      (long)S * 2 * C, T, rg.R, x.heads, x.dh, rg.Bf, rg.vt[i], s)));
+  }
+  return 0;
+}
+
+int af_set_regions(af_handle* h, const float* weights_dev, int Bf, int R, int H, int W, void* stream) {
+  if (!h) { af_set_error_msg("af_set_regions: null handle"); return AF_ERR_INVALID; }
+  if (!weights_dev || R == 0) { regions_off(h); return AF_OK; }
+  if (!h->cfg.build_unet || h->is_control) { af_set_error_msg("af_set_regions: not a U-Net handle"); return AF_ERR_STATE; }
+  if (R < 0 || R > AF_REGION_MAX) { af_set_error_msg("af_set_regions: %d regions (1 .. %d, the base prompt included)", R, AF_REGION_MAX); return AF_ERR_INVALID; }
+  if (Bf <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) { af_set_error_msg("af_set_regions: %d samples of a %d x %d weight map (H and W must be multiples of 8)", Bf, H, W); return AF_ERR_INVALID; }
+  if (!h->ctx_set || h->ctx_Bf != Bf) { af_set_error_msg("af_set_regions: call af_set_context for batch %d first", Bf); return AF_ERR_STATE; }
+  if (h->ctx_tokens % R) { af_set_error_msg("af_set_regions: the context's %d tokens are no %d segments of equal length (n_tokens %% R)", h->ctx_tokens, R); return AF_ERR_INVALID; }
+  if (h->conv_ks >= 2 && !h->conv_batch.empty()) { af_set_error_msg("af_set_regions: conv attention with a subject is active (af_set_conv_attn): not supported with regions"); return AF_ERR_STATE; }
+  if (h->ctl.res) { af_set_error_msg("af_set_regions: ControlNet residuals are attached (af_unet_set_control): not supported with regions"); return AF_ERR_STATE; }
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  af_handle::Regions& rg = h->rg;
+  AfRegionLayout L;
+  if (af_region_layout(Bf, R, H, W, &L)) return AF_ERR_INVALID;
+  const size_t pb = (size_t)L.w_floats * sizeof(float), bb = (size_t)L.b_words * sizeof(unsigned);
+  if (pb > rg.pyr_bytes || bb > rg.bits_bytes) {
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    if (rg.pyr) hipFree(rg.pyr);
+    if (rg.bits) hipFree(rg.bits);
+    rg.pyr = nullptr; rg.bits = nullptr; rg.pyr_bytes = rg.bits_bytes = 0;
+    regions_off(h);
+    HIP_CHECK_RET(hipMalloc(reinterpret_cast<void**>(&rg.pyr), pb));
+    rg.pyr_bytes = pb;
+    HIP_CHECK_RET(hipMalloc(reinterpret_cast<void**>(&rg.bits), bb));
+    rg.bits_bytes = bb;
+  }
+  regions_off(h);                      // (until everything below has been enqueued)
+  if (af_launch_region_weights(weights_dev, Bf, R, H, W, rg.pyr, rg.bits, s)) return AF_ERR_INVALID;
+  rg.R = R; rg.Bf = Bf; rg.H = H; rg.W = W; rg.L = L;
+  if (const int rc = regions_pack(h, s)) { regions_off(h); return rc; }
+  h->dc.valid = false;                 // the kept feature was computed under other regions
+  return AF_OK;
+}
+int af_region_state(af_handle* h, int out[4]) {
+  if (!h || !out) { af_set_error_msg("af_region_state: null argument"); return AF_ERR_INVALID; }
+  out[0] = h->rg.R; out[1] = h->rg.H; out[2] = h->rg.W; out[3] = h->rg.R ? h->rg.fused_sites : 0;
+  return AF_OK;
+}
+
 int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int layerwise, void* stream) {
   if (!h || !ctx_dev || Bf <= 0 || n_tokens <= 0) { af_set_error_msg("af_set_context: bad argument"); return AF_ERR_INVALID; }
   if (!h->cfg.build_unet) { af_set_error_msg("af_set_context: handle has no UNet"); return AF_ERR_STATE; }
+  if (h->rg.R && (Bf != h->ctx_Bf || n_tokens != h->ctx_tokens)) regions_off(h);   // (a context of another shape drops the regions)
   HIP_CHECK_RET(hipSetDevice(h->device));
   AF_TRY(check_loaded(h, h->unet_prefix.c_str()));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2850,6 +2992,10 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
   h->ctx_Bf = Bf;
   h->ctx_tokens = n_tokens;
   h->ctx_set = true;
+  if (h->rg.R) {   // regions kept (same Bf and n_tokens): the per-segment V^T fragments follow the new K | V
+    if (h->conv_ks >= 2 && !h->conv_batch.empty()) regions_off(h);
+    else if (const int rc = regions_pack(h, s)) { regions_off(h); return rc; }
+  }
   return 0;
 }
 
@@ -2924,6 +3070,17 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     }
     if (replay) AF_TRY(check_loaded(h, "model.diffusion_model."));   // (af_set_context, which a replay does not need, checks this otherwise)
   }
+  if (h->rg.R) {   // regional prompts (af_set_regions): everything they refuse, before anything is enqueued
+    if (pag) { af_set_error_msg("regions: the PAG form is not supported (switch them off with af_set_regions(NULL))"); return AF_ERR_STATE; }
+    if (tg.mode) { af_set_error_msg("regions: T-GATE capture / replay is not supported"); return AF_ERR_STATE; }
+    if (h->ctl.res) { af_set_error_msg("regions: ControlNet residuals are not supported"); return AF_ERR_STATE; }
+    if (h->rg.Bf != Bf || h->rg.H != H || h->rg.W != W) {
+      af_set_error_msg("regions: set for %d samples of %d x %d, this forward has %d samples of %d x %d (af_set_regions)", h->rg.Bf,
+                       h->rg.H, h->rg.W, Bf, H, W);
+      return AF_ERR_STATE;
+    }
+    if (h->conv_ks >= 2 && !h->conv_batch.empty()) { af_set_error_msg("regions: conv attention with a subject is not supported"); return AF_ERR_STATE; }
+  }
   if (h->ctl.res) {   // ControlNet residuals (af_unet_set_control): everything they refuse, before anything is enqueued
     const int n_in = (int)h->input_blocks.size(), n_out = (int)h->output_blocks.size();
     const int need = dc_mode == AF_DEEPCACHE_REUSE ? dc_depth : n_in + 1;
@@ -2984,6 +3141,7 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     tg.valid = false;                       // (until this capture has been enqueued completely)
     AF_TRY(ensure_tgate(h, s, twin ? Bf / 2 : Bf, H, W));
   }
+  h->rg.fused_sites = 0;
   if (const int rc = run()) { if (dc_mode) dc.valid = false; if (tg.mode == AF_TGATE_CAPTURE) tg.valid = false; return rc; }
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = true;
@@ -3076,6 +3234,7 @@ int af_unet_set_control(af_handle* h, const void* res_dev, int Bs, int H, int W,
   if (!h) { af_set_error_msg("af_unet_set_control: null handle"); return AF_ERR_INVALID; }
   if (!res_dev) { h->ctl.res = nullptr; h->ctl.n = 0; h->ctl.cond_only = false; return AF_OK; }
   if (!h->cfg.build_unet || h->is_control) { af_set_error_msg("af_unet_set_control: not a U-Net handle"); return AF_ERR_STATE; }
+  if (h->rg.R) { af_set_error_msg("af_unet_set_control: regions are set (af_set_regions): the control branch has cross-attention of its own"); return AF_ERR_STATE; }
   if (n < 1 || n > AF_CONTROL_MAX_SEGMENTS || n > (int)h->input_blocks.size() + 1 || !scales) {
     af_set_error_msg("af_unet_set_control: %d residuals (1 .. %d) with their scales", n, std::min((int)AF_CONTROL_MAX_SEGMENTS, (int)h->input_blocks.size() + 1));
     return AF_ERR_INVALID;

@@ -927,6 +927,118 @@ int af_op_attention(int dtype, const float* q_dev, const float* k_dev, const flo
                             stream);
 }
 
+// ---- regional prompts (af_region_attn.hip) ----
+int af_region_plan_query(int dtype, int dh, int T, int R, int64_t* out) {
+  if (!out || (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16)) {
+    af_set_error_msg("af_region_plan_query: bad argument");
+    return AF_ERR_INVALID;
+  }
+  *out = af_plan_region_attention(storage_of(dtype), dh, T, R);
+  return AF_OK;
+}
+int64_t af_region_attn_launches(void) { return g_af_region_attn_launches; }
+
+int af_op_region_weights(const float* m_dev, int Bf, int R, int H, int W, float* out_pyramid_dev, uint32_t* out_bits_dev,
+                         void* stream) {
+  if (!m_dev || !out_pyramid_dev || !out_bits_dev) { af_set_error_msg("af_op_region_weights: null argument"); return AF_ERR_INVALID; }
+  return af_launch_region_weights(m_dev, Bf, R, H, W, out_pyramid_dev, out_bits_dev, reinterpret_cast<hipStream_t>(stream))
+             ? AF_ERR_INVALID : AF_OK;
+}
+
+// The regional attention on either path, staged as the model holds its operands: K | V as columns of one [B][R T][2C + slack]
+// buffer, q and o with the same slack, NaN bytes wherever no operand is (as af_op_attention_ex).
+int af_op_region_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, const float* w_dev, float* o_dev,
+                           int B, int Nq, int R, int T, int heads, int dh, float scale, int path, int ld_slack, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Tmp tmp;
+  if ((dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) || !q_dev || !k_dev || !v_dev || !w_dev || !o_dev ||
+      B <= 0 || Nq <= 0 || T <= 0 || heads <= 0 || dh <= 0 || dh % 8 || ld_slack < 0 || ld_slack % 8 || path < 0 || path > 2) {
+    af_set_error_msg("af_op_region_attention: dtype=%d B=%d Nq=%d R=%d T=%d heads=%d dh=%d path=%d ld_slack=%d (dh and ld_slack "
+                     "multiples of 8; path 0 planner, 1 composition, 2 fused)", dtype, B, Nq, R, T, heads, dh, path, ld_slack);
+    return AF_ERR_INVALID;
+  }
+  int plan = af_plan_region_attention(storage_of(dtype), dh, T, R);
+  if (plan == AF_RGK_REFUSED) {
+    af_set_error_msg("af_op_region_attention: refused (1 .. %d regions, head dim 8, 16, 32, 40, 64, 80, 128 or 160), got R=%d dh=%d",
+                     AF_REGION_MAX, R, dh);
+    return AF_ERR_INVALID;
+  }
+  if (path == 1) plan = AF_RGK_COMPOSE;
+  if (path == 2) {
+    if (AF_TYPED(dtype, af_region_pack_elems<Elem>(B, R, heads, dh, T)) <= 0) {
+      af_set_error_msg("af_op_region_attention: no fused kernel for dtype %d, head dim %d, %d keys per segment", dtype, dh, T);
+      return AF_ERR_INVALID;
+    }
+    plan = AF_RGK_FUSED;
+  }
+  const size_t es = esize(dtype);
+  const int C = heads * dh, S = R * T;
+  const int ldq = C + ld_slack, ldo = C + ld_slack, ldk = 2 * C + ld_slack;
+  const long rq = (long)B * Nq, rk = (long)B * S, tail_rows = 128;
+  auto nan_buf = [&](long rows, int ld) -> void* {
+    const size_t bytes = (size_t)(rows + tail_rows) * ld * es;
+    void* b = tmp.get(bytes, false);
+    if (b && hipMemsetAsync(b, 0xFF, bytes, s) != hipSuccess) return nullptr;
+    return b;
+  };
+  auto put = [&](const float* src, long rows, void* dst, int ld, int off) -> int {
+    void* dense = tmp.get((size_t)rows * C * es, false);
+    if (!dense) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
+    AF_TRY(AF_TYPED(dtype, af_launch_cast_f32<Elem>(src, dense, rows * C, s)));
+    AF_TRY(AF_TYPED(dtype, af_launch_copy_channels<Elem>(dense, C, dst, ld, off, C, rows, s)));
+    return 0;
+  };
+  void* qn = nan_buf(rq, ldq);
+  void* kn = nan_buf(rk, ldk);
+  if (!qn || !kn) { af_set_error_msg("hipMalloc failed in op"); return AF_ERR_HIP; }
+  void* vn = (char*)kn + (size_t)C * es;
+  AF_TRY(put(q_dev, rq, qn, ldq, 0));
+  AF_TRY(put(k_dev, rk, kn, ldk, 0));
+  AF_TRY(put(v_dev, rk, kn, ldk, C));
+  const size_t o_bytes = (size_t)rq * ldo * es;
+  OP_ALLOC(on, o_bytes, false);
+  if (hipMemsetAsync(on, 0xFF, o_bytes, s) != hipSuccess) return AF_ERR_HIP;
+  if (plan == AF_RGK_FUSED) {
+    // the active bits of every 32-query block, from w (host: an operator for tests)
+    const int nblk = (Nq + 31) / 32;
+    std::vector<float> wh((size_t)B * R * Nq);
+    HIP_CHECK_RET(hipMemcpyAsync(wh.data(), w_dev, wh.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));
+    std::vector<unsigned> bh((size_t)B * nblk, 0u);
+    for (int b = 0; b < B; ++b)
+      for (int r = 0; r < R; ++r)
+        for (int q = 0; q < Nq; ++q)
+          if (wh[((size_t)b * R + r) * Nq + q] > 0.f) bh[(size_t)b * nblk + q / 32] |= 1u << r;
+    OP_ALLOC(bits, bh.size() * sizeof(unsigned), false);
+    HIP_CHECK_RET(hipMemcpyAsync(bits, bh.data(), bh.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
+    HIP_CHECK_RET(hipStreamSynchronize(s));   // (`bh` is a pageable host temporary)
+    const long pe = AF_TYPED(dtype, af_region_pack_elems<Elem>(B, R, heads, dh, T));
+    OP_ALLOC(vt, (size_t)pe * es, false);
+    AF_TRY(AF_TYPED(dtype, af_launch_region_pack<Elem>(vn, ldk, (long)S * ldk, T, R, heads, dh, B, vt, s)));
+    AfRegionAttnArgs a;
+    a.q = qn; a.k = kn; a.o = on; a.vt = vt; a.w = w_dev; a.bits = reinterpret_cast<const unsigned*>(bits);
+    a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.bsq = (long)Nq * ldq; a.bsk = (long)S * ldk; a.bso = (long)Nq * ldo;
+    a.B = B; a.Nq = Nq; a.R = R; a.T = T; a.heads = heads; a.dh = dh; a.scale = scale; a.level = 0;
+    AF_TRY(AF_TYPED(dtype, af_launch_region_attention<Elem>(a, s)));
+  } else {
+    // R launches of the attention kernels on the key segments (a pointer offset of r T rows, the batch stride of the whole
+    // list) into R dense outputs, then the combine
+    OP_ALLOC(parts, (size_t)R * rq * C * es + 4096, false);
+    for (int r = 0; r < R; ++r) {
+      AttnParams p;
+      p.ldq = ldq; p.ldk = p.ldv = ldk; p.ldo = C;
+      p.bsq = (long)Nq * ldq; p.bso = (long)Nq * C; p.bsk = p.bsv = (long)S * ldk;
+      p.q = qn; p.k = (char*)kn + (size_t)r * T * ldk * es; p.v = (char*)vn + (size_t)r * T * ldk * es;
+      p.o = (char*)parts + (size_t)r * rq * C * es;
+      p.lse = nullptr; p.causal = 0; p.Nq = Nq; p.Nk = T; p.H = heads; p.scale = scale; p.vt_pack = nullptr;
+      AF_TRY(AF_TYPED(dtype, af_launch_attention<Elem>(p, B, dh, s)));
+    }
+    AF_TRY(AF_TYPED(dtype, af_launch_region_combine<Elem>(parts, rq * C, w_dev, on, ldo, B, Nq, C, R, s)));
+  }
+  AF_TRY(AF_TYPED(dtype, af_launch_cast_to_f32<Elem>(on, o_dev, rq * ldo, s)));
+  return 0;
+}
+
 // Host-only diagnostic: the kernel af_launch_attention would run (AfAttnKernel); no device is touched
 int af_attn_plan_query(int dtype, int dh, int Nk, int ldq, int ldk, int ldv, int ldo, int flags, int64_t* out) {
   if (!out || (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16)) {

@@ -322,6 +322,31 @@ class Engine:
         check(self._lib.af_set_context(self._h, ptr(ctx), Bf, n_tokens, 1 if layerwise else 0, stream_ptr()),
               "af_set_context")
 
+    def set_regions(self, weights: Optional[torch.Tensor]):
+        """af_set_regions (regional prompts, adaface_amd/regions.py): weights [Bf, R, H, W] >= 0 at the latent resolution of the
+        forwards that follow, for the context set last ([.., R T, D]: R segments of T tokens, segment 0 the base prompt); None
+        switches regions off.  A later set_context of the same shape keeps them, one of another shape drops them."""
+        if weights is None:
+            check(self._lib.af_set_regions(self._h, None, 0, 0, 0, 0, stream_ptr()), "af_set_regions")
+            return
+        if weights.dim() != 4:
+            raise ValueError(f"region weights of shape {tuple(weights.shape)}: expected [Bf, R, H, W]")
+        if not torch.isfinite(weights).all() or bool((weights < 0).any()):
+            raise ValueError("region weights must be finite and >= 0")
+        w = weights.to(device=self.device, dtype=torch.float32).contiguous()
+        Bf, R, H, W = w.shape
+        check(self._lib.af_set_regions(self._h, ptr(w), Bf, R, H, W, stream_ptr()), "af_set_regions")
+
+    def region_state(self) -> dict:
+        """af_region_state: {"R" (0 = off), "H", "W", "fused_sites" of the last forward}."""
+        out = (C.c_int * 4)()
+        check(self._lib.af_region_state(self._h, out), "af_region_state")
+        return {"R": out[0], "H": out[1], "W": out[2], "fused_sites": out[3]}
+
+    def _no_regions(self, what: str):
+        if self.region_state()["R"]:
+            raise NotImplementedError(f"{what} is not supported while regional prompts are set (set_regions(None) switches them off)")
+
     def set_conv_attn(self, ks: int, batch_idx=(), token_idx=()):
         """Subject-token conv attention (attention.py:208-216), kernel size ks = 2, 3 or 4: sample `batch_idx[i]` carries a
         subject string whose first ks*ks token positions are `token_idx[i]` (a sample with several subject strings appears
@@ -332,6 +357,8 @@ class Engine:
         ti = (C.c_int * max(len(flat), 1))(*flat)
         if n and len(flat) != ks * ks * n:
             raise ValueError(f"set_conv_attn: {ks * ks} token positions per subject sample for a {ks}x{ks} kernel")
+        if n and ks > 1:
+            self._no_regions("conv attention with a subject")
         check(self._lib.af_set_conv_attn(self._h, int(ks), n, bi, ti), "af_set_conv_attn")
         self._ctx_key = None
 
@@ -343,6 +370,7 @@ class Engine:
         if tgate is None:
             yield
             return
+        self._no_regions("T-GATE capture / replay")
         check(self._lib.af_tgate_set(self._h, _lib.TGATE_MODES[tgate]), "af_tgate_set")
         try:
             yield
@@ -430,6 +458,7 @@ class Engine:
             check(self._lib.af_unet_set_control(self._h, None, 0, 0, 0, 0, None, 0), "af_unet_set_control")
             self._control_ref = None
             return
+        self._no_regions("ControlNet")
         from .ops import STORAGE_TORCH
         if source is not None:
             if DTYPES[source.dtype] != DTYPES[self.dtype]:
@@ -514,6 +543,7 @@ class Engine:
         """af_unet_forward_pag: the UNet on [x; x; x], [t; t; t] with legs (cond, uncond, perturbed); the context was set for
         3 * len(x) samples as [c; uc; c].  Leg 2 is leg 0 except that its self-attention at the set sites is the identity map.
         Returns eps [3B, C, H, W]."""
+        self._no_regions("the PAG forward")
         x = x.contiguous().float()
         t = t.contiguous().long()
         B, _, H, W = x.shape

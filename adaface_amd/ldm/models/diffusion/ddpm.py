@@ -386,6 +386,17 @@ class LatentDiffusion(DDPM):
         self.model.diffusion_model.set_pag(layers)
         return self
 
+    def set_regions(self, weights):
+        """UNetModel.set_regions: regional prompts (adaface_amd/regions.py).  weights [Bf, R, H, W] for the samples of the
+        conditioning the samplers pass (regions.build_weights; legs=2 for a run with an unconditional conditioning), whose
+        context is regions.concat_contexts' [.., R T, D]; None = off."""
+        self.model.diffusion_model.set_regions(weights)
+        return self
+
+    @property
+    def regions(self):
+        return self.model.diffusion_model.regions
+
     @property
     def pag(self) -> tuple:
         return self.model.diffusion_model.pag

@@ -237,6 +237,46 @@ class UNetModel(HipModule):
     def pag(self) -> tuple:
         return self._pag
 
+    def set_regions(self, weights):
+        """Regional prompts (attention couple; not in the reference, off by default; adaface_amd/regions.py): weights
+        [Bf, R, H, W] >= 0 at the latent resolution, for the Bf samples of the context the following forwards are given (under
+        cfg_twin: both legs, unconditional ones (1, 0, ..., 0)).  That context's token axis is R segments of equal length,
+        segment 0 the base prompt.  None = off.  cfg_pag, tgate, a ControlNet and conv attention then raise
+        NotImplementedError."""
+        if weights is not None:
+            weights = torch.as_tensor(weights)
+            if weights.dim() != 4:
+                raise ValueError(f"set_regions: weights of shape {tuple(weights.shape)}, expected [Bf, R, H, W]")
+            if not torch.isfinite(weights).all() or bool((weights < 0).any()):
+                raise ValueError("set_regions: weights must be finite and >= 0")
+            if weights.shape[2] % 8 or weights.shape[3] % 8:
+                raise ValueError(f"set_regions: weight map {tuple(weights.shape[2:])}: sides must be multiples of 8")
+            if not 1 <= weights.shape[1] <= 8:
+                raise ValueError(f"set_regions: {weights.shape[1]} regions (1 .. 8, the base prompt included)")
+            weights = weights.detach().float().contiguous()
+        object.__setattr__(self, "_regions", weights)
+        return self
+
+    @property
+    def regions(self):
+        return getattr(self, "_regions", None)
+
+    def _apply_regions(self, eng, B):
+        """Bring the engine's regions in line with set_regions for the context just set (key _ctx_key)."""
+        w = self.regions
+        applied = getattr(self, "_regions_applied", None)
+        if w is None:
+            if applied is not None:
+                eng.set_regions(None)
+                object.__setattr__(self, "_regions_applied", None)
+            return
+        if w.shape[0] not in (B, 2 * B):
+            raise ValueError(f"set_regions: weights for {w.shape[0]} samples, this forward's context has {B}")
+        key = (id(w), B, self._ctx_key, id(eng))
+        if key != applied or eng.region_state()["R"] != w.shape[1]:
+            eng.set_regions(w[:B])      # (a single-leg call of a guided run: the conditional legs, which come first)
+            object.__setattr__(self, "_regions_applied", key)
+
     def set_control(self, controlnet, hint=None, scale=1.0, scales=None, t_range=None, cond_only=False):
         """ControlNet (Zhang et al., ICCV 2023; not in the reference, off by default): every forward whose timesteps ALL lie in
         t_range = (t_lo, t_hi) (DDPM timesteps; None = always) also runs `controlnet` (a ControlNet module of this U-Net's
@@ -373,6 +413,9 @@ class UNetModel(HipModule):
             raise NotImplementedError("UNetModel.forward: T-GATE with the PAG form (the third leg has no cached counterpart)")
         if self._control is not None and (cfg_pag or tgate is not None):
             raise NotImplementedError("UNetModel.forward: ControlNet does not combine with the PAG form or T-GATE (set_control(None))")
+        if self.regions is not None and (cfg_pag or tgate is not None or self._control is not None):
+            raise NotImplementedError("UNetModel.forward: regional prompts do not combine with the PAG form, T-GATE or a ControlNet "
+                                      "(set_regions(None))")
         if tgate == "replay":
             if cfg_twin:
                 raise ValueError("UNetModel.forward: a T-GATE replay runs one leg (no cfg_twin)")
@@ -416,6 +459,10 @@ class UNetModel(HipModule):
         # Hoisted cross-attention K/V are cached per context TENSOR OBJECT: a reference to it is kept so that its
         # id / storage cannot be recycled for another prompt while the cache is live (data_ptr alone is unsafe).
         key = (id(context), getattr(context, "_version", 0), tuple(context.shape), layerwise, B, conv)
+        if self.regions is not None and conv[0]:
+            raise NotImplementedError("UNetModel.forward: regional prompts do not combine with conv attention (set_regions(None))")
+        if self.regions is None and getattr(self, "_regions_applied", None) is not None:
+            self._apply_regions(eng, B)         # (off again, before set_conv_attn below could be refused)
         if key != self._ctx_key or not cache_ok:
             if key != self._ctx_key:
                 eng.unet_cache_invalidate()     # (the kept DeepCache feature was computed under the previous conditioning)
@@ -427,6 +474,8 @@ class UNetModel(HipModule):
             eng.set_context(ctx, B, layerwise)
             object.__setattr__(self, "_ctx_key", key if cache_ok else None)
             object.__setattr__(self, "_ctx_ref", (context, given))
+        if self.regions is not None:
+            self._apply_regions(eng, B)
         if self._control is not None:
             # (the context AFTER the compel-cfg weighting, and that tensor object as the key of the control branch's K / V)
             self._apply_control(eng, x, timesteps.to(x.device), context.to(x.device), context, B1, layerwise, bool(cfg_twin), deep_cache)

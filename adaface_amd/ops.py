@@ -516,6 +516,48 @@ def attention(q, k, v, heads, scale=None, dtype="bf16", causal=False, nan_guard=
     return (o, l) if lse else o
 
 
+REGION_PATHS = {"auto": 0, "composition": 1, "fused": 2}
+
+
+def region_weights(m):
+    """af_op_region_weights (region_weights_kernel): m [Bf, R, H, W] >= 0 -> (list of the four pyramid levels, fp32
+    [Bf, R, H >> l, W >> l]; list of the active-region words per level, int64 [Bf, ceil(N_l / 32)])."""
+    from .regions import level_offsets
+    lib = _lib.load()
+    m = _dev_f32(m)
+    Bf, R, H, W = m.shape
+    w_off, b_off, n_w, n_b = level_offsets(Bf, R, H, W)
+    pyr = torch.full((max(n_w, 1),), float("nan"), dtype=torch.float32, device=m.device)
+    bits = torch.full((max(n_b, 1),), -1, dtype=torch.int32, device=m.device)
+    check(lib.af_op_region_weights(ptr(m), Bf, R, H, W, ptr(pyr), ptr(bits), stream_ptr()), "af_op_region_weights")
+    levels, words = [], []
+    for l in range(4):
+        h, w = H >> l, W >> l
+        nblk = (h * w + 31) // 32
+        levels.append(pyr[w_off[l]: w_off[l] + Bf * R * h * w].reshape(Bf, R, h, w))
+        words.append(bits[b_off[l]: b_off[l] + Bf * nblk].reshape(Bf, nblk).long() & 0xFFFFFFFF)
+    return levels, words
+
+
+def region_attention(q, k, v, w, heads, R, scale=None, dtype="bf16", path="auto", ld_slack=0):
+    """af_op_region_attention: o(p) = sum over {r : w_r(p) > 0} of w_r(p) softmax(q_p K_r^T scale) V_r per head.  q [B, Nq, C],
+    k / v [B, R T, C] (R segments of T keys), w [B, R, Nq] (normalised weights: a level of the pyramid).  path: "auto" (the
+    planner), "composition" (R attention launches + the combine) or "fused" (region_attn_kernel).  Returns the whole pitched
+    output [B, Nq, C + ld_slack]: every staged buffer holds NaN bytes wherever no operand is, as ops.attention's keyword forms."""
+    lib = _lib.load()
+    q, k, v, w = _dev_f32(q), _dev_f32(k), _dev_f32(v), _dev_f32(w)
+    B, Nq, Cn = q.shape
+    if k.shape[1] % R or tuple(w.shape) != (B, R, Nq) or k.shape != v.shape:
+        raise ValueError(f"region_attention: k {tuple(k.shape)}, w {tuple(w.shape)} for {R} regions and {Nq} queries")
+    T = k.shape[1] // R
+    dh = Cn // heads
+    scale = dh ** -0.5 if scale is None else scale
+    o = torch.empty(B, Nq, Cn + ld_slack, dtype=torch.float32, device=q.device)
+    check(lib.af_op_region_attention(DTYPES[dtype], ptr(q), ptr(k), ptr(v), ptr(w), ptr(o), B, Nq, R, T, heads, dh, scale,
+                                     REGION_PATHS[path], int(ld_slack), stream_ptr()), "af_op_region_attention")
+    return o
+
+
 CONV_ATTN_PATHS = {"auto": 0, "merge": 1, "one_pass": 2}
 
 

@@ -469,6 +469,43 @@ int af_lcm_step(const float* x_dev, const float* eps_cond_dev, const float* eps_
 /* launches of its kernel since the library was loaded */
 int64_t af_lcm_step_launches(void);
 
+/* ---- regional prompts (attention couple; af_region_attn.hip) ----
+ * Opt-in.  The context set by af_set_context is read as R segments of T = n_tokens / R keys, segment 0 the base prompt, and
+ * weights_dev [Bf][R][H][W] (fp32 device, >= 0, at the latent resolution of the forwards that follow; H and W multiples of 8)
+ * says which regions a pixel listens to.  At a cross-attention site whose map is (H / f, W / f), f in {1, 2, 4, 8}:
+ *   a_r(p) = mean of m_r over the f x f box of p;  s(p) = sum_r a_r(p), r ascending;  w_r(p) = a_r(p) / s(p) where s(p) > 0,
+ *   else w_0 = 1 and w_{r > 0} = 0;  o(p) = sum_{r : w_r(p) > 0} w_r(p) softmax(q_p K_r^T dh^-1/2) V_r, fp32 accumulation.
+ * A region with w_r(p) = 0 is selected out, not multiplied by zero: its K / V rows never reach p.  An unconditional leg uses
+ * (1, 0, ..., 0).  Everything else of the transformer block is unchanged.
+ * af_set_regions: called after af_set_context; weights_dev NULL or R = 0 switches regions off (every forward is then what it
+ *   is without this call, launch for launch, bit for bit).  One launch writes the four-level pyramid.  A later af_set_context
+ *   of the same (Bf, n_tokens) keeps the regions, one of another shape drops them.  Drops DeepCache's kept feature.  Refused
+ *   with a message (AF_ERR_INVALID): R > 8, n_tokens % R, H or W no multiple of 8; (AF_ERR_STATE): no context for Bf, conv
+ *   attention with a subject, a control handle.
+ * While regions are set: a forward at another (Bf, H, W) returns AF_ERR_STATE and launches nothing; af_unet_forward_pag, a
+ *   T-GATE mode, attached ControlNet residuals (af_unet_set_control) and af_set_conv_attn with a subject are refused
+ *   (AF_ERR_STATE).  Per site the fused kernel (bf16 / fp16, head dim 32, 40, 64, 80, 128 or 160, T <= 96) or the composition
+ *   (R attention launches on the key segments + one combine launch) runs: af_region_plan_query; knob region_fused = 0 forces
+ *   the composition.
+ * af_region_state: out = {R (0 = off), H, W, sites of the last forward that took the fused kernel}. */
+int af_set_regions(af_handle* h, const float* weights_dev, int Bf, int R, int H, int W, void* stream);
+int af_region_state(af_handle* h, int out[4]);
+/* Host only: *out = 0 refused, 1 composition, 2 fused, for a handle dtype, head dim, T keys per segment and R regions */
+int af_region_plan_query(int dtype, int dh, int T, int R, int64_t* out);
+/* launches of the fused kernel since the library was loaded */
+int64_t af_region_attn_launches(void);
+/* The weights kernel alone: m_dev [Bf][R][H][W] -> out_pyramid_dev, fp32 [level][Bf][R][(H >> level) (W >> level)], levels
+ * 0 .. 3 one after the other, and out_bits_dev, one uint32 per (level, sample, block of 32 pixels), [level][Bf][blocks]. */
+int af_op_region_weights(const float* m_dev, int Bf, int R, int H, int W, float* out_pyramid_dev, uint32_t* out_bits_dev,
+                         void* stream);
+/* The regional attention as an operator: q [B][Nq][heads dh], k / v [B][R T][heads dh], w [B][R][Nq] (already normalised: rows
+ * of the pyramid), o [B][Nq][heads dh + ld_slack], all fp32 device; path 0 = the planner's choice, 1 = composition, 2 = fused
+ * (AF_ERR_INVALID where the fused kernel does not take the case).  K | V are staged as the cached context is ([B][R T][2C] +
+ * ld_slack), with the guards of af_op_attention_ex: every buffer holds 0xFF bytes wherever no operand is (slack columns, 128
+ * tail rows) and the output holds them before the launch.  The active bits are derived from w. */
+int af_op_region_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, const float* w_dev, float* o_dev,
+                           int B, int Nq, int R, int T, int heads, int dh, float scale, int path, int ld_slack, void* stream);
+
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */
 int af_lincomb(float* out_dev, int64_t n, const float* x0_dev, float w0, const float* x1_dev, float w1,
@@ -504,8 +541,9 @@ int64_t af_arena_bytes(af_handle* h);
  * kernel: reciprocal norms, match, rank, map, LayerNorm + merge, unmerge + residual; 16-19 the FreeU kernels (af_set_freeu): hidden
  * mean + min / max, low-band sums, apply, the single-launch small-map form; 20-21 the guidance kernels (af_guidance): chunk
  * statistics, and every form that writes the output; 22 the T-GATE add kernel (af_tgate_set); 23 the ControlNet residual add kernel
- * (af_unet_set_control).  A caller that asks af_prof_collect for
- * the first 10, 16, 20, 22 or 23 classes gets
+ * (af_unet_set_control); 24 the noising + inpainting blend kernel; 25-28 the fused regional-prompt attention kernel
+ * (af_set_regions) by pyramid level 0 .. 3, 29 the regional composition's combine kernel.  A caller that asks af_prof_collect for
+ * the first 10, 16, 20, 22, 23 or 25 classes gets
  * what it got before the later ones existed.
  * While enabled every launch of a class is bracketed by hipEventRecord on ITS stream; af_prof_collect
  * sums elapsed ms, launch counts and the ALGORITHMIC flops / bytes of those launches per class. */

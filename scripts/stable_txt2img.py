@@ -120,6 +120,19 @@ def parse_args(argv=None):
                     help="... to this one (1 = the last step): timesteps 999 (1 - END) .. 999 (1 - START)")
     ap.add_argument("--control_cond_only", action="store_true",
                     help="--controlnet: control on the conditional guidance leg only (the unconditional leg is left as it is)")
+    ap.add_argument("--region_emb", type=str, nargs="+", default=None, metavar="PATH",
+                    help="regional prompts: one pre-computed embedding per region, as --prompt_emb (which stays the base prompt, "
+                         "heard everywhere at --region_base_weight); with --region_box or --region_mask, one per embedding.  At most "
+                         "7 regions.  Composes with every sampler, --dtype, --deep_cache, --tome, --freeu, --lora, --img2img, "
+                         "--inpaint_mask, --noise philox and --gpus; not with --pag_scale, --tgate or --controlnet")
+    ap.add_argument("--region_box", type=str, nargs="+", default=None, metavar="X0,Y0,X1,Y1[:W]",
+                    help="--region_emb: the regions as boxes in image fractions, optionally with a weight (default 1)")
+    ap.add_argument("--region_mask", type=str, nargs="+", default=None, metavar="IMG",
+                    help="--region_emb: the regions as mask images (white = the region), area-averaged to the latent grid")
+    ap.add_argument("--region_base_weight", type=float, default=0.2, metavar="F",
+                    help="regional prompts: the weight of the base prompt in every latent cell (the regions' weights are their masks)")
+    ap.add_argument("--regions", type=str, default=None, metavar="synthetic:N",
+                    help="regional prompts without files: N seeded synthetic region contexts on N vertical strips")
     ap.add_argument("--img2img", type=str, nargs="+", default=None, metavar="PATH",
                     help="img2img by strength: the image(s) to start from, resized to H x W: one for all samples, or one per "
                          "global sample index.  The run executes the last --strength share of the schedule from the noised "
@@ -238,6 +251,41 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error(f"--control_start / --control_end: {e}")
         opt.controlnet = (path, scale)
+    opt.region_n = 0
+    if opt.regions is not None:
+        kind, _, n = opt.regions.partition(":")
+        if kind != "synthetic" or not n.isdigit() or not 1 <= int(n) <= 7:
+            ap.error("--regions synthetic:N with 1 <= N <= 7")
+        if opt.region_emb or opt.region_box or opt.region_mask:
+            ap.error("--regions synthetic:N makes its own contexts and strips: not with --region_emb / --region_box / --region_mask")
+        opt.region_n = int(n)
+    if (opt.region_box or opt.region_mask) and not opt.region_emb:
+        ap.error("--region_box / --region_mask: give --region_emb PATH [PATH ...] too")
+    if opt.region_emb:
+        if bool(opt.region_box) == bool(opt.region_mask):
+            ap.error("--region_emb: give either --region_box or --region_mask, one per embedding")
+        shapes = opt.region_box or opt.region_mask
+        if len(shapes) != len(opt.region_emb) or len(shapes) > 7:
+            ap.error(f"--region_emb: {len(opt.region_emb)} embeddings but {len(shapes)} boxes / masks (one each, at most 7)")
+        if opt.region_box:
+            from adaface_amd.regions import parse_box
+            try:
+                opt.region_box = [parse_box(b) for b in opt.region_box]
+            except ValueError as e:
+                ap.error(f"--region_box: {e}")
+        opt.region_n = len(shapes)
+    if opt.region_n:
+        which = "--regions" if opt.regions is not None else "--region_emb"
+        if opt.pag_scale > 0.0:
+            ap.error(f"{which}: not built for the PAG form (--pag_scale)")
+        if opt.tgate:
+            ap.error(f"{which}: not built for T-GATE (--tgate)")
+        if opt.controlnet:
+            ap.error(f"{which}: not built for a ControlNet (--controlnet): the control branch has cross-attention of its own")
+        if not (opt.region_base_weight >= 0.0 and opt.region_base_weight != float("inf")):
+            ap.error("--region_base_weight F: a finite F >= 0")
+        if (opt.H // opt.f) % 8 or (opt.W // opt.f) % 8 or opt.H % opt.f or opt.W % opt.f:
+            ap.error(f"{which}: the latent sides (--H / --f, --W / --f) must be multiples of 8")
     if opt.strength is not None and not opt.img2img:
         ap.error("--strength: give --img2img PATH [PATH ...] too")
     if opt.inpaint_mask and not opt.img2img:
@@ -398,6 +446,24 @@ def main():
         uc_all = synth_context(B, seed=opt.seed + 2, device="cpu", shared=True)
     else:
         raise SystemExit("give --prompt_emb (pre-computed CLIP/AdaFace embedding) or --synthetic")
+    if opt.region_n:
+        # regional prompts: the context becomes [base | region 1 | ...] along the token axis (the negative prompt repeated for
+        # the unconditional legs) and the weight map of this rank's samples goes to the U-Net
+        from adaface_amd import regions as RG
+        Hl, Wl = opt.H // opt.f, opt.W // opt.f
+        n = opt.region_n
+        if opt.regions is not None:
+            embs = [synth_context(B, seed=opt.seed + 10 + i, device="cpu") for i in range(n)]
+            masks = RG.masks_from_boxes([(i / n, 0.0, (i + 1) / n, 1.0, 1.0) for i in range(n)], Hl, Wl)
+        else:
+            embs = [load_emb(p, B, "cpu") for p in opt.region_emb]
+            masks = (RG.masks_from_boxes(opt.region_box, Hl, Wl) if opt.region_box
+                     else torch.stack([RG.mask_from_image(p, Hl, Wl) for p in opt.region_mask]))
+        both = RG.concat_contexts([c_all] + embs, uc_all)
+        c_all, uc_all = both[: c_all.shape[0]].contiguous(), both[c_all.shape[0]:].contiguous()
+        model.set_regions(RG.build_weights(masks, opt.region_base_weight, b, 2))
+        if rank == 0:
+            print(f"regional prompts: {n} region(s) + the base prompt at weight {opt.region_base_weight:g}, {c_all.shape[1]} keys per sample")
     c = model.get_learned_conditioning(shard_batch(c_all, rank, world, per_sample=16).to(device))
     uc = model.get_learned_conditioning(shard_batch(uc_all, rank, world, per_sample=16).to(device))
     i2i = {}

@@ -91,6 +91,14 @@ _SIGS = [
     ("af_region_attn_launches", C.c_int64, []),
     ("af_op_region_weights", C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, _P]),
     ("af_op_region_attention", C.c_int, [C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, _P]),
+    ("af_sag_taps", C.c_int, [C.c_double, C.POINTER(C.c_double)]),
+    ("af_op_sag_mass", C.c_int, [C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [_P]),
+    ("af_sag_degrade", C.c_int, [_P, _P, _P, _P] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_double, _P]),
+    ("af_sag_set", C.c_int, [_P, C.c_int]),
+    ("af_sag_state", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("af_sag_read", C.c_int, [_P, _P, C.c_int64, _P]),
+    ("af_sag_mass_launches", C.c_int64, []),
+    ("af_sag_degrade_launches", C.c_int64, []),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -162,6 +162,18 @@ extern std::atomic<long> g_af_noise_blend_launches;   // launches since the libr
 // arguments on the host and launches ONE kernel, instantiated on (CFG, noise source) alone); af_lcm_step_launches reads this.
 extern std::atomic<long> g_af_lcm_step_launches;      // launches since the library was loaded
 
+// Self-attention guidance (af_sag.hip).  The attention mass per key of a self-attention site, all three storage
+// types: mass [B][N] fp32 = mean over heads of the column sums of softmax(q k^T dh^-0.5); q / k element (b, i, c) at
+// p[b bs + i ld + c], c < heads dh.  Two launches: one workgroup per (sample, head) writes that head's column sums into
+// part [B][heads][N] (the caller's scratch), a second kernel adds the heads in order; no atomics; N <= 256 (-1 with a message
+// above it).  The degrade kernel is fp32 only and sits behind the ABI's af_sag_degrade.  The counters: calls of each since the
+// library was loaded.
+template <typename T>
+int af_launch_sag_mass(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, float* mass, float* part, int B, int N,
+                       int heads, int dh, hipStream_t s);
+extern std::atomic<long> g_af_sag_mass_launches;
+extern std::atomic<long> g_af_sag_degrade_launches;
+
 // Regional prompts (af_region_attn.hip): the context of a sample is R <= AF_REGION_MAX segments of T keys, a weight
 // pyramid says which regions a pixel of a site listens to.  The layout of the pyramid of an H x W map (sides multiples of 8):
 // level l (f = 2^l) holds w [Bf][R][N_l] fp32 at float w_off[l] and one word of active-region bits per (sample, 32-query

@@ -232,6 +232,7 @@ struct CtxKV {  // cached cross-attention K/V for one transformer block
   size_t vt_bytes = 0;
   void* xf_pack = nullptr;   // K and V packed per head pair for xattn_fused_kernel (bf16, C = 320, <= 80 keys), or null
   size_t xf_bytes = 0;
+  size_t kv_cap = 0, vt_cap = 0, xf_cap = 0;   // bytes allocated behind kv / vt / xf_pack (af_set_context keeps a buffer that is large enough)
 };
 
 struct af_handle {
@@ -435,6 +436,22 @@ struct af_handle {
       off += (size_t)B * (H / x.ds) * (W / x.ds) * (x.heads * x.dh);
     }
     return off;
+  }
+
+  // Self-attention guidance (af_sag_set): while on, a forward that runs the middle block also writes the attention mass
+  // of its attn1 (first transformer block), fp32 [B][N] for all B samples of the call, into this handle-owned buffer.
+  struct Sag {
+    bool on = false;
+    float* buf = nullptr;
+    size_t bytes = 0;
+    bool valid = false;
+    int B = 0, N = 0;                 // the capture that wrote the buffer
+  } sag;
+  // the middle block's transformer (-1: none)
+  int sag_xfmr() const {
+    for (const auto& l : middle_block.layers)
+      if (l.kind == L_XFMR) return l.idx;
+    return -1;
   }
 
   // ControlNet.  A control handle (cfg.build_controlnet) is the U-Net's encoder under unet_prefix = "control_model."
@@ -1024,6 +1041,9 @@ struct Runner {
   // T-GATE (set by unet_forward_impl only; the VAE and CLIP runners never look): AF_TGATE_* of this forward, the legs a capture
   // averages, and the latent's sides (the cache layout's key)
   int tgate = 0, tg_legs = 1, tg_H = 0, tg_W = 0;
+  // self-attention guidance (set by unet_forward_impl around the middle block only): where attn1 of the block's first
+  // transformer block writes its attention mass, [B][N] fp32; NULL in every other place and while af_sag_set is off
+  float* sag_out = nullptr;
   Runner(af_handle* h_, hipStream_t s_) : h(h_), s(s_), dt(h_->dtype), dry(h_->arena.dry), A(h_->arena) {}
 
   Act alloc_act(int B, int H, int W, int C, int ld = 0) {
@@ -1479,6 +1499,14 @@ static int xfmr_self_attention(const XfmrCtx& X, const XfmrBlockW& blk, size_t d
     AF_TRY(R.copy_channels(vsrc, adst, 0));
   } else {
     AF_TRY(R.attention(R.cols_of(qkv, 0, N), R.cols_of(qkv, C, N), R.cols_of(qkv, 2 * C, N), ap, N, N, X.w.heads, X.w.dh));
+    if (R.sag_out && d == 0) {
+      // self-attention guidance: the attention mass per key of this site, from the q and k columns the attention just read
+      if (Bp != B) { af_set_error_msg("SAG: the middle block's attn1 runs on %d of %d samples", Bp, B); return AF_ERR_STATE; }
+      const Strided qs = R.cols_of(qkv, 0, N), ks = R.cols_of(qkv, C, N);
+      if (AF_TYPED(R.dt, af_launch_sag_mass<Elem>(qs.p, qs.ld, qs.bs, ks.p, ks.ld, ks.bs, R.sag_out, R.sag_out + (size_t)B * N, B, N,
+                                                  X.w.heads, X.w.dh, R.s)))
+        return AF_ERR_INVALID;
+    }
   }
   t1 = R.alloc_act(B, H, W, C);
   Act t1p = pv(t1);
@@ -2149,7 +2177,9 @@ static int unet_forward_impl(af_handle* h, hipStream_t s, const float* x_dev, co
     Act o;
     const Act dst = view(cat[0], 0, ch_h[0]);
     AF_TRY(pag_widen(n_in, &hcur));
+    if (h->sag.on && !R.dry) R.sag_out = h->sag.buf;   // (the entry point sized the buffer and refused what has no map)
     AF_TRY(run_block(h->middle_block, hcur, o, n_out > 0 ? &dst : nullptr, pag_nb(), false));
+    R.sag_out = nullptr;
     hcur = o;
     AF_TRY(tap(n_in, hcur));
   }
@@ -2652,6 +2682,7 @@ void af_destroy(af_handle* h) {
   if (h->ctx_cast) hipFree(h->ctx_cast);
   if (h->dc.buf) hipFree(h->dc.buf);
   if (h->tg.buf) hipFree(h->tg.buf);
+  if (h->sag.buf) hipFree(h->sag.buf);
   if (h->rg.pyr) hipFree(h->rg.pyr);
   if (h->rg.bits) hipFree(h->rg.bits);
   for (void* p : h->rg.vt) if (p) hipFree(p);
@@ -2766,7 +2797,8 @@ static int load_tensor_impl(af_handle* h, const char* name, const float* host_da
   s.loaded = true;
   h->dc.valid = false;
   h->tg.valid = false;
-  h->hint_B = 0;               // (a control handle's hint feature was made with the weights as they were: af_control_set_hint again)
+  h->sag.valid = false;
+  h->hint_B = 0;              // (a control handle's hint feature was made with the weights as they were: af_control_set_hint again)
   h->ln_fold_dirty = true;
   h->fp8_dirty = true;
   h->up4_dirty = true;
@@ -2886,35 +2918,35 @@ int af_set_context(af_handle* h, const float* ctx_dev, int Bf, int n_tokens, int
   }
   const size_t n = (size_t)Bf * L * n_tokens * D;
   if (n * esize(dt) > h->ctx_cast_bytes || h->ctx_Bf != Bf || h->ctx_tokens != n_tokens) {
-    HIP_CHECK_RET(hipStreamSynchronize(s));
-    if (h->ctx_cast) hipFree(h->ctx_cast);
-    h->ctx_cast = nullptr;
-    HIP_CHECK_RET(hipMalloc(&h->ctx_cast, n * esize(dt)));
-    h->ctx_cast_bytes = n * esize(dt);
+    // Another shape: every buffer is sized for it.  A buffer that is large enough already is kept (two callers that alternate
+    // between a batch and its half -- a guided step's twin call and its single-leg call -- then allocate once, not per call);
+    // vt_bytes / xf_bytes stay the LOGICAL sizes of this context, which the consumers divide by its batch.
+    bool synced = false;
+    auto grow = [&](void** buf, size_t* cap, size_t need) -> int {
+      if (need <= *cap && (need > 0 || !*buf)) return 0;
+      if (!synced) { HIP_CHECK_RET(hipStreamSynchronize(s)); synced = true; }
+      if (*buf) hipFree(*buf);
+      *buf = nullptr;
+      *cap = 0;
+      if (need == 0) return 0;                       // (a pack this context does not have: the pointer says so)
+      HIP_CHECK_RET(hipMalloc(buf, need));
+      *cap = need;
+      return 0;
+    };
+    AF_TRY(grow(&h->ctx_cast, &h->ctx_cast_bytes, n * esize(dt)));
     for (size_t i = 0; i < h->ctx_kv.size(); ++i) {
-      if (h->ctx_kv[i].kv) hipFree(h->ctx_kv[i].kv);
+      CtxKV& kv = h->ctx_kv[i];
       const XfmrW& x = h->xf[h->ca_list[i].first];
       const int C = x.heads * x.dh;
-      h->ctx_kv[i].C = C;
-      h->ctx_kv[i].kv = nullptr;
-      HIP_CHECK_RET(hipMalloc(&h->ctx_kv[i].kv, (size_t)Bf * n_tokens * 2 * C * esize(dt)));
-      if (h->ctx_kv[i].vt) hipFree(h->ctx_kv[i].vt);
-      h->ctx_kv[i].vt = nullptr;
-      h->ctx_kv[i].vt_bytes = 0;
+      kv.C = C;
+      AF_TRY(grow(&kv.kv, &kv.kv_cap, (size_t)Bf * n_tokens * 2 * C * esize(dt)));
       const long pe = dt == AF_DTYPE_BF16 ? af_attn_short_pack_elems<bf16>(Bf, x.heads, x.dh, n_tokens) : 0;
-      if (pe > 0) {
-        HIP_CHECK_RET(hipMalloc(&h->ctx_kv[i].vt, (size_t)pe * 2));
-        h->ctx_kv[i].vt_bytes = (size_t)pe * 2;
-      }
-      if (h->ctx_kv[i].xf_pack) hipFree(h->ctx_kv[i].xf_pack);
-      h->ctx_kv[i].xf_pack = nullptr;
-      h->ctx_kv[i].xf_bytes = 0;
+      AF_TRY(grow(&kv.vt, &kv.vt_cap, pe > 0 ? (size_t)pe * 2 : 0));
+      kv.vt_bytes = pe > 0 ? (size_t)pe * 2 : 0;
       const long xe = (dt == AF_DTYPE_BF16 && C == x.heads * x.dh && x.blocks[h->ca_list[i].second].out2_perm)
                           ? af_xattn_fused_pack_elems(Bf, x.heads, x.dh, n_tokens) : 0;
-      if (xe > 0) {
-        HIP_CHECK_RET(hipMalloc(&h->ctx_kv[i].xf_pack, (size_t)xe * 2));
-        h->ctx_kv[i].xf_bytes = (size_t)xe * 2;
-      }
+      AF_TRY(grow(&kv.xf_pack, &kv.xf_cap, xe > 0 ? (size_t)xe * 2 : 0));
+      kv.xf_bytes = xe > 0 ? (size_t)xe * 2 : 0;
     }
   }
   if (h->conv_ks >= 2 && !h->conv_batch.empty()) {
@@ -3037,6 +3069,25 @@ static int ensure_tgate(af_handle* h, hipStream_t s, int B, int H, int W) {
   return 0;
 }
 
+// the attention-mass buffer of a SAG capture of B samples with N middle-block tokens, [B][N], and behind it the kernel's per-head
+// scratch [B][heads][N]; growing it drops what it held
+static int ensure_sag(af_handle* h, hipStream_t s, int B, int N, int heads) {
+  const size_t need = (size_t)B * N * (1 + heads) * sizeof(float);
+  if (need <= h->sag.bytes) return 0;
+  HIP_CHECK_RET(hipStreamSynchronize(s));
+  if (h->sag.buf) hipFree(h->sag.buf);
+  h->sag.buf = nullptr;
+  h->sag.bytes = 0;
+  h->sag.valid = false;
+  if (hipMalloc(reinterpret_cast<void**>(&h->sag.buf), need) != hipSuccess) {
+    h->sag.buf = nullptr;
+    af_set_error_msg("hipMalloc of the %zu-byte SAG attention-mass buffer failed", need);
+    return AF_ERR_HIP;
+  }
+  h->sag.bytes = need;
+  return 0;
+}
+
 static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t_dev, float* eps_dev, int Bf, int H, int W,
                               void* stream, int form, int dc_mode = 0, int dc_depth = 0) {
   if (!h || !x_dev || !t_dev || !eps_dev) { af_set_error_msg("af_unet_forward: null argument"); return AF_ERR_INVALID; }
@@ -3069,6 +3120,23 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
       return AF_ERR_STATE;
     }
     if (replay) AF_TRY(check_loaded(h, "model.diffusion_model."));   // (af_set_context, which a replay does not need, checks this otherwise)
+  }
+  af_handle::Sag& sg = h->sag;
+  int sag_N = 0;
+  if (sg.on) {   // self-attention guidance capture (af_sag_set): everything it refuses, before anything is enqueued
+    const int xi = h->sag_xfmr();
+    if (xi < 0) { af_set_error_msg("SAG capture: the middle block has no transformer"); return AF_ERR_STATE; }
+    const XfmrW& xw = h->xf[xi];
+    if (pag) { af_set_error_msg("SAG capture: the PAG form is not supported (both act on the middle block's self-attention)"); return AF_ERR_INVALID; }
+    if (tg.mode) { af_set_error_msg("SAG capture: T-GATE capture / replay is not supported"); return AF_ERR_INVALID; }
+    if (h->fp8_on) { af_set_error_msg("SAG capture: the fp8 mode is not supported"); return AF_ERR_STATE; }
+    if (dc_mode == AF_DEEPCACHE_REUSE) { af_set_error_msg("SAG capture: a DeepCache reuse step does not run the middle block, so there is no map"); return AF_ERR_INVALID; }
+    if (h->rg.R) { af_set_error_msg("SAG capture: regional prompts are not supported"); return AF_ERR_STATE; }
+    if (h->ctl.res) { af_set_error_msg("SAG capture: ControlNet residuals are not supported"); return AF_ERR_STATE; }
+    if (h->tome_merges(xw)) { af_set_error_msg("SAG capture: the middle block merges tokens (af_set_tome, max_downsample %d): its attention has no map over the full grid", h->tome_max_down); return AF_ERR_STATE; }
+    if (H % xw.ds || W % xw.ds) { af_set_error_msg("SAG capture: H,W must be multiples of %d", xw.ds); return AF_ERR_INVALID; }
+    sag_N = (H / xw.ds) * (W / xw.ds);
+    if (sag_N > 256) { af_set_error_msg("SAG capture: the middle block has %d tokens, the attention-mass kernel takes at most 256", sag_N); return AF_ERR_INVALID; }
   }
   if (h->rg.R) {   // regional prompts (af_set_regions): everything they refuse, before anything is enqueued
     if (pag) { af_set_error_msg("regions: the PAG form is not supported (switch them off with af_set_regions(NULL))"); return AF_ERR_STATE; }
@@ -3141,8 +3209,16 @@ static int unet_forward_entry(af_handle* h, const float* x_dev, const int64_t* t
     tg.valid = false;                       // (until this capture has been enqueued completely)
     AF_TRY(ensure_tgate(h, s, twin ? Bf / 2 : Bf, H, W));
   }
+  if (sg.on) {
+    sg.valid = false;                       // (until this capture has been enqueued completely)
+    AF_TRY(ensure_sag(h, s, Bf, sag_N, h->xf[h->sag_xfmr()].heads));
+  }
   h->rg.fused_sites = 0;
   if (const int rc = run()) { if (dc_mode) dc.valid = false; if (tg.mode == AF_TGATE_CAPTURE) tg.valid = false; return rc; }
+  if (sg.on) {
+    sg.valid = true;
+    sg.B = Bf; sg.N = sag_N;
+  }
   if (dc_mode == AF_DEEPCACHE_REFRESH) {
     dc.valid = true;
     dc.Bf = Bf; dc.H = H; dc.W = W; dc.twin = form; dc.depth = dc_depth;
@@ -3449,6 +3525,32 @@ int af_tgate_read_site(af_handle* h, int site, float* out_dev, void* stream) {
   if (end * esize(h->dtype) > tg.bytes) { af_set_error_msg("af_tgate_read_site: the cache does not hold site %d", site); return AF_ERR_STATE; }
   const void* src = reinterpret_cast<const char*>(tg.buf) + off * esize(h->dtype);
   AF_TRY(AF_TYPED(h->dtype, af_launch_cast_to_f32<Elem>(src, out_dev, (long)(end - off), reinterpret_cast<hipStream_t>(stream))));
+  return AF_OK;
+}
+
+int af_sag_set(af_handle* h, int on) {
+  if (!h) { af_set_error_msg("af_sag_set: null handle"); return AF_ERR_INVALID; }
+  if (on != 0 && on != 1) { af_set_error_msg("af_sag_set: on = %d (0 or 1)", on); return AF_ERR_INVALID; }
+  if (on && !h->cfg.build_unet) { af_set_error_msg("af_sag_set: handle has no UNet"); return AF_ERR_STATE; }
+  if (on && h->is_control) { af_set_error_msg("af_sag_set: a control handle has no SAG capture"); return AF_ERR_STATE; }
+  if (on && h->sag_xfmr() < 0) { af_set_error_msg("af_sag_set: the middle block has no transformer"); return AF_ERR_STATE; }
+  h->sag.on = on != 0;
+  return AF_OK;
+}
+int af_sag_state(af_handle* h, int out[3]) {
+  if (!h || !out) { af_set_error_msg("af_sag_state: null argument"); return AF_ERR_INVALID; }
+  const bool v = h->sag.valid && h->sag.buf;
+  out[0] = h->sag.on ? 1 : 0; out[1] = v ? h->sag.B : 0; out[2] = v ? h->sag.N : 0;
+  return AF_OK;
+}
+int af_sag_read(af_handle* h, float* out_dev, int64_t n, void* stream) {
+  if (!h || !out_dev) { af_set_error_msg("af_sag_read: null argument"); return AF_ERR_INVALID; }
+  const af_handle::Sag& sg = h->sag;
+  if (!sg.valid || !sg.buf) { af_set_error_msg("af_sag_read: no capture (af_sag_set(1), then a forward that runs the middle block)"); return AF_ERR_STATE; }
+  const int64_t have = (int64_t)sg.B * sg.N;
+  if (n != have) { af_set_error_msg("af_sag_read: room for %lld values, the capture holds %d x %d", (long long)n, sg.B, sg.N); return AF_ERR_INVALID; }
+  HIP_CHECK_RET(hipSetDevice(h->device));
+  HIP_CHECK_RET(hipMemcpyAsync(out_dev, sg.buf, (size_t)have * sizeof(float), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)));
   return AF_OK;
 }
 

@@ -1328,6 +1328,19 @@ int af_op_tgate_add(int dtype, const void* t1_dev, const void* src_dev, void* t2
   return AF_OK;
 }
 
+// The attention-mass kernel of self-attention guidance (af_sag.hip) on caller-owned q / k of `dtype` elements: [B][N][ld], the
+// first heads * dh columns of a row are the operand (column views of a wider buffer pass their first element and its row stride);
+// part_dev: fp32 scratch of B * heads * N values (the per-head column sums)
+int af_op_sag_mass(int dtype, const void* q_dev, const void* k_dev, float* mass_dev, float* part_dev, int B, int N, int heads, int dh,
+                   int ld_q, int ld_k, void* stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype != AF_DTYPE_BF16 && dtype != AF_DTYPE_F32 && dtype != AF_DTYPE_F16) { af_set_error_msg("af_op_sag_mass: storage type %d", dtype); return AF_ERR_INVALID; }
+  if (B <= 0) { af_set_error_msg("af_op_sag_mass: bad argument"); return AF_ERR_INVALID; }
+  const int rc = AF_TYPED(dtype, af_launch_sag_mass<Elem>(q_dev, ld_q, (long)N * ld_q, k_dev, ld_k, (long)N * ld_k, mass_dev, part_dev, B, N, heads,
+                                                          dh, s));
+  return rc == 0 ? AF_OK : rc == -2 ? AF_ERR_HIP : AF_ERR_INVALID;
+}
+
 // The ControlNet residual add (af_controlnet.hip) on caller-owned buffers of `dtype` elements: one launch for all n segments
 int af_op_control_add(int dtype, int n, void* const* dst_dev, const void* const* src_dev, const int* C, const int* ld,
                       const int64_t* rows_per_sample, const float* scales, int Bs, int Bd, void* stream) {

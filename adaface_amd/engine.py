@@ -515,6 +515,31 @@ class Engine:
         check(self._lib.af_tgate_read_site(self._h, int(i), ptr(out), stream_ptr()), "af_tgate_read_site")
         return out
 
+    def set_sag(self, on: bool = True):
+        """af_sag_set (self-attention guidance): while on, every forward that runs the middle block also writes the
+        attention mass per key of its attn1, for all samples of the call, into a buffer the handle owns (sag_mass reads it).
+        The forward's own launches and results are unchanged.  Off: the forwards are what they are without this call."""
+        if on:
+            self._no_regions("self-attention guidance")
+        check(self._lib.af_sag_set(self._h, 1 if on else 0), "af_sag_set")
+        self.sag = bool(on)
+
+    def sag_state(self) -> dict:
+        """af_sag_state: {"on", "B", "N"}: the setting, and the batch and token count of the last capture (0, 0: none)."""
+        out = (C.c_int * 3)()
+        check(self._lib.af_sag_state(self._h, out), "af_sag_state")
+        return {"on": bool(out[0]), "B": int(out[1]), "N": int(out[2])}
+
+    def sag_mass(self) -> torch.Tensor:
+        """af_sag_read: the attention mass of the last capture as fp32 [B, N] (B: every sample of that forward, cond first for
+        the twin form; N: the middle block's tokens)."""
+        st = self.sag_state()
+        if not st["B"]:
+            raise _lib.AfError("sag_mass: no capture (set_sag(True), then a forward that runs the middle block)")
+        out = torch.empty(st["B"], st["N"], device=self.device, dtype=torch.float32)
+        check(self._lib.af_sag_read(self._h, ptr(out), out.numel(), stream_ptr()), "af_sag_read")
+        return out
+
     def set_pag(self, sites=()):
         """af_set_pag: the self-attention layers whose attention map is the identity on the third leg of unet_forward_pag --
         names ("mid", "down.blocks.2", "up.blocks.1", ...) and / or site numbers (pag_layout); None or () = off.  The plain and

@@ -60,7 +60,8 @@ class HipModule(nn.Module):
         object.__setattr__(self, "_tome", (0.0, 1))           # token merging (UNetModel.set_token_merging), kept the same way
         object.__setattr__(self, "_freeu", (0, 1.0, 1.0, 1.0, 1.0))   # FreeU (UNetModel.set_freeu), kept the same way
         object.__setattr__(self, "_pag", ())                          # PAG sites (UNetModel.set_pag), kept the same way
-        object.__setattr__(self, "_lora", [])                         # LoRA adapters [(weights, scale)] (set_lora), kept the same way
+        object.__setattr__(self, "_sag", False)                       # SAG capture (UNetModel.set_sag), kept the same way
+        object.__setattr__(self, "_lora", [])                       # LoRA adapters [(weights, scale)] (set_lora), kept the same way
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._after_load_state_dict())
 
     # ---- weight synchronisation -----------------------------------------------------------
@@ -86,6 +87,8 @@ class HipModule(nn.Module):
             raise ValueError(dtype)
         if dtype in ("f16", "fp8") and self._tome[0] > 0.0:
             raise ValueError(f"compute dtype {dtype!r} does not combine with token merging (set_token_merging(0) first)")
+        if dtype == "fp8" and self._sag:
+            raise ValueError("compute dtype 'fp8' does not combine with self-attention guidance (set_sag(False) first)")
         if dtype != self.compute_dtype:
             self.compute_dtype = dtype
             if self._engine is not None:
@@ -143,6 +146,8 @@ class HipModule(nn.Module):
                     self._engine.set_freeu(*self._freeu)
                 if self._pag:
                     self._engine.set_pag(self._pag)
+                if self._sag:
+                    self._engine.set_sag(True)
             except Exception:
                 # (an engine whose configuration failed is not kept: the next call builds and configures again)
                 self._engine.close()

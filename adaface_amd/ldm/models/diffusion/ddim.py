@@ -85,7 +85,7 @@ class DDIMSampler(object):
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, guidance_scale=1.,
                unconditional_conditioning=None, noise_source=None, deep_cache_interval=None, deep_cache_depth=2,
                pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False,
-               **kwargs):
+               sag_scale=0., sag_blur_sigma=1.0, **kwargs):
         """ddim.py:71-132.  noise_source: None = the reference's generators (torch.randn on the device); an
         adaface_amd.noise.PhiloxNoise = every draw of the loop keyed by (seed, global sample id, stream, step).
         deep_cache_interval: None or 1 = off; N >= 2 = the full U-Net on loop indices i % N == 0 only, or an explicit
@@ -97,7 +97,10 @@ class DDIMSampler(object):
         outputs, from loop index g on the U-Net runs on one leg with them and without guidance.
         strength: None = off; a number in (0, 1] (needs x0) = img2img, the run executes the n = max(1, int(len * strength))
         smallest of the grid's timesteps from x0 noised to the largest of them (blend.py); S in the other arguments' rules
-        above is then n.  fused_blend: the blend of mask= / x0= in front of each step as one launch with the same bits."""
+        above is then n.  fused_blend: the blend of mask= / x0= in front of each step as one launch with the same bits.
+        sag_scale / sag_blur_sigma: self-attention guidance (guidance.py): every step also runs one single-leg forward on the
+        input blurred where the middle block's self-attention looks; not with pag_scale, guidance_rescale, tgate_step or
+        deep_cache_interval."""
         _check_noise_source(noise_source, noise_dropout)
         check_strength(strength, x0)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -114,7 +117,7 @@ class DDIMSampler(object):
                                   noise_source=noise_source, deep_cache_interval=deep_cache_interval,
                                   deep_cache_depth=deep_cache_depth, pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
                                   guidance_rescale=guidance_rescale, tgate_step=tgate_step, strength=strength,
-                                  fused_blend=fused_blend, **kwargs)
+                                  fused_blend=fused_blend, sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma, **kwargs)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
@@ -122,7 +125,7 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, verbose=False, noise_source=None,
                       deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
-                      tgate_step=None, strength=None, fused_blend=False, **kwargs):
+                      tgate_step=None, strength=None, fused_blend=False, sag_scale=0., sag_blur_sigma=1.0, **kwargs):
         """ddim.py:135-220: the S-iteration loop with annealed guidance (:169-180,215-218).  With a noise_source the start
         code (x_T None) is its stream 0, the blend's q_sample noise its stream 2 and the step noise its stream 1, each at
         step = the loop index.  strength / fused_blend: as sample(); with strength, x_T is the noise added to x0."""
@@ -131,6 +134,9 @@ class DDIMSampler(object):
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
         refuse_guided(tgate_step, pag_scale, guidance_rescale)
+        if sag_scale != 0. or sag_blur_sigma != 1.0:
+            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
+            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale, tgate_step, deep_cache_interval)
         self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
         self._guided_twin_cache = None
         device = self.model.betas.device
@@ -171,6 +177,7 @@ class DDIMSampler(object):
         self.tgate_log = tg_run.log
         blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
 
+        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -191,7 +198,7 @@ class DDIMSampler(object):
                                               noise_source=noise_source, noise_step=i, deep_cache_run=dc_run,
                                               pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
                                               guidance_rescale=guidance_rescale, timestep=int(step),
-                                              tgate_run=tg_run)
+                                              tgate_run=tg_run, **sag_kw)
             if callback:
                 callback(i)
             if img_callback:
@@ -222,7 +229,7 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0,
                       deep_cache_run=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timestep=None,
-                      tgate_run=None):
+                      tgate_run=None, sag_scale=0., sag_blur_sigma=1.0):
         """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
         torch.randn; repeat_noise then gives every sample the first sample's id.  deep_cache_run: the loop's DeepCacheRun
         (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse).
@@ -232,7 +239,7 @@ class DDIMSampler(object):
         _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
         single = unconditional_conditioning is None or guidance_scale == 1.
-        guided = G.is_on(pag_scale, guidance_rescale)
+        guided = G.is_on(pag_scale, guidance_rescale) or bool(sag_scale)
         phase = None
         form = (not single, b, x.shape[2], x.shape[3])
         if tgate_run is not None:
@@ -247,7 +254,7 @@ class DDIMSampler(object):
         elif guided:
             e_c = G.guided_eps(self, x, t, c, unconditional_conditioning, guidance_scale,
                                int(t[0]) if timestep is None else timestep, pag_scale, pag_adaptive_scale, guidance_rescale,
-                               deep_cache_run, noise_step)
+                               deep_cache_run, noise_step, **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}))
             e_u = None
         elif single:
             e_c = self.model.apply_model(x, t, c) if dc is None else self.model.apply_model(x, t, c, deep_cache=dc)

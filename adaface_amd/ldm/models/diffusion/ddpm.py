@@ -386,6 +386,16 @@ class LatentDiffusion(DDPM):
         self.model.diffusion_model.set_pag(layers)
         return self
 
+    def set_sag(self, on=True):
+        """UNetModel.set_sag: while on, every U-Net forward that runs the middle block also keeps the attention mass of its
+        self-attention (self-attention guidance, guidance.py); sag_mass reads the last one.  The samplers switch it per call."""
+        self.model.diffusion_model.set_sag(on)
+        return self
+
+    def sag_mass(self):
+        """UNetModel.sag_mass: fp32 [B, N] of the last forward made with set_sag on."""
+        return self.model.diffusion_model.sag_mass()
+
     def set_regions(self, weights):
         """UNetModel.set_regions: regional prompts (adaface_amd/regions.py).  weights [Bf, R, H, W] for the samples of the
         conditioning the samplers pass (regions.build_weights; legs=2 for a run with an unconditional conditioning), whose

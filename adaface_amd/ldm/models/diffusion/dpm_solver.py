@@ -126,7 +126,8 @@ class DPMSolverSampler(object):
                x_T=None, verbose=True, log_every_t=100, guidance_scale=1., unconditional_guidance_scale=None,
                unconditional_conditioning=None, order=2, lower_order_final=True, skip_type="time_uniform", timesteps=None,
                algorithm="dpmsolver++", noise_source=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
-               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False, **kwargs):
+               pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False, sag_scale=0.,
+               sag_blur_sigma=1.0, **kwargs):
         """(img, intermediates) as DDIMSampler.sample.  guidance_scale: a scalar or [max, min] (annealed as ddim_sampling
         does); unconditional_guidance_scale: the PLMS / CompVis spelling of the scalar.  timesteps: an explicit strictly
         increasing integer array, overriding S and skip_type.  algorithm: "dpmsolver++" (deterministic) or "sde-dpmsolver++"
@@ -136,7 +137,8 @@ class DPMSolverSampler(object):
         and guidance rescale, as DDIMSampler.sample (guidance.py).  tgate_step: T-GATE, as DDIMSampler.sample (tgate.py).
         strength / fused_blend: img2img by strength and the one-launch inpainting blend, as DDIMSampler.sample (blend.py).
         The schedule of a run by strength is dpmpp_schedule on its n executed timesteps: its first step is first order, and
-        the n < 15 rule of lower_order_final applies to n."""
+        the n < 15 rule of lower_order_final applies to n.  sag_scale / sag_blur_sigma: self-attention guidance, as
+        DDIMSampler.sample (guidance.py)."""
         check_strength(strength, x0)
         if algorithm not in ALGORITHMS:
             raise NotImplementedError(f'There is no DPM-Solver algorithm called "{algorithm}" ({", ".join(ALGORITHMS)})')
@@ -172,7 +174,9 @@ class DPMSolverSampler(object):
                                         temperature=temperature, deep_cache_interval=deep_cache_interval,
                                         deep_cache_depth=deep_cache_depth, pag_scale=pag_scale,
                                         pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
-                                        tgate_step=tgate_step, strength=strength, fused_blend=fused_blend)
+                                        tgate_step=tgate_step, strength=strength, fused_blend=fused_blend,
+                                        **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma)
+                                           if sag_scale != 0. or sag_blur_sigma != 1.0 else {}))
 
     def _twin_condition(self, c, uc):
         """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
@@ -192,7 +196,8 @@ class DPMSolverSampler(object):
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
                             log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1.,
                             deep_cache_interval=None, deep_cache_depth=2, pag_scale=0., pag_adaptive_scale=0.,
-                            guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False):
+                            guidance_rescale=0., tgate_step=None, strength=None, fused_blend=False, sag_scale=0.,
+                            sag_blur_sigma=1.0):
         """schedule: a dpmpp_schedule table; one with the COL_CN column runs the SDE update.  strength not None: the table is
         that of the executed steps already (sample() builds it), and the run starts from x0 noised to its first timestep
         with x_T as the noise; fused_blend: as sample()."""
@@ -201,6 +206,11 @@ class DPMSolverSampler(object):
         G.check_model(self.model, unconditional_conditioning, pag_scale)
         refuse_guided(tgate_step, pag_scale, guidance_rescale)
         guided = G.is_on(pag_scale, guidance_rescale)
+        if sag_scale != 0. or sag_blur_sigma != 1.0:
+            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
+            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale, tgate_step, deep_cache_interval)
+            guided = guided or bool(sag_scale)
+        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
         self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
         self._guided_twin_cache = None
         device = self.model.betas.device
@@ -249,7 +259,7 @@ class DPMSolverSampler(object):
                 e_c, e_u = gated_eps(self, img, ts, cond, unconditional_conditioning, single, phase, dc)
             elif guided:      # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
                 e_c = G.guided_eps(self, img, ts, cond, unconditional_conditioning, guide_scale, int(row[COL_T]), pag_scale,
-                                   pag_adaptive_scale, guidance_rescale, dc_run, i)
+                                   pag_adaptive_scale, guidance_rescale, dc_run, i, **sag_kw)
                 e_u = None
             elif single:
                 e_c = self.model.apply_model(img, ts, cond) if dc is None else self.model.apply_model(img, ts, cond, deep_cache=dc)

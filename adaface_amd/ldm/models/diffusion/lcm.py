@@ -130,6 +130,9 @@ class LCMSampler(object):
             raise NotImplementedError(f"{', '.join(unsupported)}: not built for the LCM / TCD sampler (DeepCache and T-GATE "
                                       "target long schedules; the noise of a consistency step is the sampler's own, scaled by "
                                       "temperature=)")
+        if kwargs.get("sag_scale") not in (None, 0, 0.):
+            raise NotImplementedError("sag_scale: self-attention guidance is not built for the LCM / TCD sampler (a distilled model "
+                                      "runs without guidance legs; use DDIMSampler, PLMSSampler or DPMSolverSampler)")
         temperature = kwargs.get("temperature")
         temperature = 1. if temperature is None else float(temperature)
         if unconditional_guidance_scale is not None:

@@ -53,13 +53,14 @@ class PLMSSampler(object):
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, deep_cache_interval=None, deep_cache_depth=2, pag_scale=0.,
                pag_adaptive_scale=0., guidance_rescale=0., tgate_step=None, noise_source=None, strength=None,
-               fused_blend=False, **kwargs):
+               fused_blend=False, sag_scale=0., sag_blur_sigma=1.0, **kwargs):
         """plms.py:71-117.  pag_scale / pag_adaptive_scale / guidance_rescale (not in the reference): perturbed-attention
         guidance and guidance rescale on every model call of the run, see guidance.py.  noise_source (not in the reference):
         an adaface_amd.noise.PhiloxNoise for the start code (stream 0) and the blend's q_sample noise (stream 2) -- nothing
         else: the eta = 0 update has no noise of its own.  strength / fused_blend (not in the reference): img2img by strength
         and the one-launch inpainting blend, as DDIMSampler.sample (blend.py); a run by strength starts an eps history of its
-        own, so its first executed step is the two-call one."""
+        own, so its first executed step is the two-call one.  sag_scale / sag_blur_sigma (not in the reference):
+        self-attention guidance on every model call of the run, as DDIMSampler.sample (guidance.py)."""
         from adaface_amd.ldm.models.diffusion.deep_cache import is_off
         check_strength(strength, x0)
         if not is_off(deep_cache_interval):
@@ -77,20 +78,25 @@ class PLMSSampler(object):
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, pag_scale=pag_scale,
                                   pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
-                                  noise_source=noise_source, strength=strength, fused_blend=fused_blend)
+                                  noise_source=noise_source, strength=strength, fused_blend=fused_blend,
+                                  **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale != 0. or sag_blur_sigma != 1.0 else {}))
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0.,
-                      noise_source=None, strength=None, fused_blend=False):
+                      noise_source=None, strength=None, fused_blend=False, sag_scale=0., sag_blur_sigma=1.0):
         """plms.py:119-173.  noise_source / strength / fused_blend: as sample(); with strength, x_T is the noise added to x0."""
         check_strength(strength, x0, timesteps=timesteps)
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps is not used by txt2img")
         pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
         G.check_model(self.model, unconditional_conditioning, pag_scale)
+        if sag_scale != 0. or sag_blur_sigma != 1.0:
+            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
+            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale)
+        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
         self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
         self._guided_twin_cache = None
         device = self.model.betas.device
@@ -136,7 +142,8 @@ class PLMSSampler(object):
                                                    unconditional_conditioning=unconditional_conditioning,
                                                    old_eps=old_eps, t_next=ts_next, pag_scale=pag_scale,
                                                    pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
-                                                   timesteps=(int(step), int(time_range[min(i + 1, len(time_range) - 1)])))
+                                                   timesteps=(int(step), int(time_range[min(i + 1, len(time_range) - 1)])),
+                                                   **sag_kw)
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
@@ -168,7 +175,7 @@ class PLMSSampler(object):
     def p_sample_plms(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, old_eps=None, t_next=None,
-                      pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timesteps=None):
+                      pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timesteps=None, sag_scale=0., sag_blur_sigma=1.0):
         """plms.py:175-253.  pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes every model call of the step
         and its combine; timesteps: (t, t_next) as host integers (None: read from the tensors)."""
         if quantize_denoised or score_corrector is not None or use_original_steps:
@@ -177,10 +184,11 @@ class PLMSSampler(object):
         f32 = lambda v: float(np.float32(float(v)))
 
         def get_model_output(xx, tt):
-            if G.is_on(pag_scale, guidance_rescale):
+            if G.is_on(pag_scale, guidance_rescale) or sag_scale:
                 th = int(tt[0]) if timesteps is None else timesteps[0 if tt is t else 1]
                 return G.guided_eps(self, xx, tt, c, unconditional_conditioning, unconditional_guidance_scale, th, pag_scale,
-                                    pag_adaptive_scale, guidance_rescale)
+                                    pag_adaptive_scale, guidance_rescale,
+                                    **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}))
             if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
                 return self.model.apply_model(xx, tt, c)
             twin = self._twin_condition(c, unconditional_conditioning)

@@ -237,6 +237,30 @@ class UNetModel(HipModule):
     def pag(self) -> tuple:
         return self._pag
 
+    def set_sag(self, on=True):
+        """Self-attention guidance capture (Hong et al., ICCV 2023; not in the reference, off by default): while on, every
+        forward that runs the middle block also keeps the attention mass per key of middle_block.1.transformer_blocks.0.attn1 for
+        all samples of the call (sag_mass reads it); the forward's result is unchanged.  Kept for every later engine; a live one
+        is switched now.  Every compute dtype except fp8; cfg_pag, tgate, a ControlNet, regional prompts and a DeepCache reuse
+        step then raise NotImplementedError."""
+        on = bool(on)
+        if on and self.compute_dtype == "fp8":
+            raise ValueError("self-attention guidance does not run with the compute dtype 'fp8'")
+        if self._engine is not None:
+            self._engine.set_sag(on)
+        object.__setattr__(self, "_sag", on)
+        return self
+
+    @property
+    def sag(self) -> bool:
+        return self._sag
+
+    def sag_mass(self):
+        """The attention mass of the last forward made while set_sag was on, fp32 [B, N] (Engine.sag_mass)."""
+        if self._engine is None:
+            raise RuntimeError("sag_mass: no forward has run yet")
+        return self._engine.sag_mass()
+
     def set_regions(self, weights):
         """Regional prompts (attention couple; not in the reference, off by default; adaface_amd/regions.py): weights
         [Bf, R, H, W] >= 0 at the latent resolution, for the Bf samples of the context the following forwards are given (under
@@ -416,6 +440,10 @@ class UNetModel(HipModule):
         if self.regions is not None and (cfg_pag or tgate is not None or self._control is not None):
             raise NotImplementedError("UNetModel.forward: regional prompts do not combine with the PAG form, T-GATE or a ControlNet "
                                       "(set_regions(None))")
+        if self._sag and (cfg_pag or tgate is not None or self._control is not None or self.regions is not None or
+                          (deep_cache is not None and deep_cache[0] == "reuse")):
+            raise NotImplementedError("UNetModel.forward: self-attention guidance capture does not combine with the PAG form, T-GATE, "
+                                      "a ControlNet, regional prompts or a DeepCache reuse step (set_sag(False))")
         if tgate == "replay":
             if cfg_twin:
                 raise ValueError("UNetModel.forward: a T-GATE replay runs one leg (no cfg_twin)")

@@ -825,6 +825,67 @@ def lcm_step_launches() -> int:
     return int(_lib.load().af_lcm_step_launches())
 
 
+SAG_MAX_TOKENS = 256   # the attention-mass kernel's cap on N (csrc/af_sag.hip)
+
+
+def sag_taps(sigma=1.0):
+    """af_sag_taps (host only, no GPU): the nine Gaussian taps of self-attention guidance's blur, as doubles summing to 1."""
+    import ctypes
+    out = (ctypes.c_double * 9)()
+    check(_lib.load().af_sag_taps(float(sigma), out), "af_sag_taps")
+    return tuple(float(v) for v in out)
+
+
+def sag_mass(q, k, heads):
+    """af_op_sag_mass: the attention mass per key, fp32 [B, N] = mean over heads of the column sums of
+    softmax(q k^T dh^-0.5).  q, k: [B, N, heads * dh] GPU tensors of one storage dtype (bf16, fp16 or f32), nothing converted;
+    column views of a wider [B, N, ld] buffer are taken as they are (unit column stride, rows ld apart, samples N * ld apart)."""
+    names = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}
+    if q.dtype not in names or k.dtype != q.dtype or not (q.is_cuda and k.is_cuda):
+        raise ValueError(f"sag_mass: storage dtypes {q.dtype} / {k.dtype} (GPU tensors of one of bf16, fp16, f32)")
+    if q.dim() != 3 or k.shape != q.shape or q.shape[2] % int(heads):
+        raise ValueError(f"sag_mass: q {tuple(q.shape)} / k {tuple(k.shape)} for {heads} heads")
+    B, N, Cn = (int(v) for v in q.shape)
+    lds = []
+    for name, t in (("q", q), ("k", k)):
+        sb, sr, sc = t.stride()
+        if sc != 1 or sr < Cn or (B > 1 and sb != N * sr):
+            raise ValueError(f"sag_mass: {name} has strides {t.stride()}: rows must be contiguous and evenly spaced")
+        lds.append(int(sr))
+    out = torch.empty(B, N, device=q.device, dtype=torch.float32)
+    part = torch.empty(B, int(heads), N, device=q.device, dtype=torch.float32)      # the per-head column sums (kernel scratch)
+    check(_lib.load().af_op_sag_mass(DTYPES[names[q.dtype]], ptr(q), ptr(k), ptr(out), ptr(part), B, N, int(heads), Cn // int(heads),
+                                     lds[0], lds[1], stream_ptr()), "af_op_sag_mass")
+    return out
+
+
+def sag_degrade(x, eps, mass, alpha, sigma, blur_sigma=1.0, out=None):
+    """af_sag_degrade, one launch on fp32 latents [B, C, H, W]: x0 = (x - sigma eps) / alpha, its nine-tap Gaussian blur under
+    reflect padding where mass [B, (H / 8)(W / 8)] > 1 (each cell an 8 x 8 block), re-noised: alpha d + sigma eps.  out: a
+    contiguous fp32 GPU tensor of x's size that overlaps no input; allocated when None."""
+    for name, t in (("x", x), ("eps", eps), ("mass", mass)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"sag_degrade: {name} must be a contiguous fp32 GPU tensor")
+    if x.dim() != 4 or eps.shape != x.shape:
+        raise ValueError(f"sag_degrade: x {tuple(x.shape)} / eps {tuple(eps.shape)} ([B, C, H, W] both)")
+    B, Cn, H, W = (int(v) for v in x.shape)
+    if mass.numel() != B * (H // 8) * (W // 8):
+        raise ValueError(f"sag_degrade: mass has {mass.numel()} values, x needs {B} x {(H // 8) * (W // 8)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError("sag_degrade: out must be a contiguous fp32 GPU tensor of x's shape")
+    check(_lib.load().af_sag_degrade(ptr(x), ptr(eps), ptr(mass), ptr(out), B, Cn, H, W, float(alpha), float(sigma), float(blur_sigma),
+                                     stream_ptr()), "af_sag_degrade")
+    return out
+
+
+def sag_launches() -> dict:
+    """Launches of the two self-attention-guidance kernels since the library was loaded (not part of plan_counts)."""
+    lib = _lib.load()
+    return {"mass": int(lib.af_sag_mass_launches()), "degrade": int(lib.af_sag_degrade_launches())}
+
+
 STREAM_QSAMPLE = 2    # noise.STREAM_QSAMPLE (csrc/af_philox.h), stated here because noise.py imports this module
 
 

@@ -506,6 +506,43 @@ int af_op_region_weights(const float* m_dev, int Bf, int R, int H, int W, float*
 int af_op_region_attention(int dtype, const float* q_dev, const float* k_dev, const float* v_dev, const float* w_dev, float* o_dev,
                            int B, int Nq, int R, int T, int heads, int dh, float scale, int path, int ld_slack, void* stream);
 
+/* ---- self-attention guidance (af_sag.hip) ----
+ * Hong, Lee, Jang, Kim, "Improving Sample Quality of Diffusion Models Using Self-Attention Guidance", ICCV 2023; the arithmetic of
+ * diffusers' StableDiffusionSAGPipeline (kernel size 9, threshold 1.0).  Opt-in.
+ * af_sag_taps: pure host function (no GPU, no handle), in double; the only statement of the Gaussian: nine taps
+ *   w_i = exp(-0.5 ((i - 4) / sigma)^2) / sum.  A sigma that is not a positive finite number: AF_ERR_INVALID.
+ * af_op_sag_mass: the attention mass per key, mass [B][N] fp32 = (1 / heads) sum_h sum_i softmax_j(q_bhi . k_bhj dh^-0.5), from
+ *   q / k of `dtype` elements, [B][N][ld] with the operand in the first heads * dh columns of a row (a column view of a wider
+ *   buffer passes its first element and the buffer's row stride).  fp32 accumulation, the exact max-subtracted softmax.  Two
+ *   launches: one workgroup per (sample, head) writes that head's column sums into part_dev (fp32 scratch, B * heads * N values),
+ *   a second kernel adds the heads in ascending order.  Fixed summation order, no atomics: a sample's bits do not depend on its
+ *   batch position or on how the batch is split.  N <= 256; above it, a row stride below heads * dh or a bad shape:
+ *   AF_ERR_INVALID with a message.  Any alignment: 16-byte loads where pointers, strides and dh allow them.
+ * af_sag_degrade: ONE launch, fp32 [B][C][H][W]: x0 = (x - sigma e) / alpha; blur = separable nine-tap Gaussian (af_sag_taps of
+ *   blur_sigma, rounded to fp32 once) of x0 per plane under reflect padding of 4; d = mass[b][(r / 8)(W / 8) + c / 8] > 1 ? blur
+ *   : x0; out = alpha d + sigma e.  mass_dev fp32 [B][(H / 8)(W / 8)].  No intermediate reaches memory.  Refused (AF_ERR_INVALID):
+ *   an output that overlaps x, eps or the mass, alpha or blur_sigma that is not positive, H or W no multiple of 8, W > 256,
+ *   B C > 65535.  Any 4-byte alignment.
+ * af_sag_set: on = 1: every forward that runs the middle block (plain and twin forms; DeepCache mode none or REFRESH) also
+ *   launches the mass kernels at middle_block.1.transformer_blocks.0.attn1 on all Bf samples of the call, into a handle-owned
+ *   buffer; the forward's own launches and its eps are unchanged (the capture only reads).  on = 0: the forwards are what they are
+ *   without this call, launch for launch.  While on, refused before any launch: the PAG form, a T-GATE mode, a REUSE step
+ *   (AF_ERR_INVALID); the fp8 mode, regions, attached ControlNet residuals, token merging at the middle block, more than 256
+ *   middle-block tokens (AF_ERR_STATE / AF_ERR_INVALID).  Every af_load_tensor* drops the capture.
+ * af_sag_state: out = {on, B, N of the last capture (0, 0: none)}.  af_sag_read: the capture, fp32 [B][N], n = B N values.
+ * af_sag_mass_launches / af_sag_degrade_launches: calls that launched the mass kernels (a pair per call) / the degrade kernel
+ * since the library was loaded. */
+int af_sag_taps(double sigma, double out[9]);
+int af_op_sag_mass(int dtype, const void* q_dev, const void* k_dev, float* mass_dev, float* part_dev, int B, int N, int heads, int dh,
+                   int ld_q, int ld_k, void* stream);
+int af_sag_degrade(const float* x_dev, const float* eps_dev, const float* mass_dev, float* out_dev, int B, int C, int H, int W,
+                   float alpha, float sigma, double blur_sigma, void* stream);
+int af_sag_set(af_handle* h, int on);
+int af_sag_state(af_handle* h, int out[3]);
+int af_sag_read(af_handle* h, float* out_dev, int64_t n, void* stream);
+int64_t af_sag_mass_launches(void);
+int64_t af_sag_degrade_launches(void);
+
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */
 int af_lincomb(float* out_dev, int64_t n, const float* x0_dev, float w0, const float* x1_dev, float w1,

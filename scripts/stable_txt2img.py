@@ -98,6 +98,14 @@ def parse_args(argv=None):
     ap.add_argument("--guidance_rescale", type=float, default=0.0, metavar="PHI",
                     help="guidance rescale, 0 .. 1 (0 = off): the combined prediction is scaled towards the conditional one's "
                          "standard deviation, the remedy for over-exposure at high guidance; every sampler")
+    ap.add_argument("--sag_scale", type=float, default=0.0, metavar="S",
+                    help="self-attention guidance: e += S (e_guide - e_degraded), one more single-leg U-Net call per step on the "
+                         "input blurred where the middle block's self-attention looks (0 = off; diffusers' default is 0.75); works "
+                         "with --scale 1 too.  DDIM, --plms and --dpm_solver; composes with --dtype bf16 / f32 / fp16, --lora, --freeu, "
+                         "--img2img, --inpaint_mask, --noise philox, --gpus, and --tome where the middle block does not merge; not with "
+                         "--pag_scale, --guidance_rescale, --tgate, --deep_cache, --controlnet, regional prompts, --lcm or --dtype fp8")
+    ap.add_argument("--sag_blur_sigma", type=float, default=1.0, metavar="F",
+                    help="--sag_scale: the sigma of the 9-tap Gaussian blur, F > 0 (default 1.0)")
     ap.add_argument("--tgate", type=int, default=None, metavar="G",
                     help="T-GATE: step G - 1 also keeps the cross-attention outputs (averaged over the guidance legs); from step G "
                          "on the U-Net runs on one leg with them, without cross-attention or guidance; 1 <= G <= steps - 1 "
@@ -220,6 +228,36 @@ def parse_args(argv=None):
             if merging:
                 ap.error(f"--pag_layers: --tome merges tokens at sites {merging}; a merged self-attention cannot be perturbed")
         opt.pag_layers = layers
+    if not (opt.sag_scale >= 0.0 and opt.sag_scale != float("inf")):
+        ap.error("--sag_scale S: a finite S >= 0")
+    if not (opt.sag_blur_sigma > 0.0 and opt.sag_blur_sigma != float("inf")):
+        ap.error("--sag_blur_sigma F: a finite F > 0")
+    if opt.sag_scale == 0.0 and opt.sag_blur_sigma != 1.0:
+        ap.error("--sag_blur_sigma: give --sag_scale S > 0 too")
+    if opt.sag_scale > 0.0:
+        if opt.pag_scale > 0.0:
+            ap.error("--sag_scale: not with --pag_scale (both perturb or read the middle block's self-attention)")
+        if opt.guidance_rescale > 0.0:
+            ap.error("--sag_scale: not with --guidance_rescale (its reference is the CFG combine alone)")
+        if opt.tgate:
+            ap.error("--sag_scale: not built for T-GATE (--tgate): the degraded leg has no cached cross-attention")
+        if opt.deep_cache not in (None, 1):
+            ap.error("--sag_scale: not with --deep_cache (a reuse step does not run the middle block, so there is no map)")
+        if opt.controlnet:
+            ap.error("--sag_scale: not built for a ControlNet (--controlnet)")
+        if opt.regions is not None or opt.region_emb:
+            ap.error("--sag_scale: not built for regional prompts (--regions / --region_emb)")
+        if opt.lcm:
+            ap.error("--sag_scale: not built for --lcm (a distilled model runs without guidance legs)")
+        if opt.dtype == "fp8":
+            ap.error("--sag_scale: not built for --dtype fp8")
+        if opt.tome > 0.0 and not opt.config:
+            from adaface_amd.configs import sd15_config
+            unet = sd15_config()["model"]["params"]["unet_config"]["params"]
+            if 2 ** (len(unet["channel_mult"]) - 1) <= opt.tome_max_downsample:
+                ap.error("--sag_scale: --tome merges tokens at the middle block, whose attention then has no map over the full grid")
+        if (opt.H // opt.f) % 8 or (opt.W // opt.f) % 8 or opt.H % opt.f or opt.W % opt.f:
+            ap.error("--sag_scale: the latent sides (--H / --f, --W / --f) must be multiples of 8")
     if opt.tgate is not None and opt.tgate < 0:
         ap.error("--tgate G: G >= 1 (0 = off)")
     if opt.tgate:
@@ -575,6 +613,8 @@ def main():
             guided = {}
             if opt.pag_scale > 0.0 or opt.guidance_rescale > 0.0:
                 guided = dict(pag_scale=opt.pag_scale, pag_adaptive_scale=opt.pag_adaptive_scale, guidance_rescale=opt.guidance_rescale)
+            if opt.sag_scale > 0.0:
+                guided = dict(sag_scale=opt.sag_scale, sag_blur_sigma=opt.sag_blur_sigma)
             kw.update(guided)
             if opt.deep_cache not in (None, 1):
                 kw.update(deep_cache_interval=opt.deep_cache, deep_cache_depth=opt.deep_cache_depth)

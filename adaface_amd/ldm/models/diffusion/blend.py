@@ -9,6 +9,9 @@ is one step off).  n = min(len(ts), max(1, int(len(ts) * strength))).
 fused_blend: the blend in front of a step, q_sample(x0, t) * mask + (1 - mask) * img, as ONE launch (ops.noise_blend) with
 the bits of that composition.  With a noise_source its noise is generated inside the launch (stream 2, step = the loop index).
 
+The four sampler loops share two functions of this file: initial_latent, the latent a run starts from (by strength, x_T, the
+noise source's start code or torch.randn), and step_blend, the blend in front of a step (fused, or the reference's torch ops).
+
 This file is host logic only: the arithmetic is af_noise_blend's (csrc/af_inpaint.hip).
 """
 from __future__ import annotations
@@ -89,3 +92,35 @@ class FusedBlend:
         if self.noise_source is None:
             return ops.noise_blend(img, self.x0, self.mask, sa, s1, noise=torch.randn_like(self.x0))
         return ops.noise_blend(img, self.x0, self.mask, sa, s1, stream=STREAM_QSAMPLE, step=i, **self.key)
+
+
+def initial_latent(model, shape, x_T, noise_source, strength, x0, t_first, device):
+    """The latent a run starts from: by strength, x0 noised to t_first (start_code); else x_T if given; else the start code of
+    the noise source (stream 0, step 0), or torch.randn on the device without one."""
+    if strength is not None:
+        return start_code(model, x0, t_first, x_T, noise_source)
+    if x_T is not None:
+        return x_T
+    if noise_source is None:
+        return torch.randn(shape, device=device)
+    return noise_source.randn(shape, STREAM_XT, 0, device)
+
+
+def step_blend(model, mask, x0, noise_source=None, fused_blend=False):
+    """One run's blend in front of a step, blend(img, ts, t, i) at loop index i with the timestep as the tensor ts [B] and as
+    the host integer t: None without a mask; the FusedBlend launch; or the reference's q_sample(x0, ts) * mask + (1 - mask) * img
+    in torch, its noise the source's stream 2 at step i, or q_sample's own torch.randn_like without a source."""
+    if mask is None:
+        return None
+    assert x0 is not None
+    if fused_blend:
+        fused = FusedBlend(model, mask, x0, noise_source)
+        return lambda img, ts, t, i: fused(img, t, i)
+
+    def blend(img, ts, t, i):
+        if noise_source is None:
+            img_orig = model.q_sample(x0, ts)
+        else:
+            img_orig = model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, ts.device))
+        return img_orig * mask + (1. - mask) * img
+    return blend

@@ -5,7 +5,8 @@ makes it MI355X-native and device-agnostic:
   * register_buffer does not force "cuda" (the reference does, ddim.py:22-26);
   * the CFG combine and the x_{t-1} update are ONE fused HIP kernel (af_ddim_step);
   * the (cond, uncond) context pair is concatenated once per sample() call, not once per
-    step, so the UNet's hoisted cross-attention K/V stay cached across the 50 steps;
+    step, so the UNet's hoisted cross-attention K/V stay cached across the 50 steps; which entry point of the model a
+    step calls, with which keywords, is decided by the run's ModelCalls (model_calls.py);
   * a scalar guidance_scale means "no annealing" instead of the reference's
     UnboundLocalError (ddim.py:169-173, SURVEY.md §8a a4);
   * deep_cache_interval= / deep_cache_depth= (opt-in, not in the reference): DeepCache, see deep_cache.py;
@@ -20,13 +21,11 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
-from adaface_amd.ldm.models.diffusion import guidance as G
-from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
-from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
-from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
+from adaface_amd.ldm.models.diffusion.blend import check_strength, initial_latent, step_blend, strength_timesteps
+from adaface_amd.ldm.models.diffusion.model_calls import ModelCalls
 from adaface_amd.ldm.modules.diffusionmodules.util import (extract_into_tensor, make_ddim_sampling_parameters,
                                                            make_ddim_timesteps, noise_like)
-from adaface_amd.noise import STREAM_QSAMPLE, STREAM_STEP, STREAM_XT
+from adaface_amd.noise import STREAM_STEP
 
 
 def _check_noise_source(noise_source, noise_dropout):
@@ -41,7 +40,6 @@ class DDIMSampler(object):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule
-        self._twin_cache = None
         self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
         self.tgate_log = []           # None / "capture" / "replay" per step of the last run
 
@@ -131,14 +129,6 @@ class DDIMSampler(object):
         step = the loop index.  strength / fused_blend: as sample(); with strength, x_T is the noise added to x0."""
         check_strength(strength, x0, timesteps=timesteps, ddim_use_original_steps=ddim_use_original_steps)
         _check_noise_source(noise_source, noise_dropout)
-        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
-        G.check_model(self.model, unconditional_conditioning, pag_scale)
-        refuse_guided(tgate_step, pag_scale, guidance_rescale)
-        if sag_scale != 0. or sag_blur_sigma != 1.0:
-            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
-            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale, tgate_step, deep_cache_interval)
-        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
-        self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
         if strength is not None:
@@ -149,17 +139,13 @@ class DDIMSampler(object):
         elif not ddim_use_original_steps:
             subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
             timesteps = self.ddim_timesteps[:subset_end]
-        if strength is not None:
-            img = start_code(self.model, x0, int(timesteps[-1]), x_T, noise_source)
-        elif x_T is not None:
-            img = x_T
-        elif noise_source is None:
-            img = torch.randn(shape, device=device)
-        else:
-            img = noise_source.randn(shape, STREAM_XT, 0, device)
-        intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = reversed(range(0, timesteps)) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
+        calls = ModelCalls(self, cond, unconditional_conditioning, total_steps, deep_cache_interval, deep_cache_depth, pag_scale,
+                           pag_adaptive_scale, guidance_rescale, tgate_step, sag_scale, sag_blur_sigma)
+        img = initial_latent(self.model, shape, x_T, noise_source, strength, x0,
+                             None if strength is None else int(timesteps[-1]), device)
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
         if verbose:
             print(f"Running DDIM Sampling with {total_steps} timesteps")
 
@@ -170,35 +156,19 @@ class DDIMSampler(object):
         max_guide_anneal_steps = total_steps - 1
         delta = (max_guide_scale - min_guide_scale) / max_guide_anneal_steps if max_guide_anneal_steps > 0 else 0.
         guide_scale = max_guide_scale
-        self._twin_cache = None
-        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
-        self.deep_cache_log = dc_run.log
-        tg_run = TGateRun(self.model, total_steps, tgate_step)
-        self.tgate_log = tg_run.log
-        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
+        blend = step_blend(self.model, mask, x0, noise_source, fused_blend)
 
-        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if blend is not None:
-                img = blend(img, int(step), i)
-            elif mask is not None:
-                assert x0 is not None
-                if noise_source is None:
-                    img_orig = self.model.q_sample(x0, ts)
-                else:
-                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
-                img = img_orig * mask + (1. - mask) * img
+                img = blend(img, ts, int(step), i)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, use_original_steps=ddim_use_original_steps,
                                               quantize_denoised=quantize_denoised, temperature=temperature,
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
                                               corrector_kwargs=corrector_kwargs, guidance_scale=guide_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              noise_source=noise_source, noise_step=i, deep_cache_run=dc_run,
-                                              pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale,
-                                              guidance_rescale=guidance_rescale, timestep=int(step),
-                                              tgate_run=tg_run, **sag_kw)
+                                              noise_source=noise_source, noise_step=i, timestep=int(step), calls=calls)
             if callback:
                 callback(i)
             if img_callback:
@@ -207,68 +177,23 @@ class DDIMSampler(object):
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0)
             guide_scale = guide_scale - delta if i <= max_guide_anneal_steps else 1
-        self._twin_cache = None
         return img, intermediates
-
-    def _twin_condition(self, c, uc):
-        """(cond, uncond) concatenated in the reference's order — cond FIRST (ddim.py:236-247) — built once."""
-        key = (id(c), id(uc))
-        if self._twin_cache is not None and self._twin_cache[0] == key:
-            return self._twin_cache[1]
-        if isinstance(c, tuple):
-            c_c, c_in_c, extra_info = c
-            c_u, c_in_u, _ = uc
-            twin = (torch.cat([c_c, c_u]), sum([list(c_in_c), list(c_in_u)], []), extra_info)
-        else:
-            twin = torch.cat([c, uc])
-        self._twin_cache = (key, twin, c, uc)  # keep c / uc alive so the ids stay unique
-        return twin
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0,
-                      deep_cache_run=None, pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timestep=None,
-                      tgate_run=None, sag_scale=0., sag_blur_sigma=1.0):
+                      guidance_scale=1., unconditional_conditioning=None, noise_source=None, noise_step=0, timestep=None,
+                      calls=None):
         """ddim.py:222-296.  noise_source: the step noise is its stream 1 at step noise_step (the loop index) instead of
-        torch.randn; repeat_noise then gives every sample the first sample's id.  deep_cache_run: the loop's DeepCacheRun
-        (it decides, from noise_step and this step's call form, between the full forward, a refresh and a reuse).
-        pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes the model call and the combine, and the update
-        below takes its result as a plain eps; timestep: t as a host integer (None: read from t).  tgate_run: the loop's
-        TGateRun (tgate.py) -- it names this step's phase from noise_step; a replay step is a single-leg call."""
+        torch.randn; repeat_noise then gives every sample the first sample's id.  calls: the loop's ModelCalls
+        (model_calls.py), which makes this step's model call from noise_step -- with the run's DeepCache, T-GATE and guidance
+        settings -- for the update below to take; None: one made here from c and unconditional_conditioning without any of
+        them, the reference's call.  timestep: t as a host integer (None: read from t where needed)."""
         _check_noise_source(noise_source, noise_dropout)
         b, device = x.shape[0], x.device
-        single = unconditional_conditioning is None or guidance_scale == 1.
-        guided = G.is_on(pag_scale, guidance_rescale) or bool(sag_scale)
-        phase = None
-        form = (not single, b, x.shape[2], x.shape[3])
-        if tgate_run is not None:
-            if guided and tgate_run.active:
-                refuse_guided(1, pag_scale, guidance_rescale)
-            phase = tgate_run.step(noise_step)
-            single = single or phase == "replay"
-            form = tgate_run.form((not single, b, x.shape[2], x.shape[3]), phase)
-        dc = None if deep_cache_run is None or guided else deep_cache_run.step(noise_step, form)
-        if phase is not None:
-            e_c, e_u = gated_eps(self, x, t, c, unconditional_conditioning, single, phase, dc)
-        elif guided:
-            e_c = G.guided_eps(self, x, t, c, unconditional_conditioning, guidance_scale,
-                               int(t[0]) if timestep is None else timestep, pag_scale, pag_adaptive_scale, guidance_rescale,
-                               deep_cache_run, noise_step, **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}))
-            e_u = None
-        elif single:
-            e_c = self.model.apply_model(x, t, c) if dc is None else self.model.apply_model(x, t, c, deep_cache=dc)
-            e_u = None
-        else:
-            twin = self._twin_condition(c, unconditional_conditioning)
-            if dc is not None:      # (a DeepCacheRun is active only on a model with the twin entry point)
-                e = self.model.apply_model_cfg_twin(x, t, twin, deep_cache=dc)
-            elif hasattr(self.model, "apply_model_cfg_twin"):
-                # [x; x] without the concatenation: the UNet computes its context-independent prefix once (af_unet_forward_twin)
-                e = self.model.apply_model_cfg_twin(x, t, twin)
-            else:
-                e = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), twin)
-            e_c, e_u = e[:b], e[b:]
+        if calls is None:
+            calls = ModelCalls.bare(self, c, unconditional_conditioning)
+        e_c, e_u = calls.eps(x, t, noise_step, timestep, guidance_scale)
 
         alphas = self.model.alphas_cumprod if use_original_steps else self.ddim_alphas
         alphas_prev = self.model.alphas_cumprod_prev if use_original_steps else self.ddim_alphas_prev
@@ -329,30 +254,22 @@ class DDIMSampler(object):
                guidance_rescale=0.):
         """ddim.py:315-350 (img2img tail): anneals guidance from `guidance_scale` to min(2, guidance_scale).
         deep_cache_interval / deep_cache_depth / pag_scale / pag_adaptive_scale / guidance_rescale: as sample()."""
-        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
-        G.check_model(self.model, unconditional_conditioning, pag_scale)
-        self.guidance_log = []
-        self._guided_twin_cache = None
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
+        calls = ModelCalls(self, cond, unconditional_conditioning, total_steps, deep_cache_interval, deep_cache_depth, pag_scale,
+                           pag_adaptive_scale, guidance_rescale, stepped=("deep_cache",))
         max_g = guidance_scale
         min_g = min(2.0, max_g)
         delta = (max_g - min_g) / (total_steps - 1) if total_steps > 1 else 0.
         g = max_g
         x_dec = x_latent
-        self._twin_cache = None
-        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
-        self.deep_cache_log = dc_run.log
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
                                           guidance_scale=g, unconditional_conditioning=unconditional_conditioning,
-                                          noise_step=i, deep_cache_run=dc_run, pag_scale=pag_scale,
-                                          pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
-                                          timestep=int(step))
+                                          noise_step=i, timestep=int(step), calls=calls)
             g = g - delta
-        self._twin_cache = None
         return x_dec

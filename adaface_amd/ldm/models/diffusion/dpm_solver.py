@@ -3,10 +3,11 @@ reference's `ldm` package descends from but does not ship: DPM-Solver++(2M), the
 Bao, Chen, Li, Zhu, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models" (2022), Algorithm 2.
 One UNet evaluation per step; made for 15-25 steps where DDIM wants 50.
 
-The loop is ddim_sampling's (inpainting blend in front of each step, twin classifier-free-guidance forward with the context
-pair built once, annealed guidance), the update is ONE fused HIP kernel per step (af_dpmpp_step: CFG combine, data
-prediction, multistep blend, update, history write), and the per-step scalars come from ONE host function
-(af_dpmpp_coeffs) -- the formulas are stated there and nowhere in this file.  A first-order step is DDIM with eta = 0.
+The loop is ddim_sampling's (inpainting blend in front of each step, the model call of the run's ModelCalls -- model_calls.py:
+twin classifier-free-guidance forward with the context pair built once -- annealed guidance), the update is ONE fused HIP kernel
+per step (af_dpmpp_step: CFG combine, data prediction, multistep blend, update, history write), and the per-step scalars come
+from ONE host function (af_dpmpp_coeffs) -- the formulas are stated there and nowhere in this file.  A first-order step is DDIM
+with eta = 0.
 
 Two timestep grids.  "time_uniform" is make_ddim_timesteps(S), DDIM's grid, which is far from uniform in
 lambda = log(alpha / sigma): at S = 20 on the SD schedule the step-size ratio r = h_prev / h runs from 0.24 to 4.9, and the
@@ -24,12 +25,9 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
-from adaface_amd.ldm.models.diffusion import guidance as G
-from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
-from adaface_amd.ldm.models.diffusion.deep_cache import DeepCacheRun
-from adaface_amd.ldm.models.diffusion.tgate import TGateRun, gated_eps, refuse_guided
+from adaface_amd.ldm.models.diffusion.blend import check_strength, initial_latent, step_blend, strength_timesteps
+from adaface_amd.ldm.models.diffusion.model_calls import ModelCalls
 from adaface_amd.ldm.modules.diffusionmodules.util import make_ddim_timesteps
-from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
 
 # columns of a dpmpp_schedule row
 COL_T, COL_G, COL_ALPHA, COL_SIGMA, COL_CX, COL_CD, COL_WCUR, COL_WPREV, COL_H, COL_R = range(10)
@@ -112,7 +110,6 @@ class DPMSolverSampler(object):
         super().__init__()
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
-        self._twin_cache = None
         self.deep_cache_log = []      # "full" / "refresh" / "reuse" per step of the last run
         self.tgate_log = []           # None / "capture" / "replay" per step of the last run
 
@@ -175,22 +172,7 @@ class DPMSolverSampler(object):
                                         deep_cache_depth=deep_cache_depth, pag_scale=pag_scale,
                                         pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
                                         tgate_step=tgate_step, strength=strength, fused_blend=fused_blend,
-                                        **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma)
-                                           if sag_scale != 0. or sag_blur_sigma != 1.0 else {}))
-
-    def _twin_condition(self, c, uc):
-        """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
-        key = (id(c), id(uc))
-        if self._twin_cache is not None and self._twin_cache[0] == key:
-            return self._twin_cache[1]
-        if isinstance(c, tuple):
-            c_c, c_in_c, extra_info = c
-            c_u, c_in_u, _ = uc
-            twin = (torch.cat([c_c, c_u]), sum([list(c_in_c), list(c_in_u)], []), extra_info)
-        else:
-            twin = torch.cat([c, uc])
-        self._twin_cache = (key, twin, c, uc)  # keep c / uc alive so the ids stay unique
-        return twin
+                                        sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma)
 
     @torch.no_grad()
     def dpm_solver_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
@@ -202,77 +184,27 @@ class DPMSolverSampler(object):
         that of the executed steps already (sample() builds it), and the run starts from x0 noised to its first timestep
         with x_T as the noise; fused_blend: as sample()."""
         check_strength(strength, x0)
-        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
-        G.check_model(self.model, unconditional_conditioning, pag_scale)
-        refuse_guided(tgate_step, pag_scale, guidance_rescale)
-        guided = G.is_on(pag_scale, guidance_rescale)
-        if sag_scale != 0. or sag_blur_sigma != 1.0:
-            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
-            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale, tgate_step, deep_cache_interval)
-            guided = guided or bool(sag_scale)
-        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
-        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
-        self._guided_twin_cache = None
+        total_steps = schedule.shape[0]
+        calls = ModelCalls(self, cond, unconditional_conditioning, total_steps, deep_cache_interval, deep_cache_depth, pag_scale,
+                           pag_adaptive_scale, guidance_rescale, tgate_step, sag_scale, sag_blur_sigma)
         device = self.model.betas.device
         b = shape[0]
         sde = schedule.shape[1] > COL_CN
-        if strength is not None:
-            img = start_code(self.model, x0, int(schedule[0, COL_T]), x_T, noise_source)
-        elif x_T is not None:
-            img = x_T
-        elif noise_source is None:
-            img = torch.randn(shape, device=device)
-        else:
-            img = noise_source.randn(shape, STREAM_XT, 0, device)
+        img = initial_latent(self.model, shape, x_T, noise_source, strength, x0, int(schedule[0, COL_T]), device)
         ids_dev, first_id = (None, 0) if noise_source is None else noise_source.ids_device(b, device)
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        total_steps = schedule.shape[0]
         f32 = lambda v: float(np.float32(v))
         # the x0 history: the kernel writes one buffer while the next step's blend reads the other
         hist = [torch.empty(shape, device=device, dtype=torch.float32) for _ in range(2)]
         x0_prev = None
-        self._twin_cache = None
-        dc_run = DeepCacheRun(self.model, total_steps, deep_cache_interval, deep_cache_depth)
-        self.deep_cache_log = dc_run.log
-        tg_run = TGateRun(self.model, total_steps, tgate_step)
-        self.tgate_log = tg_run.log
-        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
+        blend = step_blend(self.model, mask, x0, noise_source, fused_blend)
         for i, row in enumerate(schedule):
             index = total_steps - i - 1
             guide_scale = float(row[COL_G])
             ts = torch.full((b,), int(row[COL_T]), device=device, dtype=torch.long)
             if blend is not None:
-                img = blend(img, int(row[COL_T]), i)
-            elif mask is not None:
-                assert x0 is not None
-                if noise_source is None:
-                    img_orig = self.model.q_sample(x0, ts)
-                else:
-                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
-                img = img_orig * mask + (1. - mask) * img
-            single = unconditional_conditioning is None or guide_scale == 1.
-            phase = tg_run.step(i)
-            single = single or phase == "replay"      # (T-GATE: one leg from the gate on)
-            # None: the full forward, as without DeepCache
-            dc = None if guided else dc_run.step(i, tg_run.form((not single, b, img.shape[2], img.shape[3]), phase))
-            if phase is not None:
-                e_c, e_u = gated_eps(self, img, ts, cond, unconditional_conditioning, single, phase, dc)
-            elif guided:      # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
-                e_c = G.guided_eps(self, img, ts, cond, unconditional_conditioning, guide_scale, int(row[COL_T]), pag_scale,
-                                   pag_adaptive_scale, guidance_rescale, dc_run, i, **sag_kw)
-                e_u = None
-            elif single:
-                e_c = self.model.apply_model(img, ts, cond) if dc is None else self.model.apply_model(img, ts, cond, deep_cache=dc)
-                e_u = None
-            else:
-                twin = self._twin_condition(cond, unconditional_conditioning)
-                if dc is not None:      # (a DeepCacheRun is active only on a model with the twin entry point)
-                    e = self.model.apply_model_cfg_twin(img, ts, twin, deep_cache=dc)
-                elif hasattr(self.model, "apply_model_cfg_twin"):
-                    e = self.model.apply_model_cfg_twin(img, ts, twin)   # [x; x] without the concatenation (af_unet_forward_twin)
-                else:
-                    e = self.model.apply_model(torch.cat([img] * 2), torch.cat([ts] * 2), twin)
-                e_c, e_u = e[:b], e[b:]
+                img = blend(img, ts, int(row[COL_T]), i)
+            e_c, e_u = calls.eps(img, ts, i, int(row[COL_T]), guide_scale)
             second = row[COL_WPREV] != 0.
             if not sde:
                 img, pred_x0 = ops.dpmpp_step(img, e_c, e_u, x0_prev if second else None, guide_scale, f32(row[COL_ALPHA]),
@@ -294,5 +226,4 @@ class DPMSolverSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0.clone())   # the history buffers are rewritten two steps on
-        self._twin_cache = None
         return img, intermediates

@@ -3,10 +3,11 @@ Li, Zhao, "Latent Consistency Models: Synthesizing High-Resolution Images with F
 also serves LCM-LoRA (Luo et al., 2023: a plain LoRA, loaded with set_lora), and the strategic stochastic sampling of Zheng,
 Ma, Peng, Chen, Fu, "Trajectory Consistency Distillation" (2024), Algorithm 4 (tcd_gamma).  2-8 UNet evaluations per image.
 
-The loop is dpm_solver_sampling's without the history buffers (inpainting blend in front of each step, twin classifier-free-
-guidance forward with the context pair built once, annealed guidance, PAG / guidance rescale through guidance.py), the update is
-ONE fused HIP kernel per step (af_lcm_step: CFG combine, x0, the denoised sample D, re-noising to the next timestep), and the
-per-step scalars come from ONE host function (af_lcm_coeffs) -- the formulas are stated there and nowhere in this file.
+The loop is dpm_solver_sampling's without the history buffers (inpainting blend in front of each step, the model call of the
+run's ModelCalls -- model_calls.py: twin classifier-free-guidance forward with the context pair built once, PAG / guidance
+rescale -- annealed guidance), the update is ONE fused HIP kernel per step (af_lcm_step: CFG combine, x0, the denoised sample D,
+re-noising to the next timestep), and the per-step scalars come from ONE host function (af_lcm_coeffs) -- the formulas are stated
+there and nowhere in this file.
 
 LCM: D = c_out x0 + c_skip x (the boundary condition of the consistency function), x' = sqrt(acp_prev) D + sqrt(1 - acp_prev) z.
 TCD: D = x0; the step goes deterministically (DDIM) to the intermediate timestep s = floor((1 - gamma) t_prev) and is re-noised
@@ -26,9 +27,9 @@ import torch
 
 from adaface_amd import ops
 from adaface_amd.ldm.models.diffusion import guidance as G
-from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
+from adaface_amd.ldm.models.diffusion.blend import check_strength, initial_latent, step_blend, strength_timesteps
 from adaface_amd.ldm.models.diffusion.dpm_solver import guidance_values
-from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
+from adaface_amd.ldm.models.diffusion.model_calls import ModelCalls
 
 # columns of an lcm_schedule row
 COL_T, COL_G, COL_ALPHA, COL_SIGMA, COL_KOUT, COL_KSKIP, COL_CX, COL_C0, COL_CN, COL_S = range(10)
@@ -96,7 +97,6 @@ class LCMSampler(object):
         super().__init__()
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
-        self._twin_cache = None
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -172,20 +172,6 @@ class LCMSampler(object):
         finally:
             self.model.set_guidance_embedding(before)
 
-    def _twin_condition(self, c, uc):
-        """(cond, uncond) concatenated once per sample() call, cond FIRST as the DDIM sampler (ddim.py:236-247)."""
-        key = (id(c), id(uc))
-        if self._twin_cache is not None and self._twin_cache[0] == key:
-            return self._twin_cache[1]
-        if isinstance(c, tuple):
-            c_c, c_in_c, extra_info = c
-            c_u, c_in_u, _ = uc
-            twin = (torch.cat([c_c, c_u]), sum([list(c_in_c), list(c_in_u)], []), extra_info)
-        else:
-            twin = torch.cat([c, uc])
-        self._twin_cache = (key, twin, c, uc)  # keep c / uc alive so the ids stay unique
-        return twin
-
     @torch.no_grad()
     def lcm_sampling(self, cond, shape, schedule, x_T=None, callback=None, img_callback=None, mask=None, x0=None,
                      log_every_t=100, unconditional_conditioning=None, noise_source=None, temperature=1., pag_scale=0.,
@@ -193,55 +179,23 @@ class LCMSampler(object):
         """schedule: an lcm_schedule table.  strength not None: the table is that of the executed steps already (sample() builds
         it), and the run starts from x0 noised to its first timestep with x_T as the noise; fused_blend: as sample()."""
         check_strength(strength, x0)
-        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
-        G.check_model(self.model, unconditional_conditioning, pag_scale)
-        guided = G.is_on(pag_scale, guidance_rescale)
-        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
-        self._guided_twin_cache = None
+        total_steps = schedule.shape[0]
+        calls = ModelCalls(self, cond, unconditional_conditioning, total_steps, pag_scale=pag_scale,
+                           pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale, stepped=())
         device = self.model.betas.device
         b = shape[0]
-        if strength is not None:
-            img = start_code(self.model, x0, int(schedule[0, COL_T]), x_T, noise_source)
-        elif x_T is not None:
-            img = x_T
-        elif noise_source is None:
-            img = torch.randn(shape, device=device)
-        else:
-            img = noise_source.randn(shape, STREAM_XT, 0, device)
+        img = initial_latent(self.model, shape, x_T, noise_source, strength, x0, int(schedule[0, COL_T]), device)
         ids_dev, first_id = (None, 0) if noise_source is None else noise_source.ids_device(b, device)
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        total_steps = schedule.shape[0]
         f32 = lambda v: float(np.float32(v))
-        self._twin_cache = None
-        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
+        blend = step_blend(self.model, mask, x0, noise_source, fused_blend)
         for i, row in enumerate(schedule):
             index = total_steps - i - 1
             guide_scale = float(row[COL_G])
             ts = torch.full((b,), int(row[COL_T]), device=device, dtype=torch.long)
             if blend is not None:
-                img = blend(img, int(row[COL_T]), i)
-            elif mask is not None:
-                assert x0 is not None
-                if noise_source is None:
-                    img_orig = self.model.q_sample(x0, ts)
-                else:
-                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
-                img = img_orig * mask + (1. - mask) * img
-            single = unconditional_conditioning is None or guide_scale == 1.
-            if guided:        # (guidance.py makes the model call and the combine; the step takes its result as a plain eps)
-                e_c = G.guided_eps(self, img, ts, cond, unconditional_conditioning, guide_scale, int(row[COL_T]), pag_scale,
-                                   pag_adaptive_scale, guidance_rescale, None, i)
-                e_u = None
-            elif single:
-                e_c = self.model.apply_model(img, ts, cond)
-                e_u = None
-            else:
-                twin = self._twin_condition(cond, unconditional_conditioning)
-                if hasattr(self.model, "apply_model_cfg_twin"):
-                    e = self.model.apply_model_cfg_twin(img, ts, twin)   # [x; x] without the concatenation (af_unet_forward_twin)
-                else:
-                    e = self.model.apply_model(torch.cat([img] * 2), torch.cat([ts] * 2), twin)
-                e_c, e_u = e[:b], e[b:]
+                img = blend(img, ts, int(row[COL_T]), i)
+            e_c, e_u = calls.eps(img, ts, i, int(row[COL_T]), guide_scale)
             c_n = f32(row[COL_CN] * temperature)
             # z in registers from the key (stream 1, step = the loop index); without a source, torch's device generator
             z = torch.randn(shape, device=device) if (noise_source is None and c_n != 0.) else None
@@ -256,5 +210,4 @@ class LCMSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0)
-        self._twin_cache = None
         return img, intermediates

@@ -2,7 +2,9 @@
 scripts/stable_txt2img.py.  Same constructor / sample / plms_sampling / p_sample_plms signatures.  Note the
 reference's quirks, kept: classifier-free guidance concatenates (UNCOND, COND) — the opposite order of the DDIM
 sampler (plms.py:193-199) — takes `unconditional_guidance_scale` (a scalar, no annealing), and eta must be 0.
-All tensor arithmetic runs in HIP kernels (af_lincomb, af_ddim_step); the sampler itself is host logic.
+All tensor arithmetic runs in HIP kernels (af_lincomb, af_ddim_step); the sampler itself is host logic.  The model calls
+are the run's ModelCalls' (model_calls.py, twin_order="uncond_first"); the combine of the unguided twin call and the second
+call of the first step at t_next are this sampler's own.
 """
 from __future__ import annotations
 
@@ -10,11 +12,10 @@ import numpy as np
 import torch
 
 from adaface_amd import ops
-from adaface_amd.ldm.models.diffusion import guidance as G
-from adaface_amd.ldm.models.diffusion.blend import FusedBlend, check_strength, start_code, strength_timesteps
+from adaface_amd.ldm.models.diffusion.blend import check_strength, initial_latent, step_blend, strength_timesteps
+from adaface_amd.ldm.models.diffusion.model_calls import ModelCalls
 from adaface_amd.ldm.modules.diffusionmodules.util import (make_ddim_sampling_parameters, make_ddim_timesteps,
                                                             noise_like)
-from adaface_amd.noise import STREAM_QSAMPLE, STREAM_XT
 
 
 class PLMSSampler(object):
@@ -23,7 +24,6 @@ class PLMSSampler(object):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
         self.schedule = schedule
-        self._twin_cache = None
 
     def register_buffer(self, name, attr):
         if isinstance(attr, torch.Tensor) and attr.device != self.model.device:
@@ -79,7 +79,7 @@ class PLMSSampler(object):
                                   unconditional_conditioning=unconditional_conditioning, pag_scale=pag_scale,
                                   pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
                                   noise_source=noise_source, strength=strength, fused_blend=fused_blend,
-                                  **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale != 0. or sag_blur_sigma != 1.0 else {}))
+                                  sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
@@ -91,14 +91,6 @@ class PLMSSampler(object):
         check_strength(strength, x0, timesteps=timesteps)
         if ddim_use_original_steps:
             raise NotImplementedError("ddim_use_original_steps is not used by txt2img")
-        pag_scale, pag_adaptive_scale, guidance_rescale = G.check_args(pag_scale, pag_adaptive_scale, guidance_rescale)
-        G.check_model(self.model, unconditional_conditioning, pag_scale)
-        if sag_scale != 0. or sag_blur_sigma != 1.0:
-            sag_scale, sag_blur_sigma = G.check_sag_args(sag_scale, sag_blur_sigma)
-            G.refuse_sag(self.model, sag_scale, pag_scale, guidance_rescale)
-        sag_kw = dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}
-        self.guidance_log = []        # (legs, PAG scale) per guided model call of the last run
-        self._guided_twin_cache = None
         device = self.model.betas.device
         b = shape[0]
         if strength is not None:
@@ -108,42 +100,30 @@ class PLMSSampler(object):
         else:
             subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
             timesteps = self.ddim_timesteps[:subset_end]
-        if strength is not None:
-            img = start_code(self.model, x0, int(timesteps[-1]), x_T, noise_source)
-        elif x_T is not None:
-            img = x_T
-        elif noise_source is None:
-            img = torch.randn(shape, device=device)
-        else:
-            img = noise_source.randn(shape, STREAM_XT, 0, device)
-        intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
+        calls = ModelCalls(self, cond, unconditional_conditioning, total_steps, pag_scale=pag_scale,
+                           pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale, sag_scale=sag_scale,
+                           sag_blur_sigma=sag_blur_sigma, twin_order="uncond_first", stepped=())
+        img = initial_latent(self.model, shape, x_T, noise_source, strength, x0,
+                             None if strength is None else int(timesteps[-1]), device)
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
         old_eps = []
-        self._twin_cache = None
-        blend = FusedBlend(self.model, mask, x0, noise_source) if fused_blend and mask is not None else None
+        blend = step_blend(self.model, mask, x0, noise_source, fused_blend)
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, len(time_range) - 1)]), device=device, dtype=torch.long)
             if blend is not None:
-                img = blend(img, int(step), i)
-            elif mask is not None:
-                assert x0 is not None
-                if noise_source is None:
-                    img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
-                else:
-                    img_orig = self.model.q_sample(x0, ts, noise=noise_source.randn(x0.shape, STREAM_QSAMPLE, i, device))
-                    img = img_orig * mask + (1. - mask) * img
+                img = blend(img, ts, int(step), i)
             img, pred_x0, e_t = self.p_sample_plms(img, cond, ts, index=index, quantize_denoised=quantize_denoised,
                                                    temperature=temperature, noise_dropout=noise_dropout,
                                                    score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
                                                    unconditional_guidance_scale=unconditional_guidance_scale,
                                                    unconditional_conditioning=unconditional_conditioning,
-                                                   old_eps=old_eps, t_next=ts_next, pag_scale=pag_scale,
-                                                   pag_adaptive_scale=pag_adaptive_scale, guidance_rescale=guidance_rescale,
+                                                   old_eps=old_eps, t_next=ts_next,
                                                    timesteps=(int(step), int(time_range[min(i + 1, len(time_range) - 1)])),
-                                                   **sag_kw)
+                                                   calls=calls)
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
@@ -154,49 +134,28 @@ class PLMSSampler(object):
             if index % log_every_t == 0 or index == total_steps - 1:
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0)
-        self._twin_cache = None
         return img, intermediates
-
-    def _twin_condition(self, c, uc):
-        """(UNCOND, COND) — the reference's PLMS order (plms.py:193-199) — concatenated once per sampling run."""
-        key = (id(c), id(uc))
-        if self._twin_cache is not None and self._twin_cache[0] == key:
-            return self._twin_cache[1]
-        if isinstance(c, tuple):
-            c_c, c_in_c, info = c
-            c_u, c_in_u, _ = uc
-            twin = (torch.cat([c_u, c_c]), sum([list(c_in_u), list(c_in_c)], []), info)
-        else:
-            twin = torch.cat([uc, c])
-        self._twin_cache = (key, twin, c, uc)
-        return twin
 
     @torch.no_grad()
     def p_sample_plms(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, old_eps=None, t_next=None,
-                      pag_scale=0., pag_adaptive_scale=0., guidance_rescale=0., timesteps=None, sag_scale=0., sag_blur_sigma=1.0):
-        """plms.py:175-253.  pag_scale / pag_adaptive_scale / guidance_rescale: guidance.py makes every model call of the step
-        and its combine; timesteps: (t, t_next) as host integers (None: read from the tensors)."""
+                      timesteps=None, calls=None):
+        """plms.py:175-253.  calls: the loop's ModelCalls (model_calls.py), which makes every model call of the step with the
+        run's guidance settings; None: one made here from c and unconditional_conditioning without any, the reference's calls.
+        timesteps: (t, t_next) as host integers (None: read from the tensors where needed)."""
         if quantize_denoised or score_corrector is not None or use_original_steps:
             raise NotImplementedError("quantize_denoised / score_corrector / use_original_steps are not on the txt2img path")
-        b = x.shape[0]
         f32 = lambda v: float(np.float32(float(v)))
+        if calls is None:
+            calls = ModelCalls.bare(self, c, unconditional_conditioning, "uncond_first")
 
         def get_model_output(xx, tt):
-            if G.is_on(pag_scale, guidance_rescale) or sag_scale:
-                th = int(tt[0]) if timesteps is None else timesteps[0 if tt is t else 1]
-                return G.guided_eps(self, xx, tt, c, unconditional_conditioning, unconditional_guidance_scale, th, pag_scale,
-                                    pag_adaptive_scale, guidance_rescale,
-                                    **(dict(sag_scale=sag_scale, sag_blur_sigma=sag_blur_sigma) if sag_scale else {}))
-            if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-                return self.model.apply_model(xx, tt, c)
-            twin = self._twin_condition(c, unconditional_conditioning)
-            if hasattr(self.model, "apply_model_cfg_twin"):
-                e = self.model.apply_model_cfg_twin(xx, tt, twin)   # [x; x] without the concatenation (af_unet_forward_twin)
-            else:
-                e = self.model.apply_model(torch.cat([xx] * 2), torch.cat([tt] * 2), twin)
-            return ops.lincomb([(e[b:], unconditional_guidance_scale), (e[:b], 0.0)], cfg=True)  # e_u + g (e_c - e_u)
+            th = None if timesteps is None else timesteps[0 if tt is t else 1]
+            e_c, e_u = calls.eps(xx, tt, 0, th, unconditional_guidance_scale)
+            if e_u is None:
+                return e_c
+            return ops.lincomb([(e_c, unconditional_guidance_scale), (e_u, 0.0)], cfg=True)  # e_u + g (e_c - e_u)
 
         def get_x_prev_and_pred_x0(e, idx):
             # one noise_like draw per call, as the reference (plms.py:236), so the device generator advances

@@ -4,7 +4,8 @@ cross-attention output, averaged over the guidance legs (af_tgate_set, include/a
 U-Net runs on one leg with those outputs in place of cross-attention, and guidance is no longer applied.  Not part of the
 reference; opt-in.
 
-This file is the schedule and the per-run bookkeeping, both host-only.
+This file is the schedule and the per-run bookkeeping, both host-only; the capture and replay calls themselves are made
+where every step's model call is (model_calls.py).
 """
 from __future__ import annotations
 
@@ -57,16 +58,3 @@ class TGateRun:
 
     def form(self, base: tuple, phase) -> tuple:
         return tuple(base) + ((phase,) if self.active else ())
-
-
-def gated_eps(sampler, x, t, c, uc, single: bool, phase: str, dc=None):
-    """The model call of a capture or replay step: (e_c, e_u).  capture: this step's ordinary call form (twin unless
-    `single`), which also keeps the cross-attention outputs; replay: one leg, no context, e_u None -- the step kernels then
-    ignore the guidance scale."""
-    model = sampler.model
-    b = x.shape[0]
-    if phase == "replay" or single:
-        return model.apply_model(x, t, c, deep_cache=dc, tgate=phase), None
-    twin = sampler._twin_condition(c, uc)
-    e = model.apply_model_cfg_twin(x, t, twin, deep_cache=dc, tgate=phase)
-    return e[:b], e[b:]

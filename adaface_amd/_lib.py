@@ -99,6 +99,12 @@ _SIGS = [
     ("af_sag_read", C.c_int, [_P, _P, C.c_int64, _P]),
     ("af_sag_mass_launches", C.c_int64, []),
     ("af_sag_degrade_launches", C.c_int64, []),
+    ("af_resample_taps", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("af_resample_plan_create", C.c_int, [C.c_int] * 5 + [C.POINTER(_P)]),
+    ("af_resample_plan_destroy", C.c_int, [_P]),
+    ("af_resample_plan_tables", C.c_int, [_P, C.POINTER(C.c_int), _P, _P, _P, _P]),
+    ("af_resample2d", C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    ("af_resample2d_launches", C.c_int64, []),
     ("af_lincomb", C.c_int, [_P, C.c_int64, _P, C.c_float, _P, C.c_float, _P, C.c_float, _P, C.c_float, C.c_int, _P]),
     ("af_vae_decode", C.c_int, [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("af_to_uint8", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -19,6 +19,21 @@ STREAM_STEP = 1       # sampler step noise (DDIM eta > 0, DPM-Solver++ SDE); af_
 STREAM_QSAMPLE = 2    # q_sample noise of the inpainting blend
 
 
+# the per-tag constants of PhiloxNoise.derive; a new tag takes a new constant, an existing one never changes
+DERIVE_TAGS = {"hires": 0x68697265735F3031}    # ASCII "hires_01"
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def splitmix64(x: int) -> int:
+    """One output of splitmix64 (Steele, Lea, Flood, "Fast Splittable Pseudorandom Number Generators", OOPSLA 2014) from state x:
+    z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31,
+    all mod 2^64."""
+    z = (int(x) + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
 class PhiloxNoise:
     """The noise of the samples `sample_ids` (global indices; None: first_id, first_id + 1, ...) under `seed`.
 
@@ -55,6 +70,14 @@ class PhiloxNoise:
     def repeated(self, n):
         """A source whose n samples all carry this source's first id (the samplers' repeat_noise)."""
         return PhiloxNoise(self.seed, sample_ids=[self.ids(1)[0]] * n)
+
+    def derive(self, tag: str):
+        """A source for the same sample ids whose seed is splitmix64(seed + DERIVE_TAGS[tag]) mod 2^64: a second run of the same
+        samples (the hires fix's pass two) draws noise uncorrelated with this source's, still a pure function of (seed, global
+        sample index)."""
+        if tag not in DERIVE_TAGS:
+            raise ValueError(f"PhiloxNoise.derive: tag {tag!r} (one of {', '.join(DERIVE_TAGS)})")
+        return PhiloxNoise(splitmix64(self.seed + DERIVE_TAGS[tag]), sample_ids=self.sample_ids, first_id=self.first_id)
 
     def randn(self, shape, stream, step, device):
         shape = tuple(int(s) for s in shape)

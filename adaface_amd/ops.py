@@ -886,6 +886,99 @@ def sag_launches() -> dict:
     return {"mass": int(lib.af_sag_mass_launches()), "degrade": int(lib.af_sag_degrade_launches())}
 
 
+RESAMPLE_MODES = {"nearest-exact": 0, "bilinear": 1, "bicubic": 2, "lanczos3": 3}   # AF_RESAMPLE_* (include/adaface_hip.h)
+RESAMPLE_MAX_TAPS = 7      # AF_RESAMPLE_MAX_TAPS
+RESAMPLE_TILE = (16, 64)   # the kernel's output tile, rows x columns (TH, TW of csrc/af_resample.hip)
+
+
+def _resample_mode(mode):
+    if mode not in RESAMPLE_MODES:
+        raise ValueError(f"resample: mode {mode!r} (one of {', '.join(RESAMPLE_MODES)})")
+    return RESAMPLE_MODES[mode]
+
+
+def resample_taps(mode, n_in, n_out):
+    """af_resample_taps (host only, no GPU): the tap table of one axis, (idx int64 [n_out, taps], w float64 [n_out, taps]);
+    unused taps carry weight 0 and a valid index."""
+    import ctypes
+    n = max(int(n_out), 1) * RESAMPLE_MAX_TAPS
+    idx, w, taps = (ctypes.c_int32 * n)(), (ctypes.c_double * n)(), ctypes.c_int()
+    check(_lib.load().af_resample_taps(_resample_mode(mode), int(n_in), int(n_out), idx, w, ctypes.byref(taps)), "af_resample_taps")
+    t = taps.value
+    return (torch.tensor(idx[:n_out * t], dtype=torch.int64).view(n_out, t),
+            torch.tensor(w[:n_out * t], dtype=torch.float64).view(n_out, t))
+
+
+class _ResamplePlan:
+    """An af_resample_plan: the tables of one (mode, H, W, Ho, Wo) on the current device; freed with the object."""
+
+    def __init__(self, mode, H, W, Ho, Wo):
+        self.shape = (int(H), int(W), int(Ho), int(Wo))
+        self.handle = C.c_void_p()
+        lib = _lib.load()
+        self._destroy = lib.af_resample_plan_destroy      # (held here: module globals may be gone when the last plan is collected)
+        check(lib.af_resample_plan_create(_resample_mode(mode), *self.shape, C.byref(self.handle)), "af_resample_plan_create")
+
+    def tables(self):
+        """The plan's own tables as the kernel reads them: (iy int32 [Ho, T], wy fp32 [Ho, T], ix [Wo, T], wx [Wo, T]), host."""
+        _, _, Ho, Wo = self.shape
+        taps = C.c_int()
+        lib = _lib.load()
+        check(lib.af_resample_plan_tables(self.handle, C.byref(taps), None, None, None, None), "af_resample_plan_tables")
+        t = taps.value
+        iy, wy = torch.empty(Ho, t, dtype=torch.int32), torch.empty(Ho, t, dtype=torch.float32)
+        ix, wx = torch.empty(Wo, t, dtype=torch.int32), torch.empty(Wo, t, dtype=torch.float32)
+        check(lib.af_resample_plan_tables(self.handle, C.byref(taps), ptr(iy), ptr(wy), ptr(ix), ptr(wx)), "af_resample_plan_tables")
+        return iy, wy, ix, wx
+
+    def __del__(self):
+        destroy, handle = getattr(self, "_destroy", None), getattr(self, "handle", None)
+        if destroy is not None and handle:
+            self.handle = None
+            destroy(handle)
+
+
+_resample_plans = {}
+
+
+def resample_plan(mode, H, W, Ho, Wo, device=None):
+    """The cached plan of (mode, H, W, Ho, Wo, device); made on first use (needs the GPU: the plan owns device tables)."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (mode, int(H), int(W), int(Ho), int(Wo), device.index)
+    if key not in _resample_plans:
+        with torch.cuda.device(device):
+            _resample_plans[key] = _ResamplePlan(mode, H, W, Ho, Wo)
+    return _resample_plans[key]
+
+
+def resample2d(x, size, mode, out=None):
+    """af_resample2d, one launch: [B, C, H, W] fp32 on the GPU -> [B, C, size[0], size[1]] under `mode` (RESAMPLE_MODES; upscaling
+    only).  Any 4-byte alignment of x's and out's storage; out: a contiguous fp32 GPU tensor of the result's shape that does not
+    overlap x, allocated when None."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4):
+        raise ValueError("resample2d: x must be a contiguous fp32 GPU tensor [B, C, H, W]")
+    B, Cn, H, W = (int(v) for v in x.shape)
+    Ho, Wo = int(size[0]), int(size[1])
+    plan = resample_plan(mode, H, W, Ho, Wo, x.device)
+    if out is None:
+        out = torch.empty(B, Cn, Ho, Wo, device=x.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, Cn, Ho, Wo)
+              and out.device == x.device):
+        raise ValueError(f"resample2d: out must be a contiguous fp32 GPU tensor of shape {(B, Cn, Ho, Wo)} on x's device")
+    if B * Cn == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(_lib.load().af_resample2d(plan.handle, ptr(x), ptr(out), B * Cn, stream_ptr()), "af_resample2d")
+    return out
+
+
+def resample2d_launches() -> int:
+    """Launches of the resampling kernel since the library was loaded (not part of plan_counts)."""
+    return int(_lib.load().af_resample2d_launches())
+
+
 STREAM_QSAMPLE = 2    # noise.STREAM_QSAMPLE (csrc/af_philox.h), stated here because noise.py imports this module
 
 

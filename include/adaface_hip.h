@@ -543,6 +543,34 @@ int af_sag_read(af_handle* h, float* out_dev, int64_t n, void* stream);
 int64_t af_sag_mass_launches(void);
 int64_t af_sag_degrade_launches(void);
 
+/* ---- hires fix: separable 2-D resampling from tap tables (af_resample.hip) ----
+ * Upscaling of fp32 planes [planes][H][W] -> [planes][Ho][Wo].  The kernel knows no filter: it applies two tap tables,
+ *   y[p][oy][ox] = sum_ty wy[oy][ty] * ( sum_tx wx[ox][tx] * x[p][iy[oy][ty]][ix[ox][tx]] ),
+ * each sum an fmaf chain in ascending tap order that starts from the first product, the horizontal pass first: Tx + Ty fp32
+ * roundings on an output's longest path, whatever the tile, the batch split or the path (16-byte or element accesses).
+ * af_resample_taps: pure host function (no GPU, no handle), in double; the only statement of the filters.  One axis of n_in ->
+ *   n_out elements: idx / w [n_out][*taps] (the caller provides n_out * AF_RESAMPLE_MAX_TAPS entries each), unused taps weight 0
+ *   with a valid index.  nearest-exact: 1 tap, min(floor((o + 0.5) n_in / n_out), n_in - 1).  bilinear (2) and bicubic (4, A =
+ *   -0.75): torch.nn.functional.interpolate with align_corners=False (bilinear clamps the source coordinate at 0, both clamp the
+ *   indices to the edge).  lanczos3 (7): Pillow's Image.resize(..., LANCZOS): centre (o + 0.5) n_in / n_out, window
+ *   [int(c - 3 + 0.5), int(c + 3 + 0.5)) cut to the axis, weights renormalised over what remains.
+ * af_resample_plan_create: both axes' tables for one (mode, H, W, Ho, Wo), weights rounded to fp32 once, every index checked to
+ *   lie in [0, n_in) and every weight to be finite on the host, then copied to the current device; the plan owns the copies.
+ * Refused by both (AF_ERR_INVALID with a message, before the device is touched): an unknown mode, n_in < 1, n_out < n_in on
+ *   either axis (upscaling only), n_out > 8192, n_out > 8 n_in, a null pointer.
+ * af_resample_plan_tables: the plan's host copies, iy / wy [Ho][*taps], ix / wx [Wo][*taps] (NULL: skipped).
+ * af_resample2d: ONE launch on `planes` planes.  Any 4-byte alignment; y must not overlap x (AF_ERR_INVALID).
+ * af_resample2d_launches: launches since the library was loaded. */
+enum { AF_RESAMPLE_NEAREST_EXACT = 0, AF_RESAMPLE_BILINEAR = 1, AF_RESAMPLE_BICUBIC = 2, AF_RESAMPLE_LANCZOS3 = 3 };
+#define AF_RESAMPLE_MAX_TAPS 7
+typedef struct af_resample_plan af_resample_plan;
+int af_resample_taps(int mode, int n_in, int n_out, int32_t* idx, double* w, int* taps);
+int af_resample_plan_create(int mode, int H, int W, int Ho, int Wo, af_resample_plan** plan);
+int af_resample_plan_destroy(af_resample_plan* plan);
+int af_resample_plan_tables(const af_resample_plan* plan, int* taps, int32_t* iy, float* wy, int32_t* ix, float* wx);
+int af_resample2d(const af_resample_plan* plan, const float* x_dev, float* y_dev, int64_t planes, void* stream);
+int64_t af_resample2d_launches(void);
+
 /* out = w0 x0 + w1 x1 + w2 x2 + w3 x3 (NULL inputs skipped), fp32, n elements; mode 1: out = x1 + w0 (x0 - x1) = the CFG
  * combine.  PLMS's Adams-Bashforth mixes of noise predictions (ldm/models/diffusion/plms.py:199,236-249). */
 int af_lincomb(float* out_dev, int64_t n, const float* x0_dev, float w0, const float* x1_dev, float w1,

@@ -6,7 +6,8 @@ Keeps the reference's flag names for everything that reaches the denoising path
 --seed --outdir --skip_save --fixed_code --gpu --bs --plms --dpm_solver --dpm_sde --lcm --tcd_gamma --noise --deep_cache --init_img_paths --init_img_weight.  Text conditioning is the one difference: the CLIP tower /
 EmbeddingManager are out of scope offline, so prompts are given as pre-computed embeddings
 (--prompt_emb file.pt/.npy with a [B*16,77,768] or [77,768] tensor) or --synthetic.
-Not in the reference: --img2img / --strength / --inpaint_mask (img2img by strength and inpainting, adaface_amd/img2img.py).
+Not in the reference: --img2img / --strength / --inpaint_mask (img2img by strength and inpainting, adaface_amd/img2img.py);
+--hires_scale / --hires_size / --hires_upscaler / --hires_strength / --hires_steps (hires fix, adaface_amd/hires.py).
 
     python scripts/stable_txt2img.py --synthetic --n_samples 8 --ddim_steps 50 --skip_save
     python scripts/stable_txt2img.py --synthetic --n_samples 64 --gpus 8      # starts the 8 ranks itself
@@ -153,6 +154,22 @@ def parse_args(argv=None):
                     help="--img2img: inpainting mask(s), white = repaint, resized to H x W: one for all samples, or one per "
                          "global sample index.  A latent cell with any white pixel is repainted; the rest is the image's own "
                          "encoding.  A checkpoint or config with a 9-channel U-Net (sd-v1-5-inpainting) needs it")
+    ap.add_argument("--hires_scale", type=float, default=None, metavar="F",
+                    help="hires fix: --H x --W is the first pass's size; its result is upscaled by F in (1, 4] (each latent side "
+                         "rounded to a multiple of 8) and a second img2img pass runs at that size.  Composes with every sampler, "
+                         "--dtype bf16 / f32 / fp16, --deep_cache, --tome, --freeu, --lora, --pag_scale, --guidance_rescale, "
+                         "--sag_scale, --tgate, --lcm, --noise philox and --gpus; not with --img2img, --inpaint_mask, --controlnet, "
+                         "regional prompts, --init_img_paths or --dtype fp8")
+    ap.add_argument("--hires_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="hires fix by target size in pixels instead of --hires_scale: multiples of 64, no smaller than --H x --W")
+    ap.add_argument("--hires_upscaler", choices=["latent", "latent-bicubic", "latent-nearest", "pixel-bicubic", "pixel-lanczos"],
+                    default="latent",
+                    help="hires fix: latent* resample the latent (bilinear / bicubic / nearest); pixel-* decode, resample the "
+                         "image (bicubic / Lanczos-3) and encode it again")
+    ap.add_argument("--hires_strength", type=float, default=0.7, metavar="F",
+                    help="hires fix: the share of the second pass's schedule that runs, in (0, 1] (default 0.7)")
+    ap.add_argument("--hires_steps", type=int, default=0, metavar="N",
+                    help="hires fix: the second pass's schedule length (0 = --ddim_steps)")
     ap.add_argument("--lora_strict", action="store_true", help="--lora: refuse a file with keys that map onto no layer")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--gpu", type=int, default=None)
@@ -339,6 +356,40 @@ def parse_args(argv=None):
                 ap.error(f"{flag}: one image, or one per sample ({opt.n_samples}), got {len(paths)}")
         if opt.H % opt.f or opt.W % opt.f:
             ap.error(f"--img2img: --H and --W must be multiples of --f ({opt.f})")
+    opt.hires = None
+    hires_extras = opt.hires_upscaler != "latent" or opt.hires_strength != 0.7 or opt.hires_steps != 0
+    if opt.hires_scale is None and opt.hires_size is None:
+        if hires_extras:
+            ap.error("--hires_upscaler / --hires_strength / --hires_steps: give --hires_scale F or --hires_size H W too")
+    else:
+        from adaface_amd import hires as HR
+        if opt.hires_scale is not None and opt.hires_size is not None:
+            ap.error("--hires_scale / --hires_size: give one of them")
+        if opt.H % opt.f or opt.W % opt.f:
+            ap.error(f"hires fix: --H and --W must be multiples of --f ({opt.f})")
+        if opt.hires_size is not None and any(v < 64 or v % 64 for v in opt.hires_size):
+            ap.error("--hires_size H W: positive multiples of 64")
+        if not 0.0 < opt.hires_strength <= 1.0:
+            ap.error("--hires_strength F: 0 < F <= 1")
+        if opt.hires_steps < 0:
+            ap.error("--hires_steps N: N >= 0 (0 = --ddim_steps)")
+        if opt.lcm and opt.hires_steps > opt.lcm_original_steps:
+            ap.error(f"--hires_steps: with --lcm at most --lcm_original_steps ({opt.lcm_original_steps})")
+        if opt.img2img or opt.inpaint_mask:
+            ap.error("hires fix: not with --img2img / --inpaint_mask (its second pass is the img2img of the first pass's result)")
+        if opt.controlnet:
+            ap.error("hires fix: not built for a ControlNet (--controlnet): the hint is bound to one size")
+        if opt.region_n:
+            ap.error("hires fix: not built for regional prompts (--regions / --region_emb): the weight map is bound to one size")
+        if opt.init_img_paths:
+            ap.error("hires fix: not with --init_img_paths (the blended start code belongs to one size)")
+        if opt.dtype == "fp8":
+            ap.error("hires fix: not built for --dtype fp8 (the static activation scales are calibrated at one size)")
+        try:
+            size = None if opt.hires_size is None else (opt.hires_size[0] // opt.f, opt.hires_size[1] // opt.f)
+            opt.hires = HR.target_size(opt.H // opt.f, opt.W // opt.f, scale=opt.hires_scale, size=size)
+        except ValueError as e:
+            ap.error(f"--hires_scale / --hires_size: {e}")
     if opt.noise == "philox" and opt.plms:
         ap.error("--noise philox: PLMS draws no noise and takes no noise source (use DDIM or --dpm_solver)")
     if opt.lora_strict and not opt.lora:
@@ -358,6 +409,8 @@ def hybrid_problem(opt, hybrid):
     """What keeps a hybrid model (9-channel inpainting U-Net) from running with these options, as a message; None: nothing."""
     if not hybrid:
         return None
+    if getattr(opt, "hires", None):
+        return "hires fix: not built for a 9-channel (inpainting) U-Net (its concatenated condition is bound to one size)"
     if not (opt.img2img and opt.inpaint_mask):
         return "a 9-channel (inpainting) U-Net needs --img2img PATH and --inpaint_mask PATH: it reads the mask and the masked image"
     if opt.controlnet:
@@ -596,6 +649,13 @@ def main():
         start_code = avg * opt.init_img_weight
         if noise_source is None:
             start_code = start_code + torch.randn([B] + shape, generator=gen) * (1.0 - opt.init_img_weight)
+    hires_code = None
+    if opt.hires is not None:
+        from adaface_amd import hires as HR
+        from adaface_amd.noise import STREAM_XT
+        if rank == 0:
+            print(f"hires fix: {opt.H}x{opt.W} -> {opt.hires[0] * opt.f}x{opt.hires[1] * opt.f}, upscaler {opt.hires_upscaler}, "
+                  f"strength {opt.hires_strength:g}, {opt.hires_steps or opt.ddim_steps} steps")
     os.makedirs(opt.outdir, exist_ok=True)
     tic = time.time()
     count = 0
@@ -623,22 +683,36 @@ def main():
             kw.update(i2i)        # (--img2img: x_T is then the noise added to x0, not a latent)
             guided.update(i2i)
             if opt.plms:
-                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
-                                            unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
-                                            eta=opt.ddim_eta, x_T=x_T, **guided)
+                call = dict(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                            unconditional_guidance_scale=opt.scale[0], unconditional_conditioning=uc,
+                            eta=opt.ddim_eta, x_T=x_T, **guided)
             elif opt.dpm_solver:
-                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
-                                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
-                                            skip_type=opt.dpm_skip, algorithm="sde-dpmsolver++" if opt.dpm_sde else "dpmsolver++",
-                                            **kw)
+                call = dict(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
+                            skip_type=opt.dpm_skip, algorithm="sde-dpmsolver++" if opt.dpm_sde else "dpmsolver++",
+                            **kw)
             elif opt.lcm:
-                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
-                                            guidance_scale=gs, unconditional_conditioning=uc, x_T=x_T,
-                                            original_steps=opt.lcm_original_steps, tcd_gamma=opt.tcd_gamma,
-                                            guidance_embedding=opt.lcm_guidance_embedding, **kw)
+                call = dict(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                            guidance_scale=gs, unconditional_conditioning=uc, x_T=x_T,
+                            original_steps=opt.lcm_original_steps, tcd_gamma=opt.tcd_gamma,
+                            guidance_embedding=opt.lcm_guidance_embedding, **kw)
             else:
-                samples, _ = sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
-                                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T, **kw)
+                call = dict(S=opt.ddim_steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
+                            guidance_scale=gs, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T, **kw)
+            if opt.hires is None:
+                samples, _ = sampler.sample(**call)
+            else:
+                # pass two: the same sampler, guidance and opt-ins on the upscaled result; its noise from the derived Philox
+                # source, or from the host generator the start code came from (the same for every world size)
+                second = HR.second_kwargs(call, steps=opt.hires_steps)
+                shape2 = [opt.C, *opt.hires]
+                if noise_source is None:
+                    if hires_code is None or not opt.fixed_code:
+                        hires_code = torch.randn([B] + shape2, generator=gen)
+                    z2 = shard_batch(hires_code, rank, world).to(device)
+                else:
+                    z2 = second["noise_source"].randn([b] + shape2, STREAM_XT, 0 if opt.fixed_code else n, device)
+                samples, _ = HR.two_pass(sampler, call, second, opt.hires, opt.hires_upscaler, opt.hires_strength, noise=z2)
             if keep is not None:      # the kept region is the image's own encoding, without the last blend's noise
                 samples = I2I.finish(samples, x0, keep)
             frames = gather_frames(model.decode_first_stage_uint8(samples), global_batch=B)
@@ -651,7 +725,8 @@ def main():
     toc = time.time()
     if rank == 0:
         n_img = B * opt.n_repeat
-        print(f"{n_img} images of {opt.H}x{opt.W} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M) SDE' if opt.dpm_sde else 'DPM-Solver++(2M)' if opt.dpm_solver else 'TCD' if opt.tcd_gamma is not None else 'LCM' if opt.lcm else 'DDIM'} steps in {toc - tic:.2f} s "
+        out_h, out_w = (opt.H, opt.W) if opt.hires is None else (opt.hires[0] * opt.f, opt.hires[1] * opt.f)
+        print(f"{n_img} images of {out_h}x{out_w} @ {opt.ddim_steps} {'PLMS' if opt.plms else 'DPM-Solver++(2M) SDE' if opt.dpm_sde else 'DPM-Solver++(2M)' if opt.dpm_solver else 'TCD' if opt.tcd_gamma is not None else 'LCM' if opt.lcm else 'DDIM'} steps in {toc - tic:.2f} s "
               f"({n_img / (toc - tic):.2f} images/s incl. first-call warm-up) on {world} GPU(s); outputs: {opt.outdir}")
     if dist.is_initialized():
         dist.destroy_process_group()
